@@ -14,8 +14,10 @@ With --gpus N the channels are sharded (1024 per GPU, weak scaling, configs[3] a
 batch of front-end I/Q is broadcast from rank 0 over RCCL by the product's own fan-out (kq_fanout_* of
 include/ka9q_hip.h: ncclBroadcast on the library's side stream, two slots; `--fanout torch` selects the
 torch.distributed twin); started without torch.distributed.run, `--gpus N` launches its own N ranks.
-At N=1 the line also carries `with_host_io` (the same step fed from pinned host memory and delivering audio + status
-to pinned host memory every step, copies overlapped), `cold_first_steps_ms` (no spin-up) and the CPU baseline rows.
+The line carries `cold_first_steps_ms` (no spin-up).  With --full it also carries, at N=1, `with_host_io` (the same step
+fed from pinned host memory and delivering audio + status to pinned host memory every step, copies overlapped), the
+secondary row, the other shapes, the real-time legs and the CPU baseline rows; at N > 1 `per_rank` and `host_ingest`.
+--dump-outputs DIR writes the last timed step's audio and status planes as .npy files.
 
 Prints ONE JSON line on rank 0.
 """
@@ -64,8 +66,8 @@ def parse():
                     help="N > 0: export NCCL_MAX_NCHANNELS=N before RCCL initialises (default 0: RCCL's own choice; the "
                          "broadcast's footprint costs the step <= 2.5 %% at any count, profiles/r04/bcast_side_kernel_probe.txt)")
     ap.add_argument("--per-rank", action="store_true",
-                    help="emit the per_rank diagnostics (step, kernel, broadcast and stall time of every rank) at N = 1 too; "
-                         "with --gpus N > 1 they are always on the line")
+                    help="emit the per_rank diagnostics (step, kernel, broadcast and stall time of every rank) without "
+                         "--full, and at N = 1 too; with --full and --gpus N > 1 they are always on the line")
     ap.add_argument("--no-host-io", action="store_true", help="skip the with_host_io measurement")
     ap.add_argument("--no-rows", action="store_true",
                     help="skip the `rows` object: BASELINE.json's other single-GPU shapes (cfg2, cfg3, cfg5 per-GPU share), each "
@@ -77,7 +79,55 @@ def parse():
                     help="length of the paced run that has to go without a late delivery")
     ap.add_argument("--gpu-state", action="store_true",
                     help="sample shader clock and power at 50 Hz over the spin-up steps (disturbs the timed steps by about 1 %%)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the demodulator kernel times, with_host_io(_pcm), the "
+                         "secondary compute_n0 row, the `rows` shapes, the `realtime` legs, the CPU baselines, and at N > 1 "
+                         "per_rank and host_ingest (each still subject to its --no-* switch).  Without it the run sets up, "
+                         "spins up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed -- audio.npy (float32 [channels][blocks]"
+                         "[2 olen], zero past each channel-block's nout) and status_<field>.npy (float64 [channels][blocks]) "
+                         "of every status field the path measures -- to DIR (rank 0).  A field NaN throughout (plfreq "
+                         "without the PL tone task, n0 without compute_n0) is not written; one measured in part has its "
+                         "unmeasured entries 0 and status_<field>_finite.npy (1 where measured) beside it.  The spin-up then runs a fixed number of steps (--spinup, or "
+                         "DUMP_SPINUP_STEPS) instead of a time, so that the bank's state depends on the arguments alone")
     return ap.parse_args()
+
+
+# --dump-outputs: spin-up steps when --spinup is not given.  The channels' state (oscillator phases, AGC, squelch and lock
+# counters) advances with every step, so a spin-up sized by time would make the dumped outputs depend on the build's speed.
+DUMP_SPINUP_STEPS = 8000
+
+
+def dump_outputs(path, kq, bank, C, B):
+    """The planes a caller of the timed path receives for its last call (kq_bank_pull_planes_async into page-locked memory):
+    audio [C][B][2 olen] float32 with each row zeroed past status.nout (the library leaves that tail as it was), and the
+    fields of the status records [C][B] as float64.  The library reports a quantity a channel does not measure as NaN
+    (plfreq without the PL tone task, n0 without compute_n0, snr of a linear channel): a field NaN throughout is left
+    out, and one measured in part is written with 0 where unmeasured and a 0 / 1 mask status_<field>_finite.npy."""
+    os.makedirs(path, exist_ok=True)
+    olen = bank.olen
+    audio = kq.HostBuffer(C * B * 2 * olen * 4)
+    status = kq.HostBuffer(C * B * kq.bank.STATUS_DTYPE.itemsize)
+    try:
+        bank.pull_planes_async(audio.ptr, status.ptr)
+        bank.host_io_wait()
+        a = audio.array(np.float32).reshape(C, B, 2 * olen).copy()
+        s = status.array(kq.bank.STATUS_DTYPE).reshape(C, B).copy()
+    finally:
+        audio.free()
+        status.free()
+    a[np.arange(2 * olen)[None, None, :] >= s["nout"][:, :, None]] = 0.0
+    np.save(os.path.join(path, "audio.npy"), a)
+    for name in kq.bank.STATUS_DTYPE.names:
+        v = s[name].astype(np.float64)
+        ok = np.isfinite(v)
+        if not ok.any():
+            continue
+        if not ok.all():
+            np.save(os.path.join(path, "status_%s_finite.npy" % name), ok.astype(np.float64))
+            v = np.where(ok, v, 0.0)
+        np.save(os.path.join(path, "status_%s.npy" % name), v)
 
 
 def usable_cores():
@@ -590,6 +640,8 @@ def main():
     under_profiler = any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ) or "rocprofiler" in os.environ.get("LD_PRELOAD", "")
     if a.spinup < 0 and under_profiler:
         a.spinup = 300      # a trace or counter pass of ten thousand serialised launches takes minutes and gigabytes
+    if a.spinup < 0 and a.dump_outputs:
+        a.spinup = DUMP_SPINUP_STEPS
     if a.spinup >= 0:
         spin = 2 * (a.spinup // 2)
     else:   # by time, from the cold steps just measured; every rank runs the same count (the steps post collectives)
@@ -640,6 +692,8 @@ def main():
     if reader:
         reader.join()
         gpu_state = reading.get("state")
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, kq, bank, C, B)
     elapsed = t1 - t0
     elapsed_local = elapsed
     rank_ms = [elapsed / a.steps * 1e3] * 2      # fastest / slowest rank
@@ -656,7 +710,7 @@ def main():
     # the consumer stream's waits for its batch timed (two event records per acquire that has to wait), then every rank's
     # step time, filter-kernel time, broadcast time and stall time travel to rank 0.
     per_rank = None
-    if world > 1 or a.per_rank:
+    if (world > 1 and a.full) or a.per_rank:
         nd = 40
         if use_c:
             fan.enable_timing(True)
@@ -693,7 +747,7 @@ def main():
     # the side stream and broadcasts it from there -- H2D, ncclBroadcast and the ranks' compute in one pipeline, which the
     # resident steps above (the root re-broadcasts a slot in place) do not exercise (VERDICT r5 #6a).  Beside `value`, never it.
     host_ingest = None
-    if use_c and ((world > 1 and a.ingest in ("host", "both")) or (world == 1 and a.ingest == "host")):
+    if use_c and ((world > 1 and (a.ingest == "host" or (a.full and a.ingest == "both"))) or (world == 1 and a.ingest == "host")):
         iq_pin_all = torch.from_numpy(np.ascontiguousarray(iq_host)).pin_memory() if rank == 0 else None
         src = iq_pin_all.data_ptr() if rank == 0 else None
 
@@ -729,11 +783,14 @@ def main():
                        "note": "every step's batch leaves pinned host memory on the root: kq_fanout_post(src_is_device = 0) = H2D into "
                                "the slot + ncclBroadcast on the side stream, two slots deep, beside the ranks' compute"}
     # the demodulator kernels' time comes from a few extra, untimed steps with the full set of events
-    bank.enable_timing(2)
-    for k in range(4):       # (an even count: the slots keep their parity)
-        step(spin + a.warmup + a_steps_done + k)
-    torch.cuda.synchronize()
-    tm2 = bank.timing(reset=True)
+    demod_ms = None
+    if a.full:
+        bank.enable_timing(2)
+        for k in range(4):       # (an even count: the slots keep their parity)
+            step(spin + a.warmup + a_steps_done + k)
+        torch.cuda.synchronize()
+        tm2 = bank.timing(reset=True)
+        demod_ms = tm2["demod_ms"] / max(1, tm2["filter_launches"])
     bank.enable_timing(0)
 
     # The path to its real ends (1 GPU only): the reference's path starts at a host packet (radio.c:106-147) and ends in a
@@ -741,7 +798,7 @@ def main():
     # (kq_bank_push_iq_async -> ring -> kq_bank_process) and audio + status of every step go back to pinned host memory
     # (kq_bank_pull_planes_async); the copies ride on the bank's copy streams under the kernels.  Beside `value`, never it.
     host_io = host_io_pcm = None
-    if world == 1 and not a.no_host_io:
+    if world == 1 and a.full and not a.no_host_io:
         import ctypes
         olen = L // D
         iq_pin = torch.from_numpy(np.ascontiguousarray(iq_host[M - 1:M - 1 + B * L])).pin_memory()
@@ -803,7 +860,7 @@ def main():
     # transform to the N/D bins the slave reads.  Reported beside the headline, never as `value`.
     fwd_used = {1: "full", 2: "pruned"}[bank.fwd_mode]
     second = None
-    if world == 1 and not a.no_second_row and a.fwd == "auto":
+    if world == 1 and a.full and not a.no_second_row and a.fwd == "auto":
         bank.close()
         bank = kq.Bank(fs, L, M, D, C, B, device=dev_index, compute_n0=not a.n0, fwd_mode=kq.KQ_FWD_AUTO,
                        stream=stream.cuda_stream, pl_tone=pl_tone)
@@ -828,14 +885,14 @@ def main():
 
     # BASELINE.json's other single-GPU shapes, each measured the same way on this box in this run
     rows = None
-    if world == 1 and not a.no_rows and a.config == "cfg4" and not under_profiler:
+    if world == 1 and a.full and not a.no_rows and a.config == "cfg4" and not under_profiler:
         rows = {}
         for name, blocks in (("cfg2", 64), ("cfg3", 64), ("cfg5", 16)):
             rows[name] = measure_row(torch, kq, wl, name, blocks, dev_index, stream, pci_bus)
 
     # "channels @ real-time", the second half of BASELINE.json's metric, measured (1 GPU, default workload only)
     realtime = None
-    if world == 1 and not a.no_realtime and a.config == "cfg4" and not under_profiler:
+    if world == 1 and a.full and not a.no_realtime and a.config == "cfg4" and not under_profiler:
         bank.close()
         realtime = measure_channels_at_realtime(torch, kq, wl, dev_index, stream, a.realtime_seconds)
 
@@ -870,11 +927,12 @@ def main():
                 "realtime_factor": round(front_end_msps * 1e6 / fs, 2),
                 "channels_at_realtime": (realtime["channels"] if realtime else None),
                 "channels_at_realtime_note": "MEASURED, = realtime.channels: one bank, 2 blocks per call, host I/O, paced, zero late "
-                                             "deliveries (null when the realtime legs were not run: N > 1, --no-realtime, profiler)",
+                                             "deliveries (null when the realtime legs were not run: no --full, N > 1, --no-realtime, "
+                                             "profiler)",
                 "channels_x_factor_extrapolated": int(total_ch * front_end_msps * 1e6 / fs),
                 "parallelism": "channels sharded x%d, front-end I/Q broadcast over RCCL" % world if world > 1 else "1 GPU",
             },
-            "roofline": roofline(k_ms, bool(a.n0), fwd_used, tm2["demod_ms"] / max(1, tm2["filter_launches"])),
+            "roofline": roofline(k_ms, bool(a.n0), fwd_used, demod_ms),
             "cold_first_steps_ms": cold,
             "gpu_state": gpu_state,
             "ms_per_step_ranks": {"min": round(rank_ms[0], 4), "max": round(rank_ms[1], 4)},
@@ -914,7 +972,7 @@ def main():
             second["note"] = ("the same workload %s compute_n0 (radio.c:383-425, status only): the bank then runs its %s "
                               "forward path" % ("with" if second["compute_n0"] else "without", second["fwd"]))
             out["with_compute_n0" if second["compute_n0"] else "without_compute_n0"] = second
-        if not a.no_cpu_baseline and world == 1:   # the CPU leg runs on rank 0 at N=1 only
+        if a.full and not a.no_cpu_baseline and world == 1:   # the CPU leg runs on rank 0 at N=1 only
             out["cpu_baseline"] = cpu_baseline(a.config, geom, plan, iq_host[M - 1:], a.cpu_seconds, compute_n0=a.n0)
             # SURVEY 8d's second row: compute_n0 the other way, next to the GPU row configured the same way
             other = cpu_baseline(a.config, geom, plan, iq_host[M - 1:], a.cpu_seconds / 2, compute_n0=int(not a.n0))

@@ -354,7 +354,7 @@ def test_bench_launches_itself_as_two_ranks(gpu, config, blocks, channels, total
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "6", "--spinup", "20",
            "--config", config, "--blocks", str(blocks), "--channels", str(channels),
-           "--no-cpu-baseline", "--no-rows", "--no-realtime", "--no-host-io", "--no-second-row"]
+           "--full", "--no-cpu-baseline", "--no-rows", "--no-realtime", "--no-host-io", "--no-second-row"]
     p = subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, start_new_session=True)
     try:
         out, err = p.communicate(timeout=420)

@@ -671,7 +671,8 @@ def test_operator_thread_beside_the_receiver_thread(gpu):
                     assert bank.add_channel(bank_cfg(plan[away])) == away
                     away = None
                 else:
-                    assert bank.num_channels == C and bank.channel_active(int(rng.integers(0, 1024)))
+                    # one past the highest live channel: a hole at the end is dropped (include/ka9q_hip.h)
+                    assert bank.num_channels == (C - 1 if away == C - 1 else C) and bank.channel_active(int(rng.integers(0, 1024)))
                 ops[0] += 1
             if away is not None:
                 assert bank.add_channel(bank_cfg(plan[away])) == away

@@ -2,7 +2,7 @@
 # cfg 2: k_demod_fm256 with 8 against 16 waves per channel (KQ_FM256_WAVES), alternating, one box:  gpurun -- 'bash tools/ab_fm256.sh'
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd $R
-Q="--config cfg2 --steps 200 --no-cpu-baseline --no-second-row --no-rows --no-host-io --no-realtime --spinup-seconds 6"
+Q="--full --config cfg2 --steps 200 --no-cpu-baseline --no-second-row --no-rows --no-host-io --no-realtime --spinup-seconds 6"
 for round in 1 2 3; do
   for w in 8 16; do
     KQ_FM256_WAVES=$w python bench.py $Q 2>/dev/null | python -c "
