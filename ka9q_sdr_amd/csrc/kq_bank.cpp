@@ -1332,18 +1332,15 @@ int run_blocks_timed(kq_bank *b, const float2 *window, unsigned nblocks, const u
   }
   size_t const ret_off = 8 * Cmax * sizeof(double) + ((b->cfg.max_blocks + 7) & ~7u);
   const int *retune_list = reinterpret_cast<const int *>(reinterpret_cast<const unsigned char *>(b->osc_dev2[pp]) + ret_off);
-  // full-spectrum path: the register-resident N = 16384 kernel where it applies (KQ_FULL_LDS=1 forces the LDS one)
-  static bool const lds_only = getenv("KQ_FULL_LDS") && atoi(getenv("KQ_FULL_LDS")) != 0;
-  bool const use16k = !lds_only && kq::full16k_supported(g);
+  // full-spectrum path: the register-resident N = 16384 kernel where it applies
+  bool const use16k = kq::full16k_supported(g);
   // No sweep anywhere: the register-resident kernel runs without its per-sample oscillator path; the first block of
   // a channel retuned since the last call (history still on the old oscillator) is then redone below with the
   // general variant, as the pruned path does.
   // (N = 65536: the steady-state variant takes sweeps up to full64k_sweep_limit() itself)
   // (N = 16384: swept channels inside full16k_sweep_limit() have a steady-state variant of their own, `swept_steady`)
   bool const plain = b->use64k ? b->n_fast == 0 : b->n_swept == 0;
-  static bool const swept_steady_off = getenv("KQ_SWEPT_STEADY") && atoi(getenv("KQ_SWEPT_STEADY")) == 0;  // A/B switch
-  bool const swept_steady = use16k && !b->use64k && b->fwd_mode != KQ_FWD_PRUNED && !spectrum && b->n_swept > 0 && b->n_fast == 0 &&
-                            !swept_steady_off;
+  bool const swept_steady = use16k && !b->use64k && b->fwd_mode != KQ_FWD_PRUNED && !spectrum && b->n_swept > 0 && b->n_fast == 0;
   bool const swept64k = b->use64k && b->n_swept > 0;
   // N = 16384 with swept and unswept channels side by side: two launches over two lists (see list_unswept_dev)
   bool const mixed = use16k && !b->use64k && b->fwd_mode != KQ_FWD_PRUNED && !spectrum && b->n_swept > 0 && b->n_swept < b->n_active;
@@ -1528,15 +1525,11 @@ int run_blocks_timed(kq_bank *b, const float2 *window, unsigned nblocks, const u
     if (kq::demod64_supported(g)) {
       kq::launch_demod64(ds, g, chd, pl, b->list_dev[0], nfm, b->list_dev[1], nam, b->list_dev[2], nlin, (int)nblocks,
                          b->cfg.compute_n0);
-    } else if (kq::demod_agc_wave_supported(g)) {  // wave-per-channel AM / linear, generic FM
+    } else {  // wave-per-channel AM / linear, generic FM
       kq::launch_demod64(ds, g, chd, pl, b->list_dev[0], 0, b->list_dev[1], nam, b->list_dev[2], nlin, (int)nblocks,
                          b->cfg.compute_n0);
-      kq::launch_demods(ds, g, chd, pl, b->tw, b->list_dev[0], nfm, b->list_dev[1], 0, b->list_dev[2], 0, (int)nblocks,
-                        b->cfg.compute_n0, b->fmout, b->fm_hist[b->fm_hist_cur], b->fm_hist[b->fm_hist_cur ^ 1]);
-      if (nfm > 0) b->fm_hist_cur ^= 1;
-    } else {
-      kq::launch_demods(ds, g, chd, pl, b->tw, b->list_dev[0], nfm, b->list_dev[1], nam, b->list_dev[2], nlin,
-                        (int)nblocks, b->cfg.compute_n0, b->fmout, b->fm_hist[b->fm_hist_cur], b->fm_hist[b->fm_hist_cur ^ 1]);
+      kq::launch_demod_fm(ds, g, chd, pl, b->tw, b->list_dev[0], nfm, (int)nblocks, b->cfg.compute_n0, b->fmout,
+                          b->fm_hist[b->fm_hist_cur], b->fm_hist[b->fm_hist_cur ^ 1]);
       if (nfm > 0) b->fm_hist_cur ^= 1;
     }
   }
@@ -1764,9 +1757,8 @@ kq_bank *kq_bank_create(const kq_bank_config *cfg) {
   g.dsamprate = (float)cfg->samprate / cfg->decimate;
 
   // N = 65536 with compute_n0 (cfg 5 as the reference runs it), or the full path asked for by name: the 16384-point
-  // register kernel in four sibling workgroups per channel-block (KQ_FULL_SPLIT=1 keeps the older split kernel, no n0)
-  static bool const split_only = getenv("KQ_FULL_SPLIT") && atoi(getenv("KQ_FULL_SPLIT")) != 0;
-  bool const can64k = kq::full64k_supported(g) && !split_only;
+  // register kernel in four sibling workgroups per channel-block
+  bool const can64k = kq::full64k_supported(g);
   bool const can_prune = kq::pruned_supported(g) && !cfg->compute_n0;
   if (cfg->fwd_mode == KQ_FWD_PRUNED) {
     if (!can_prune) {
@@ -2124,6 +2116,34 @@ static void pll_release(kq_bank *b, int c) {
   if (slot >= 0) b->pll_free.push_back(slot);
   slot = -1;
 }
+
+// what kq_bank_add_channel(s) and kq_bank_set_mode refuse in a channel configuration (`entry`: its index in a batch, or -1)
+static int check_channel_config(const kq_bank *b, const kq_channel_config &k, int entry = -1) {
+  char at[32] = "";
+  if (entry >= 0) snprintf(at, sizeof at, " (entry %d)", entry);
+  if (k.demod_type < KQ_LINEAR_DEMOD || k.demod_type > KQ_FM_DEMOD) {
+    set_err("unknown demod_type %d%s", k.demod_type, at);
+    return -1;
+  }
+  if (std::isnan(k.low) || std::isnan(k.high)) {  // filter.c:504-505
+    set_err("NaN filter edge%s", at);
+    return -1;
+  }
+  if (k.demod_type == KQ_FM_DEMOD && !kq::demod64_supported(b->g) && kq::demod_fm_lds_bytes(b->g) > 160 * 1024) {
+    // the FM kernels keep one block of samples / the N/D-point audio master in LDS (N/D <= 8192)
+    set_err("FM working set of %zu bytes exceeds the 160 KiB of LDS at this geometry", kq::demod_fm_lds_bytes(b->g));
+    return -1;
+  }
+  return 0;
+}
+
+// oscillator setter scalings: radio.c:299, radio.c:182, radio.c:309
+static void set_oscillators(const kq_bank *b, HostChan &h, const kq_channel_config &k) {
+  double const fs = b->g.samprate;
+  h.lo2.set(k.second_lo == 0 ? 0.0 : k.second_lo / fs, 0.0, b->n_abs);
+  h.dop.set(-k.doppler / fs, -k.doppler_rate / (fs * fs), b->n_abs);
+  h.shift.set(k.shift == 0 ? 0.0 : k.shift * b->g.D / fs, 0.0, b->out_abs);
+}
 }  // namespace
 
 int kq_bank_add_channel(kq_bank *b, const kq_channel_config *cfg) {
@@ -2143,28 +2163,12 @@ int kq_bank_add_channel(kq_bank *b, const kq_channel_config *cfg) {
     set_err("bank is full (%u channels)", b->cfg.max_channels);
     return -1;
   }
-  if (cfg->demod_type < KQ_LINEAR_DEMOD || cfg->demod_type > KQ_FM_DEMOD) {
-    set_err("unknown demod_type %d", cfg->demod_type);
-    return -1;
-  }
-  if (std::isnan(cfg->low) || std::isnan(cfg->high)) {  // filter.c:504-505
-    set_err("NaN filter edge");
-    return -1;
-  }
-  if (cfg->demod_type == KQ_FM_DEMOD && !kq::demod64_supported(b->g) && kq::demod_fm_lds_bytes(b->g) > 160 * 1024) {
-    // the FM kernels keep one block of samples / the N/D-point audio master in LDS (N/D <= 8192)
-    set_err("FM working set of %zu bytes exceeds the 160 KiB of LDS at this geometry", kq::demod_fm_lds_bytes(b->g));
-    return -1;
-  }
+  if (check_channel_config(b, *cfg)) return -1;
   if (is_pll(*cfg) && pll_admit(b, *cfg)) return -1;
   HostChan h;
   h.cfg = *cfg;
   h.out_type = (cfg->demod_type == KQ_LINEAR_DEMOD && cfg->isb) ? kq::FT_CROSS_CONJ : kq::FT_COMPLEX;
-  double const fs = b->g.samprate;
-  // oscillator setter scalings: radio.c:299, radio.c:182, radio.c:309
-  h.lo2.set(cfg->second_lo == 0 ? 0.0 : cfg->second_lo / fs, 0.0, b->n_abs);
-  h.dop.set(-cfg->doppler / fs, -cfg->doppler_rate / (fs * fs), b->n_abs);
-  h.shift.set(cfg->shift == 0 ? 0.0 : cfg->shift * b->g.D / fs, 0.0, b->out_abs);
+  set_oscillators(b, h, *cfg);
   bool const appended = c == (int)b->chans.size();
   if (appended)
     b->chans.push_back(h);
@@ -2228,24 +2232,10 @@ int kq_bank_add_channels(kq_bank *b, const kq_channel_config *cfgs, unsigned n, 
     set_err("bank is full (%u channels): %zu present, %u more asked for", b->cfg.max_channels, c0, n);
     return -1;
   }
-  for (unsigned i = 0; i < n; i++) {
-    kq_channel_config const &k = cfgs[i];
-    if (k.demod_type < KQ_LINEAR_DEMOD || k.demod_type > KQ_FM_DEMOD) {
-      set_err("unknown demod_type %d (entry %u)", k.demod_type, i);
-      return -1;
-    }
-    if (std::isnan(k.low) || std::isnan(k.high)) {  // filter.c:504-505
-      set_err("NaN filter edge (entry %u)", i);
-      return -1;
-    }
-    if (k.demod_type == KQ_FM_DEMOD && !kq::demod64_supported(g) && kq::demod_fm_lds_bytes(g) > 160 * 1024) {
-      set_err("FM working set of %zu bytes exceeds the 160 KiB of LDS at this geometry", kq::demod_fm_lds_bytes(g));
-      return -1;
-    }
-  }
+  for (unsigned i = 0; i < n; i++)
+    if (check_channel_config(b, cfgs[i], (int)i)) return -1;
   // responses: every distinct (out_type, edges, beta) once, one launch per out_type
   std::vector<HostChan> hs(n);
-  double const fs = g.samprate;
   struct Key {
     float lo, hi, beta;
     bool operator<(Key const &o) const { return lo != o.lo ? lo < o.lo : hi != o.hi ? hi < o.hi : beta < o.beta; }
@@ -2294,10 +2284,7 @@ int kq_bank_add_channels(kq_bank *b, const kq_channel_config *cfgs, unsigned n, 
     kq_channel_config const &k = cfgs[i];
     HostChan &h = hs[i];
     h.cfg = k;
-    // oscillator setter scalings: radio.c:299, radio.c:182, radio.c:309
-    h.lo2.set(k.second_lo == 0 ? 0.0 : k.second_lo / fs, 0.0, b->n_abs);
-    h.dop.set(-k.doppler / fs, -k.doppler_rate / (fs * fs), b->n_abs);
-    h.shift.set(k.shift == 0 ? 0.0 : k.shift * g.D / fs, 0.0, b->out_abs);
+    set_oscillators(b, h, k);
     if (k.demod_type == KQ_FM_DEMOD && !k.flat) {
       auto it = aresp_by_beta.find(k.kaiser_beta);
       if (it == aresp_by_beta.end()) {
@@ -2460,18 +2447,7 @@ int kq_bank_set_mode(kq_bank *b, int ch, const kq_channel_config *m) {
     set_err("bad channel or NULL mode");
     return -1;
   }
-  if (m->demod_type < KQ_LINEAR_DEMOD || m->demod_type > KQ_FM_DEMOD) {
-    set_err("unknown demod_type %d", m->demod_type);
-    return -1;
-  }
-  if (std::isnan(m->low) || std::isnan(m->high)) {
-    set_err("NaN filter edge");
-    return -1;
-  }
-  if (m->demod_type == KQ_FM_DEMOD && !kq::demod64_supported(b->g) && kq::demod_fm_lds_bytes(b->g) > 160 * 1024) {
-    set_err("FM working set exceeds the LDS at this geometry");
-    return -1;
-  }
+  if (check_channel_config(b, *m)) return -1;
   // pthread_join of the old demodulator thread (radio.c:335-337): the new state is written on the main stream behind the
   // last call's demodulators (upload_channel); only carrier-loop slots, moved by synchronous copies, need the device idle
   HostChan &h = b->chans[ch];

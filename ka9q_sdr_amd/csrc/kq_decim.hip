@@ -65,14 +65,9 @@ struct GroupArgs {
 // 5.4 TB/s.  The later groups read what the group before them has just written (an eighth of the size, normally still in
 // the Infinity Cache) with plain loads: nontemporal there was 2 % slower on the whole call.
 typedef float vf4 __attribute__((ext_vector_type(4)));
-typedef float vf2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float4 load_once(const float4 *p) {
   vf4 const w = __builtin_nontemporal_load(reinterpret_cast<const vf4 *>(p));
   return make_float4(w.x, w.y, w.z, w.w);
-}
-__device__ __forceinline__ float2 load_once(const float2 *p) {
-  vf2 const w = __builtin_nontemporal_load(reinterpret_cast<const vf2 *>(p));
-  return make_float2(w.x, w.y);
 }
 
 __device__ __forceinline__ float2 rot90(float2 v, int phase) {
@@ -452,7 +447,6 @@ struct kq_decimator {
   unsigned epoch = 0;
   size_t n_partial = 0;
   unsigned num_cus = 256;
-  int max_fuse = kMaxFuse;
 };
 
 void kq_internal_set_error(const char *fmt, ...);
@@ -486,7 +480,7 @@ static int decim_alloc(kq_decimator *d) {
   while (done < S) {
     d->groups.emplace_back();  // in the list before it owns anything, so that a failure below still frees it
     Group &g = d->groups.back();
-    g.nstages = std::min(d->max_fuse, S - done);
+    g.nstages = std::min(kMaxFuse, S - done);
     g.shift_in = S - done;
     for (int s = 0; s < g.nstages; s++) {
       int const j = S - 1 - (done + s);
@@ -535,7 +529,6 @@ kq_decimator *kq_decim_create(const kq_decim_config *cfg) {
   d->coeffs[2] = -116. / 802;
   d->coeffs[1] = 33. / 802;
   d->coeffs[0] = -6. / 802;
-  if (const char *e = getenv("KQ_DECIM_FUSE")) d->max_fuse = std::max(1, std::min(kMaxFuse, atoi(e)));  // diagnostic
   if (decim_alloc(d) != 0) {
     kq_decim_destroy(d);
     return nullptr;

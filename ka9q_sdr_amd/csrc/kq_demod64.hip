@@ -790,8 +790,10 @@ __device__ void agc_channel(const Geom &g, const ChanDev &ch, const Planes &pl, 
 // The same for any block length (the generic geometries: N/D = 128 ... 16384, mixed radix included): one wave per
 // channel, a block in groups of 64 samples (the last one may be short), gain / hang counter / carrier estimate carried
 // from group to group in wave-uniform registers.  Where the 64-sample form keeps a block's end state per half, a block
-// here ends with a group, so the state after the group is the block's.  k_demod_am / k_demod_linear (one LANE per
-// channel, kq_kernels.hip) did this work before round 6: 1024 channels were 16 waves on a device with 1024 SIMDs.
+// here ends with a group, so the state after the group is the block's.  Kernels with one LANE per channel did this work
+// before round 6: 1024 channels were 16 waves on a device with 1024 SIMDs (and their in-sequence power sums missed the
+// 2e-6 float64 bar of tests/test_gpu_parity.py's keyed-signal case at 600 samples per block, which the per-lane partial
+// sums here meet).
 // FULL: the group has 64 samples and the serial loops unroll; the short last group of a block runs them as loops.
 
 // carrier tracking (am.c:62), serial; lane i keeps the value after sample i
@@ -997,26 +999,18 @@ __global__ void __launch_bounds__(THREADS) k_demod64(Geom g, ChanDev ch, Planes 
 
 // Register-resident demodulators exist for olen = 32 (all three types) and olen = 64 (AM / linear)
 bool demod64_supported(const Geom &g) { return g.Ndec == 64 && g.olen == 32 && g.Mdec == 33; }
-// wave-per-channel AM / linear: every block length (KQ_AGC_WAVE=0: the one-lane-per-channel kernels for the lengths other
-// than 32 and 64 -- an A/B switch for tools/bench_mixed.py only: their in-sequence power sums miss the 2e-6 float64 bar of
-// tests/test_gpu_parity.py's keyed-signal case at 600 samples per block, which the per-lane partial sums here meet)
-bool demod_agc_wave_supported(const Geom &g) {
-  static bool const off = getenv("KQ_AGC_WAVE") && atoi(getenv("KQ_AGC_WAVE")) == 0;
-  return g.olen == 64 || g.olen == 32 || !off;
-}
 
+// olen = 32: all three types; any other length: AM / linear, one wave per channel (FM on launch_demod_fm)
 void launch_demod64(hipStream_t s, const Geom &g, const ChanDev &ch, const Planes &pl, const int *list_fm, int n_fm,
                     const int *list_am, int n_am, const int *list_lin, int n_lin, int nblocks, int compute_n0) {
   if (g.olen == 32) {
     int const wgs = n_fm + n_am + n_lin;
     if (wgs == 0) return;
-    // KQ_DEMOD_ONE_WAVE=1 / 0: the one-wave forms of the FM and AM demodulators always / never (A/B switch).  Otherwise by
-    // the number of channels: the multi-wave pipelines exist to fill a device that has one wave per SIMD to run (1024
-    // channels); with more than two waves' worth of channels per SIMD the one-wave forms do the same work in fewer
-    // instructions, without the LDS hand-overs and the pipeline's fill and drain (rocprofv3, 32768 channels x 2 blocks:
-    // 82 us against 157; 8192 x 8: 46 against 61; 1024 x 64: 79 against 47)
-    static int const forced = getenv("KQ_DEMOD_ONE_WAVE") ? atoi(getenv("KQ_DEMOD_ONE_WAVE")) : -1;
-    bool const one_wave = forced >= 0 ? forced != 0 : wgs > 2048;
+    // The one-wave forms of the FM and AM demodulators by the number of channels: the multi-wave pipelines exist to fill a
+    // device that has one wave per SIMD to run (1024 channels); with more than two waves' worth of channels per SIMD the
+    // one-wave forms do the same work in fewer instructions, without the LDS hand-overs and the pipeline's fill and drain
+    // (rocprofv3, 32768 channels x 2 blocks: 82 us against 157; 8192 x 8: 46 against 61; 1024 x 64: 79 against 47)
+    bool const one_wave = wgs > 2048;
     if (n_fm + n_am > 0 && !one_wave)
       hipLaunchKernelGGL((k_demod64<32, 256>), dim3(wgs), dim3(256), 0, s, g, ch, pl, list_fm, n_fm, list_am, n_am, list_lin,
                          n_lin, nblocks, compute_n0);
@@ -1027,7 +1021,7 @@ void launch_demod64(hipStream_t s, const Geom &g, const ChanDev &ch, const Plane
     int const wgs = n_am + n_lin;
     if (wgs == 0) return;
     hipLaunchKernelGGL(k_demod_agc_any, dim3(wgs), dim3(64), 0, s, g, ch, pl, list_am, n_am, list_lin, n_lin, nblocks, compute_n0);
-  } else {  // olen = 64: AM / linear only; FM stays on the generic kernel (launch_demods)
+  } else {  // olen = 64: AM / linear only; FM stays on the generic kernel (launch_demod_fm)
     int const wgs = n_am + n_lin;
     if (wgs == 0) return;
     hipLaunchKernelGGL((k_demod64<64, 64>), dim3(wgs), dim3(64), 0, s, g, ch, pl, list_fm, 0, list_am, n_am, list_lin, n_lin,

@@ -5,7 +5,7 @@
 //   k_filter_full       per (channel, block): NCO mix -> N-point FFT in LDS -> [compute_n0] ->
 //                       response multiply / CROSS_CONJ -> N/D-point IFFT -> last olen samples
 //                       (radio.c:132-139, filter.c:151, radio.c:383-425, filter.c:206-250)
-//   k_demod_fm/am/lin   demodulators with state carried across calls in HBM (fm.c, am.c, linear.c)
+//   k_demod_fm          FM demodulator with state carried across calls in HBM (fm.c; AM / linear: kq_demod64.hip)
 //
 // The pruned forward path lives in kq_pruned.hip.
 #include <algorithm>
@@ -252,9 +252,7 @@ void launch_copy_to_host(hipStream_t s, const float *audio, float *haudio, int r
   // 1.59 ms per step with 32 workgroups, 1.48 with 4-8, 1.64 with 2, which no longer finish inside the step).  One per
   // 2 MiB is 26 GB/s at cfg 4.
   size_t const bytes = rows * ((haudio ? (size_t)row * sizeof(float) : 0) + (hstatus ? sizeof(kq_chan_status) : 0));
-  unsigned wgs = (unsigned)std::min<size_t>(64, std::max<size_t>(4, (bytes + (2u << 20) - 1) >> 21));
-  static int const forced = getenv("KQ_COPY_WGS") ? atoi(getenv("KQ_COPY_WGS")) : 0;  // diagnostic (tools/ab_env_hostio.sh)
-  if (forced > 0) wgs = (unsigned)forced;
+  unsigned const wgs = (unsigned)std::min<size_t>(64, std::max<size_t>(4, (bytes + (2u << 20) - 1) >> 21));
   hipLaunchKernelGGL(k_copy_to_host, dim3(wgs), dim3(256), 0, s, audio, haudio, row, status, (u32x4 *)hstatus, rows,
                      rows * sizeof(kq_chan_status) / 16);
 }
@@ -346,9 +344,7 @@ void launch_copy_pcm_to_host(hipStream_t s, const float *audio, short *hpcm, uns
                              const kq_chan_status *status, void *hstatus, size_t rows, const int *mode_compact, int max_blocks) {
   size_t const sbytes = hstatus ? (mode_compact ? sizeof(kq_chan_status_compact) : sizeof(kq_chan_status)) : 0;
   size_t const bytes = rows * ((size_t)row * sizeof(short) + 4 + sbytes);
-  unsigned wgs = (unsigned)std::min<size_t>(64, std::max<size_t>(4, (bytes + (2u << 20) - 1) >> 21));
-  static int const forced = getenv("KQ_COPY_WGS") ? atoi(getenv("KQ_COPY_WGS")) : 0;
-  if (forced > 0) wgs = (unsigned)forced;
+  unsigned const wgs = (unsigned)std::min<size_t>(64, std::max<size_t>(4, (bytes + (2u << 20) - 1) >> 21));
   if (mode_compact)
     hipLaunchKernelGGL(k_copy_pcm_to_host<true>, dim3(wgs), dim3(256), 0, s, audio, hpcm, hmask, row, status, (u32x4 *)hstatus, rows,
                        rows * sizeof(kq_chan_status) / 16, mode_compact, max_blocks);
@@ -468,13 +464,12 @@ void launch_filter_full(hipStream_t s, const Geom &g, const ChanDev &ch, const P
                         const int *chan_list) {
   size_t const lds_bytes = (size_t)g.N * sizeof(float2) * (g.Ndec == g.N ? 2 : 1);
   ensure_dynamic_lds((const void *)k_filter_full, lds_bytes);
-  static int const forced = getenv("KQ_FULL_THREADS") ? atoi(getenv("KQ_FULL_THREADS")) : 0;  // A/B switch (tools/bench_mixed.py)
   // By how many workgroups a CU's 160 KiB of LDS hold: 256 threads where there are four or more of them, 512 where two or
-  // three, 1024 where one workgroup has the CU to itself (tools/bench_mixed.py and a sweep over N with KQ_FULL_THREADS, filter
-  // kernel ms for 1024 channels x 8 blocks at 1024 / 512 / 256 threads: N = 2048 0.33 / 0.16 / 0.13, 4096 0.53 / 0.29 / 0.28,
+  // three, 1024 where one workgroup has the CU to itself (tools/bench_mixed.py and a sweep over N, filter kernel ms for
+  // 1024 channels x 8 blocks at 1024 / 512 / 256 threads: N = 2048 0.33 / 0.16 / 0.13, 4096 0.53 / 0.29 / 0.28,
   // 6144 0.94 / 0.51 / 0.66, 8192 0.90 / 0.64 / 0.74, 9600 1.20 / 0.87 / 1.32, 10240 1.37 / 1.64 / 2.61, 15360 1.74 / 2.10 / 3.44;
   // until round 6 it was 1024 from N = 4096 on)
-  int const threads = forced > 0 ? forced : lds_bytes <= 40 * 1024 ? 256 : 2 * lds_bytes + 512 <= 160 * 1024 ? 512 : 1024;
+  int const threads = lds_bytes <= 40 * 1024 ? 256 : 2 * lds_bytes + 512 <= 160 * 1024 ? 512 : 1024;
   hipLaunchKernelGGL(k_filter_full, dim3(nchan, nblocks), dim3(threads), lds_bytes, s, g, ch, pl, window, tw, compute_n0,
                      spec_dump, spec_ch, chan_list);
 }
@@ -880,7 +875,7 @@ __global__ void __launch_bounds__(256) k_fm_audio(Geom g, ChanDev ch, Planes pl,
                                                  float *__restrict__ hist_out, const int *__restrict__ list, int nblocks) {
   extern __shared__ __attribute__((aligned(16))) float2 lds[];
   int const c = list[blockIdx.x], b = blockIdx.y;
-  int const lane = threadIdx.x, nthr = blockDim.x;  // 64 ... 256 threads (launch_demods): every loop strides by the workgroup
+  int const lane = threadIdx.x, nthr = blockDim.x;  // 64 ... 256 threads (launch_demod_fm): every loop strides by the workgroup
   int const AN = g.Ndec, AM = g.Mdec, AL = g.olen;
   float2 *F = lds;
   float *AIN = reinterpret_cast<float *>(F + AN);
@@ -984,8 +979,9 @@ __global__ void __launch_bounds__(256) k_fm_audio(Geom g, ChanDev ch, Planes pl,
   for (int n = lane; n < AL; n += nthr) aud[n] = F[AN - AL + n].x * gain;  // fm.c:169-170
 }
 
-// The same de-emphasis overlap-save for AN = 256 (AL = 128, AM = 129: BASELINE cfg 2's geometry) with the PL measurement off:
-// one wave per PAIR of blocks, registers and lane exchanges only (k_demod64's scheme for 64 points, four values per lane).
+// The same de-emphasis overlap-save for AN = 256 (AL = 128, AM = 129: BASELINE cfg 2's geometry) with the PL measurement on
+// (PL_N = 8, PL_L = 4; without it k_demod_fm256 does the whole demodulator): one wave per PAIR of blocks, registers and lane
+// exchanges only (k_demod64's scheme for 64 points, four values per lane).
 // The two real windows [b-1 | b] and [b | b+1] are the real and imaginary part of ONE complex 256-point sequence z; both are
 // filtered by the same response, so Y0 + i Y1 = HAf . (W0 + i W1) = HAf . Z with HAf the response's Hermitian extension
 // (real at DC and Nyquist, whose imaginary parts the c2r transform ignores, filter.c:250) -- no separation of the two
@@ -1011,16 +1007,14 @@ __global__ void __launch_bounds__(64) k_fm_audio256(Geom g, ChanDev ch, Planes p
   }
   float *aud0 = pl.audio + ((size_t)c * g.max_blocks + b0) * (2 * (size_t)AL);
   float *aud1 = aud0 + 2 * AL;
-  bool const pl_on = g.pl_n == 8 && pl.plout != nullptr;  // the PL slave (fm.c:201-234) reads bins 0..4 of the same transform
   bool const flat = (ch.flags[c] & FLAG_FLAT) != 0;
-  if (flat) {  // fm.c:164-172: no filter, no gain
+  if (flat) {  // fm.c:164-172: no filter, no gain (the PL slave below still runs)
     aud0[lane] = c0;
     aud0[lane + 64] = c1;
     if (have1) {
       aud1[lane] = n0;
       aud1[lane + 64] = n1;
     }
-    if (!pl_on) return;
   }
   // response on this lane's four bins k = 4 bitrev6(lane) + r, Hermitian-extended
   const float2 *HA = ch.aresp + (size_t)c * (AN / 2 + 1);
@@ -1089,7 +1083,7 @@ __global__ void __launch_bounds__(64) k_fm_audio256(Geom g, ChanDev ch, Planes p
     }
     u[r] = r ? cmul(z, cconj(w4[r - 1])) : z;
   }
-  if (pl_on) {
+  {
     // PL slave of both blocks (fm.c:219,234: REAL -> REAL, decimate 32, 8 points, the last 4 kept): it needs bins 0..4 of each
     // window's own transform, W0[k] = (X[k] + conj X[256 - k]) / 2 and W1[k] = (X[k] - conj X[256 - k]) / 2i -- nine values
     // of the packed transform, held by lanes 0 (bins 0..3), 32 (bin 4) and 63 (bins 252..255).  Lane j < 8 forms output
@@ -1132,12 +1126,12 @@ __global__ void __launch_bounds__(64) k_fm_audio256(Geom g, ChanDev ch, Planes p
 
 // The whole FM demodulator of one channel in ONE launch for N/D = 256 (cfg 2's geometry: 128 samples per block, de-emphasis
 // filter of 129 taps) without the PL measurement: k_demod_fm's four phases and k_fm_audio256's overlap-save on the same
-// 16-wave workgroup, the call's blocks held in LDS from the first load to the audio store.  What the two-kernel form pays
+// 8-wave workgroup, the call's blocks held in LDS from the first load to the audio store.  What the two-kernel form pays
 // and this does not: the second launch, the detected samples' round trip through memory (8 MB per call at cfg 2), and one
 // exposed memory latency per block and phase -- a wave asks for all its blocks' samples at once here, and phase C finds
 // them in LDS.  Per-block expressions and reduction orders are those of k_demod_fm / k_fm_audio256 (and so of the
 // sequential loop of fm.c:91-171): the results are theirs bit for bit.
-// Static LDS: S[64][128] float2 (64 KiB) | FO[65][128] float (row 0 = the block before the chunk) | Y[16][128] float.
+// Static LDS: S[64][128] float2 (64 KiB) | FO[65][128] float (row 0 = the block before the chunk) | Y[8][128] float.
 namespace {
 struct Audio256 {  // k_fm_audio256's transform pair, set up once per wave
   // wf / wi: the lane-exchange stages' twiddles as the lane applies them -- the stage's twiddle in the upper lane of a
@@ -1218,13 +1212,13 @@ struct Audio256 {  // k_fm_audio256's transform pair, set up once per wave
 };
 }  // namespace
 
-// W waves per channel: 8 (two per SIMD, 173 registers) or 16 (four per SIMD: the 128 registers that leaves spill 19 since the
-// exchange stages of round 6 -- 112 before, when 16 was first tried and dropped); KQ_FM256_WAVES picks, see launch_demods
-template <int W>
-__global__ void __launch_bounds__(64 * W) k_demod_fm256(Geom g, ChanDev ch, Planes pl, const float *__restrict__ hist_in,
-                                                         float *__restrict__ hist_out, const int *__restrict__ list, int nblocks,
-                                                         int compute_n0) {
-  constexpr int olen = 128;
+// 8 waves per channel, two per SIMD (173 registers).  16 -- four per SIMD -- leave 128 registers, which spill 19 since the
+// exchange stages of round 6, and measured no faster (three alternating rounds on one box: 35.3 / 35.2 / 35.7 us against
+// 35.3 / 35.6 / 35.4 -- the launch is bound by its vector instruction count, 55 000 issue cycles per SIMD either way)
+__global__ void __launch_bounds__(512) k_demod_fm256(Geom g, ChanDev ch, Planes pl, const float *__restrict__ hist_in,
+                                                     float *__restrict__ hist_out, const int *__restrict__ list, int nblocks,
+                                                     int compute_n0) {
+  constexpr int olen = 128, W = 8;
   __shared__ __attribute__((aligned(16))) float2 S[64 * olen];
   __shared__ __attribute__((aligned(16))) float FO[65 * olen];
   __shared__ float Yall[W * olen];
@@ -1509,120 +1503,6 @@ __global__ void __launch_bounds__(64 * W) k_demod_fm256(Geom g, ChanDev ch, Plan
   }
 }
 
-// AM: envelope, carrier removal, hang AGC -- a strictly sequential recurrence per channel
-// (am.c:55-75), so one lane per channel and channels across lanes.
-__global__ void k_demod_am(Geom g, ChanDev ch, Planes pl, const int *__restrict__ list, int nchan, int nblocks,
-                           int compute_n0) {
-  int const t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= nchan) return;
-  int const c = list[t];
-  int const olen = g.olen;
-  float const headroom = ch.headroom[c], recovery = ch.recovery[c];
-  int const hangmax = ch.hangmax[c];
-  float gain = ch.gain[c], dc = ch.dc[c];
-  int hang = ch.hang[c];
-  for (int b = 0; b < nblocks; b++) {
-    const float2 *in = pl.filt + ((size_t)c * g.max_blocks + b) * olen;
-    float *aud = pl.audio + ((size_t)c * g.max_blocks + b) * (2 * (size_t)olen);
-    float signal = 0;
-    for (int n = 0; n < olen; n++) {
-      float const sq = cnrm(in[n]);
-      signal += sq;
-      float const samp = sqrtf(sq);
-      dc += 0.0001f * (samp - dc);  // am.c:34,62
-      if (isnan(gain)) {
-        gain = headroom / dc;
-      } else if (gain * dc > headroom) {
-        gain = headroom / dc;
-        hang = hangmax;
-      } else if (hang != 0) {
-        hang--;
-      } else {
-        gain *= recovery;
-      }
-      aud[n] = (samp - dc) * gain;
-    }
-    kq_chan_status st;
-    status_common(st, g, ch, pl, c, b, compute_n0, .001);
-    st.bb_power = signal / (2 * olen);  // am.c:78
-    st.snr = 0;
-    st.foffset = 0;
-    st.pdeviation = 0;
-    st.agc_gain = gain;
-    st.squelch_count = 0;
-    st.hangcount = hang;
-    st.blanked = 0;
-    st.nout = olen;
-    pl.status[(size_t)c * g.max_blocks + b] = st;
-  }
-  ch.gain[c] = gain;
-  ch.dc[c] = dc;
-  ch.hang[c] = hang;
-}
-
-// Linear (SSB/CW/IQ/ISB without carrier PLL): hang AGC on |s|, optional shift NCO, mono = Re or
-// stereo = I/Q (linear.c:251-300).
-__global__ void k_demod_linear(Geom g, ChanDev ch, Planes pl, const int *__restrict__ list, int nchan, int nblocks,
-                               int compute_n0) {
-  int const t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= nchan) return;
-  int const c = list[t];
-  int const olen = g.olen;
-  float const headroom = ch.headroom[c], recovery = ch.recovery[c];
-  int const hangmax = ch.hangmax[c];
-  bool const stereo = (ch.flags[c] & FLAG_STEREO) != 0;
-  double const sh_ph = ch.sh_phase[c], sh_f = ch.sh_freq[c];
-  float gain = ch.gain[c];
-  int hang = ch.hang[c];
-  for (int b = 0; b < nblocks; b++) {
-    const float2 *in = pl.filt + ((size_t)c * g.max_blocks + b) * olen;
-    float *aud = pl.audio + ((size_t)c * g.max_blocks + b) * (2 * (size_t)olen);
-    float signal = 0, noise = 0;
-    for (int n = 0; n < olen; n++) {
-      float2 s = in[n];
-      float const rp = s.x * s.x, ip = s.y * s.y;
-      signal += rp;
-      noise += ip;
-      float const amplitude = sqrtf(rp + ip);
-      if (isnan(gain)) {
-        gain = headroom / amplitude;
-      } else if (amplitude * gain > headroom) {
-        gain = headroom / amplitude;
-        hang = hangmax;
-      } else if (hang != 0) {
-        hang--;
-      } else {
-        gain *= recovery;
-      }
-      s = make_float2(s.x * gain, s.y * gain);
-      if (sh_f != 0.0) {  // linear.c:283-289
-        double const j = (double)b * olen + n;
-        s = cmul(s, phasor_turns(sh_ph + sh_f * j));
-      }
-      if (stereo) {
-        aud[2 * n] = s.x;
-        aud[2 * n + 1] = s.y;
-      } else {
-        aud[n] = s.x;
-      }
-    }
-    kq_chan_status st;
-    status_common(st, g, ch, pl, c, b, compute_n0, .001);
-    st.bb_power = (signal + noise) / (2 * olen);  // linear.c:302
-    st.snr = NAN;                                 // linear.c:309
-    st.foffset = 0;
-    st.pdeviation = 0;
-    st.agc_gain = gain;
-    st.squelch_count = 0;
-    st.hangcount = hang;
-    st.blanked = 0;
-    st.nout = stereo ? 2 * olen : olen;
-    pl.status[(size_t)c * g.max_blocks + b] = st;
-  }
-  ch.gain[c] = gain;
-  ch.hang[c] = hang;
-}
-
 // PL tone tracker (fm.c:236-277): per FM channel, blocks in sequence: append the PL filter output to the
 // 16384-sample ring; after every >= 512 new samples transform the ring (in storage order, as the reference
 // does) and pick the peak bin.  One workgroup per channel; the ring transform runs in LDS (128 KiB).
@@ -1731,46 +1611,26 @@ static size_t fm_audio_lds_bytes(const Geom &g) {
 }
 size_t demod_fm_lds_bytes(const Geom &g) { return std::max(fm_disc_lds_bytes(g), fm_audio_lds_bytes(g)); }
 
-void launch_demods(hipStream_t s, const Geom &g, const ChanDev &ch, const Planes &pl, const float2 *tw, const int *list_fm,
-                   int n_fm, const int *list_am, int n_am, const int *list_lin, int n_lin, int nblocks, int compute_n0,
-                   float *fmout, const float *fm_hist_in, float *fm_hist_out) {
-  // cfg 2's geometry without the PL measurement: one fused launch (KQ_FM_FUSED=0: the two-kernel form, A/B switch)
-  static bool const fused_off = getenv("KQ_FM_FUSED") && atoi(getenv("KQ_FM_FUSED")) == 0;
-  bool const fused = g.Ndec == 256 && g.olen == 128 && g.Mdec == 129 && g.pl_n == 0 && !fused_off;
-  if (n_fm > 0 && fused) {
-    // (8 against 16 waves per channel, tools/ab_fm256.sh, three alternating rounds on one box: 35.3 / 35.2 / 35.7 us against
-    //  35.3 / 35.6 / 35.4 -- the launch is bound by its vector instruction count, 55 000 issue cycles per SIMD either way)
-    static int const waves = getenv("KQ_FM256_WAVES") ? atoi(getenv("KQ_FM256_WAVES")) : 8;
-    if (waves != 16)
-      hipLaunchKernelGGL(k_demod_fm256<8>, dim3(n_fm), dim3(512), 0, s, g, ch, pl, fm_hist_in, fm_hist_out, list_fm, nblocks,
-                         compute_n0);
-    else
-      hipLaunchKernelGGL(k_demod_fm256<16>, dim3(n_fm), dim3(1024), 0, s, g, ch, pl, fm_hist_in, fm_hist_out, list_fm, nblocks,
-                         compute_n0);
-  } else if (n_fm > 0) {
-    int const waves = fm_disc_waves(g, nblocks);
-    size_t const lds_a = fm_disc_lds_bytes(g, waves), lds_b = fm_audio_lds_bytes(g);
-    ensure_dynamic_lds((const void *)k_demod_fm, lds_a);
-    ensure_dynamic_lds((const void *)k_fm_audio, lds_b);
-    hipLaunchKernelGGL(k_demod_fm, dim3(n_fm), dim3(64 * waves), lds_a, s, g, ch, pl, fmout, list_fm, nblocks, compute_n0);
-    if (g.Ndec == 256 && g.olen == 128 && g.Mdec == 129 && (g.pl_n == 0 || (g.pl_n == 8 && g.pl_l == 4)))  // cfg 2's geometry: registers only
-      hipLaunchKernelGGL(k_fm_audio256, dim3(n_fm, (nblocks + 1) / 2), dim3(64), 0, s, g, ch, pl, fmout, fm_hist_in, fm_hist_out,
-                         list_fm, nblocks);
-    else
-    {
-      // one wave per block up to a 512-point audio master; four from there on (the transform's passes are loops over the
-      // workgroup with a barrier each: tools/bench_mixed.py, KQ_FM_AUDIO_THREADS)
-      static int const forced = getenv("KQ_FM_AUDIO_THREADS") ? atoi(getenv("KQ_FM_AUDIO_THREADS")) : 0;
-      int const thr = forced > 0 ? forced : g.Ndec >= 1024 ? 256 : 64;
-      hipLaunchKernelGGL(k_fm_audio, dim3(n_fm, nblocks), dim3(thr), lds_b, s, g, ch, pl, tw, fmout, fm_hist_in, fm_hist_out,
-                         list_fm, nblocks);
-    }
+void launch_demod_fm(hipStream_t s, const Geom &g, const ChanDev &ch, const Planes &pl, const float2 *tw, const int *list_fm,
+                     int n_fm, int nblocks, int compute_n0, float *fmout, const float *fm_hist_in, float *fm_hist_out) {
+  if (n_fm <= 0) return;
+  bool const cfg2 = g.Ndec == 256 && g.olen == 128 && g.Mdec == 129;  // cfg 2's geometry
+  if (cfg2 && g.pl_n == 0) {  // without the PL measurement: one fused launch
+    hipLaunchKernelGGL(k_demod_fm256, dim3(n_fm), dim3(512), 0, s, g, ch, pl, fm_hist_in, fm_hist_out, list_fm, nblocks, compute_n0);
+    return;
   }
-  if (n_am > 0)
-    hipLaunchKernelGGL(k_demod_am, dim3((n_am + 63) / 64), dim3(64), 0, s, g, ch, pl, list_am, n_am, nblocks, compute_n0);
-  if (n_lin > 0)
-    hipLaunchKernelGGL(k_demod_linear, dim3((n_lin + 63) / 64), dim3(64), 0, s, g, ch, pl, list_lin, n_lin, nblocks,
-                       compute_n0);
+  int const waves = fm_disc_waves(g, nblocks);
+  size_t const lds_a = fm_disc_lds_bytes(g, waves), lds_b = fm_audio_lds_bytes(g);
+  ensure_dynamic_lds((const void *)k_demod_fm, lds_a);
+  ensure_dynamic_lds((const void *)k_fm_audio, lds_b);
+  hipLaunchKernelGGL(k_demod_fm, dim3(n_fm), dim3(64 * waves), lds_a, s, g, ch, pl, fmout, list_fm, nblocks, compute_n0);
+  if (cfg2 && g.pl_n == 8 && g.pl_l == 4)  // with the PL measurement: the audio filter and the PL slave in registers
+    hipLaunchKernelGGL(k_fm_audio256, dim3(n_fm, (nblocks + 1) / 2), dim3(64), 0, s, g, ch, pl, fmout, fm_hist_in, fm_hist_out,
+                       list_fm, nblocks);
+  else  // one wave per block up to a 512-point audio master; four from there on (the transform's passes are loops over the
+        // workgroup with a barrier each: tools/bench_mixed.py)
+    hipLaunchKernelGGL(k_fm_audio, dim3(n_fm, nblocks), dim3(g.Ndec >= 1024 ? 256 : 64), lds_b, s, g, ch, pl, tw, fmout, fm_hist_in,
+                       fm_hist_out, list_fm, nblocks);
 }
 
 // ---------------------------------------------------------------- PCM output stage

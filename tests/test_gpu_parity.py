@@ -735,8 +735,9 @@ def test_every_form_of_the_agc_recurrence_on_a_keyed_signal(gpu, N, L, M, D, fs)
 
 @pytest.mark.parametrize("seed,per_call", [(5, 4), (6, 5), (7, 11), (8, 1)])
 def test_cfg2_geometry_without_the_pl_measurement(gpu, seed, per_call):
-    """cfg 2 as SURVEY 8d measures it (pltask off): the de-emphasis overlap-save then runs in k_fm_audio256 -- one wave per
-    pair of blocks, both real windows through one 256-point lane-exchange transform pair -- instead of the LDS kernel.
+    """cfg 2 as SURVEY 8d measures it (pltask off): the whole FM demodulator then runs in k_demod_fm256, one launch with the
+    call's blocks in LDS, its de-emphasis overlap-save one wave per pair of blocks, both real windows through one 256-point
+    lane-exchange transform pair -- instead of k_demod_fm and the LDS audio kernel.
     Eleven blocks (an odd count: the last wave has one block only) in calls of 4, 5, 11 and 1, so that the history hand-over
     between calls is met at even and odd block counts; FM with and without de-emphasis among randomised plans."""
     g = wl.GEOMETRY["cfg2"]
