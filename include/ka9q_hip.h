@@ -521,8 +521,9 @@ int kq_decim_reset(kq_decimator *d);
 typedef struct kq_afsk_bank kq_afsk_bank;
 enum kq_pcm_format {
   KQ_PCM_F32 = 0,   /* float samples, what packet.c:207 stores into input.r[] */
-  KQ_PCM_S16BE = 1  /* 16-bit big-endian PCM words as they arrive in the RTP payload, converted as packet.c:207 does:
+  KQ_PCM_S16BE = 1, /* 16-bit big-endian PCM words as they arrive in the RTP payload, converted as packet.c:207 does:
                        ntohs() is unsigned, so a negative word w becomes (w + 65536) / 32768 (quirk kept) */
+  KQ_PCM_S16 = 2    /* int16 in host byte order scaled by 1/SHRT_MAX (modulate.c:24,136-141); kq_mod_process only */
 };
 typedef struct kq_afsk_config {
   int device;
@@ -553,6 +554,68 @@ int kq_afsk_clear_frames(kq_afsk_bank *bank);
 /* filter.out->output.c of the last decoded block (1000 complex) and the decoder state, for parity checks */
 int kq_afsk_pull_filter_output(kq_afsk_bank *bank, unsigned session, float *dst_re_im, size_t cap_complex);
 int kq_afsk_pull_state(kq_afsk_bank *bank, unsigned session, kq_afsk_state *out);
+
+/* --- modulator bank: many stations summed into one wideband I/Q stream ---------------------------------------------
+ * modulate.c for thousands of stations at once.  Each station is one modulate.c instance with the zero-stuffing factor 4
+ * generalised to `interp`: per block of L output samples it takes L / interp audio samples, zero-stuffs them into the REAL
+ * input of an overlap-save filter (modulate.c:136-145) whose response is gain interp / N between `low` and `high`
+ * (modulate.c:113-128, f evaluated in float) shaped by window_filter(L, M, response, kaiser_beta) (modulate.c:130), takes the
+ * COMPLEX output at decimate 1 (modulate.c:131-132, filter.c:206-216), adds `carrier` (modulate.c:149-153) and multiplies by
+ * step_osc(&osc) * amplitude (modulate.c:155-157).  The bank outputs the sum of its active stations, added in slot order
+ * in a fixed tree (same calls, same bits; one block per call or max_blocks per call, same bits).
+ * KQ_MOD_FM goes beyond the reference: m[n] = real part of the filter output, theta[n] = theta[n-1] + 2 pi deviation / Fs
+ * m[n] (carried across blocks in double, wrapped at block boundaries, 0 when a station is added or turns to FM), baseband
+ * exp(i theta[n]); `carrier` is ignored.
+ * Deviation from the reference: int16 output is trunc(x * 32767) as modulate.c:160-163 but saturates outside the int16
+ * range, where the reference's float-to-short conversion is undefined.
+ * Limits: N = L + M - 1 even and 2^a 3^b 5^c 7^d up to 16384; interp >= 1 dividing L and M - 1; up to 65536 stations.
+ * Stations with equal (low, high, kaiser_beta) share one designed response. */
+typedef struct kq_mod_bank kq_mod_bank;
+enum kq_mod_type {
+  KQ_MOD_LINEAR = 0,  /* modulate.c:70-94: AM / USB / LSB / AME by the edges and the carrier */
+  KQ_MOD_FM = 1       /* frequency modulation of the filtered audio (not in the reference) */
+};
+typedef struct kq_mod_config {
+  int device;
+  int samprate;             /* modulate.c:26 Samprate: output rate Fs; the audio rate is Fs / interp */
+  unsigned L, M;            /* modulate.c:111-112: new samples per block, impulse length (N = L + M - 1, modulate.c:113) */
+  unsigned interp;          /* modulate.c:136-145: zero-stuffing factor (4 there) */
+  unsigned max_stations;    /* slots 0 .. max_stations - 1 */
+  unsigned max_blocks;      /* largest nblocks of one kq_mod_process call */
+  void *stream;             /* hipStream_t to run on, NULL = private stream */
+} kq_mod_config;
+typedef struct kq_station_config {
+  int mod_type;             /* enum kq_mod_type */
+  float low, high;          /* modulate.c:70-94: passband edges in Hz (AM -5000..5000, USB 0..3000, LSB -3000..0, AME 0..3000) */
+  float carrier;            /* modulate.c:72,86: added to every filter output sample (0 or 1; linear only) */
+  float kaiser_beta;        /* modulate.c:130: window_filter's beta, 3.0 there */
+  float deviation;          /* FM peak deviation in Hz per unit of filtered audio */
+  double frequency;         /* modulate.c:43,104: carrier frequency in Hz (set_osc's f * Fs, osc.c:22) */
+  double sweep;             /* modulate.c:45,106: Hz per second (set_osc's r * Fs^2, osc.c:22) */
+  double amplitude_dbfs;    /* modulate.c:44,105: amplitude = 10^(dBFS / 20) */
+} kq_station_config;
+/* NULL on failure; the configuration is checked before any HIP call.
+ * Control plane: kq_mod_set_station, kq_mod_remove_station and kq_mod_reset are synchronous -- each waits for the bank's
+ * stream, so for every kq_mod_process still queued there, before it returns (a new (low, high, kaiser_beta) also waits
+ * for its response design).  Set stations up before the stream is busy; only kq_mod_process is asynchronous. */
+kq_mod_bank *kq_mod_create(const kq_mod_config *cfg);
+int kq_mod_destroy(kq_mod_bank *bank);
+/* Add a station to an empty slot or change one.  A new station starts cold at the next call's first block (zero filter
+ * history as filter.c:76, phasor 1); changing frequency, sweep or amplitude keeps the phase as set_osc does (osc.c:24-27);
+ * changing the mode, the edges or beta swaps the response from the next block and keeps the history. */
+int kq_mod_set_station(kq_mod_bank *bank, unsigned slot, const kq_station_config *station);
+/* The station stops contributing from the next block */
+int kq_mod_remove_station(kq_mod_bank *bank, unsigned slot);
+/* Synthesise nblocks * L output samples.  pcm: station `slot`'s audio at pcm + slot * stride elements, nblocks * L / interp
+ * samples each, in pcm_format KQ_PCM_F32 or KQ_PCM_S16; rows of empty slots are ignored, but host memory is read for
+ * every row 0 .. the highest occupied slot, so the buffer must hold that many rows.  out_cf32 (nblocks * L interleaved complex floats) and out_s16 (nblocks * L interleaved
+ * I,Q int16) may each be NULL, not both.  on_device != 0: every pointer is device memory and the call is asynchronous on the
+ * bank's stream; otherwise host memory, synchronous. */
+int kq_mod_process(kq_mod_bank *bank, const void *pcm, int pcm_format, size_t stride, unsigned nblocks, int on_device,
+                   float *out_cf32, int16_t *out_s16);
+int kq_mod_sync(kq_mod_bank *bank);
+/* Every station restarts cold (history, oscillator and FM phase), keeping its settings */
+int kq_mod_reset(kq_mod_bank *bank);
 
 #ifdef __cplusplus
 }
