@@ -617,6 +617,81 @@ int kq_mod_sync(kq_mod_bank *bank);
 /* Every station restarts cold (history, oscillator and FM phase), keeping its settings */
 int kq_mod_reset(kq_mod_bank *bank);
 
+/* --- spectrum bank: averaged power spectra of the I/Q stream --------------------------------------------------------
+ * Many analyzers over one wideband I/Q stream, each a view an operator places channels by: an overview of the whole
+ * band or a zoom on part of it, optionally following a Doppler sweep.  Per analyzer and input sample x[n] (n counted from
+ * create or kq_spec_reset across calls, x[n] = 0 for n < 0; s16 / s8 scaled as kq_bank_push_iq does, radio.c:110-122):
+ *   mix       m[n] = x[n] exp(-2 pi i phi(n) / 2^64), phi(n) = inc n + inc2 d (d - 1) / 2 in uint64 arithmetic, d = n - s0
+ *             (s0 = the stream index where the analyzer was set), inc = round(center / Fs 2^64), inc2 = round(sweep / Fs^2 2^64);
+ *             exact, so the views do not drift and do not depend on how the stream is split into calls
+ *   decimate  Dz = 1: y[j] = m[s0 + j].  Dz > 1: y[j] = sum_t h[t] m[s0 + j Dz - t], Lh = 24 Dz + 1 taps of a Kaiser (3.0)
+ *             windowed sinc, cut-off at the decimated Nyquist, sum h = 1; the input history makes a new analyzer start clean
+ *   frames    frame f = y[f H .. f H + Nf - 1] times w = make_kaiser(Nf, kaiser_beta) (filter.c:337-357), Nf-point transform,
+ *             P_f[k] = |X_f[k]|^2 / (sum w)^2
+ *   rows      row r = (1/K) sum of frames r K .. r K + K - 1 of P_f[k] / C[k] for k = -B/2 .. B/2 - 1 (row element 0 is the
+ *             lowest frequency); C[k] = |H(k / (Dz Nf))|^2 undoes the decimator's passband shape (1 when Dz = 1).
+ * Readings: a tone A e^{i w n} on a bin centre reads A^2; white noise of density N0 reads N0 enbw_bins bin_bw.
+ * Frames are added in frame order with the accumulator carried across calls: the same input split differently gives the
+ * same bits.
+ * Device memory per analyzer: about (Nf + max_samples / Dz) 8 + B 4 (max_rows + 1) bytes, plus the frame powers of one call
+ * (at most 2^21 floats; longer calls run in rounds), plus one bank-wide input history of 2 (6144 + max_samples) 8 bytes.
+ * kq_spec_create touches no device: its checks need no GPU, and device memory is allocated by the first kq_spec_set.
+ * Calls: kq_spec_process with device memory (on_device != 0) is asynchronous on the handle's stream and reads nothing back;
+ * with host memory it is synchronous.  kq_spec_set, kq_spec_remove, kq_spec_reset and kq_spec_pull wait for the stream;
+ * kq_spec_get_info answers from the host's account of the calls without waiting.  A change takes effect at the first sample of the next kq_spec_process.  One lock per handle: an operator
+ * thread may set and remove analyzers while another thread processes and pulls. */
+typedef struct kq_spec_bank kq_spec_bank;
+typedef struct kq_spec_config {
+  int device;
+  int samprate;              /* Fs of the I/Q stream */
+  float gain_factor;         /* demod->sdr.gain_factor, applied to every format as kq_bank_push_iq does (radio.c:122) */
+  unsigned max_specs;        /* analyzer slots 0 .. max_specs - 1 (limit 4096) */
+  size_t max_samples;        /* largest nsamples of one kq_spec_process call */
+  unsigned max_rows;         /* output rows buffered per analyzer before new ones are dropped (and counted) */
+  void *stream;              /* hipStream_t, NULL = own stream; kq_bank_stream(bank) puts it beside a receiver bank */
+} kq_spec_config;
+typedef struct kq_spec_params {
+  double center;             /* Hz relative to the stream's centre, |center| <= samprate / 2 */
+  double sweep;              /* Hz/s: the centre moves from the analyzer's start (Doppler-following views) */
+  unsigned decimate;         /* Dz, 1..256 */
+  unsigned fft_size;         /* Nf, even 2^a 3^b 5^c 7^d, 16..16384 */
+  unsigned bins;             /* B, even; <= Nf when Dz = 1, <= 3 Nf / 4 when Dz > 1 */
+  unsigned hop;              /* H, 1..Nf decimated samples between frames (Nf / 2 = 50 % overlap) */
+  unsigned average;          /* K frames per output row, >= 1 */
+  float kaiser_beta;         /* frame window, make_kaiser convention (filter.c:337-357), >= 0 */
+} kq_spec_params;
+typedef struct kq_spec_row {
+  uint64_t start_sample;     /* s0 + r K H Dz: the stream index of the row's first frame's first decimated sample */
+  uint32_t frames;           /* K */
+  uint32_t generation;       /* the kq_spec_set that made the parameters of this row (1 for the first) */
+} kq_spec_row;
+typedef struct kq_spec_info {
+  double bin_bw;             /* Fs / (Dz Nf) */
+  double first_bin_hz;       /* centre of row element 0 at the analyzer's start: center - B / 2 bin_bw */
+  double enbw_bins;          /* Nf sum w^2 / (sum w)^2 */
+  double delay_samples;      /* the decimator's group delay in input samples: 12 Dz (0 when Dz = 1) */
+  uint64_t rows_ready, rows_dropped;
+  uint32_t frames_pending;   /* frames in the row being averaged */
+  uint32_t generation;
+} kq_spec_info;
+
+kq_spec_bank *kq_spec_create(const kq_spec_config *cfg);
+int kq_spec_destroy(kq_spec_bank *bank);
+/* Add an analyzer to `slot` or replace the one there (generation + 1).  It starts at the next call's first sample with an
+ * empty average; unpulled rows of the slot stay (with their old generation) unless B changes, then they count as dropped. */
+int kq_spec_set(kq_spec_bank *bank, unsigned slot, const kq_spec_params *params);
+/* The analyzer stops from the next call; its unpulled rows are discarded */
+int kq_spec_remove(kq_spec_bank *bank, unsigned slot);
+/* nsamples (0 .. max_samples) I/Q samples in `format` (enum kq_iq_format) */
+int kq_spec_process(kq_spec_bank *bank, const void *iq, int format, size_t nsamples, int on_device);
+/* Copy up to max_rows of the slot's oldest rows (B floats each) to host `rows` and, when meta is not NULL, their kq_spec_row;
+ * returns the number copied */
+int kq_spec_pull(kq_spec_bank *bank, unsigned slot, float *rows, unsigned max_rows, kq_spec_row *meta);
+int kq_spec_get_info(kq_spec_bank *bank, unsigned slot, kq_spec_info *out);
+int kq_spec_sync(kq_spec_bank *bank);
+/* Stream index back to 0, input history zeroed, every analyzer restarts with its settings; unpulled rows are discarded */
+int kq_spec_reset(kq_spec_bank *bank);
+
 #ifdef __cplusplus
 }
 #endif
