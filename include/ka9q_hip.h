@@ -692,6 +692,86 @@ int kq_spec_sync(kq_spec_bank *bank);
 /* Stream index back to 0, input history zeroed, every analyzer restarts with its settings; unpulled rows are discarded */
 int kq_spec_reset(kq_spec_bank *bank);
 
+/* --- wideband FM stereo decoder bank ---------------------------------------------------------------------------------
+ * Up to 4096 decoder slots, each turning one broadcast FM composite ("stereo multiplex") into left and right audio.  The
+ * composite is the unfiltered discriminator output of a flat FM channel (kq_channel_config.flat = 1) in rad/sample at
+ * Fc = comp_rate; a receiver bank's audio plane (kq_bank_audio_device_ptr) can be decoded in place on its stream, after
+ * kq_bank_join(bank) (the bank may write that plane from a second stream: see kq_bank_join).
+ * The reference has no stereo decoder: the algorithm is defined here.
+ * Geometry: Da = decimate, Fo = Fc / Da, frames of L new samples, filter length M (odd), N = L + M - 1, D = (M - 1) / 2.
+ * Per slot, x[n] is the composite; n counts samples since create or kq_wfm_reset on a grid shared by every slot, and
+ * x[n] = 0 before the slot was set.
+ *   responses  each an ideal response sampled on the N bins, shaped by window_filter's procedure (filter.c:365-413: inverse
+ *              transform, centre moved to M/2, make_kaiser(M, kaiser_beta), zero pad, forward transform) in double and used
+ *              as float; both delay by D.  h_m (mono/audio): 1 for |f| <= 15 kHz times the de-emphasis 1 / (1 + j 2 pi f
+ *              tau), tau = deemph_us (0 = none), Hermitian (real taps), one per distinct tau.  h_p (pilot, one-sided):
+ *              1 for |f - 19000| <= pilot_bw / 2.
+ *   pilot      p[n] = (h_p * x)[n], u[n] = p[n] / |p[n]| (0 where |p| = 0) ~ exp(j theta(n - D))
+ *   difference d[n] = 2 x[n - D] Re(u[n]^2)
+ *   sum, diff  a[n] = (h_m * x)[n - D], s[n] = (h_m * d)[n]: both delayed by 2 D
+ *   output     j-th output at n = j Da: L_j = g (a + sigma s), R_j = g (a - sigma s), g = Fc / (2 pi 0.9 deviation_hz), so the
+ *              standard multiplex 0.45 (L + R) + 0.45 (L - R) cos 2 theta + 0.1 cos theta at peak deviation reads 1.0 at full
+ *              scale; sigma is the stereo flag of the frame holding n (sigma = 0: L == R exactly).
+ *   status     frame f covers n in [f L, (f + 1) L): w = arg sum p[n] conj(p[n - 1]) over the frame's L - 1 adjacent pairs,
+ *              C = |mean p[n] exp(-j w (n - f L))|^2, T = mean |p[n]|^2; pilot_hz = w Fc / 2 pi, pilot_dev_hz = 2 sqrt(C)
+ *              Fc / 2 pi, pilot_snr_db = 10 log10(C / (T - C)), 100 where T - C <= 0.
+ *   flag       turns on when pilot_snr_db >= pilot_on_db, pilot_dev_hz >= pilot_min_hz and |pilot_hz - 19000| <=
+ *              pilot_tol_hz all hold; turns off when pilot_snr_db < pilot_off_db or one of the other two fails.  The state
+ *              is carried across frames and calls (off when a slot is set); force_mono pins sigma (and status.stereo) to 0.
+ * Samples that do not complete a frame are carried to the next call, so the same composite split differently into calls
+ * or blocks gives the same bits.
+ * Limits (refused by kq_wfm_create with the reason in kq_last_error): Fc >= 128000, Fo >= 32000, Da divides L and M - 1,
+ * M odd, N even, 2^a 3^b 5^c 7^d and <= 16384, and 15 kHz + the transition band 2 Fc sqrt(1 + kaiser_beta^2) / M (the
+ * window's main lobe) <= 19 kHz - pilot_bw / 2; max_slots <= 4096.
+ * Device memory per slot: (Rx + Rd) 4 + Fmax 20 bytes, Rx = max_samples + L - 1 + M - 1 + D, Rd = Fmax L + M - 1,
+ * Fmax = ceil(max_samples / L): about (2 max_samples + 2 L + 2.5 M) 4 bytes; plus one h_m (N 8 bytes) per distinct deemph_us.
+ * Calls: kq_wfm_create touches no device.  kq_wfm_process with device memory is asynchronous on the handle's stream and
+ * reads nothing back; with host memory it is synchronous.  kq_wfm_set, kq_wfm_remove and kq_wfm_reset wait for the stream
+ * and take effect at the first sample of the next kq_wfm_process.  One lock per handle. */
+typedef struct kq_wfm_bank kq_wfm_bank;
+typedef struct kq_wfm_config {
+  int device;
+  int comp_rate;             /* Fc: composite samples per second */
+  unsigned decimate;         /* Da: Fo = Fc / Da */
+  unsigned L, M;             /* new samples per frame, filter length (odd) */
+  float kaiser_beta;         /* window_filter's beta for both responses (make_kaiser convention) */
+  float pilot_bw;            /* Hz: width of h_p's passband around 19 kHz */
+  unsigned max_slots;        /* slots 0 .. max_slots - 1 (limit 4096) */
+  size_t max_samples;        /* largest nblocks * block_len of one kq_wfm_process call */
+  void *stream;              /* hipStream_t, NULL = own stream; kq_bank_stream(bank) puts it beside a receiver bank */
+} kq_wfm_config;
+typedef struct kq_wfm_params {
+  unsigned source;           /* input row this slot decodes (a receiver bank's channel index) */
+  float deviation_hz;        /* peak deviation of a full-scale multiplex, 75000 for broadcast FM */
+  float deemph_us;           /* de-emphasis time constant: 75, 50 or 0 (none) */
+  float pilot_on_db, pilot_off_db;  /* hysteresis thresholds on pilot_snr_db, off <= on */
+  float pilot_min_hz;        /* least pilot_dev_hz for stereo */
+  float pilot_tol_hz;        /* largest |pilot_hz - 19000| for stereo */
+  int force_mono;
+} kq_wfm_params;
+typedef struct kq_wfm_status {
+  float pilot_hz, pilot_dev_hz, pilot_snr_db;
+  int32_t stereo;            /* sigma of the frame */
+} kq_wfm_status;
+
+kq_wfm_bank *kq_wfm_create(const kq_wfm_config *cfg);
+int kq_wfm_destroy(kq_wfm_bank *bank);
+/* Put a decoder in `slot` (or replace the one there): a cold start at the next call's first sample (zero history, flag off) */
+int kq_wfm_set(kq_wfm_bank *bank, unsigned slot, const kq_wfm_params *params);
+/* The slot stops from the next call */
+int kq_wfm_remove(kq_wfm_bank *bank, unsigned slot);
+/* Composite sample i of block k for row r is comp[r src_stride + k row_stride + i], i < block_len, k < nblocks (a receiver
+ * bank's audio plane: row_stride = 2 olen, block_len = olen, src_stride = max_blocks 2 olen).  Returns F, the frames
+ * completed in this call (the same for every slot, known without the device).  out[slot out_stride + 2 j + {0, 1}] holds
+ * L / R for j < F L / Da; status[slot status_stride + f] for f < F (strides in floats / in kq_wfm_status); either may be
+ * NULL.  on_device != 0: comp, out and status are device memory and the call is asynchronous on the handle's stream. */
+int kq_wfm_process(kq_wfm_bank *bank, const float *comp, size_t src_stride, size_t row_stride, unsigned block_len,
+                   unsigned nblocks, int on_device, float *out, size_t out_stride, kq_wfm_status *status,
+                   size_t status_stride);
+int kq_wfm_sync(kq_wfm_bank *bank);
+/* Stream index back to 0; every slot restarts cold with its settings */
+int kq_wfm_reset(kq_wfm_bank *bank);
+
 #ifdef __cplusplus
 }
 #endif

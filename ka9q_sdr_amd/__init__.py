@@ -33,3 +33,4 @@ from .packet import AfskBank, KQ_PCM_F32, KQ_PCM_S16BE  # noqa: F401,E402
 from . import iqfile  # noqa: F401,E402
 from .modulate import KQ_MOD_FM, KQ_MOD_LINEAR, ModBank, StationConfig, station_config  # noqa: F401,E402
 from .spectrum import SpecBank, SpecParams, plan, spec_params  # noqa: F401,E402
+from .wfm import STATUS_DTYPE, WfmBank, WfmParams, wfm_params  # noqa: F401,E402
