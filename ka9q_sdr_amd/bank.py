@@ -247,8 +247,28 @@ def channel_config(demod_type=KQ_FM_DEMOD, low=-8000.0, high=8000.0, second_lo=0
     return c
 
 
-class Bank:
+class Handle:
+    """What the handle types share: the library `lib`, the handle `h`, close / __del__ and the return-code check.  A
+    subclass names its destroy function in `_destroy` and sets `lib` and `h` in its __init__."""
+    _destroy = None
+
+    def close(self):
+        if getattr(self, "h", None):
+            getattr(self.lib, self._destroy)(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def _chk(self, rc, what):
+        if rc < 0:
+            raise KqError("%s: %s" % (what, _err(self.lib)))
+        return rc
+
+
+class Bank(Handle):
     """A bank of receiver channels sharing one front-end I/Q stream on one GPU."""
+    _destroy = "kq_bank_destroy"
 
     def __init__(self, samprate, L, M, decimate, max_channels, max_blocks, device=0, gain_factor=1.0,
                  compute_n0=False, fwd_mode=KQ_FWD_AUTO, stream=None, pl_tone=True):
@@ -263,19 +283,6 @@ class Bank:
         self.Ndec = self.N // decimate
         self.olen = self.lib.kq_bank_olen(self.h)
         self.max_blocks = max_blocks
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.kq_bank_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        self.close()
-
-    def _chk(self, rc, what):
-        if rc < 0:
-            raise KqError("%s: %s" % (what, _err(self.lib)))
-        return rc
 
     def add_channel(self, cfg):
         return self._chk(self.lib.kq_bank_add_channel(self.h, C.byref(cfg)), "kq_bank_add_channel")

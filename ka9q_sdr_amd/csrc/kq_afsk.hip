@@ -20,9 +20,8 @@
 
 #include "ka9q_hip.h"
 #include "kq_design.hpp"
+#include "kq_host.hpp"
 #include "kq_ldsfft.hpp"
-
-void kq_internal_set_error(const char *fmt, ...);
 
 namespace {
 
@@ -241,61 +240,31 @@ __global__ __launch_bounds__(kThreads) void k_afsk(AfskArgs a) {
 
 }  // namespace
 
-struct kq_afsk_bank {
+struct kq_afsk_bank : kq::HostSide {
   kq_afsk_config cfg;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
   int fill = 0;
   float *pend = nullptr, *hist = nullptr;
-  float2 *resp = nullptr, *tw = nullptr, *last_out = nullptr;
+  float2 *resp = nullptr, *last_out = nullptr;
+  const float2 *tw = nullptr;  // kq::half_twiddles(LOG2AN): shared, not the bank's to free
   double2 *mark_tab = nullptr, *space_tab = nullptr;
   AfskState *state = nullptr;
   unsigned char *hdlc = nullptr, *frames = nullptr;
   int *frame_len = nullptr, *nframes = nullptr, *dropped = nullptr;
-  void *staging = nullptr;
+  char *staging = nullptr;
   size_t staging_bytes = 0;
   uint64_t blocks = 0;
 };
-
-#define AF_TRY(expr)                                                                                  \
-  do {                                                                                                \
-    hipError_t e_ = (expr);                                                                           \
-    if (e_ != hipSuccess) {                                                                           \
-      kq_internal_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return -1;                                                                                      \
-    }                                                                                                 \
-  } while (0)
 
 static int afsk_alloc(kq_afsk_bank *b) {
   kq_afsk_config const &c = b->cfg;
   size_t const S = c.max_sessions;
   kq::DeviceScope dev_scope_(c.device);  // the caller's current device is restored on return
-  if (c.stream)
-    b->stream = (hipStream_t)c.stream;
-  else {
-    AF_TRY(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
-    b->own_stream = true;
-  }
-  AF_TRY(hipMalloc(&b->pend, S * AL * sizeof(float)));
-  AF_TRY(hipMalloc(&b->hist, S * (AM - 1) * sizeof(float)));
-  AF_TRY(hipMalloc(&b->resp, AN * sizeof(float2)));
-  AF_TRY(hipMalloc(&b->tw, (AN / 2) * sizeof(float2)));
-  AF_TRY(hipMalloc(&b->last_out, S * AL * sizeof(float2)));
-  AF_TRY(hipMalloc(&b->mark_tab, MARK_PERIOD * sizeof(double2)));
-  AF_TRY(hipMalloc(&b->space_tab, SPACE_PERIOD * sizeof(double2)));
-  AF_TRY(hipMalloc(&b->state, S * sizeof(AfskState)));
-  AF_TRY(hipMalloc(&b->hdlc, S * FRAME_MAX));
-  AF_TRY(hipMalloc(&b->frames, S * c.max_frames * FRAME_MAX));
-  AF_TRY(hipMalloc(&b->frame_len, S * c.max_frames * sizeof(int)));
-  AF_TRY(hipMalloc(&b->nframes, S * sizeof(int)));
-  AF_TRY(hipMalloc(&b->dropped, S * sizeof(int)));
-  AF_TRY(hipMemsetAsync(b->pend, 0, S * AL * sizeof(float), b->stream));
-  AF_TRY(hipMemsetAsync(b->hist, 0, S * (AM - 1) * sizeof(float), b->stream));
-  AF_TRY(hipMemsetAsync(b->last_out, 0, S * AL * sizeof(float2), b->stream));
-  AF_TRY(hipMemsetAsync(b->state, 0, S * sizeof(AfskState), b->stream));
-  AF_TRY(hipMemsetAsync(b->hdlc, 0, S * FRAME_MAX, b->stream));
-  AF_TRY(hipMemsetAsync(b->nframes, 0, S * sizeof(int), b->stream));
-  AF_TRY(hipMemsetAsync(b->dropped, 0, S * sizeof(int), b->stream));
+  if (b->open_stream(c.stream)) return -1;
+  if (b->alloc(&b->pend, S * AL, true) || b->alloc(&b->hist, S * (AM - 1), true) || b->alloc(&b->resp, AN) ||
+      b->alloc(&b->last_out, S * AL, true) || b->alloc(&b->mark_tab, MARK_PERIOD) || b->alloc(&b->space_tab, SPACE_PERIOD) ||
+      b->alloc(&b->state, S, true) || b->alloc(&b->hdlc, S * FRAME_MAX, true) || b->alloc(&b->frames, S * c.max_frames * FRAME_MAX) ||
+      b->alloc(&b->frame_len, S * c.max_frames) || b->alloc(&b->nframes, S, true) || b->alloc(&b->dropped, S, true))
+    return -1;
 
   // packet.c:273 set_filter(filter, +100/Samprate, +4000/Samprate, 3.0) on a slave with decimate 1
   std::vector<kq::cfloat> const r = kq::design_response(AN, AL, AM, kq::FT_COMPLEX, 100.f / 48000.f, 4000.f / 48000.f, 3.0f);
@@ -303,13 +272,11 @@ static int afsk_alloc(kq_afsk_bank *b) {
     kq_internal_set_error("kq_afsk_create: response design returned %zu bins", r.size());
     return -1;
   }
-  AF_TRY(hipMemcpyAsync(b->resp, r.data(), AN * sizeof(float2), hipMemcpyHostToDevice, b->stream));
-  std::vector<float2> tw(AN / 2);
-  for (int k = 0; k < AN / 2; k++) {
-    double const ang = -2.0 * M_PI * k / AN;
-    tw[k] = make_float2((float)cos(ang), (float)sin(ang));
+  KQ_TRY(hipMemcpyAsync(b->resp, r.data(), AN * sizeof(float2), hipMemcpyHostToDevice, b->stream));
+  if (!(b->tw = kq::half_twiddles(LOG2AN))) {
+    kq_internal_set_error("kq_afsk_create: no twiddle table of period %d", AN);
+    return -1;
   }
-  AF_TRY(hipMemcpyAsync(b->tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice, b->stream));
   // replica phasors exp(-j 2 pi f t / 48000), f = 1200 and 2200 (packet.c:279,284), exact periods 40 and 240
   std::vector<double2> mt(MARK_PERIOD), stb(SPACE_PERIOD);
   for (int t = 0; t < MARK_PERIOD; t++) {
@@ -320,9 +287,9 @@ static int afsk_alloc(kq_afsk_bank *b) {
     double const ang = -2.0 * M_PI * ((11 * t) % SPACE_PERIOD) / SPACE_PERIOD;
     stb[t] = make_double2(cos(ang), sin(ang));
   }
-  AF_TRY(hipMemcpyAsync(b->mark_tab, mt.data(), mt.size() * sizeof(double2), hipMemcpyHostToDevice, b->stream));
-  AF_TRY(hipMemcpyAsync(b->space_tab, stb.data(), stb.size() * sizeof(double2), hipMemcpyHostToDevice, b->stream));
-  AF_TRY(hipStreamSynchronize(b->stream));
+  KQ_TRY(hipMemcpyAsync(b->mark_tab, mt.data(), mt.size() * sizeof(double2), hipMemcpyHostToDevice, b->stream));
+  KQ_TRY(hipMemcpyAsync(b->space_tab, stb.data(), stb.size() * sizeof(double2), hipMemcpyHostToDevice, b->stream));
+  KQ_TRY(hipStreamSynchronize(b->stream));
   return 0;
 }
 
@@ -345,11 +312,7 @@ kq_afsk_bank *kq_afsk_create(const kq_afsk_config *cfg) {
 int kq_afsk_destroy(kq_afsk_bank *b) {
   kq::DeviceScope dev_scope_(b ? b->cfg.device : -1);
   if (!b) return -1;
-  if (b->stream) (void)hipStreamSynchronize(b->stream);
-  void *ptrs[] = {b->pend, b->hist, b->resp, b->tw, b->last_out, b->mark_tab, b->space_tab, b->state,
-                  b->hdlc, b->frames, b->frame_len, b->nframes, b->dropped, b->staging};
-  for (void *p : ptrs) (void)hipFree(p);
-  if (b->own_stream) (void)hipStreamDestroy(b->stream);
+  b->close();
   delete b;
   return 0;
 }
@@ -379,14 +342,8 @@ int kq_afsk_push(kq_afsk_bank *b, const void *samples, int format, unsigned nses
   size_t stride = session_stride;
   if (!on_device) {
     size_t const need = (size_t)nsessions * nsamples * esize;
-    if (need > b->staging_bytes) {
-      AF_TRY(hipStreamSynchronize(b->stream));
-      (void)hipFree(b->staging);
-      b->staging = nullptr;
-      AF_TRY(hipMalloc(&b->staging, need));
-      b->staging_bytes = need;
-    }
-    AF_TRY(hipMemcpy2DAsync(b->staging, nsamples * esize, samples, session_stride * esize, nsamples * esize, nsessions,
+    if (b->grow(&b->staging, &b->staging_bytes, need)) return -1;
+    KQ_TRY(hipMemcpy2DAsync(b->staging, nsamples * esize, samples, session_stride * esize, nsamples * esize, nsessions,
                             hipMemcpyHostToDevice, b->stream));
     src = b->staging;
     stride = nsamples;
@@ -412,19 +369,19 @@ int kq_afsk_push(kq_afsk_bank *b, const void *samples, int format, unsigned nses
   a.max_frames = (int)b->cfg.max_frames;
   a.last_out = b->last_out;
   hipLaunchKernelGGL(k_afsk, dim3(nsessions), dim3(kThreads), 0, b->stream, a);
-  AF_TRY(hipGetLastError());
+  KQ_TRY(hipGetLastError());
   size_t const total = (size_t)b->fill + nsamples;
   int const nblk = (int)(total / AL);
   b->fill = (int)(total % AL);
   b->blocks += nblk;
-  if (!on_device) AF_TRY(hipStreamSynchronize(b->stream));  // the staging buffer is reused by the next call
+  if (!on_device) KQ_TRY(hipStreamSynchronize(b->stream));  // the staging buffer is reused by the next call
   return nblk;
 }
 
 int kq_afsk_sync(kq_afsk_bank *b) {
   kq::DeviceScope dev_scope_(b ? b->cfg.device : -1);
   if (!b) return -1;
-  AF_TRY(hipStreamSynchronize(b->stream));
+  KQ_TRY(hipStreamSynchronize(b->stream));
   return 0;
 }
 
@@ -432,8 +389,8 @@ int kq_afsk_num_frames(kq_afsk_bank *b, unsigned session) {
   kq::DeviceScope dev_scope_(b ? b->cfg.device : -1);
   if (!b || session >= b->cfg.max_sessions) return -1;
   int n = 0;
-  AF_TRY(hipStreamSynchronize(b->stream));
-  AF_TRY(hipMemcpy(&n, b->nframes + session, sizeof n, hipMemcpyDeviceToHost));
+  KQ_TRY(hipStreamSynchronize(b->stream));
+  KQ_TRY(hipMemcpy(&n, b->nframes + session, sizeof n, hipMemcpyDeviceToHost));
   return n;
 }
 
@@ -441,8 +398,8 @@ int kq_afsk_dropped_frames(kq_afsk_bank *b, unsigned session) {
   kq::DeviceScope dev_scope_(b ? b->cfg.device : -1);
   if (!b || session >= b->cfg.max_sessions) return -1;
   int n = 0;
-  AF_TRY(hipStreamSynchronize(b->stream));
-  AF_TRY(hipMemcpy(&n, b->dropped + session, sizeof n, hipMemcpyDeviceToHost));
+  KQ_TRY(hipStreamSynchronize(b->stream));
+  KQ_TRY(hipMemcpy(&n, b->dropped + session, sizeof n, hipMemcpyDeviceToHost));
   return n;
 }
 
@@ -456,25 +413,25 @@ int kq_afsk_pull_frame(kq_afsk_bank *b, unsigned session, unsigned index, unsign
   }
   int len = 0;
   size_t const slot = (size_t)session * b->cfg.max_frames + index;
-  AF_TRY(hipMemcpy(&len, b->frame_len + slot, sizeof len, hipMemcpyDeviceToHost));
+  KQ_TRY(hipMemcpy(&len, b->frame_len + slot, sizeof len, hipMemcpyDeviceToHost));
   size_t const take = std::min(cap, (size_t)len);
-  AF_TRY(hipMemcpy(dst, b->frames + slot * FRAME_MAX, take, hipMemcpyDeviceToHost));
+  KQ_TRY(hipMemcpy(dst, b->frames + slot * FRAME_MAX, take, hipMemcpyDeviceToHost));
   return len;
 }
 
 int kq_afsk_clear_frames(kq_afsk_bank *b) {
   kq::DeviceScope dev_scope_(b ? b->cfg.device : -1);
   if (!b) return -1;
-  AF_TRY(hipMemsetAsync(b->nframes, 0, b->cfg.max_sessions * sizeof(int), b->stream));
-  AF_TRY(hipMemsetAsync(b->dropped, 0, b->cfg.max_sessions * sizeof(int), b->stream));
+  KQ_TRY(hipMemsetAsync(b->nframes, 0, b->cfg.max_sessions * sizeof(int), b->stream));
+  KQ_TRY(hipMemsetAsync(b->dropped, 0, b->cfg.max_sessions * sizeof(int), b->stream));
   return 0;
 }
 
 int kq_afsk_pull_filter_output(kq_afsk_bank *b, unsigned session, float *dst_re_im, size_t cap_complex) {
   kq::DeviceScope dev_scope_(b ? b->cfg.device : -1);
   if (!b || !dst_re_im || session >= b->cfg.max_sessions || cap_complex < (size_t)AL) return -1;
-  AF_TRY(hipStreamSynchronize(b->stream));
-  AF_TRY(hipMemcpy(dst_re_im, b->last_out + (size_t)session * AL, AL * sizeof(float2), hipMemcpyDeviceToHost));
+  KQ_TRY(hipStreamSynchronize(b->stream));
+  KQ_TRY(hipMemcpy(dst_re_im, b->last_out + (size_t)session * AL, AL * sizeof(float2), hipMemcpyDeviceToHost));
   return AL;
 }
 
@@ -482,8 +439,8 @@ int kq_afsk_pull_state(kq_afsk_bank *b, unsigned session, kq_afsk_state *out) {
   kq::DeviceScope dev_scope_(b ? b->cfg.device : -1);
   if (!b || !out || session >= b->cfg.max_sessions) return -1;
   AfskState st;
-  AF_TRY(hipStreamSynchronize(b->stream));
-  AF_TRY(hipMemcpy(&st, b->state + session, sizeof st, hipMemcpyDeviceToHost));
+  KQ_TRY(hipStreamSynchronize(b->stream));
+  KQ_TRY(hipMemcpy(&st, b->state + session, sizeof st, hipMemcpyDeviceToHost));
   out->symphase = st.symphase;
   out->frame_bit = st.frame_bit;
   out->flagsync = st.flagsync;

@@ -21,6 +21,7 @@
 
 #include "ka9q_hip.h"
 #include "kq_device.hpp"
+#include "kq_host.hpp"
 
 // hipcc contracts a*b+c into an FMA by default (and its __fmul_rn/__fadd_rn are plain operators), which would change
 // the rounding with respect to decimate.c built for x86-64: switch contraction off for this translation unit.
@@ -430,10 +431,8 @@ struct Group {
 
 }  // namespace
 
-struct kq_decimator {
+struct kq_decimator : kq::HostSide {
   kq_decim_config cfg;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
   std::vector<Group> groups;
   int rot_phase = 0;
   float atten = 1;
@@ -443,42 +442,26 @@ struct kq_decimator {
   int16_t *out16_dev = nullptr;
   unsigned long long *partial = nullptr;  // tagged per-workgroup energies of the last group's launch
   float *energy_dev = nullptr;
-  int *err = nullptr;  // pinned host word the kernel sets when a tile's energy never arrived
+  int *err = nullptr;  // pinned host word the kernel sets when a tile's energy never arrived (hipHostMalloc: freed by hand)
   unsigned epoch = 0;
   size_t n_partial = 0;
   unsigned num_cus = 256;
 };
-
-void kq_internal_set_error(const char *fmt, ...);
-
-#define DEC_TRY(expr)                                                                         \
-  do {                                                                                        \
-    hipError_t e_ = (expr);                                                                   \
-    if (e_ != hipSuccess) {                                                                   \
-      kq_internal_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return -1;                                                                              \
-    }                                                                                         \
-  } while (0)
 
 static int decim_alloc(kq_decimator *d) {
   kq_decim_config const &c = d->cfg;
   kq::DeviceScope dev_scope_(c.device);  // the caller's current device is restored on return
   {
     hipDeviceProp_t prop;
-    DEC_TRY(hipGetDeviceProperties(&prop, c.device));
+    KQ_TRY(hipGetDeviceProperties(&prop, c.device));
     d->num_cus = (unsigned)prop.multiProcessorCount;
   }
-  if (c.stream)
-    d->stream = (hipStream_t)c.stream;
-  else {
-    DEC_TRY(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
-    d->own_stream = true;
-  }
+  if (d->open_stream(c.stream)) return -1;
   // stages in processing order: j = log_decimate-1 .. 0, 1-2-1 while j >= stage_threshold (hackrf.c:297-300)
   int const S = c.log_decimate;
   int done = 0;
   while (done < S) {
-    d->groups.emplace_back();  // in the list before it owns anything, so that a failure below still frees it
+    d->groups.emplace_back();
     Group &g = d->groups.back();
     g.nstages = std::min(kMaxFuse, S - done);
     g.shift_in = S - done;
@@ -490,19 +473,17 @@ static int decim_alloc(kq_decimator *d) {
     for (int s = g.nstages - 1; s >= 0; s--) need = 2 * need + ((g.mask >> s) & 1 ? 14 : 1);
     g.halo = need;
     done += g.nstages;
-    float2 *h = nullptr;
-    DEC_TRY(hipMalloc(&h, sizeof(float2) * (need + 2)));
+    float2 *h = nullptr;  // the owner frees `h`; the group keeps h + 2
+    if (d->alloc(&h, (size_t)need + 2, true)) return -1;
     g.hist = h + 2;
-    DEC_TRY(hipMemsetAsync(h, 0, sizeof(float2) * (need + 2), d->stream));
-    if (done < S) DEC_TRY(hipMalloc(&g.out, sizeof(float2) * (c.max_out << (S - done))));
+    if (done < S && d->alloc(&g.out, c.max_out << (S - done))) return -1;
   }
   d->n_partial = (size_t)d->num_cus * 16 + 1;  // one per workgroup of the last launch
-  DEC_TRY(hipMalloc(&d->partial, sizeof(unsigned long long) * d->n_partial));
-  DEC_TRY(hipMemsetAsync(d->partial, 0, sizeof(unsigned long long) * d->n_partial, d->stream));  // epoch 0 = never written
-  DEC_TRY(hipHostMalloc((void **)&d->err, sizeof(int), hipHostMallocDefault));
+  if (d->alloc(&d->partial, d->n_partial, true)) return -1;  // epoch 0 = never written
+  KQ_TRY(hipHostMalloc((void **)&d->err, sizeof(int), hipHostMallocDefault));
   *d->err = 0;
-  DEC_TRY(hipMalloc(&d->energy_dev, sizeof(float)));
-  DEC_TRY(hipStreamSynchronize(d->stream));
+  if (d->alloc(&d->energy_dev, 1)) return -1;
+  KQ_TRY(hipStreamSynchronize(d->stream));
   return 0;
 }
 
@@ -539,18 +520,8 @@ kq_decimator *kq_decim_create(const kq_decim_config *cfg) {
 int kq_decim_destroy(kq_decimator *d) {
   kq::DeviceScope dev_scope_(d ? d->cfg.device : -1);
   if (!d) return -1;
-  if (d->stream) (void)hipStreamSynchronize(d->stream);
-  for (Group &g : d->groups) {
-    if (g.hist) (void)hipFree(g.hist - 2);
-    (void)hipFree(g.out);
-  }
-  (void)hipFree(d->in_dev);
-  (void)hipFree(d->out_dev);
-  (void)hipFree(d->out16_dev);
-  (void)hipFree(d->partial);
-  (void)hipFree(d->energy_dev);
+  d->close();
   if (d->err) (void)hipHostFree(d->err);
-  if (d->own_stream) (void)hipStreamDestroy(d->stream);
   delete d;
   return 0;
 }
@@ -581,11 +552,11 @@ int kq_decim_process(kq_decimator *d, const float *iq_in, int on_device, size_t 
   int16_t *final16 = out_s16;
   if (!on_device) {
     if (!d->in_dev) {
-      DEC_TRY(hipMalloc(&d->in_dev, sizeof(float2) * (d->cfg.max_out << S)));
-      DEC_TRY(hipMalloc(&d->out_dev, sizeof(float2) * d->cfg.max_out));
-      DEC_TRY(hipMalloc(&d->out16_dev, sizeof(int16_t) * 2 * d->cfg.max_out));
+      if (d->alloc(&d->in_dev, d->cfg.max_out << S) || d->alloc(&d->out_dev, d->cfg.max_out) ||
+          d->alloc(&d->out16_dev, 2 * d->cfg.max_out))
+        return -1;
     }
-    DEC_TRY(hipMemcpyAsync(d->in_dev, iq_in, sizeof(float2) * n_in, hipMemcpyHostToDevice, d->stream));
+    KQ_TRY(hipMemcpyAsync(d->in_dev, iq_in, sizeof(float2) * n_in, hipMemcpyHostToDevice, d->stream));
     src = d->in_dev;
     final_out = d->out_dev;
     final16 = out_s16 ? d->out16_dev : nullptr;
@@ -631,7 +602,7 @@ int kq_decim_process(kq_decimator *d, const float *iq_in, int on_device, size_t 
     size_t const lds_bytes = sizeof(float2) * lds_elems;
     if (g.resident_for != lds_bytes) {
       int nb = 0;
-      DEC_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)kern, kThreads, lds_bytes));
+      KQ_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)kern, kThreads, lds_bytes));
       g.resident = (unsigned)std::max(1, nb);
       g.resident_for = lds_bytes;
     }
@@ -640,15 +611,15 @@ int kq_decim_process(kq_decimator *d, const float *iq_in, int on_device, size_t 
     src = g.out;
     n_g_in >>= g.nstages;
   }
-  DEC_TRY(hipGetLastError());
+  KQ_TRY(hipGetLastError());
   d->rot_phase = (int)((d->rot_phase + (long long)(n_in & 3) * (d->cfg.offset & 3)) & 3);
   if (out_energy && !on_device)
-    DEC_TRY(hipMemcpyAsync(out_energy, d->energy_dev, sizeof(float), hipMemcpyDeviceToHost, d->stream));
+    KQ_TRY(hipMemcpyAsync(out_energy, d->energy_dev, sizeof(float), hipMemcpyDeviceToHost, d->stream));
   if (!on_device) {
-    DEC_TRY(hipMemcpyAsync(out_cf32, d->out_dev, sizeof(float2) * n_out, hipMemcpyDeviceToHost, d->stream));
+    KQ_TRY(hipMemcpyAsync(out_cf32, d->out_dev, sizeof(float2) * n_out, hipMemcpyDeviceToHost, d->stream));
     if (out_s16)
-      DEC_TRY(hipMemcpyAsync(out_s16, d->out16_dev, sizeof(int16_t) * 2 * n_out, hipMemcpyDeviceToHost, d->stream));
-    DEC_TRY(hipStreamSynchronize(d->stream));
+      KQ_TRY(hipMemcpyAsync(out_s16, d->out16_dev, sizeof(int16_t) * 2 * n_out, hipMemcpyDeviceToHost, d->stream));
+    KQ_TRY(hipStreamSynchronize(d->stream));
     if (decim_lost(d)) return -1;
   }
   return 0;
@@ -657,7 +628,7 @@ int kq_decim_process(kq_decimator *d, const float *iq_in, int on_device, size_t 
 int kq_decim_sync(kq_decimator *d) {
   kq::DeviceScope dev_scope_(d ? d->cfg.device : -1);
   if (!d) return -1;
-  DEC_TRY(hipStreamSynchronize(d->stream));
+  KQ_TRY(hipStreamSynchronize(d->stream));
   return decim_lost(d) ? -1 : 0;
 }
 
@@ -665,7 +636,7 @@ int kq_decim_reset(kq_decimator *d) {
   kq::DeviceScope dev_scope_(d ? d->cfg.device : -1);
   if (!d) return -1;
   for (Group &g : d->groups)
-    DEC_TRY(hipMemsetAsync(g.hist, 0, sizeof(float2) * g.halo, d->stream));
+    KQ_TRY(hipMemsetAsync(g.hist, 0, sizeof(float2) * g.halo, d->stream));
   d->rot_phase = 0;
   return 0;
 }

@@ -17,10 +17,9 @@
 
 #include "kq_design.hpp"
 #include "kq_device.hpp"
+#include "kq_host.hpp"
 #include "kq_ldsfft.hpp"
 #include "kq_ctl.hpp"
-
-void kq_internal_set_error(const char *fmt, ...);
 
 namespace kq {
 
@@ -141,8 +140,10 @@ __global__ void k_design(FftDim dim, int M, int spec, const DesignJob *__restric
   if (threadIdx.x == 0 && targets && targets[blockIdx.x].noise_gain) *targets[blockIdx.x].noise_gain = targets[blockIdx.x].ng_scale * acc;
 }
 
-// twiddle tables exp(-2 pi i k / T), k < T/2, per device and size (built in double, rounded once)
-const float2 *design_twiddles(int log2T) {
+}  // namespace
+
+// half-circle twiddle tables exp(-2 pi i k / T), k < T/2, per device and size (built in double, rounded once)
+const float2 *half_twiddles(int log2T) {
   static std::mutex mu;
   static std::map<std::pair<int, int>, float2 *> tabs;
   int dev = 0;
@@ -165,8 +166,6 @@ const float2 *design_twiddles(int log2T) {
   tabs[{dev, log2T}] = d;
   return d;
 }
-
-}  // namespace
 
 bool fft_size_ok(int n) {
   if (n < 2 || n > 65536 || (n & 1)) return false;
@@ -308,7 +307,7 @@ int design_batch(int L, int M, bool real_taps, int spec, const std::vector<Desig
     return -1;
   }
   size_t const count = jobs.size(), nbins = real_taps ? (size_t)N / 2 + 1 : (size_t)N;
-  const float2 *tw = design_twiddles(log2n);
+  const float2 *tw = half_twiddles(log2n);
   std::lock_guard<std::mutex> lk(g_design_mu);
   Workspace *w = workspace();
   size_t const b_jobs = count * sizeof(DesignJob), b_in = given ? count * nbins * sizeof(float2) : 0,
@@ -411,7 +410,7 @@ int design_prepare(int L_dec, int M_dec) {
   bool ok = false;
   FftDim const dim = fft_dim(N, &ok);
   if (!ok) return -1;
-  return design_twiddles(dim.log2n >= 0 ? dim.log2n : 1) ? 0 : -1;
+  return half_twiddles(dim.log2n >= 0 ? dim.log2n : 1) ? 0 : -1;
 }
 int design_launch(void *stream, int L_dec, int M_dec, const DesignJob *jobs, const DesignTarget *targets, unsigned count,
                   void *scratch, const void *ctl_queue, unsigned ctl_records) {
@@ -420,7 +419,7 @@ int design_launch(void *stream, int L_dec, int M_dec, const DesignJob *jobs, con
   FftDim const dim = fft_dim(N, &dim_ok);  // (cached since design_prepare: no allocation here)
   int const log2n = dim.log2n >= 0 ? dim.log2n : 1;
   hipStream_t const st = static_cast<hipStream_t>(stream);
-  const float2 *tw = design_twiddles(log2n);
+  const float2 *tw = half_twiddles(log2n);
   if (!tw || !dim_ok || count == 0) return (tw && dim_ok) ? 0 : -1;
   size_t const lds_bytes = (size_t)N * sizeof(float2);
   ensure_dynamic_lds((const void *)k_design<false>, lds_bytes);

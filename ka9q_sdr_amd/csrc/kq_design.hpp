@@ -3,6 +3,8 @@
 // set_filter / window_filter / window_rfilter (filter.c:337-546) and the FM de-emphasis response of fm.c:54-66.
 // Every function runs on the calling thread's current device and fails (-1 / empty vector) without one.
 #pragma once
+#include <hip/hip_runtime.h>
+
 #include <complex>
 #include <vector>
 
@@ -46,6 +48,23 @@ int design_prepare(int L_dec, int M_dec);
 int design_launch(void *stream, int L_dec, int M_dec, const DesignJob *jobs, const DesignTarget *targets, unsigned count, void *scratch,
                   const void *ctl_queue = nullptr, unsigned ctl_records = 0);
 void design_scales(int N, int out_type, float *gain, float *ng_scale);
+
+// Half-circle twiddle table exp(-2 pi i k / T), k < T / 2, T = 1 << log2T, as lds_fft / fft_any read it: on the current
+// device, built in double and rounded once, cached per (device, size) and never freed (like fft_dim's tables), so it
+// outlives the handle that asked first.  Null when the allocation fails.
+const float2 *half_twiddles(int log2T);
+
+// modified Bessel function I0 in double (power series), for the host-side Kaiser designs of the satellite banks
+inline double i0_double(double x) {
+  double const q = 0.25 * x * x;
+  double term = 1, sum = 1;
+  for (int k = 1; k < 500; k++) {
+    term *= q / ((double)k * k);
+    sum += term;
+    if (term < 1e-17 * sum) break;
+  }
+  return sum;
+}
 
 // FM post-detection response (fm.c:42, 56-65): 300 Hz high-pass, -6 dB/octave to 6 kHz, Kaiser
 // windowed for a REAL->REAL filter of AL new samples and AM taps.  Returns AN/2+1 bins.

@@ -289,5 +289,7 @@ __device__ __forceinline__ void fft_any(float2 *s, const FftDim &d, const float2
   else
     lds_fft_mixed<SIGN>(s, d);
 }
+// workgroup size of a kernel that runs one n-point fft_any in LDS (n / threads <= 16)
+inline int fft_threads(int n) { return n > 4096 ? 1024 : n > 1024 ? 256 : 64; }
 
 }  // namespace kq

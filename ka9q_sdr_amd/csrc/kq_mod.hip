@@ -30,9 +30,8 @@
 #include "ka9q_hip.h"
 #include "kq_design.hpp"
 #include "kq_device.hpp"
+#include "kq_host.hpp"
 #include "kq_ldsfft.hpp"
-
-void kq_internal_set_error(const char *fmt, ...);
 
 namespace {
 
@@ -206,15 +205,6 @@ __global__ __launch_bounds__(256) void k_mod_reduce(const float2 *__restrict__ p
 
 size_t synth_lds_bytes(int N, int G) { return (size_t)N * sizeof(float2) + (size_t)G * (sizeof(ModParam) + sizeof(ModOsc)); }
 
-int threads_for(int N) { return N > 4096 ? 1024 : N > 1024 ? 256 : 64; }  // (N / threads <= 16)
-
-bool smooth7(unsigned n) {
-  if (n == 0) return false;
-  for (unsigned p : {2u, 3u, 5u, 7u})
-    while (n % p == 0) n /= p;
-  return n == 1;
-}
-
 struct RespKey {
   float low, high, beta;
   bool operator<(const RespKey &o) const {
@@ -224,12 +214,10 @@ struct RespKey {
 
 }  // namespace
 
-struct kq_mod_bank {
+struct kq_mod_bank : kq::HostSide {
   kq_mod_config cfg;
   int N = 0, Na = 0, Hn = 0, La = 0, G = 1, groups = 0, threads = 64;
   FftDim dN{}, dA{};
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
   // host mirror
   std::vector<ModParam> par;
   std::vector<kq_station_config> st;
@@ -239,37 +227,23 @@ struct kq_mod_bank {
   std::vector<int> resp_refs;
   int resp_cap = 0;
   // device
-  float2 *tw = nullptr;
+  const float2 *tw = nullptr;  // kq::half_twiddles(tw_log2): shared, not the bank's to free
   int tw_log2 = 0;
   ModParam *d_par = nullptr;
   ModOsc *d_osc = nullptr;
   float *d_hist = nullptr;
   float2 *d_resp = nullptr, *d_part = nullptr, *d_aspec = nullptr, *d_out = nullptr;
   int16_t *d_s16 = nullptr;
-  void *d_pcm = nullptr;
+  char *d_pcm = nullptr;
   size_t pcm_bytes = 0;
 };
-
-#define MOD_TRY(expr)                                                                                 \
-  do {                                                                                                \
-    hipError_t e_ = (expr);                                                                           \
-    if (e_ != hipSuccess) {                                                                           \
-      kq_internal_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return -1;                                                                                      \
-    }                                                                                                 \
-  } while (0)
 
 namespace {
 
 int mod_alloc(kq_mod_bank *b) {
   kq_mod_config const &c = b->cfg;
   kq::DeviceScope dev_scope_(c.device);
-  if (c.stream) {
-    b->stream = (hipStream_t)c.stream;
-  } else {
-    MOD_TRY(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
-    b->own_stream = true;
-  }
+  if (b->open_stream(c.stream)) return -1;
   bool okN = false, okA = false;
   b->dN = kq::fft_dim(b->N, &okN);
   b->dA = kq::fft_dim(b->Na, &okA);
@@ -279,25 +253,16 @@ int mod_alloc(kq_mod_bank *b) {
   }
   b->tw_log2 = 1;
   while ((1 << b->tw_log2) < b->N) b->tw_log2++;
-  size_t const T = (size_t)1 << b->tw_log2;
-  std::vector<float2> tw(T / 2);
-  for (size_t k = 0; k < T / 2; k++) {
-    double const ang = -2.0 * M_PI * (double)k / (double)T;
-    tw[k] = make_float2((float)std::cos(ang), (float)std::sin(ang));
+  if (!(b->tw = kq::half_twiddles(b->tw_log2))) {
+    kq_internal_set_error("kq_mod_create: no twiddle table of period 2^%d", b->tw_log2);
+    return -1;
   }
   size_t const S = c.max_stations, L = c.L;
-  MOD_TRY(hipMalloc(&b->tw, tw.size() * sizeof(float2)));
-  MOD_TRY(hipMemcpyAsync(b->tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice, b->stream));
-  MOD_TRY(hipMalloc(&b->d_par, S * sizeof(ModParam)));
-  MOD_TRY(hipMalloc(&b->d_osc, S * sizeof(ModOsc)));
-  MOD_TRY(hipMalloc(&b->d_hist, std::max<size_t>(1, S * b->Hn) * sizeof(float)));
-  MOD_TRY(hipMalloc(&b->d_part, (size_t)b->groups * c.max_blocks * L * sizeof(float2)));
-  MOD_TRY(hipMalloc(&b->d_aspec, (size_t)b->groups * b->Na * sizeof(float2)));
-  MOD_TRY(hipMalloc(&b->d_out, (size_t)c.max_blocks * L * sizeof(float2)));
-  MOD_TRY(hipMalloc(&b->d_s16, (size_t)c.max_blocks * L * 2 * sizeof(int16_t)));
-  MOD_TRY(hipMemsetAsync(b->d_par, 0, S * sizeof(ModParam), b->stream));
-  MOD_TRY(hipMemsetAsync(b->d_osc, 0, S * sizeof(ModOsc), b->stream));
-  MOD_TRY(hipStreamSynchronize(b->stream));
+  if (b->alloc(&b->d_par, S, true) || b->alloc(&b->d_osc, S, true) || b->alloc(&b->d_hist, std::max<size_t>(1, S * b->Hn)) ||
+      b->alloc(&b->d_part, (size_t)b->groups * c.max_blocks * L) || b->alloc(&b->d_aspec, (size_t)b->groups * b->Na) ||
+      b->alloc(&b->d_out, (size_t)c.max_blocks * L) || b->alloc(&b->d_s16, (size_t)c.max_blocks * L * 2))
+    return -1;
+  KQ_TRY(hipStreamSynchronize(b->stream));
   b->par.assign(S, ModParam{});
   b->st.assign(S, kq_station_config{});
   return 0;
@@ -341,12 +306,12 @@ int acquire_response(kq_mod_bank *b, const RespKey &k) {
     if (idx >= b->resp_cap) {  // grow the table: queued kernels read the old one, so wait for them first
       int const cap = std::max(4, 2 * b->resp_cap);
       float2 *nr = nullptr;
-      MOD_TRY(hipStreamSynchronize(b->stream));
-      MOD_TRY(hipMalloc(&nr, (size_t)cap * b->N * sizeof(float2)));
+      KQ_TRY(hipStreamSynchronize(b->stream));
+      if (b->alloc(&nr, (size_t)cap * b->N)) return -1;
       if (b->resp_cap)
-        MOD_TRY(hipMemcpyAsync(nr, b->d_resp, (size_t)b->resp_cap * b->N * sizeof(float2), hipMemcpyDeviceToDevice, b->stream));
-      MOD_TRY(hipStreamSynchronize(b->stream));
-      (void)hipFree(b->d_resp);
+        KQ_TRY(hipMemcpyAsync(nr, b->d_resp, (size_t)b->resp_cap * b->N * sizeof(float2), hipMemcpyDeviceToDevice, b->stream));
+      KQ_TRY(hipStreamSynchronize(b->stream));
+      b->release(&b->d_resp);
       b->d_resp = nr;
       b->resp_cap = cap;
     }
@@ -354,8 +319,8 @@ int acquire_response(kq_mod_bank *b, const RespKey &k) {
     b->resp_key.push_back(k);
   }
   // stream order: kernels queued before this call still read the slot's old contents
-  MOD_TRY(hipMemcpyAsync(b->d_resp + (size_t)idx * b->N, r.data(), (size_t)b->N * sizeof(float2), hipMemcpyHostToDevice, b->stream));
-  MOD_TRY(hipStreamSynchronize(b->stream));
+  KQ_TRY(hipMemcpyAsync(b->d_resp + (size_t)idx * b->N, r.data(), (size_t)b->N * sizeof(float2), hipMemcpyHostToDevice, b->stream));
+  KQ_TRY(hipStreamSynchronize(b->stream));
   b->resp_refs[idx] = 1;
   b->resp_key[idx] = k;
   b->resp_of[k] = idx;
@@ -376,8 +341,8 @@ RespKey key_of(const kq_station_config &c) {
 }
 
 int upload_param(kq_mod_bank *b, unsigned slot) {
-  MOD_TRY(hipMemcpyAsync(b->d_par + slot, &b->par[slot], sizeof(ModParam), hipMemcpyHostToDevice, b->stream));
-  MOD_TRY(hipStreamSynchronize(b->stream));
+  KQ_TRY(hipMemcpyAsync(b->d_par + slot, &b->par[slot], sizeof(ModParam), hipMemcpyHostToDevice, b->stream));
+  KQ_TRY(hipStreamSynchronize(b->stream));
   return 0;
 }
 
@@ -402,7 +367,7 @@ kq_mod_bank *kq_mod_create(const kq_mod_config *cfg) {
     kq_internal_set_error("kq_mod_create: samprate, L and M must be positive");
     return nullptr;
   }
-  if (N > (unsigned long)kMaxN || (N & 1) || !smooth7((unsigned)N)) {
+  if (N > (unsigned long)kMaxN || (N & 1) || !kq::fft_size_ok((int)N)) {
     kq_internal_set_error("kq_mod_create: N = L + M - 1 = %lu must be even and 2^a 3^b 5^c 7^d up to %d", N, kMaxN);
     return nullptr;
   }
@@ -422,7 +387,7 @@ kq_mod_bank *kq_mod_create(const kq_mod_config *cfg) {
   b->La = (int)(L / I);
   b->G = (int)((cfg->max_stations + kGroups - 1) / kGroups);
   b->groups = (int)((cfg->max_stations + b->G - 1) / b->G);
-  b->threads = threads_for(b->N);
+  b->threads = kq::fft_threads(b->N);
   if (mod_alloc(b) != 0) {
     kq_mod_destroy(b);
     return nullptr;
@@ -436,11 +401,7 @@ int kq_mod_destroy(kq_mod_bank *b) {
     return -1;
   }
   kq::DeviceScope dev_scope_(b->cfg.device);
-  if (b->stream) (void)hipStreamSynchronize(b->stream);
-  void *ptrs[] = {b->tw, b->d_par, b->d_osc, b->d_hist, b->d_resp, b->d_part, b->d_aspec, b->d_out, b->d_s16, b->d_pcm};
-  for (void *p : ptrs)
-    if (p) (void)hipFree(p);
-  if (b->own_stream) (void)hipStreamDestroy(b->stream);
+  b->close();
   delete b;
   return 0;
 }
@@ -489,12 +450,12 @@ int kq_mod_set_station(kq_mod_bank *b, unsigned slot, const kq_station_config *c
   o.f = c->frequency / Fs;
   o.r = c->sweep / (Fs * Fs);
   if (!was_active) {
-    MOD_TRY(hipMemcpyAsync(b->d_osc + slot, &o, sizeof o, hipMemcpyHostToDevice, b->stream));
-    if (b->Hn) MOD_TRY(hipMemsetAsync(b->d_hist + (size_t)slot * b->Hn, 0, (size_t)b->Hn * sizeof(float), b->stream));  // filter.c:76
+    KQ_TRY(hipMemcpyAsync(b->d_osc + slot, &o, sizeof o, hipMemcpyHostToDevice, b->stream));
+    if (b->Hn) KQ_TRY(hipMemsetAsync(b->d_hist + (size_t)slot * b->Hn, 0, (size_t)b->Hn * sizeof(float), b->stream));  // filter.c:76
   } else {
-    MOD_TRY(hipMemcpyAsync(&b->d_osc[slot].f, &o.f, 2 * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    KQ_TRY(hipMemcpyAsync(&b->d_osc[slot].f, &o.f, 2 * sizeof(double), hipMemcpyHostToDevice, b->stream));
     if (c->mod_type == KQ_MOD_FM && p.type != KQ_MOD_FM)  // theta starts at 0 where a station turns to FM
-      MOD_TRY(hipMemsetAsync(&b->d_osc[slot].theta, 0, sizeof(double), b->stream));
+      KQ_TRY(hipMemsetAsync(&b->d_osc[slot].theta, 0, sizeof(double), b->stream));
   }
   p.active = 1;
   p.type = c->mod_type;
@@ -551,23 +512,16 @@ int kq_mod_process(kq_mod_bank *b, const void *pcm, int pcm_format, size_t strid
   float2 *out = on_device ? reinterpret_cast<float2 *>(out_cf32) : (out_cf32 ? b->d_out : nullptr);
   int16_t *s16 = on_device ? out_s16 : (out_s16 ? b->d_s16 : nullptr);
   if (hi < 0) {  // nothing on the air: silence
-    if (out) MOD_TRY(hipMemsetAsync(out, 0, total * sizeof(float2), b->stream));
-    if (s16) MOD_TRY(hipMemsetAsync(s16, 0, total * 2 * sizeof(int16_t), b->stream));
+    if (out) KQ_TRY(hipMemsetAsync(out, 0, total * sizeof(float2), b->stream));
+    if (s16) KQ_TRY(hipMemsetAsync(s16, 0, total * 2 * sizeof(int16_t), b->stream));
   } else {
     size_t const esize = pcm_format == KQ_PCM_S16 ? 2 : 4;
     const void *src = pcm;
     size_t row = stride;
     if (!on_device) {  // rows 0 .. hi to the device
       size_t const need = (size_t)(hi + 1) * nnew * esize;
-      if (need > b->pcm_bytes) {
-        MOD_TRY(hipStreamSynchronize(b->stream));
-        if (b->d_pcm) (void)hipFree(b->d_pcm);
-        b->d_pcm = nullptr;
-        b->pcm_bytes = 0;
-        MOD_TRY(hipMalloc(&b->d_pcm, need));
-        b->pcm_bytes = need;
-      }
-      MOD_TRY(hipMemcpy2DAsync(b->d_pcm, nnew * esize, pcm, stride * esize, nnew * esize, (size_t)hi + 1, hipMemcpyHostToDevice,
+      if (b->grow(&b->d_pcm, &b->pcm_bytes, need)) return -1;
+      KQ_TRY(hipMemcpy2DAsync(b->d_pcm, nnew * esize, pcm, stride * esize, nnew * esize, (size_t)hi + 1, hipMemcpyHostToDevice,
                                b->stream));
       src = b->d_pcm;
       row = nnew;
@@ -599,15 +553,15 @@ int kq_mod_process(kq_mod_bank *b, const void *pcm, int pcm_format, size_t strid
     size_t const lds = synth_lds_bytes(b->N, b->G);
     kq::ensure_dynamic_lds((const void *)k_mod_synth, lds);
     hipLaunchKernelGGL(k_mod_synth, dim3(groups), dim3(b->threads), lds, b->stream, a);
-    MOD_TRY(hipGetLastError());
+    KQ_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_mod_reduce, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, b->stream, (const float2 *)b->d_part, groups,
                        total, out, s16);
-    MOD_TRY(hipGetLastError());
+    KQ_TRY(hipGetLastError());
   }
   if (!on_device) {
-    if (out_cf32) MOD_TRY(hipMemcpyAsync(out_cf32, b->d_out, total * sizeof(float2), hipMemcpyDeviceToHost, b->stream));
-    if (out_s16) MOD_TRY(hipMemcpyAsync(out_s16, b->d_s16, total * 2 * sizeof(int16_t), hipMemcpyDeviceToHost, b->stream));
-    MOD_TRY(hipStreamSynchronize(b->stream));
+    if (out_cf32) KQ_TRY(hipMemcpyAsync(out_cf32, b->d_out, total * sizeof(float2), hipMemcpyDeviceToHost, b->stream));
+    if (out_s16) KQ_TRY(hipMemcpyAsync(out_s16, b->d_s16, total * 2 * sizeof(int16_t), hipMemcpyDeviceToHost, b->stream));
+    KQ_TRY(hipStreamSynchronize(b->stream));
   }
   return 0;
 }
@@ -618,7 +572,7 @@ int kq_mod_sync(kq_mod_bank *b) {
     return -1;
   }
   kq::DeviceScope dev_scope_(b->cfg.device);
-  MOD_TRY(hipStreamSynchronize(b->stream));
+  KQ_TRY(hipStreamSynchronize(b->stream));
   return 0;
 }
 
@@ -637,9 +591,9 @@ int kq_mod_reset(kq_mod_bank *b) {
       o[s].r = b->st[s].sweep / ((double)b->cfg.samprate * b->cfg.samprate);
     }
   }
-  MOD_TRY(hipMemcpyAsync(b->d_osc, o.data(), S * sizeof(ModOsc), hipMemcpyHostToDevice, b->stream));
-  if (b->Hn) MOD_TRY(hipMemsetAsync(b->d_hist, 0, S * b->Hn * sizeof(float), b->stream));
-  MOD_TRY(hipStreamSynchronize(b->stream));
+  KQ_TRY(hipMemcpyAsync(b->d_osc, o.data(), S * sizeof(ModOsc), hipMemcpyHostToDevice, b->stream));
+  if (b->Hn) KQ_TRY(hipMemsetAsync(b->d_hist, 0, S * b->Hn * sizeof(float), b->stream));
+  KQ_TRY(hipStreamSynchronize(b->stream));
   return 0;
 }
 

@@ -27,10 +27,10 @@
 #include <vector>
 
 #include "ka9q_hip.h"
+#include "kq_design.hpp"
 #include "kq_device.hpp"
+#include "kq_host.hpp"
 #include "kq_ldsfft.hpp"
-
-void kq_internal_set_error(const char *fmt, ...);
 
 namespace {
 
@@ -281,14 +281,6 @@ __global__ __launch_bounds__(256) void k_spec_rows(CallArgs a) {
 }
 
 size_t decim_lds_bytes(int Dz, int Q) { return (size_t)Dz * Q * sizeof(float2); }
-int frames_threads(int Nf) { return Nf > 4096 ? 1024 : Nf > 1024 ? 256 : 64; }  // (Nf / threads <= 16)
-
-bool smooth7(unsigned n) {
-  if (n == 0) return false;
-  for (unsigned q : {2u, 3u, 5u, 7u})
-    while (n % q == 0) n /= q;
-  return n == 1;
-}
 
 // filter.c:282-293 and 337-357 in the reference's own float arithmetic (the window of every frame)
 float i0f_ref(float const x) {
@@ -315,28 +307,17 @@ void make_kaiser_ref(float *window, unsigned M, float beta) {
   if (M & 1) window[(M - 1) / 2] = 1;
 }
 
-double i0_double(double x) {
-  double const q = 0.25 * x * x;
-  double term = 1, sum = 1;
-  for (int k = 1; k < 500; k++) {
-    term *= q / ((double)k * k);
-    sum += term;
-    if (term < 1e-17 * sum) break;
-  }
-  return sum;
-}
-
 // h[t] = g kaiser(Lh, 3.0)[t] sinc((t - G Dz / 2) / Dz), sum h = 1, designed in double (symmetric by construction), float
 std::vector<float> design_taps(int Dz) {
   if (Dz == 1) return {1.f};
   int const Lh = kGuard * Dz + 1, c = kGuard * Dz / 2;
   std::vector<double> h(Lh);
-  double const a = M_PI * kTapBeta, den = i0_double(a);
+  double const a = M_PI * kTapBeta, den = kq::i0_double(a);
   double sum = 0;
   for (int t = 0; t < Lh; t++) {
     int const u = std::abs(t - c);
     double const pp = (double)u / c;  // |2 t / (Lh - 1) - 1|
-    double const w = i0_double(a * std::sqrt(std::max(0.0, 1.0 - pp * pp))) / den;
+    double const w = kq::i0_double(a * std::sqrt(std::max(0.0, 1.0 - pp * pp))) / den;
     double const xx = (double)u / Dz;
     double const sinc = u == 0 ? 1.0 : std::sin(M_PI * xx) / (M_PI * xx);
     h[t] = w * sinc;
@@ -388,12 +369,10 @@ struct Group {  // analyzers of one (Dz, Nf): one k_spec_decim and one k_spec_fr
 
 }  // namespace
 
-struct kq_spec_bank {
+struct kq_spec_bank : kq::HostSide {
   kq_spec_config cfg;
   std::mutex mu;
   bool dev_ready = false;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
   // stream state
   uint64_t n_cur = 0;  // samples taken since create / reset
   size_t nprev = 0;    // samples of the last call (the history is the last kHist of xbuf[cur])
@@ -415,64 +394,33 @@ struct kq_spec_bank {
   int cnt_half = 0;          // the half the next k_spec_rows reads
   int *d_list = nullptr;  // [all | group lists]
   float2 *xbuf[2] = {nullptr, nullptr};
-  void *d_raw = nullptr;
-  float2 *tw = nullptr;
+  float2 *d_raw = nullptr;     // [max_samples] a host-memory call's samples as they came, whatever their format
+  const float2 *tw = nullptr;  // kq::half_twiddles(kTwLog2): shared, not the bank's to free
 };
-
-#define SPEC_TRY(expr)                                                                                \
-  do {                                                                                                \
-    hipError_t e_ = (expr);                                                                           \
-    if (e_ != hipSuccess) {                                                                           \
-      kq_internal_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return -1;                                                                                      \
-    }                                                                                                 \
-  } while (0)
 
 namespace {
 
 int spec_device(kq_spec_bank *b) {
   if (b->dev_ready) return 0;
   kq_spec_config const &c = b->cfg;
-  if (c.stream) {
-    b->stream = (hipStream_t)c.stream;
-  } else {
-    SPEC_TRY(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
-    b->own_stream = true;
-  }
+  if (b->open_stream(c.stream)) return -1;
   size_t const S = c.max_specs, X = kHist + c.max_samples;
-  std::vector<float2> tw((size_t)1 << (kTwLog2 - 1));
-  for (size_t k = 0; k < tw.size(); k++) {
-    double const ang = -2.0 * M_PI * (double)k / (double)((size_t)1 << kTwLog2);
-    tw[k] = make_float2((float)std::cos(ang), (float)std::sin(ang));
+  if (!(b->tw = kq::half_twiddles(kTwLog2))) {
+    kq_internal_set_error("kq_spec: no twiddle table of period 2^%d", kTwLog2);
+    return -1;
   }
-  SPEC_TRY(hipMalloc(&b->tw, tw.size() * sizeof(float2)));
-  SPEC_TRY(hipMemcpyAsync(b->tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice, b->stream));
-  SPEC_TRY(hipMalloc(&b->d_par, S * sizeof(SpecPar)));
-  SPEC_TRY(hipMalloc(&b->d_cnt, 2 * S * sizeof(SpecCnt)));
-  SPEC_TRY(hipMalloc(&b->d_list, 2 * S * sizeof(int)));
-  for (auto &p : b->xbuf) {
-    SPEC_TRY(hipMalloc(&p, X * sizeof(float2)));
-    SPEC_TRY(hipMemsetAsync(p, 0, X * sizeof(float2), b->stream));
-  }
-  SPEC_TRY(hipMalloc(&b->d_raw, c.max_samples * sizeof(float2)));
-  SPEC_TRY(hipMemsetAsync(b->d_par, 0, S * sizeof(SpecPar), b->stream));
-  SPEC_TRY(hipMemsetAsync(b->d_cnt, 0, 2 * S * sizeof(SpecCnt), b->stream));
-  SPEC_TRY(hipStreamSynchronize(b->stream));
+  if (b->alloc(&b->d_par, S, true) || b->alloc(&b->d_cnt, 2 * S, true) || b->alloc(&b->d_list, 2 * S) ||
+      b->alloc(&b->xbuf[0], X, true) || b->alloc(&b->xbuf[1], X, true) || b->alloc(&b->d_raw, c.max_samples))
+    return -1;
+  KQ_TRY(hipStreamSynchronize(b->stream));
   b->dev_ready = true;
   return 0;
 }
 
-void free_slot_mem(SlotMem &m, bool rows_too) {
-  void *ptrs[] = {m.taps, m.win, m.scale, m.acc, m.fpow, m.y};
-  for (void *q : ptrs)
-    if (q) (void)hipFree(q);
-  m.taps = m.win = m.scale = m.acc = m.fpow = nullptr;
-  m.y = nullptr;
+void free_slot_mem(kq_spec_bank *b, SlotMem &m, bool rows_too) {
+  b->release(&m.taps, &m.win, &m.scale, &m.acc, &m.fpow, &m.y);
   if (rows_too) {
-    if (m.rows) (void)hipFree(m.rows);
-    if (m.meta) (void)hipFree(m.meta);
-    m.rows = nullptr;
-    m.meta = nullptr;
+    b->release(&m.rows, &m.meta);
     m.rowsB = 0;
   }
 }
@@ -497,7 +445,7 @@ int rebuild_lists(kq_spec_bank *b) {
       g.T = p.T;
       g.Q = p.Q;
       g.dthreads = 256;
-      g.fthreads = frames_threads(p.Nf);
+      g.fthreads = kq::fft_threads(p.Nf);
       it = gi.emplace(key, (int)b->groups.size()).first;
       b->groups.push_back(g);
     }
@@ -509,15 +457,15 @@ int rebuild_lists(kq_spec_bank *b) {
     g.n = (int)g.slots.size();
     list.insert(list.end(), g.slots.begin(), g.slots.end());
   }
-  if (!list.empty()) SPEC_TRY(hipMemcpy(b->d_list, list.data(), list.size() * sizeof(int), hipMemcpyHostToDevice));
+  if (!list.empty()) KQ_TRY(hipMemcpy(b->d_list, list.data(), list.size() * sizeof(int), hipMemcpyHostToDevice));
   return 0;
 }
 
 int upload_slot(kq_spec_bank *b, unsigned s) {
-  SPEC_TRY(hipMemcpyAsync(b->d_par + s, &b->par[s], sizeof(SpecPar), hipMemcpyHostToDevice, b->stream));
+  KQ_TRY(hipMemcpyAsync(b->d_par + s, &b->par[s], sizeof(SpecPar), hipMemcpyHostToDevice, b->stream));
   for (int h = 0; h < 2; h++)
-    SPEC_TRY(hipMemcpyAsync(b->d_cnt + h * b->cfg.max_specs + s, &b->cnt[s], sizeof(SpecCnt), hipMemcpyHostToDevice, b->stream));
-  SPEC_TRY(hipStreamSynchronize(b->stream));
+    KQ_TRY(hipMemcpyAsync(b->d_cnt + h * b->cfg.max_specs + s, &b->cnt[s], sizeof(SpecCnt), hipMemcpyHostToDevice, b->stream));
+  KQ_TRY(hipStreamSynchronize(b->stream));
   return 0;
 }
 
@@ -530,7 +478,7 @@ const char *check_params(const kq_spec_params *p) {
     snprintf(why, sizeof why, "decimate %u must be 1..%d", Dz, kMaxDz);
     return why;
   }
-  if (Nf < (unsigned)kMinNf || Nf > (unsigned)kMaxNf || (Nf & 1) || !smooth7(Nf)) {
+  if (Nf < (unsigned)kMinNf || Nf > (unsigned)kMaxNf || (Nf & 1) || !kq::fft_size_ok((int)Nf)) {
     snprintf(why, sizeof why, "fft_size %u must be even, 2^a 3^b 5^c 7^d and %d..%d", Nf, kMinNf, kMaxNf);
     return why;
   }
@@ -605,12 +553,7 @@ int kq_spec_destroy(kq_spec_bank *b) {
   }
   if (b->dev_ready) {
     kq::DeviceScope dev_scope_(b->cfg.device);
-    (void)hipStreamSynchronize(b->stream);
-    for (SlotMem &m : b->mem) free_slot_mem(m, true);
-    void *ptrs[] = {b->d_par, b->d_cnt, b->d_list, b->xbuf[0], b->xbuf[1], b->d_raw, b->tw};
-    for (void *p : ptrs)
-      if (p) (void)hipFree(p);
-    if (b->own_stream) (void)hipStreamDestroy(b->stream);
+    b->close();
   }
   delete b;
   return 0;
@@ -655,7 +598,7 @@ int kq_spec_set(kq_spec_bank *b, unsigned slot, const kq_spec_params *p) {
     kq_internal_set_error("kq_spec_set: no transform plan for fft_size %u", p->fft_size);
     return -1;
   }
-  SPEC_TRY(hipStreamSynchronize(b->stream));
+  KQ_TRY(hipStreamSynchronize(b->stream));
   int const Dz = (int)p->decimate, Nf = (int)p->fft_size, B = (int)p->bins, H = (int)p->hop, K = (int)p->average;
   int const G = Dz > 1 ? kGuard : 0;
   size_t const max_new = (b->cfg.max_samples + Dz - 1) / Dz;
@@ -694,24 +637,19 @@ int kq_spec_set(kq_spec_bank *b, unsigned slot, const kq_spec_params *p) {
   unsigned long long const unpulled = b->cnt[slot].accepted - b->cnt[slot].pulled;
   bool const keep_rows = was && m.rowsB == B;
   if (!was) b->dropped[slot] = 0;
-  free_slot_mem(m, !keep_rows);
+  free_slot_mem(b, m, !keep_rows);
   if (!keep_rows) {
     if (was) b->dropped[slot] += unpulled;
     b->cnt[slot] = SpecCnt{};
-    SPEC_TRY(hipMalloc(&m.rows, (size_t)b->cfg.max_rows * B * sizeof(float)));
-    SPEC_TRY(hipMalloc(&m.meta, (size_t)b->cfg.max_rows * sizeof(kq_spec_row)));
+    if (b->alloc(&m.rows, (size_t)b->cfg.max_rows * B) || b->alloc(&m.meta, (size_t)b->cfg.max_rows)) return -1;
     m.rowsB = B;
   }
-  SPEC_TRY(hipMalloc(&m.taps, taps.size() * sizeof(float)));
-  SPEC_TRY(hipMalloc(&m.win, (size_t)Nf * sizeof(float)));
-  SPEC_TRY(hipMalloc(&m.scale, (size_t)B * sizeof(float)));
-  SPEC_TRY(hipMalloc(&m.acc, (size_t)B * sizeof(float)));
-  SPEC_TRY(hipMalloc(&m.fpow, (size_t)np.fcap * B * sizeof(float)));
-  SPEC_TRY(hipMalloc(&m.y, (size_t)np.R * sizeof(float2)));
-  SPEC_TRY(hipMemcpyAsync(m.taps, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
-  SPEC_TRY(hipMemcpyAsync(m.win, win.data(), (size_t)Nf * sizeof(float), hipMemcpyHostToDevice, b->stream));
-  SPEC_TRY(hipMemcpyAsync(m.scale, scale.data(), (size_t)B * sizeof(float), hipMemcpyHostToDevice, b->stream));
-  SPEC_TRY(hipMemsetAsync(m.acc, 0, (size_t)B * sizeof(float), b->stream));
+  if (b->alloc(&m.taps, taps.size()) || b->alloc(&m.win, (size_t)Nf) || b->alloc(&m.scale, (size_t)B) ||
+      b->alloc(&m.acc, (size_t)B, true) || b->alloc(&m.fpow, (size_t)np.fcap * B) || b->alloc(&m.y, (size_t)np.R))
+    return -1;
+  KQ_TRY(hipMemcpyAsync(m.taps, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
+  KQ_TRY(hipMemcpyAsync(m.win, win.data(), (size_t)Nf * sizeof(float), hipMemcpyHostToDevice, b->stream));
+  KQ_TRY(hipMemcpyAsync(m.scale, scale.data(), (size_t)B * sizeof(float), hipMemcpyHostToDevice, b->stream));
   np.taps = m.taps;
   np.win = m.win;
   np.scale = m.scale;
@@ -738,8 +676,8 @@ int kq_spec_remove(kq_spec_bank *b, unsigned slot) {
     return -1;
   }
   kq::DeviceScope dev_scope_(b->cfg.device);
-  SPEC_TRY(hipStreamSynchronize(b->stream));
-  free_slot_mem(b->mem[slot], true);
+  KQ_TRY(hipStreamSynchronize(b->stream));
+  free_slot_mem(b, b->mem[slot], true);
   b->par[slot] = SpecPar{};
   b->cnt[slot] = SpecCnt{};
   if (upload_slot(b, slot)) return -1;
@@ -770,7 +708,7 @@ int kq_spec_process(kq_spec_bank *b, const void *iq, int format, size_t nsamples
   size_t const esize = format == KQ_IQ_CF32 ? 8 : format == KQ_IQ_S16 ? 4 : 2;
   const void *src = iq;
   if (!on_device) {
-    SPEC_TRY(hipMemcpyAsync(b->d_raw, iq, nsamples * esize, hipMemcpyHostToDevice, b->stream));
+    KQ_TRY(hipMemcpyAsync(b->d_raw, iq, nsamples * esize, hipMemcpyHostToDevice, b->stream));
     src = b->d_raw;
   }
   int const nxt = b->cur ^ 1;
@@ -779,7 +717,7 @@ int kq_spec_process(kq_spec_bank *b, const void *iq, int format, size_t nsamples
     unsigned const blocks = (unsigned)std::min<size_t>((total + 255) / 256, 4096);
     hipLaunchKernelGGL(k_spec_ingest, dim3(blocks), dim3(256), 0, b->stream, src, format, b->cfg.gain_factor, nsamples,
                        (const float2 *)b->xbuf[b->cur], b->nprev, b->xbuf[nxt]);
-    SPEC_TRY(hipGetLastError());
+    KQ_TRY(hipGetLastError());
   }
   uint64_t const n0 = b->n_cur, n1 = n0 + nsamples;
   CallArgs a{};
@@ -803,7 +741,7 @@ int kq_spec_process(kq_spec_bank *b, const void *iq, int format, size_t nsamples
     size_t const lds = decim_lds_bytes(g.Dz, g.Q);
     kq::ensure_dynamic_lds((const void *)k_spec_decim, lds);
     hipLaunchKernelGGL(k_spec_decim, dim3((unsigned)tiles, (unsigned)g.n), dim3(g.dthreads), lds, b->stream, a);
-    SPEC_TRY(hipGetLastError());
+    KQ_TRY(hipGetLastError());
   }
   for (int r = 0; r < rounds; r++) {
     a.round = r;
@@ -820,13 +758,13 @@ int kq_spec_process(kq_spec_bank *b, const void *iq, int format, size_t nsamples
       size_t const lds = (size_t)g.Nf * sizeof(float2);
       kq::ensure_dynamic_lds((const void *)k_spec_frames, lds);
       hipLaunchKernelGGL(k_spec_frames, dim3((unsigned)fr, (unsigned)g.n), dim3(g.fthreads), lds, b->stream, a);
-      SPEC_TRY(hipGetLastError());
+      KQ_TRY(hipGetLastError());
     }
     a.list = b->d_list;
     a.cnt_in = b->d_cnt + (size_t)b->cnt_half * b->cfg.max_specs;
     a.cnt_out = b->d_cnt + (size_t)(b->cnt_half ^ 1) * b->cfg.max_specs;
     hipLaunchKernelGGL(k_spec_rows, dim3((unsigned)((b->maxB + 255) / 256), (unsigned)b->all.size()), dim3(256), 0, b->stream, a);
-    SPEC_TRY(hipGetLastError());
+    KQ_TRY(hipGetLastError());
     b->cnt_half ^= 1;
   }
   // the host's account of the rows, by the rule k_spec_rows applies
@@ -841,7 +779,7 @@ int kq_spec_process(kq_spec_bank *b, const void *iq, int format, size_t nsamples
   b->n_cur = n1;
   b->nprev = nsamples;
   b->cur = nxt;
-  if (!on_device) SPEC_TRY(hipStreamSynchronize(b->stream));
+  if (!on_device) KQ_TRY(hipStreamSynchronize(b->stream));
   return 0;
 }
 
@@ -860,7 +798,7 @@ int kq_spec_pull(kq_spec_bank *b, unsigned slot, float *rows, unsigned max_rows,
     return -1;
   }
   kq::DeviceScope dev_scope_(b->cfg.device);
-  SPEC_TRY(hipStreamSynchronize(b->stream));
+  KQ_TRY(hipStreamSynchronize(b->stream));
   SpecCnt &c = b->cnt[slot];
   SlotMem const &m = b->mem[slot];
   unsigned long long const ready = c.accepted - c.pulled;
@@ -869,14 +807,14 @@ int kq_spec_pull(kq_spec_bank *b, unsigned slot, float *rows, unsigned max_rows,
   for (unsigned i = 0; i < n;) {  // at most two runs: up to the end of the ring, then from its start
     size_t const r = (size_t)((c.pulled + i) % cap);
     unsigned const run = (unsigned)std::min<size_t>(n - i, cap - r);
-    SPEC_TRY(hipMemcpyAsync(rows + (size_t)i * B, m.rows + r * B, (size_t)run * B * sizeof(float), hipMemcpyDeviceToHost, b->stream));
-    if (meta) SPEC_TRY(hipMemcpyAsync(meta + i, m.meta + r, run * sizeof(kq_spec_row), hipMemcpyDeviceToHost, b->stream));
+    KQ_TRY(hipMemcpyAsync(rows + (size_t)i * B, m.rows + r * B, (size_t)run * B * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    if (meta) KQ_TRY(hipMemcpyAsync(meta + i, m.meta + r, run * sizeof(kq_spec_row), hipMemcpyDeviceToHost, b->stream));
     i += run;
   }
   c.pulled += n;
   for (int h = 0; h < 2; h++)
-    SPEC_TRY(hipMemcpyAsync(b->d_cnt + h * b->cfg.max_specs + slot, &c, sizeof c, hipMemcpyHostToDevice, b->stream));
-  SPEC_TRY(hipStreamSynchronize(b->stream));
+    KQ_TRY(hipMemcpyAsync(b->d_cnt + h * b->cfg.max_specs + slot, &c, sizeof c, hipMemcpyHostToDevice, b->stream));
+  KQ_TRY(hipStreamSynchronize(b->stream));
   return (int)n;
 }
 
@@ -913,7 +851,7 @@ int kq_spec_sync(kq_spec_bank *b) {
   std::lock_guard<std::mutex> lk(b->mu);
   if (!b->dev_ready) return 0;
   kq::DeviceScope dev_scope_(b->cfg.device);
-  SPEC_TRY(hipStreamSynchronize(b->stream));
+  KQ_TRY(hipStreamSynchronize(b->stream));
   return 0;
 }
 
@@ -927,19 +865,19 @@ int kq_spec_reset(kq_spec_bank *b) {
   b->nprev = 0;
   if (!b->dev_ready) return 0;
   kq::DeviceScope dev_scope_(b->cfg.device);
-  SPEC_TRY(hipStreamSynchronize(b->stream));
+  KQ_TRY(hipStreamSynchronize(b->stream));
   size_t const X = kHist + b->cfg.max_samples;
-  for (auto &p : b->xbuf) SPEC_TRY(hipMemsetAsync(p, 0, X * sizeof(float2), b->stream));
+  for (auto &p : b->xbuf) KQ_TRY(hipMemsetAsync(p, 0, X * sizeof(float2), b->stream));
   for (int s : b->all) {
     b->par[s].s0 = 0;
     b->cnt[s] = SpecCnt{};
-    SPEC_TRY(hipMemsetAsync(b->mem[s].acc, 0, (size_t)b->par[s].B * sizeof(float), b->stream));
+    KQ_TRY(hipMemsetAsync(b->mem[s].acc, 0, (size_t)b->par[s].B * sizeof(float), b->stream));
   }
-  SPEC_TRY(hipMemcpyAsync(b->d_par, b->par.data(), b->par.size() * sizeof(SpecPar), hipMemcpyHostToDevice, b->stream));
+  KQ_TRY(hipMemcpyAsync(b->d_par, b->par.data(), b->par.size() * sizeof(SpecPar), hipMemcpyHostToDevice, b->stream));
   for (int h = 0; h < 2; h++)
-    SPEC_TRY(hipMemcpyAsync(b->d_cnt + h * b->cfg.max_specs, b->cnt.data(), b->cnt.size() * sizeof(SpecCnt), hipMemcpyHostToDevice,
+    KQ_TRY(hipMemcpyAsync(b->d_cnt + h * b->cfg.max_specs, b->cnt.data(), b->cnt.size() * sizeof(SpecCnt), hipMemcpyHostToDevice,
                             b->stream));
-  SPEC_TRY(hipStreamSynchronize(b->stream));
+  KQ_TRY(hipStreamSynchronize(b->stream));
   return 0;
 }
 

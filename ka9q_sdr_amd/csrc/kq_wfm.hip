@@ -25,10 +25,10 @@
 #include <vector>
 
 #include "ka9q_hip.h"
+#include "kq_design.hpp"
 #include "kq_device.hpp"
+#include "kq_host.hpp"
 #include "kq_ldsfft.hpp"
-
-void kq_internal_set_error(const char *fmt, ...);
 
 namespace {
 
@@ -37,7 +37,7 @@ using kq::FftDim;
 constexpr unsigned kMaxSlots = 4096;
 constexpr int kMaxN = 16384;
 constexpr int kTwLog2 = 14;      // half-circle twiddles of period 16384 serve every power of two <= kMaxN
-constexpr int kPer = 16;         // transform points per thread at most (wfm_threads)
+constexpr int kPer = 16;         // transform points per thread at most (kq::fft_threads)
 constexpr double kPilotHz = 19000.0, kAudioHz = 15000.0;
 
 struct WfmPar {  // per slot, written by the host at kq_wfm_set
@@ -285,15 +285,6 @@ __global__ __launch_bounds__(1024) void k_wfm_audio(CallArgs a) {
   }
 }
 
-int wfm_threads(int N) { return N > 4096 ? 1024 : N > 1024 ? 256 : 64; }  // N / threads <= kPer
-
-bool smooth7(unsigned n) {
-  if (n == 0) return false;
-  for (unsigned q : {2u, 3u, 5u, 7u})
-    while (n % q == 0) n /= q;
-  return n == 1;
-}
-
 // ---- host design, in double ----------------------------------------------------------------------------------------
 using cd = std::complex<double>;
 
@@ -326,27 +317,16 @@ std::vector<cd> dft(const std::vector<cd> &x, int sign) {
   return out;
 }
 
-double i0_double(double x) {
-  double const q = 0.25 * x * x;
-  double term = 1, sum = 1;
-  for (int k = 1; k < 500; k++) {
-    term *= q / ((double)k * k);
-    sum += term;
-    if (term < 1e-17 * sum) break;
-  }
-  return sum;
-}
-
 // window_filter (filter.c:365-413) in double: R on the N bins -> H; returned as float H / N (the kernels' transforms are
 // unnormalised)
 std::vector<float2> window_design(const std::vector<cd> &R, int M, double beta) {
   int const N = (int)R.size();
   std::vector<cd> t = dft(R, +1);
   std::vector<double> w(M);
-  double const den = i0_double(M_PI * beta);
+  double const den = kq::i0_double(M_PI * beta);
   for (int n = 0; n < M; n++) {
     double const pp = 2.0 * n / (M - 1) - 1.0;
-    w[n] = i0_double(M_PI * beta * std::sqrt(std::max(0.0, 1.0 - pp * pp))) / den;
+    w[n] = kq::i0_double(M_PI * beta * std::sqrt(std::max(0.0, 1.0 - pp * pp))) / den;
   }
   std::vector<cd> bb((size_t)N, 0.0);
   for (int n = 0; n < M; n++) bb[n] = t[(size_t)((n - M / 2 + N) % N)] * w[n] / (double)N;
@@ -375,12 +355,10 @@ std::vector<float2> design_pilot(int N, int M, double beta, double Fc, double bw
 
 }  // namespace
 
-struct kq_wfm_bank {
+struct kq_wfm_bank : kq::HostSide {
   kq_wfm_config cfg;
   std::mutex mu;
   bool dev_ready = false;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
   WfmGeom g{};
   uint64_t n_cur = 0;
   std::vector<WfmPar> par;
@@ -393,23 +371,14 @@ struct kq_wfm_bank {
   float *d_x = nullptr, *d_d = nullptr, *d_sig = nullptr;
   float4 *d_fst = nullptr;
   int *d_flag = nullptr;
-  float2 *d_tw = nullptr, *d_hp = nullptr;
+  float2 *d_hp = nullptr;
   // host-memory calls
   float *d_stage = nullptr;
-  size_t stage_rows = 0;
+  size_t stage_cap = 0;  // floats: source rows x max_samples
   float *d_out = nullptr;
   kq_wfm_status *d_st = nullptr;
   std::vector<int> rowmap;
 };
-
-#define WFM_TRY(expr)                                                                                 \
-  do {                                                                                                \
-    hipError_t e_ = (expr);                                                                           \
-    if (e_ != hipSuccess) {                                                                           \
-      kq_internal_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return -1;                                                                                      \
-    }                                                                                                 \
-  } while (0)
 
 namespace {
 
@@ -424,35 +393,19 @@ int wfm_device(kq_wfm_bank *b) {
     kq_internal_set_error("kq_wfm: no transform plan for N %d / N / Da %d", g.N, g.Ndec);
     return -1;
   }
-  if (c.stream) {
-    b->stream = (hipStream_t)c.stream;
-  } else {
-    WFM_TRY(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
-    b->own_stream = true;
-  }
+  if (b->open_stream(c.stream)) return -1;
   size_t const S = c.max_slots;
-  std::vector<float2> tw((size_t)1 << (kTwLog2 - 1));
-  for (size_t k = 0; k < tw.size(); k++) {
-    double const ang = -2.0 * M_PI * (double)k / (double)((size_t)1 << kTwLog2);
-    tw[k] = make_float2((float)std::cos(ang), (float)std::sin(ang));
+  if (!(g.tw = kq::half_twiddles(kTwLog2))) {  // shared, not the bank's to free
+    kq_internal_set_error("kq_wfm: no twiddle table of period 2^%d", kTwLog2);
+    return -1;
   }
   std::vector<float2> hp = design_pilot(g.N, g.M, c.kaiser_beta, c.comp_rate, c.pilot_bw);
-  WFM_TRY(hipMalloc(&b->d_tw, tw.size() * sizeof(float2)));
-  WFM_TRY(hipMalloc(&b->d_hp, hp.size() * sizeof(float2)));
-  WFM_TRY(hipMemcpyAsync(b->d_tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice, b->stream));
-  WFM_TRY(hipMemcpyAsync(b->d_hp, hp.data(), hp.size() * sizeof(float2), hipMemcpyHostToDevice, b->stream));
-  WFM_TRY(hipMalloc(&b->d_par, S * sizeof(WfmPar)));
-  WFM_TRY(hipMalloc(&b->d_list, S * sizeof(int)));
-  WFM_TRY(hipMalloc(&b->d_rowmap, S * sizeof(int)));
-  WFM_TRY(hipMalloc(&b->d_x, S * g.Rx * sizeof(float)));
-  WFM_TRY(hipMalloc(&b->d_d, S * g.Rd * sizeof(float)));
-  WFM_TRY(hipMalloc(&b->d_fst, S * g.Fmax * sizeof(float4)));
-  WFM_TRY(hipMalloc(&b->d_sig, S * g.Fmax * sizeof(float)));
-  WFM_TRY(hipMalloc(&b->d_flag, S * sizeof(int)));
-  WFM_TRY(hipMemsetAsync(b->d_par, 0, S * sizeof(WfmPar), b->stream));
-  WFM_TRY(hipMemsetAsync(b->d_flag, 0, S * sizeof(int), b->stream));
-  WFM_TRY(hipStreamSynchronize(b->stream));
-  g.tw = b->d_tw;
+  if (b->alloc(&b->d_hp, hp.size()) || b->alloc(&b->d_par, S, true) || b->alloc(&b->d_list, S) || b->alloc(&b->d_rowmap, S) ||
+      b->alloc(&b->d_x, S * g.Rx) || b->alloc(&b->d_d, S * g.Rd) || b->alloc(&b->d_fst, S * g.Fmax) ||
+      b->alloc(&b->d_sig, S * g.Fmax) || b->alloc(&b->d_flag, S, true))
+    return -1;
+  KQ_TRY(hipMemcpyAsync(b->d_hp, hp.data(), hp.size() * sizeof(float2), hipMemcpyHostToDevice, b->stream));
+  KQ_TRY(hipStreamSynchronize(b->stream));
   g.hp = b->d_hp;
   b->dev_ready = true;
   return 0;
@@ -460,20 +413,20 @@ int wfm_device(kq_wfm_bank *b) {
 
 // zero history, flag off (the stream is idle: callers synchronised it)
 int cold_start(kq_wfm_bank *b, unsigned s) {
-  WFM_TRY(hipMemsetAsync(b->d_x + (size_t)s * b->g.Rx, 0, b->g.Rx * sizeof(float), b->stream));
-  WFM_TRY(hipMemsetAsync(b->d_d + (size_t)s * b->g.Rd, 0, b->g.Rd * sizeof(float), b->stream));
-  WFM_TRY(hipMemsetAsync(b->d_flag + s, 0, sizeof(int), b->stream));
+  KQ_TRY(hipMemsetAsync(b->d_x + (size_t)s * b->g.Rx, 0, b->g.Rx * sizeof(float), b->stream));
+  KQ_TRY(hipMemsetAsync(b->d_d + (size_t)s * b->g.Rd, 0, b->g.Rd * sizeof(float), b->stream));
+  KQ_TRY(hipMemsetAsync(b->d_flag + s, 0, sizeof(int), b->stream));
   return 0;
 }
 
 int upload(kq_wfm_bank *b, unsigned s) {
-  WFM_TRY(hipMemcpyAsync(b->d_par + s, &b->par[s], sizeof(WfmPar), hipMemcpyHostToDevice, b->stream));
+  KQ_TRY(hipMemcpyAsync(b->d_par + s, &b->par[s], sizeof(WfmPar), hipMemcpyHostToDevice, b->stream));
   b->all.clear();
   for (unsigned k = 0; k < b->cfg.max_slots; k++)
     if (b->par[k].active) b->all.push_back((int)k);
   if (!b->all.empty())
-    WFM_TRY(hipMemcpyAsync(b->d_list, b->all.data(), b->all.size() * sizeof(int), hipMemcpyHostToDevice, b->stream));
-  WFM_TRY(hipStreamSynchronize(b->stream));
+    KQ_TRY(hipMemcpyAsync(b->d_list, b->all.data(), b->all.size() * sizeof(int), hipMemcpyHostToDevice, b->stream));
+  KQ_TRY(hipStreamSynchronize(b->stream));
   return 0;
 }
 
@@ -515,7 +468,7 @@ kq_wfm_bank *kq_wfm_create(const kq_wfm_config *cfg) {
     return nullptr;
   }
   unsigned long const N = (unsigned long)L + M - 1;
-  if (N > (unsigned long)kMaxN || (N & 1) || !smooth7((unsigned)N)) {
+  if (N > (unsigned long)kMaxN || (N & 1) || !kq::fft_size_ok((int)N)) {
     kq_internal_set_error("kq_wfm_create: N = L + M - 1 = %lu must be even, 2^a 3^b 5^c 7^d and <= %d", N, kMaxN);
     return nullptr;
   }
@@ -552,7 +505,7 @@ kq_wfm_bank *kq_wfm_create(const kq_wfm_config *cfg) {
   g.Ndec = (int)(N / Da);
   g.Lo = (int)(L / Da);
   g.skip = (int)((M - 1) / Da);
-  g.nthr = wfm_threads(g.N);
+  g.nthr = kq::fft_threads(g.N);
   g.Fmax = (int)((cfg->max_samples + L - 1) / L);
   g.Rx = cfg->max_samples + L - 1 + (M - 1) + g.D;
   g.Rd = (size_t)g.Fmax * L + M - 1;
@@ -569,13 +522,7 @@ int kq_wfm_destroy(kq_wfm_bank *b) {
   }
   if (b->dev_ready) {
     kq::DeviceScope dev_scope_(b->cfg.device);
-    (void)hipStreamSynchronize(b->stream);
-    for (auto &kv : b->hm) (void)hipFree(kv.second);
-    void *ptrs[] = {b->d_par, b->d_list, b->d_rowmap, b->d_x, b->d_d, b->d_sig, b->d_fst, b->d_flag, b->d_tw, b->d_hp,
-                    b->d_stage, b->d_out, b->d_st};
-    for (void *p : ptrs)
-      if (p) (void)hipFree(p);
-    if (b->own_stream) (void)hipStreamDestroy(b->stream);
+    b->close();
   }
   delete b;
   return 0;
@@ -605,13 +552,13 @@ int kq_wfm_set(kq_wfm_bank *b, unsigned slot, const kq_wfm_params *p) {
   }
   kq::DeviceScope dev_scope_(b->cfg.device);
   if (wfm_device(b)) return -1;
-  WFM_TRY(hipStreamSynchronize(b->stream));
+  KQ_TRY(hipStreamSynchronize(b->stream));
   auto it = b->hm.find(p->deemph_us);
   if (it == b->hm.end()) {
     std::vector<float2> h = design_mono(b->g.N, b->g.M, b->cfg.kaiser_beta, b->cfg.comp_rate, p->deemph_us);
     float2 *d = nullptr;
-    WFM_TRY(hipMalloc(&d, h.size() * sizeof(float2)));
-    WFM_TRY(hipMemcpy(d, h.data(), h.size() * sizeof(float2), hipMemcpyHostToDevice));
+    if (b->alloc(&d, h.size())) return -1;
+    KQ_TRY(hipMemcpy(d, h.data(), h.size() * sizeof(float2), hipMemcpyHostToDevice));
     it = b->hm.emplace(p->deemph_us, d).first;
   }
   WfmPar np{};
@@ -641,7 +588,7 @@ int kq_wfm_remove(kq_wfm_bank *b, unsigned slot) {
     return -1;
   }
   kq::DeviceScope dev_scope_(b->cfg.device);
-  WFM_TRY(hipStreamSynchronize(b->stream));
+  KQ_TRY(hipStreamSynchronize(b->stream));
   b->par[slot] = WfmPar{};
   return upload(b, slot);
 }
@@ -719,23 +666,19 @@ int kq_wfm_process(kq_wfm_bank *b, const float *comp, size_t src_stride, size_t 
       if (it == rows.end()) it = rows.emplace(src, (int)rows.size()).first;
       b->rowmap[i] = it->second;
     }
-    if (rows.size() > b->stage_rows) {
-      if (b->d_stage) WFM_TRY(hipFree(b->d_stage));
-      b->d_stage = nullptr;
-      WFM_TRY(hipMalloc(&b->d_stage, rows.size() * b->cfg.max_samples * sizeof(float)));
-      b->stage_rows = rows.size();
-    }
+    // (grow waits for the stream, which is idle here: the last host-memory call ended in a synchronise, so it returns at once)
+    if (b->grow(&b->d_stage, &b->stage_cap, rows.size() * b->cfg.max_samples)) return -1;
     for (auto const &kv : rows)
-      WFM_TRY(hipMemcpy2DAsync(b->d_stage + (size_t)kv.second * ncall, block_len * sizeof(float), comp + (size_t)kv.first * src_stride,
+      KQ_TRY(hipMemcpy2DAsync(b->d_stage + (size_t)kv.second * ncall, block_len * sizeof(float), comp + (size_t)kv.first * src_stride,
                                (nblocks > 1 ? row_stride : block_len) * sizeof(float), block_len * sizeof(float), nblocks,
                                hipMemcpyHostToDevice, b->stream));
-    WFM_TRY(hipMemcpyAsync(b->d_rowmap, b->rowmap.data(), nlist * sizeof(int), hipMemcpyHostToDevice, b->stream));
+    KQ_TRY(hipMemcpyAsync(b->d_rowmap, b->rowmap.data(), nlist * sizeof(int), hipMemcpyHostToDevice, b->stream));
     a.comp = b->d_stage;
     a.src_stride = ncall;
     a.row_stride = block_len;
     a.rowmap = b->d_rowmap;
-    if (out && !b->d_out) WFM_TRY(hipMalloc(&b->d_out, S * 2 * (size_t)g.Fmax * g.Lo * sizeof(float)));
-    if (status && !b->d_st) WFM_TRY(hipMalloc(&b->d_st, S * (size_t)g.Fmax * sizeof(kq_wfm_status)));
+    if (out && !b->d_out && b->alloc(&b->d_out, S * 2 * (size_t)g.Fmax * g.Lo)) return -1;
+    if (status && !b->d_st && b->alloc(&b->d_st, S * (size_t)g.Fmax)) return -1;
     a.out = out ? b->d_out : nullptr;
     a.ostride = 2 * (size_t)g.Fmax * g.Lo;
     a.st = status ? b->d_st : nullptr;
@@ -744,18 +687,18 @@ int kq_wfm_process(kq_wfm_bank *b, const float *comp, size_t src_stride, size_t 
   {
     unsigned const chunks = (unsigned)std::min<size_t>((ncall + 255) / 256, 1024);
     hipLaunchKernelGGL(k_wfm_ingest, dim3(chunks, (unsigned)nlist), dim3(256), 0, b->stream, a, ncall);
-    WFM_TRY(hipGetLastError());
+    KQ_TRY(hipGetLastError());
   }
   if (F > 0) {
     size_t const lds = (size_t)g.N * sizeof(float2);
     kq::ensure_dynamic_lds((const void *)k_wfm_pilot, lds);
     kq::ensure_dynamic_lds((const void *)k_wfm_audio, lds);
     hipLaunchKernelGGL(k_wfm_pilot, dim3((unsigned)F, (unsigned)nlist), dim3(g.nthr), lds, b->stream, a);
-    WFM_TRY(hipGetLastError());
+    KQ_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_wfm_flags, dim3((unsigned)((nlist + 63) / 64)), dim3(64), 0, b->stream, a, (int)nlist);
-    WFM_TRY(hipGetLastError());
+    KQ_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_wfm_audio, dim3((unsigned)F, (unsigned)nlist), dim3(g.nthr), lds, b->stream, a);
-    WFM_TRY(hipGetLastError());
+    KQ_TRY(hipGetLastError());
   }
   if (!on_device) {
     // copy back the rows of the active slots, a run of consecutive slots at a time
@@ -764,15 +707,15 @@ int kq_wfm_process(kq_wfm_bank *b, const float *comp, size_t src_stride, size_t 
       while (j < nlist && b->all[j] == b->all[j - 1] + 1) j++;
       size_t const s0 = (size_t)b->all[i], n = j - i;
       if (out)
-        WFM_TRY(hipMemcpy2DAsync(out + s0 * out_stride, out_stride * sizeof(float), b->d_out + s0 * a.ostride, a.ostride * sizeof(float),
+        KQ_TRY(hipMemcpy2DAsync(out + s0 * out_stride, out_stride * sizeof(float), b->d_out + s0 * a.ostride, a.ostride * sizeof(float),
                                  (size_t)2 * F * g.Lo * sizeof(float), n, hipMemcpyDeviceToHost, b->stream));
       if (status)
-        WFM_TRY(hipMemcpy2DAsync(status + s0 * status_stride, status_stride * sizeof(kq_wfm_status), b->d_st + s0 * a.sstride,
+        KQ_TRY(hipMemcpy2DAsync(status + s0 * status_stride, status_stride * sizeof(kq_wfm_status), b->d_st + s0 * a.sstride,
                                  a.sstride * sizeof(kq_wfm_status), (size_t)F * sizeof(kq_wfm_status), n, hipMemcpyDeviceToHost,
                                  b->stream));
       i = j;
     }
-    WFM_TRY(hipStreamSynchronize(b->stream));
+    KQ_TRY(hipStreamSynchronize(b->stream));
   }
   b->n_cur = n1;  // only once everything is queued: a call that fails leaves the stream index where it was
   return F;
@@ -786,7 +729,7 @@ int kq_wfm_sync(kq_wfm_bank *b) {
   std::lock_guard<std::mutex> lk(b->mu);
   if (!b->dev_ready) return 0;
   kq::DeviceScope dev_scope_(b->cfg.device);
-  WFM_TRY(hipStreamSynchronize(b->stream));
+  KQ_TRY(hipStreamSynchronize(b->stream));
   return 0;
 }
 
@@ -799,10 +742,10 @@ int kq_wfm_reset(kq_wfm_bank *b) {
   b->n_cur = 0;
   if (!b->dev_ready) return 0;
   kq::DeviceScope dev_scope_(b->cfg.device);
-  WFM_TRY(hipStreamSynchronize(b->stream));
+  KQ_TRY(hipStreamSynchronize(b->stream));
   for (int s : b->all)
     if (cold_start(b, (unsigned)s)) return -1;
-  WFM_TRY(hipStreamSynchronize(b->stream));
+  KQ_TRY(hipStreamSynchronize(b->stream));
   return 0;
 }
 

@@ -7,7 +7,7 @@ import ctypes as C
 
 import numpy as np
 
-from .bank import KqError, _err, load_library
+from .bank import Handle, KqError, _err, load_library
 
 
 class DecimConfig(C.Structure):
@@ -29,25 +29,18 @@ def _bind(L):
     return L
 
 
-class Decimator:
+class Decimator(Handle):
     """Cascade of log_decimate half-band stages with carried state (hackrf.c:211-216, 295-300)."""
+    _destroy = "kq_decim_destroy"
 
     def __init__(self, log_decimate, stage_threshold=8, offset=1, filter_atten=0.0, max_out=1 << 16, device=0,
                  stream=None):
-        self.L = _bind(load_library())
+        self.lib = self.L = _bind(load_library())
         cfg = DecimConfig(device, log_decimate, stage_threshold, offset, filter_atten, max_out, stream)
         self.h = self.L.kq_decim_create(C.byref(cfg))
         if not self.h:
             raise KqError("kq_decim_create: " + _err(self.L))
         self.log_decimate = log_decimate
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.kq_decim_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        self.close()
 
     def process(self, iq, want_s16=True):
         """iq: complex64[n_out << log_decimate] on the host -> (complex64[n_out], int16[n_out, 2] | None, energy)"""

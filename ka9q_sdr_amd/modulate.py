@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from .bank import KqError, _err, load_library
+from .bank import Handle, KqError, _err, load_library
 
 KQ_MOD_LINEAR, KQ_MOD_FM = 0, 1
 KQ_PCM_F32, KQ_PCM_S16 = 0, 2   # enum kq_pcm_format (KQ_PCM_S16BE = 1 is the AFSK decoder's)
@@ -55,8 +55,9 @@ def _bind(L):
     return L
 
 
-class ModBank:
+class ModBank(Handle):
     """Up to max_stations modulate.c stations on one output geometry (Fs, L, M, interp), summed."""
+    _destroy = "kq_mod_destroy"
 
     def __init__(self, samprate, L, M, interp, max_stations, max_blocks, device=0, stream=None):
         self.lib = _bind(load_library())
@@ -68,19 +69,6 @@ class ModBank:
         self.N = L + M - 1
         self.max_stations, self.max_blocks = max_stations, max_blocks
         self._slots = set()   # occupied slots: the C side reads host rows 0 .. max(self._slots)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.kq_mod_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        self.close()
-
-    def _chk(self, rc, what):
-        if rc < 0:
-            raise KqError("%s: %s" % (what, _err(self.lib)))
-        return rc
 
     def set_station(self, slot, cfg):
         """add a station to `slot` or change the one there (a StationConfig, e.g. from station_config())"""

@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from .bank import KqError, _err, load_library
+from .bank import Handle, KqError, _err, load_library
 
 KQ_PCM_F32, KQ_PCM_S16BE = 0, 1
 
@@ -39,29 +39,17 @@ def _bind(L):
     return L
 
 
-class AfskBank:
+class AfskBank(Handle):
     """`sessions` independent packet.c sessions decoded in lock step on one GPU."""
+    _destroy = "kq_afsk_destroy"
 
     def __init__(self, sessions, max_frames=64, device=0, stream=None):
-        self.L = _bind(load_library())
+        self.lib = self.L = _bind(load_library())
         cfg = AfskConfig(device, sessions, max_frames, stream)
         self.h = self.L.kq_afsk_create(C.byref(cfg))
         if not self.h:
             raise KqError("kq_afsk_create: " + _err(self.L))
         self.sessions = sessions
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.kq_afsk_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        self.close()
-
-    def _chk(self, rc, what):
-        if rc < 0:
-            raise KqError(what + ": " + _err(self.L))
-        return rc
 
     def push(self, samples):
         """samples: float32[sessions, n] (host).  Returns blocks decoded per session."""

@@ -7,7 +7,7 @@ from fractions import Fraction
 
 import numpy as np
 
-from .bank import KQ_IQ_CF32, KQ_IQ_S16, KQ_IQ_S8, KqError, _err, load_library
+from .bank import KQ_IQ_CF32, KQ_IQ_S16, KQ_IQ_S8, Handle, KqError, _err, load_library
 
 MAX_SPECS, MAX_DECIMATE, MIN_FFT, MAX_FFT = 4096, 256, 16, 16384
 
@@ -99,8 +99,9 @@ def _iq_format(dtype, shape):
     raise TypeError("I/Q must be complex64, int16 or int8 (got %s)" % dtype)
 
 
-class SpecBank:
+class SpecBank(Handle):
     """Up to max_specs analyzers over one I/Q stream of samprate samples per second."""
+    _destroy = "kq_spec_destroy"
 
     def __init__(self, samprate, max_specs, max_samples, max_rows=64, gain_factor=1.0, device=0, stream=None):
         self.lib = _bind(load_library())
@@ -110,19 +111,6 @@ class SpecBank:
             raise KqError("kq_spec_create: " + _err(self.lib))
         self.samprate, self.max_specs, self.max_samples, self.max_rows = samprate, max_specs, max_samples, max_rows
         self._bins = {}
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.kq_spec_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        self.close()
-
-    def _chk(self, rc, what):
-        if rc < 0:
-            raise KqError("%s: %s" % (what, _err(self.lib)))
-        return rc
 
     def set(self, slot, params=None, **kw):
         """add or replace the analyzer in `slot`: a SpecParams, or spec_params() keywords"""

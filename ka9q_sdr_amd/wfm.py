@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from .bank import KqError, _err, load_library
+from .bank import Handle, KqError, _err, load_library
 
 MAX_SLOTS = 4096
 PILOT_HZ = 19000.0
@@ -51,9 +51,10 @@ def _bind(L):
     return L
 
 
-class WfmBank:
+class WfmBank(Handle):
     """Up to max_slots stereo decoders on one composite geometry (Fc = comp_rate, Da = decimate, frames of L, filters of M).
     For process_bank, create it on the receiver bank's stream: WfmBank.beside(bank, ...)."""
+    _destroy = "kq_wfm_destroy"
 
     def __init__(self, comp_rate, decimate, L, M, max_slots, max_samples, kaiser_beta=3.0, pilot_bw=1000.0, device=0,
                  stream=None):
@@ -74,19 +75,6 @@ class WfmBank:
         rate = bank.samprate // bank.D
         return cls(rate, decimate, L, M, max_slots, bank.max_blocks * bank.olen, kaiser_beta, pilot_bw,
                    stream=lib.kq_bank_stream(bank.h))
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.kq_wfm_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        self.close()
-
-    def _chk(self, rc, what):
-        if rc < 0:
-            raise KqError("%s: %s" % (what, _err(self.lib)))
-        return rc
 
     def set(self, slot, params=None, **kw):
         """put a decoder in `slot` (a WfmParams, or wfm_params() keywords); it starts cold at the next call"""
