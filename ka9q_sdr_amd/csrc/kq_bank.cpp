@@ -28,12 +28,14 @@
 
 #include "kq_design.hpp"
 #include "kq_device.hpp"
+#include "kq_host.hpp"
 
 namespace {
-
 thread_local std::string g_err;
+}
 
-void set_err(const char *fmt, ...) {
+// the text kq_last_error() returns: every translation unit of the library reports through this (kq_host.hpp)
+void kq_internal_set_error(const char *fmt, ...) {
   char buf[512];
   va_list ap;
   va_start(ap, fmt);
@@ -42,23 +44,16 @@ void set_err(const char *fmt, ...) {
   g_err = buf;
 }
 
-// launch errors are sticky until read: name the launch group that failed
-#define LAUNCH_CHECK(what)                                                          \
-  do {                                                                              \
-    hipError_t e_ = hipGetLastError();                                              \
-    if (e_ != hipSuccess) {                                                         \
-      set_err("kernel launch failed in %s: %s", what, hipGetErrorString(e_));       \
-      return -1;                                                                    \
-    }                                                                               \
-  } while (0)
+namespace {
 
-#define HIP_TRY(expr)                                                                  \
-  do {                                                                                 \
-    hipError_t e_ = (expr);                                                            \
-    if (e_ != hipSuccess) {                                                            \
-      set_err("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return -1;                                                                       \
-    }                                                                                  \
+// launch errors are sticky until read: name the launch group that failed
+#define LAUNCH_CHECK(what)                                                                        \
+  do {                                                                                            \
+    hipError_t e_ = hipGetLastError();                                                            \
+    if (e_ != hipSuccess) {                                                                       \
+      kq_internal_set_error("kernel launch failed in %s: %s", what, hipGetErrorString(e_));       \
+      return -1;                                                                                  \
+    }                                                                                             \
   } while (0)
 
 // One NCO in closed form.  `frozen` mirrors osc.c:43: an oscillator whose set frequency is zero
@@ -146,7 +141,7 @@ struct EventPair {
 
 }  // namespace
 
-struct kq_bank {
+struct kq_bank : kq::HostSide {
   // One lock per handle, taken by every entry point: a receiver thread in its process / push / pull loop and an operator's
   // thread changing filters, modes and frequencies (display.c / radio_status.c beside the demodulator threads of the
   // reference) may share a bank.  The entry points that wait for the device to catch up (kq_bank_pull_wait, _host_io_wait,
@@ -154,8 +149,6 @@ struct kq_bank {
   std::recursive_mutex mu;
   kq_bank_config cfg;
   kq::Geom g;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
   int fwd_mode = KQ_FWD_FULL;
   // The demodulators are latency-bound and independent of the next batch's filter pass, so they run on a
   // second stream: filter(k+1) overlaps demod(k).  Planes the two stages hand over are double buffered.
@@ -241,12 +234,12 @@ struct kq_bank {
   bool pcm_on = false;
   short *pcm = nullptr;       // [C][max_blocks][2*olen] int16, network byte order
   unsigned *pcm_mask = nullptr;  // [C][max_blocks]
-  void *stage_dev = nullptr;  // staging for host-side raw I/Q before conversion
+  unsigned char *stage_dev = nullptr;  // staging for host-side raw I/Q before conversion
   size_t stage_cap = 0;
   // streaming host I/O (kq_bank_push_iq_async / kq_bank_pull_planes_async): copy streams of their own, two input staging
   // buffers, events that order them against the kernels
   hipStream_t copy_in = nullptr, copy_out = nullptr;
-  void *in_stage[2] = {nullptr, nullptr};
+  unsigned char *in_stage[2] = {nullptr, nullptr};
   size_t in_stage_cap[2] = {0, 0};
   bool in_used[2] = {false, false};  // in_ready[k] has been recorded at least once
   hipEvent_t in_ready[2] = {nullptr, nullptr}, in_free[2] = {nullptr, nullptr};
@@ -372,10 +365,11 @@ struct kq_bank {
 
 namespace {
 
+// a buffer made after create, cleared before the call returns: whichever of the bank's streams reads it first finds zeros
 template <typename T>
-int dev_alloc(T **p, size_t n) {
-  HIP_TRY(hipMalloc((void **)p, n * sizeof(T)));
-  HIP_TRY(hipMemset(*p, 0, n * sizeof(T)));
+int alloc_cleared(kq_bank *b, T **p, size_t n) {
+  if (b->alloc(p, n)) return -1;
+  KQ_TRY(hipMemset(*p, 0, n * sizeof(T)));
   return 0;
 }
 
@@ -454,7 +448,7 @@ int ctl_room(kq_bank *b, int side, size_t bytes) {
   kq_bank::CtlQueue &q = b->ctl[side];
   size_t const payload_cap = kq_bank::CtlQueue::kBytes - kq_bank::CtlQueue::kMaxRec * sizeof(CtlRecHost);
   if (bytes > payload_cap) {
-    set_err("control-plane write of %zu bytes exceeds the queue", bytes);
+    kq_internal_set_error("control-plane write of %zu bytes exceeds the queue", bytes);
     return -1;
   }
   if (q.nrec >= kq_bank::CtlQueue::kMaxRec || q.used + bytes > payload_cap) return ctl_flush_now(b);
@@ -567,20 +561,20 @@ int design_flush(kq_bank *b, const void *ctl_queue = nullptr, unsigned ctl_recor
   if (d.jobs.empty()) return 0;
   int const p = (int)(d.epoch & 1);
   unsigned const n = (unsigned)d.jobs.size();
-  if (d.read_set[d.cur]) HIP_TRY(hipEventSynchronize(d.read[d.cur]));  // (kDepth launches ago)
+  if (d.read_set[d.cur]) KQ_TRY(hipEventSynchronize(d.read[d.cur]));  // (kDepth launches ago)
   unsigned char *pin = d.pin[d.cur];
   memcpy(pin, d.jobs.data(), n * sizeof(kq::DesignJob));
   memcpy(pin + kq_bank::DesignQueue::kMax * sizeof(kq::DesignJob), d.targets.data(), n * sizeof(kq::DesignTarget));
   // ng_next[p] was last written two design launches ago; the records that moved those values on ran on the demodulators' stream
-  if (d.ng_moved_set[p]) HIP_TRY(hipStreamWaitEvent(b->stream, d.ng_moved[p], 0));
+  if (d.ng_moved_set[p]) KQ_TRY(hipStreamWaitEvent(b->stream, d.ng_moved[p], 0));
   if (kq::design_launch(b->stream, b->g.olen, b->g.Mdec, reinterpret_cast<const kq::DesignJob *>(pin),
                         reinterpret_cast<const kq::DesignTarget *>(pin + kq_bank::DesignQueue::kMax * sizeof(kq::DesignJob)), n,
                         d.scratch, ctl_queue, ctl_records)) {
-    set_err("response design launch failed");
+    kq_internal_set_error("response design launch failed");
     return -1;
   }
   if (took_records) *took_records = ctl_queue != nullptr && ctl_records > 0;
-  HIP_TRY(hipEventRecord(d.read[d.cur], b->stream));
+  KQ_TRY(hipEventRecord(d.read[d.cur], b->stream));
   d.read_set[d.cur] = true;
   d.cur = (d.cur + 1) % kq_bank::DesignQueue::kDepth;
   d.ng_to_record = p;
@@ -600,11 +594,11 @@ int ctl_flush(kq_bank *b, int side, hipStream_t st) {
   if (side == CTL_FILTER && design_flush(b, q.nrec ? q.buf[q.cur] : nullptr, q.nrec, &applied)) return -1;
   if (q.nrec == 0) return 0;
   if (!applied) kq::launch_ctl_apply(st, q.buf[q.cur], (int)q.nrec);
-  HIP_TRY(hipEventRecord(q.applied[q.cur], st));
+  KQ_TRY(hipEventRecord(q.applied[q.cur], st));
   q.applied_set[q.cur] = true;
   if (side == CTL_DEMOD && b->dq.ng_to_record >= 0) {
     int const p = b->dq.ng_to_record;
-    HIP_TRY(hipEventRecord(b->dq.ng_moved[p], st));
+    KQ_TRY(hipEventRecord(b->dq.ng_moved[p], st));
     b->dq.ng_moved_set[p] = true;
     b->dq.ng_to_record = -1;
   }
@@ -613,7 +607,7 @@ int ctl_flush(kq_bank *b, int side, hipStream_t st) {
   q.used = 0;
   q.at.clear();
   // the buffer gathered into next was handed to the device kDepth flushes ago: long applied
-  if (q.applied_set[q.cur]) HIP_TRY(hipEventSynchronize(q.applied[q.cur]));
+  if (q.applied_set[q.cur]) KQ_TRY(hipEventSynchronize(q.applied[q.cur]));
   return 0;
 }
 // both queues applied now, on the main stream behind the demodulators in flight (for the rare paths that go on to touch
@@ -622,7 +616,7 @@ int ctl_flush_now(kq_bank *b) {
   if (b->ctl[0].nrec == 0 && b->ctl[1].nrec == 0 && b->dq.jobs.empty()) return 0;
   if (b->calls > 0) {
     int const last = (int)((b->calls - 1) & 1);
-    if (b->demod_overlapped[last]) HIP_TRY(hipStreamWaitEvent(b->stream, b->ev_demod_done[last], 0));
+    if (b->demod_overlapped[last]) KQ_TRY(hipStreamWaitEvent(b->stream, b->ev_demod_done[last], 0));
   }
   if (ctl_flush(b, CTL_FILTER, b->stream) || ctl_flush(b, CTL_DEMOD, b->stream)) return -1;
   return 0;
@@ -673,7 +667,7 @@ int acquire_n0slot(kq_bank *b, float low, float high, bool *fresh) {
       }
     if (slot < 0) {
       if (b->n0slot_refs.size() >= (size_t)b->cfg.max_channels) {
-        set_err("compute_n0 mask slots exhausted (%zu sets for %u channels)", b->n0slot_refs.size(), b->cfg.max_channels);
+        kq_internal_set_error("compute_n0 mask slots exhausted (%zu sets for %u channels)", b->n0slot_refs.size(), b->cfg.max_channels);
         return -1;
       }
       slot = (int)b->n0slot_refs.size();
@@ -800,7 +794,7 @@ int queue_design(kq_bank *b, int c, bool runtime = false) {
   kq::Geom const &g = b->g;
   kq_bank::DesignQueue &d = b->dq;
   if (g.Ndec > 16384) {
-    set_err("response design: N / decimate = %d exceeds 16384", g.Ndec);
+    kq_internal_set_error("response design: N / decimate = %d exceeds 16384", g.Ndec);
     return -1;
   }
   float lo_n, hi_n;
@@ -861,15 +855,14 @@ int fetch_response(kq_bank *b, int c) {
   if (!h.resp.empty()) return 0;
   if (ctl_flush_now(b) || sync_all(b)) return -1;
   h.resp.resize(b->g.Ndec);
-  HIP_TRY(hipMemcpy((void *)h.resp.data(), b->chd.resp + (size_t)c * b->g.Ndec, sizeof(float2) * b->g.Ndec, hipMemcpyDeviceToHost));
+  KQ_TRY(hipMemcpy((void *)h.resp.data(), b->chd.resp + (size_t)c * b->g.Ndec, sizeof(float2) * b->g.Ndec, hipMemcpyDeviceToHost));
   return 0;
 }
 
-int ensure_events(std::vector<EventPair> &v, size_t need) {
+int ensure_events(kq_bank *b, std::vector<EventPair> &v, size_t need) {
   while (v.size() < need) {
     EventPair p;
-    HIP_TRY(hipEventCreate(&p.a));
-    HIP_TRY(hipEventCreate(&p.b));
+    if (b->new_event(&p.a, hipEventDefault) || b->new_event(&p.b, hipEventDefault)) return -1;
     v.push_back(p);
   }
   return 0;
@@ -880,18 +873,18 @@ int ensure_events(std::vector<EventPair> &v, size_t need) {
 int report_lost_sibling(kq_bank *b) {
   if (b->big.err && *b->big.err) {
     *b->big.err = 0;
-    set_err("N = 65536 filter: a sibling workgroup's compute_n0 sum never arrived (n0 of that call is NaN)");
+    kq_internal_set_error("N = 65536 filter: a sibling workgroup's compute_n0 sum never arrived (n0 of that call is NaN)");
     return -1;
   }
   return 0;
 }
 
 int sync_all(kq_bank *b) {
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  HIP_TRY(hipStreamSynchronize(b->stream2));
+  KQ_TRY(hipStreamSynchronize(b->stream));
+  KQ_TRY(hipStreamSynchronize(b->stream2));
   // the streaming copies too: "everything issued so far" (kq_bank_sync) includes a plane copy still in flight
-  if (b->copy_in) HIP_TRY(hipStreamSynchronize(b->copy_in));
-  if (b->copy_out) HIP_TRY(hipStreamSynchronize(b->copy_out));
+  if (b->copy_in) KQ_TRY(hipStreamSynchronize(b->copy_in));
+  if (b->copy_out) KQ_TRY(hipStreamSynchronize(b->copy_out));
   return 0;
 }
 
@@ -922,7 +915,7 @@ int drain_timing(kq_bank *b) {
   for (int k = 0; k < 3; k++) {
     for (size_t i = 0; i < b->ev_used[k]; i++) {
       float ms = 0;
-      HIP_TRY(hipEventElapsedTime(&ms, (*sets[k])[i].a, (*sets[k])[i].b));
+      KQ_TRY(hipEventElapsedTime(&ms, (*sets[k])[i].a, (*sets[k])[i].b));
       *dst[k] += ms;
     }
     b->ev_used[k] = 0;
@@ -939,7 +932,7 @@ struct Scope {
     if (!b->timing || (kind != 0 && b->timing < 2)) return;
     std::vector<EventPair> &v = kind == 0 ? b->ev_filter : kind == 1 ? b->ev_demod : b->ev_ingest;
     if (b->ev_used[kind] >= 512) drain_timing(b);
-    if (ensure_events(v, b->ev_used[kind] + 1)) return;
+    if (ensure_events(b, v, b->ev_used[kind] + 1)) return;
     p = &v[b->ev_used[kind]++];
     (void)hipEventRecord(p->a, st);
   }
@@ -1004,7 +997,7 @@ int stage_call_params(kq_bank *b, int64_t n_w, const unsigned char *update, unsi
   int const slot = b->stage_next;
   b->stage_next = (slot + 1) % kq_bank::kSlots;
   auto const tw0 = std::chrono::steady_clock::now();
-  HIP_TRY(hipEventSynchronize(b->stage_ev[slot]));  // the call that last read this slot has got past its filter
+  KQ_TRY(hipEventSynchronize(b->stage_ev[slot]));  // the call that last read this slot has got past its filter
   auto const tw1 = std::chrono::steady_clock::now();
   b->host_acc.slot_wait_ms += std::chrono::duration<double, std::milli>(tw1 - tw0).count();
   if (harvest_slot(b, slot)) return -1;
@@ -1205,7 +1198,7 @@ int run_blocks_timed(kq_bank *b, const float2 *window, unsigned nblocks, const u
     b->cache_any = any;
   }  // (steady: kept up to date by kq_bank_add_channel / kq_bank_remove_channel)
   if (!b->cache_any) {
-    set_err("no channels in bank");
+    kq_internal_set_error("no channels in bank");
     return -1;
   }
   if (b->lists_dirty && upload_lists(b)) return -1;
@@ -1218,11 +1211,11 @@ int run_blocks_timed(kq_bank *b, const float2 *window, unsigned nblocks, const u
     // both must stay far below the 1e-5 parity budget over one window.
     double const cross = 2 * M_PI * std::fabs(r) * (double)g.N * g.D, quad = std::fabs(r) * (double)g.D * g.D * 0.5;
     if (g.Ndec == 256) {
-      set_err("swept NCO at N/D = 256 is only available on the full forward path: use KQ_FWD_FULL");
+      kq_internal_set_error("swept NCO at N/D = 256 is only available on the full forward path: use KQ_FWD_FULL");
       return false;
     }
     if (cross > 3e-4 || quad > 2e-7) {
-      set_err("sweep rate too large for the pruned forward path (cross term %.3g rad): use KQ_FWD_FULL", cross);
+      kq_internal_set_error("sweep rate too large for the pruned forward path (cross term %.3g rad): use KQ_FWD_FULL", cross);
       return false;
     }
     return true;
@@ -1297,7 +1290,7 @@ int run_blocks_timed(kq_bank *b, const float2 *window, unsigned nblocks, const u
   // (asked of the host first: a wait on another stream's event costs the stream a barrier packet, several microseconds
   // of idle device even when the event fired long ago -- and two calls later it always has)
   if (b->demod_overlapped[pp] && hipEventQuery(b->ev_demod_done[pp]) != hipSuccess)
-    HIP_TRY(hipStreamWaitEvent(b->stream, b->ev_demod_done[pp], 0));
+    KQ_TRY(hipStreamWaitEvent(b->stream, b->ev_demod_done[pp], 0));
   int slot = 0, nret = 0, npatch = 0;
   int64_t const n_w = b->n_abs - (g.M - 1);
   if (stage_call_params(b, n_w, update_host, nblocks, &slot, &nret, steady, &npatch)) return -1;
@@ -1374,7 +1367,7 @@ int run_blocks_timed(kq_bank *b, const float2 *window, unsigned nblocks, const u
   }
   LAUNCH_CHECK("IF power");
   if (b->timing) {
-    HIP_TRY(hipEventRecord(b->stage_t0[slot], b->stream));
+    KQ_TRY(hipEventRecord(b->stage_t0[slot], b->stream));
     b->stage_timed[slot] = true;
     b->stage_h0[slot] = std::chrono::steady_clock::now();
     b->stage_launch[slot] = b->acc.filter_launches;
@@ -1479,7 +1472,7 @@ int run_blocks_timed(kq_bank *b, const float2 *window, unsigned nblocks, const u
     b->acc.filter_launches++;
     b->acc.channel_blocks += (uint64_t)C * nblocks;
   }
-  HIP_TRY(hipEventRecord(b->stage_ev[slot], b->stream));
+  KQ_TRY(hipEventRecord(b->stage_ev[slot], b->stream));
   if (b->timing) b->stage_submit_ms[slot] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - b->stage_h0[slot]).count();
   // Where the demodulators of this call run.  On a second stream they overlap the next call's filter pass -- but that
   // kernel leaves no room beside it (500 of a SIMD's 512 registers), so what they take it loses, and at N = 65536 a
@@ -1497,11 +1490,11 @@ int run_blocks_timed(kq_bank *b, const float2 *window, unsigned nblocks, const u
   hipStream_t const ds = overlap ? b->stream2 : b->stream;
   int const prev = pp ^ 1;
   if (overlap)
-    HIP_TRY(hipStreamWaitEvent(ds, b->stage_ev[slot], 0));  // behind this call's filter, hence behind the last call's demodulators if they ran on the main stream
+    KQ_TRY(hipStreamWaitEvent(ds, b->stage_ev[slot], 0));  // behind this call's filter, hence behind the last call's demodulators if they ran on the main stream
   else if (b->calls > 0 && b->demod_overlapped[prev])
-    HIP_TRY(hipStreamWaitEvent(ds, b->ev_demod_done[prev], 0));  // the channel state they carry
+    KQ_TRY(hipStreamWaitEvent(ds, b->ev_demod_done[prev], 0));  // the channel state they carry
   if (b->out_pending) {  // kq_bank_pull_planes_async is still reading the audio / status planes of the last call
-    HIP_TRY(hipStreamWaitEvent(ds, b->pull_done[(b->pulls - 1) % kq_bank::kPullRing], 0));
+    KQ_TRY(hipStreamWaitEvent(ds, b->pull_done[(b->pulls - 1) % kq_bank::kPullRing], 0));
     b->out_pending = false;
   }
   // the IF-power recurrence over the call's blocks: one wave, consumed by the demodulators only.  Where the call has a
@@ -1515,7 +1508,7 @@ int run_blocks_timed(kq_bank *b, const float2 *window, unsigned nblocks, const u
   if (ctl_flush(b, CTL_DEMOD, ds)) return -1;
   if (spectrum)  // the IF power belongs to whoever fed the master (radio.c:123,143-145): status.if_power = 0, not what a
                  // normal call two calls back left in this parity's plane
-    HIP_TRY(hipMemsetAsync(pl.if_power, 0, nblocks * sizeof(float), ds));
+    KQ_TRY(hipMemsetAsync(pl.if_power, 0, nblocks * sizeof(float), ds));
   else if (!iir_done)
     kq::launch_block_energy_iir(ds, pl.if_power + b->cfg.max_blocks, g.L, (int)nblocks,
                                 reinterpret_cast<const unsigned char *>(b->osc_dev2[pp] + 8 * Cmax), b->energy_state, pl.if_power);
@@ -1544,7 +1537,7 @@ int run_blocks_timed(kq_bank *b, const float2 *window, unsigned nblocks, const u
     kq::launch_pcm(ds, g, pl, b->pcm, b->pcm_mask, holes ? (int)b->list_active_host.size() : C, (int)nblocks,
                    holes ? b->list_active_ds_dev : nullptr);
   }
-  if (overlap) HIP_TRY(hipEventRecord(b->ev_demod_done[pp], ds));
+  if (overlap) KQ_TRY(hipEventRecord(b->ev_demod_done[pp], ds));
   b->demod_overlapped[pp] = overlap;
   LAUNCH_CHECK("PLL / PL tone / PCM stage");
   b->pl = pl;  // what the pull functions read
@@ -1630,16 +1623,6 @@ void note_patch(kq_bank *b, int ch) {
 
 }  // namespace
 
-// error reporting for the other translation units of the library (kq_decim.hip)
-void kq_internal_set_error(const char *fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  g_err = buf;
-}
-
 extern "C" {
 
 const char *kq_last_error(void) { return g_err.c_str(); }
@@ -1656,7 +1639,7 @@ void *kq_host_alloc(size_t bytes) {
   void *p = nullptr;
   hipError_t const e = hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocPortable);
   if (e != hipSuccess) {
-    set_err("hipHostMalloc of %zu bytes failed: %s", bytes, hipGetErrorString(e));
+    kq_internal_set_error("hipHostMalloc of %zu bytes failed: %s", bytes, hipGetErrorString(e));
     return nullptr;
   }
   return p;
@@ -1665,61 +1648,56 @@ void kq_host_free(void *p) {
   if (p) (void)hipHostFree(p);
 }
 
-kq_bank *kq_bank_create(const kq_bank_config *cfg) {
+namespace {
+// kq_bank_create in three steps: what can be refused from the configuration alone ...
+static int create_check(const kq_bank_config *cfg) {
   if (!cfg) {
-    set_err("NULL config");
-    return nullptr;
+    kq_internal_set_error("NULL config");
+    return -1;
   }
   unsigned const N = cfg->L + cfg->M - 1;
   // FFTW plans any N (filter.c:78); here a power of two, or -- on the generic kernels, one LDS block -- an even 2^a 3^b 5^c 7^d
   // up to 16384 (a front end whose rate is not 48 kHz x 2^k: 240 kHz gives decimate 5, radio_status.c:266)
   bool const n_pow2 = (N & (N - 1)) == 0;
   if (cfg->L == 0 || cfg->M < 2 || N < 16 || (!n_pow2 && (!kq::fft_size_ok((int)N) || N > 65536))) {
-    set_err("L+M-1 = %u must be a power of two >= 16, or an even 2^a 3^b 5^c 7^d in 16..65536", N);
-    return nullptr;
+    kq_internal_set_error("L+M-1 = %u must be a power of two >= 16, or an even 2^a 3^b 5^c 7^d in 16..65536", N);
+    return -1;
   }
   if (cfg->decimate < 1 || N % cfg->decimate != 0 || cfg->L % cfg->decimate != 0 || (cfg->M - 1) % cfg->decimate != 0) {
-    set_err("decimate %u must be >= 1 and divide N, L and M-1", cfg->decimate);
-    return nullptr;
+    kq_internal_set_error("decimate %u must be >= 1 and divide N, L and M-1", cfg->decimate);
+    return -1;
   }
   // decimate = samprate / 48000 = 1 (radio_status.c:266: a 48 kHz front end, a sound-card receiver): the slave's transform is
   // as long as the master's and needs a buffer of its own beside it in LDS (k_filter_full)
   if (cfg->decimate == 1 && N > 8192) {
-    set_err("decimate 1 needs L+M-1 = %u <= 8192 (master and slave transform side by side in LDS)", N);
-    return nullptr;
+    kq_internal_set_error("decimate 1 needs L+M-1 = %u <= 8192 (master and slave transform side by side in LDS)", N);
+    return -1;
   }
   unsigned const Ndec = N / cfg->decimate;
   if (Ndec < 4 || ((Ndec & (Ndec - 1)) != 0 && (!kq::fft_size_ok((int)Ndec) || Ndec > 16384))) {
-    set_err("N/decimate = %u must be a power of two >= 4, or an even 2^a 3^b 5^c 7^d in 4..16384", Ndec);
-    return nullptr;
+    kq_internal_set_error("N/decimate = %u must be a power of two >= 4, or an even 2^a 3^b 5^c 7^d in 4..16384", Ndec);
+    return -1;
   }
   if (cfg->max_channels == 0 || cfg->max_blocks == 0 || cfg->samprate <= 0) {
-    set_err("max_channels, max_blocks and samprate must be positive");
-    return nullptr;
+    kq_internal_set_error("max_channels, max_blocks and samprate must be positive");
+    return -1;
   }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    set_err("no HIP device available (the gfx950 kernels are the only compute path)");
-    return nullptr;
+    kq_internal_set_error("no HIP device available (the gfx950 kernels are the only compute path)");
+    return -1;
   }
   if (cfg->device < 0 || cfg->device >= ndev) {
-    set_err("device %d out of range (%d visible)", cfg->device, ndev);
-    return nullptr;
+    kq_internal_set_error("device %d out of range (%d visible)", cfg->device, ndev);
+    return -1;
   }
-  // the handle lives on cfg->device; the calling thread's current device is put back on the way out, error paths
-  // included, like every other entry point (kq_device.hpp DeviceScope)
-  kq::DeviceScope dev_scope_(cfg->device);
-  {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != cfg->device) {
-      set_err("hipSetDevice(%d) failed", cfg->device);
-      return nullptr;
-    }
-  }
+  return 0;
+}
 
-  kq_bank *b = new kq_bank();
-  b->cfg = *cfg;
-  b->chans.reserve(cfg->max_channels);  // the elements never move (kq_bank_rtp_from_planes keeps an address past the lock)
+// ... the geometry and the forward path that follow from it ...
+static int create_geometry(kq_bank *b) {
+  const kq_bank_config *cfg = &b->cfg;
+  unsigned const N = cfg->L + cfg->M - 1, Ndec = N / cfg->decimate;
   kq::Geom &g = b->g;
   g.N = (int)N;
   g.L = (int)cfg->L;
@@ -1748,9 +1726,8 @@ kq_bank *kq_bank_create(const kq_bank_config *cfg) {
     g.dNdec = kq::fft_dim(g.Ndec, &ok_d);
     g.dPl = g.pl_n > 0 ? kq::fft_dim(g.pl_n, &ok_p) : kq::FftDim{};
     if (!ok_n || !ok_d || !ok_p) {
-      set_err("transform plan for N = %d / N/decimate = %d failed", g.N, g.Ndec);
-      delete b;
-      return nullptr;
+      kq_internal_set_error("transform plan for N = %d / N/decimate = %d failed", g.N, g.Ndec);
+      return -1;
     }
   }
   g.max_blocks = (int)cfg->max_blocks;
@@ -1762,9 +1739,8 @@ kq_bank *kq_bank_create(const kq_bank_config *cfg) {
   bool const can_prune = kq::pruned_supported(g) && !cfg->compute_n0;
   if (cfg->fwd_mode == KQ_FWD_PRUNED) {
     if (!can_prune) {
-      set_err("pruned forward path unavailable for this geometry or with compute_n0 enabled");
-      delete b;
-      return nullptr;
+      kq_internal_set_error("pruned forward path unavailable for this geometry or with compute_n0 enabled");
+      return -1;
     }
     b->fwd_mode = KQ_FWD_PRUNED;
   } else if (cfg->fwd_mode == KQ_FWD_FULL) {
@@ -1776,73 +1752,63 @@ kq_bank *kq_bank_create(const kq_bank_config *cfg) {
   }
   b->use64k = b->fwd_mode == KQ_FWD_FULL && can64k;
   if (b->fwd_mode == KQ_FWD_FULL && N > 16384 && !b->use64k && (!kq::split_supported(g) || cfg->compute_n0)) {
-    set_err("N = %u: the full path beyond 16384 points needs N = 65536, or compute_n0 off and a split N = S x N1 with N1 <= 16384 a "
-            "size of its own (N = 32768; 19200, 24000, 38400, 48000 ...) and N/D small enough to sit beside it in LDS", N);
-    delete b;
-    return nullptr;
+    kq_internal_set_error("N = %u: the full path beyond 16384 points needs N = 65536, or compute_n0 off and a split N = S x N1 with N1 <= 16384 a "
+                          "size of its own (N = 32768; 19200, 24000, 38400, 48000 ...) and N/D small enough to sit beside it in LDS", N);
+    return -1;
   }
+  return 0;
+}
 
-  if (cfg->stream) {
-    b->stream = (hipStream_t)cfg->stream;
-  } else {
-    if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess) {
-      set_err("hipStreamCreate failed");
-      delete b;
-      return nullptr;
-    }
-    b->own_stream = true;
-  }
-
+// ... and everything the handle owns from the start.  The buffers are cleared on the main stream, which is waited for once,
+// behind the last of them: no stream ever sees one uncleared
+static int create_alloc(kq_bank *b) {
+  const kq_bank_config *cfg = &b->cfg;
+  kq::Geom const &g = b->g;
+  if (b->open_stream(cfg->stream)) return -1;
   size_t const C = cfg->max_channels, B = cfg->max_blocks;
   // max_blocks blocks plus L - 1 samples of slack: a partly filled block never stands in the way of a batch that fits the
   // ring as such (kq_bank_push_rtp); kq_bank_process still takes at most max_blocks blocks per call
   b->ring_cap = (size_t)(g.M - 1) + B * (size_t)g.L + (size_t)(g.L - 1);
-  int rc = 0;
-  rc |= dev_alloc(&b->ring[0], b->ring_cap);
-  rc |= dev_alloc(&b->ring[1], b->ring_cap);
-  rc |= dev_alloc(&b->tw, (size_t)1 << (g.tw_log2 - 1));
-  rc |= dev_alloc(&b->chd.mode, C);
-  rc |= dev_alloc(&b->chd.flags, C);
-  rc |= dev_alloc(&b->chd.low, C);
-  rc |= dev_alloc(&b->chd.high, C);
-  rc |= dev_alloc(&b->chd.resp, C * g.Ndec);
-  rc |= dev_alloc(&b->chd.aresp, C * (g.Ndec / 2 + 1));
-  rc |= dev_alloc(&b->chd.fm_gain, C);
-  rc |= dev_alloc(&b->chd.headroom, C);
-  rc |= dev_alloc(&b->chd.recovery, C);
-  rc |= dev_alloc(&b->chd.hangmax, C);
-  rc |= dev_alloc(&b->chd.noise_gain, C);
-  rc |= dev_alloc(&b->chd.hist_len, C);
-  rc |= dev_alloc(&b->chd.hist2_len, C * kq::kOldLevels);
-  rc |= dev_alloc(&b->chd.hist2_osc, 3 * C * kq::kOldLevels);
+  if (b->alloc(&b->ring[0], b->ring_cap, true)) return -1;
+  if (b->alloc(&b->ring[1], b->ring_cap, true)) return -1;
+  if (b->alloc(&b->tw, (size_t)1 << (g.tw_log2 - 1), true)) return -1;
+  if (b->alloc(&b->chd.mode, C, true)) return -1;
+  if (b->alloc(&b->chd.flags, C, true)) return -1;
+  if (b->alloc(&b->chd.low, C, true)) return -1;
+  if (b->alloc(&b->chd.high, C, true)) return -1;
+  if (b->alloc(&b->chd.resp, C * g.Ndec, true)) return -1;
+  if (b->alloc(&b->chd.aresp, C * (g.Ndec / 2 + 1), true)) return -1;
+  if (b->alloc(&b->chd.fm_gain, C, true)) return -1;
+  if (b->alloc(&b->chd.headroom, C, true)) return -1;
+  if (b->alloc(&b->chd.recovery, C, true)) return -1;
+  if (b->alloc(&b->chd.hangmax, C, true)) return -1;
+  if (b->alloc(&b->chd.noise_gain, C, true)) return -1;
+  if (b->alloc(&b->chd.hist_len, C, true)) return -1;
+  if (b->alloc(&b->chd.hist2_len, C * kq::kOldLevels, true)) return -1;
+  if (b->alloc(&b->chd.hist2_osc, 3 * C * kq::kOldLevels, true)) return -1;
   b->chd.n0lane = nullptr;
   b->chd.n0meta = nullptr;
   b->chd.n0slot = nullptr;
   if (b->cfg.compute_n0 && kq::full16k_supported(g)) {
-    rc |= dev_alloc(&b->chd.n0lane, C * 256);
-    rc |= dev_alloc(&b->chd.n0meta, C);
-    rc |= dev_alloc(&b->chd.n0slot, C);
+    if (b->alloc(&b->chd.n0lane, C * 256, true)) return -1;
+    if (b->alloc(&b->chd.n0meta, C, true)) return -1;
+    if (b->alloc(&b->chd.n0slot, C, true)) return -1;
   }
   if (b->use64k) {
     if (b->cfg.compute_n0) {
-      rc |= dev_alloc(&b->chd.n0lane, C * 4 * 256);
-      rc |= dev_alloc(&b->chd.n0meta, C * 4);
-      rc |= dev_alloc(&b->chd.n0slot, C);
+      if (b->alloc(&b->chd.n0lane, C * 4 * 256, true)) return -1;
+      if (b->alloc(&b->chd.n0meta, C * 4, true)) return -1;
+      if (b->alloc(&b->chd.n0slot, C, true)) return -1;
     }
-    rc |= dev_alloc(&b->big.sync, C * cfg->max_blocks * 12);
-    rc |= dev_alloc(&b->big.n0part, C * cfg->max_blocks * 4);
-    rc |= dev_alloc(&b->big.xs, C * cfg->max_blocks * (size_t)g.Ndec);
-    if (hipHostMalloc((void **)&b->big.err, sizeof(int), hipHostMallocDefault) != hipSuccess) {
-      set_err("pinned allocation failed");
-      rc = -1;
-    } else {
-      *b->big.err = 0;
-    }
+    if (b->alloc(&b->big.sync, C * cfg->max_blocks * 12, true)) return -1;
+    if (b->alloc(&b->big.n0part, C * cfg->max_blocks * 4, true)) return -1;
+    if (b->alloc(&b->big.xs, C * cfg->max_blocks * (size_t)g.Ndec, true)) return -1;
+    if (b->alloc_pinned(&b->big.err, 1)) return -1;
+    *b->big.err = 0;
   }
-  // eight oscillator planes + the per-block IF-power flags of one call
   // eight oscillator planes | the per-block IF-power flags | the list of channels retuned since the last call
   for (int k = 0; k < 2; k++)
-    rc |= dev_alloc(&b->osc_dev2[k], 8 * C + (B + sizeof(double) - 1) / sizeof(double) + (C * sizeof(int) + 7) / 8);
+    if (b->alloc(&b->osc_dev2[k], 8 * C + (B + sizeof(double) - 1) / sizeof(double) + (C * sizeof(int) + 7) / 8, true)) return -1;
   b->chd.lo_phase = b->chd.lo_freq = b->chd.lo_rate = b->chd.sh_phase = b->chd.sh_freq = nullptr;  // set per call
   b->chd.hist_phase = b->chd.hist_freq = b->chd.hist_rate = nullptr;
   // the demodulators' own stream (run_blocks says when it is used); KQ_DEMOD_OVERLAP=0 leaves it out
@@ -1855,97 +1821,85 @@ kq_bank *kq_bank_create(const kq_bank_config *cfg) {
   // so that the next call's first kernels are not dispatched behind the demodulators' waiting workgroups -- round 5:
   // 1.483 -> 1.692 ms per call at 32768 channels x 2 blocks, the demodulators starve until the filter pass ends and the
   // call after next waits for them; default priority it is)
-  if ((overlap && hipStreamCreateWithFlags(&b->stream2, hipStreamNonBlocking) != hipSuccess) ||
-      hipEventCreateWithFlags(&b->ev_demod_done[0], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&b->ev_demod_done[1], hipEventDisableTiming) != hipSuccess) {
-    set_err("second stream / event creation failed");
-    rc = -1;
-  }
+  if (overlap && b->new_stream(&b->stream2)) return -1;
+  for (hipEvent_t &e : b->ev_demod_done)
+    if (b->new_event(&e, hipEventDisableTiming)) return -1;
   b->stage_bytes = 8 * C * sizeof(double) + ((B + 7) & ~(size_t)7) + ((C * sizeof(int) + 7) & ~(size_t)7);  // copied in 8-byte words
   b->patch_off = b->stage_bytes;               // the retune patches' records (never copied as a whole: the patch role of k_block_energy_sum reads them)
   b->stage_bytes += (size_t)kq_bank::kMaxPatch * kq_bank::kPatchBytes;
   b->bits_off = b->stage_bytes;
   b->stage_bytes += ((C + 63) / 64) * sizeof(unsigned long long);
   static_assert(kq_bank::kSlots == 4, "slot_bit_words");
-  for (int k = 0; k < kq_bank::kSlots && !rc; k++) {
-    if (hipHostMalloc((void **)&b->stage_host[k], b->stage_bytes, hipHostMallocDefault) != hipSuccess ||
-        hipEventCreate(&b->stage_ev[k]) != hipSuccess || hipEventCreate(&b->stage_t0[k]) != hipSuccess) {
-      set_err("pinned staging allocation failed");
-      rc = -1;
-    } else {
-      memset(b->stage_host[k] + b->bits_off, 0, b->stage_bytes - b->bits_off);
-    }
+  for (int k = 0; k < kq_bank::kSlots; k++) {
+    if (b->alloc_pinned(&b->stage_host[k], b->stage_bytes) || b->new_event(&b->stage_ev[k], hipEventDefault) ||
+        b->new_event(&b->stage_t0[k], hipEventDefault))
+      return -1;
+    memset(b->stage_host[k] + b->bits_off, 0, b->stage_bytes - b->bits_off);
   }
-  rc |= dev_alloc(&b->chd.fm_state, C);
-  rc |= dev_alloc(&b->chd.lastaudio, C);
-  rc |= dev_alloc(&b->chd.sq_count, C);
-  rc |= dev_alloc(&b->chd.ahist, C * (size_t)(g.Mdec > 1 ? g.Mdec - 1 : 1));
+  if (b->alloc(&b->chd.fm_state, C, true)) return -1;
+  if (b->alloc(&b->chd.lastaudio, C, true)) return -1;
+  if (b->alloc(&b->chd.sq_count, C, true)) return -1;
+  if (b->alloc(&b->chd.ahist, C * (size_t)(g.Mdec > 1 ? g.Mdec - 1 : 1), true)) return -1;
   if (!kq::demod64_supported(g)) {
-    rc |= dev_alloc(&b->fmout, C * B * (size_t)g.olen);
-    for (int k = 0; k < 2; k++) rc |= dev_alloc(&b->fm_hist[k], C * (size_t)(g.Mdec > 1 ? g.Mdec - 1 : 1));
+    if (b->alloc(&b->fmout, C * B * (size_t)g.olen, true)) return -1;
+    for (float *&h : b->fm_hist)
+      if (b->alloc(&h, C * (size_t)(g.Mdec > 1 ? g.Mdec - 1 : 1), true)) return -1;
   }
-  rc |= dev_alloc(&b->chd.foffset, C);
-  rc |= dev_alloc(&b->chd.pdev, C);
-  rc |= dev_alloc(&b->chd.gain, C);
-  rc |= dev_alloc(&b->chd.hang, C);
-  rc |= dev_alloc(&b->chd.dc, C);
-  rc |= dev_alloc(&b->chd.n0, C);
+  if (b->alloc(&b->chd.foffset, C, true)) return -1;
+  if (b->alloc(&b->chd.pdev, C, true)) return -1;
+  if (b->alloc(&b->chd.gain, C, true)) return -1;
+  if (b->alloc(&b->chd.hang, C, true)) return -1;
+  if (b->alloc(&b->chd.dc, C, true)) return -1;
+  if (b->alloc(&b->chd.n0, C, true)) return -1;
   b->chd.plresp = nullptr;
   b->chd.plring = nullptr;
-  rc |= dev_alloc(&b->chd.pl_ptr, C);
-  rc |= dev_alloc(&b->chd.pl_last, C);
-  rc |= dev_alloc(&b->chd.plfreq, C);
+  if (b->alloc(&b->chd.pl_ptr, C, true)) return -1;
+  if (b->alloc(&b->chd.pl_last, C, true)) return -1;
+  if (b->alloc(&b->chd.plfreq, C, true)) return -1;
   if (g.pl_n > 0) {
-    rc |= dev_alloc(&b->chd.plresp, (size_t)g.pl_n / 2 + 1);
-    rc |= dev_alloc(&b->chd.plring, C * 16384);
+    if (b->alloc(&b->chd.plresp, (size_t)g.pl_n / 2 + 1, true)) return -1;
+    if (b->alloc(&b->chd.plring, C * 16384, true)) return -1;
   }
-  rc |= dev_alloc(&b->pl.audio, C * B * 2 * (size_t)g.olen);
-  rc |= dev_alloc(&b->pl.status, C * B);
+  if (b->alloc(&b->pl.audio, C * B * 2 * (size_t)g.olen, true)) return -1;
+  if (b->alloc(&b->pl.status, C * B, true)) return -1;
   for (int k = 0; k < 2; k++) {  // filter -> demod hand-over planes, one set per call parity
     b->pl2[k].audio = b->pl.audio;
     b->pl2[k].status = b->pl.status;
-    rc |= dev_alloc(&b->pl2[k].filt, C * B * g.olen);
-    rc |= dev_alloc(&b->pl2[k].n0raw, C * B);
-    rc |= dev_alloc(&b->pl2[k].if_power, B * (1 + kq::kEnergySplitMax));  // + the partial sums of k_block_energy_sum
+    if (b->alloc(&b->pl2[k].filt, C * B * g.olen, true)) return -1;
+    if (b->alloc(&b->pl2[k].n0raw, C * B, true)) return -1;
+    if (b->alloc(&b->pl2[k].if_power, B * (1 + kq::kEnergySplitMax), true)) return -1;  // + the partial sums of k_block_energy_sum
     b->pl2[k].plout = nullptr;
-    if (g.pl_n > 0) rc |= dev_alloc(&b->pl2[k].plout, C * B * g.pl_l);
+    if (g.pl_n > 0 && b->alloc(&b->pl2[k].plout, C * B * g.pl_l, true)) return -1;
   }
   b->pl = b->pl2[0];
-  rc |= dev_alloc(&b->energy_state, 2);
-  if (kq::full16k_paired_supported(b->g)) rc |= dev_alloc(&b->win_paired, (size_t)(b->g.M - 1) + (size_t)B * b->g.L);
-  for (int k = 0; k < 3; k++) rc |= dev_alloc(&b->list_dev[k], C);
+  if (b->alloc(&b->energy_state, 2, true)) return -1;
+  if (kq::full16k_paired_supported(g) && b->alloc(&b->win_paired, (size_t)(g.M - 1) + (size_t)B * g.L, true)) return -1;
+  for (int *&l : b->list_dev)
+    if (b->alloc(&l, C, true)) return -1;
   for (kq_bank::CtlQueue &q : b->ctl)
     for (int k = 0; k < kq_bank::CtlQueue::kDepth; k++)
-      if (hipHostMalloc((void **)&q.buf[k], kq_bank::CtlQueue::kBytes, hipHostMallocDefault) != hipSuccess ||
-          hipEventCreateWithFlags(&q.applied[k], hipEventDisableTiming) != hipSuccess) {
-        set_err("pinned control queue allocation failed");
-        rc = -1;
-      }
+      if (b->alloc_pinned(&q.buf[k], kq_bank::CtlQueue::kBytes) || b->new_event(&q.applied[k], hipEventDisableTiming)) return -1;
   {
     kq_bank::DesignQueue &d = b->dq;
     size_t const per_job = (size_t)g.Ndec * sizeof(float2);
     d.max_jobs = (unsigned)std::max<size_t>(1, std::min<size_t>(kq_bank::DesignQueue::kMax, ((size_t)64 << 20) / per_job));
-    rc |= dev_alloc(&d.scratch, (size_t)d.max_jobs * g.Ndec);
-    rc |= dev_alloc(&d.ng_next, 2 * C);
+    if (b->alloc(&d.scratch, (size_t)d.max_jobs * g.Ndec, true)) return -1;
+    if (b->alloc(&d.ng_next, 2 * C, true)) return -1;
     for (int k = 0; k < kq_bank::DesignQueue::kDepth; k++)
-      if (hipHostMalloc((void **)&d.pin[k], kq_bank::DesignQueue::kMax * (sizeof(kq::DesignJob) + sizeof(kq::DesignTarget)),
-                        hipHostMallocDefault) != hipSuccess ||
-          hipEventCreateWithFlags(&d.read[k], hipEventDisableTiming) != hipSuccess)
-        rc = -1;
-    for (int k = 0; k < 2; k++)
-      if (hipEventCreateWithFlags(&d.ng_moved[k], hipEventDisableTiming) != hipSuccess) rc = -1;
-    if (g.Ndec <= 16384 && kq::design_prepare(g.olen, g.Mdec)) rc = -1;  // (the twiddle table of the design kernel, built now)
+      if (b->alloc_pinned(&d.pin[k], kq_bank::DesignQueue::kMax * (sizeof(kq::DesignJob) + sizeof(kq::DesignTarget))) ||
+          b->new_event(&d.read[k], hipEventDisableTiming))
+        return -1;
+    for (hipEvent_t &e : d.ng_moved)
+      if (b->new_event(&e, hipEventDisableTiming)) return -1;
+    if (g.Ndec <= 16384 && kq::design_prepare(g.olen, g.Mdec)) return -1;  // (the twiddle table of the design kernel, built now)
   }
-  rc |= dev_alloc(&b->list_active_dev, C);
-  rc |= dev_alloc(&b->list_active_ds_dev, C);
-  rc |= dev_alloc(&b->chd.fflags, C);
-  rc |= dev_alloc(&b->list_unswept_dev, C);
-  rc |= dev_alloc(&b->list_swept_dev, C);
-  if (b->fwd_mode == KQ_FWD_PRUNED) rc |= dev_alloc(&b->chan_tw, C * kq::pruned_table_elems(g));
-  if (rc) {
-    kq_bank_destroy(b);
-    return nullptr;
-  }
+  if (b->alloc(&b->list_active_dev, C, true)) return -1;
+  if (b->alloc(&b->list_active_ds_dev, C, true)) return -1;
+  if (b->alloc(&b->chd.fflags, C, true)) return -1;
+  if (b->alloc(&b->list_unswept_dev, C, true)) return -1;
+  if (b->alloc(&b->list_swept_dev, C, true)) return -1;
+  if (b->fwd_mode == KQ_FWD_PRUNED && b->alloc(&b->chan_tw, C * kq::pruned_table_elems(g), true)) return -1;
+  KQ_TRY(hipStreamSynchronize(b->stream));  // the clears are over: the blocking copies below do not meet them
   if (g.pl_n > 0) {
     // PL low-pass: bins with 0 < f < 300 Hz, Kaiser beta 2.0 (fm.c:207-218)
     int const PL_M = g.pl_n - g.pl_l + 1;
@@ -1954,15 +1908,12 @@ kq_bank *kq_bank_create(const kq_bank_config *cfg) {
       float const f = (float)j * g.dsamprate / g.Ndec;
       if (f > 0 && f < 300) r[j] = 1;
     }
-    if (kq::window_rfilter(g.pl_l, PL_M, r, 2.0)) {
-      kq_bank_destroy(b);
-      return nullptr;
-    }
-    (void)hipMemcpy(b->chd.plresp, r.data(), r.size() * sizeof(float2), hipMemcpyHostToDevice);
+    if (kq::window_rfilter(g.pl_l, PL_M, r, 2.0)) return -1;
+    KQ_TRY(hipMemcpy(b->chd.plresp, r.data(), r.size() * sizeof(float2), hipMemcpyHostToDevice));
   }
   {
     std::vector<float> nanv(C, NAN);
-    (void)hipMemcpy(b->chd.plfreq, nanv.data(), C * sizeof(float), hipMemcpyHostToDevice);
+    KQ_TRY(hipMemcpy(b->chd.plfreq, nanv.data(), C * sizeof(float), hipMemcpyHostToDevice));
   }
   // twiddles exp(-2*pi*i*k/T) in double, rounded once
   {
@@ -1972,11 +1923,30 @@ kq_bank *kq_bank_create(const kq_bank_config *cfg) {
       double const a = -2.0 * M_PI * (double)k / (double)T;
       tw[k] = make_float2((float)std::cos(a), (float)std::sin(a));
     }
-    if (hipMemcpy(b->tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess) {
-      set_err("twiddle upload failed");
-      kq_bank_destroy(b);
+    KQ_TRY(hipMemcpy(b->tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice));
+  }
+  return 0;
+}
+}  // namespace
+
+kq_bank *kq_bank_create(const kq_bank_config *cfg) {
+  if (create_check(cfg)) return nullptr;
+  // the handle lives on cfg->device; the calling thread's current device is put back on the way out, error paths
+  // included, like every other entry point (kq_device.hpp DeviceScope)
+  kq::DeviceScope dev_scope_(cfg->device);
+  {
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess || cur != cfg->device) {
+      kq_internal_set_error("hipSetDevice(%d) failed", cfg->device);
       return nullptr;
     }
+  }
+  kq_bank *b = new kq_bank();
+  b->cfg = *cfg;
+  b->chans.reserve(cfg->max_channels);  // the elements never move (kq_bank_rtp_from_planes keeps an address past the lock)
+  if (create_geometry(b) || create_alloc(b)) {
+    kq_bank_destroy(b);
+    return nullptr;
   }
   return b;
 }
@@ -1984,71 +1954,7 @@ kq_bank *kq_bank_create(const kq_bank_config *cfg) {
 int kq_bank_destroy(kq_bank *b) {
   kq::DeviceScope dev_scope_(b ? b->cfg.device : -1);  // (not the handle's lock: nobody else may be using a handle that is being destroyed)
   if (!b) return 0;
-  if (b->stream) (void)hipStreamSynchronize(b->stream);
-  if (b->stream2 && b->stream2 != b->stream) (void)hipStreamSynchronize(b->stream2);
-  for (hipStream_t st : {b->copy_in, b->copy_out})  // before any plane they read or write is freed
-    if (st) (void)hipStreamSynchronize(st);
-  void *ptrs[] = {b->ring[0], b->ring[1], b->tw, b->chan_tw, b->chd.mode, b->chd.flags, b->chd.low, b->chd.high, b->chd.resp,
-                  b->chd.aresp, b->chd.fm_gain, b->chd.headroom, b->chd.recovery, b->chd.hangmax, b->chd.noise_gain, b->chd.hist_len, b->chd.hist2_len, b->chd.hist2_osc, b->chd.n0lane, b->chd.n0meta, b->chd.n0slot, b->fmout, b->fm_hist[0], b->fm_hist[1],
-                  b->osc_dev2[0], b->osc_dev2[1], b->chd.fm_state,
-                  b->chd.lastaudio, b->chd.sq_count, b->chd.ahist, b->chd.foffset, b->chd.pdev, b->chd.gain, b->chd.hang,
-                  b->chd.dc, b->chd.n0, b->chd.plresp, b->chd.plring, b->chd.pl_ptr, b->chd.pl_last, b->chd.plfreq,
-                  b->pl2[0].plout, b->pl2[1].plout, b->pl.audio, b->pl.status, b->pl2[0].filt, b->pl2[0].n0raw, b->pl2[0].if_power,
-                  b->pl2[1].filt, b->pl2[1].n0raw, b->pl2[1].if_power, b->energy_state, b->win_paired,
-                  b->big.sync, b->big.n0part, b->big.xs,
-                  b->list_dev[0], b->list_dev[1], b->list_dev[2], b->list_active_dev, b->list_active_ds_dev, b->chd.fflags, b->list_unswept_dev, b->list_swept_dev, b->spec_dump, b->stage_dev, b->pcm, b->pcm_mask, b->list_pll_dev, b->pll_slot_dev, b->pll_chunks_dev,
-                  b->dq.scratch, b->dq.ng_next};
-  for (kq::PllChunk const &ck : b->pll_chunks) {
-    if (ck.state) (void)hipFree(ck.state);
-    if (ck.rings) (void)hipFree(ck.rings);
-    if (ck.side) (void)hipFree(ck.side);
-  }
-  b->pll_chunks.clear();
-  for (void *p : ptrs)
-    if (p) (void)hipFree(p);
-  for (auto *v : {&b->ev_filter, &b->ev_demod, &b->ev_ingest})
-    for (EventPair &p : *v) {
-      (void)hipEventDestroy(p.a);
-      (void)hipEventDestroy(p.b);
-    }
-  if (b->big.err) (void)hipHostFree(b->big.err);
-  for (kq_bank::CtlQueue &q : b->ctl)
-    for (int k = 0; k < kq_bank::CtlQueue::kDepth; k++) {
-      if (q.buf[k]) (void)hipHostFree(q.buf[k]);
-      if (q.applied[k]) (void)hipEventDestroy(q.applied[k]);
-    }
-  for (int k = 0; k < kq_bank::DesignQueue::kDepth; k++) {
-    if (b->dq.pin[k]) (void)hipHostFree(b->dq.pin[k]);
-    if (b->dq.read[k]) (void)hipEventDestroy(b->dq.read[k]);
-  }
-  for (int k = 0; k < 2; k++)
-    if (b->dq.ng_moved[k]) (void)hipEventDestroy(b->dq.ng_moved[k]);
-  for (hipStream_t st : {b->copy_in, b->copy_out})
-    if (st) {
-      (void)hipStreamSynchronize(st);
-      (void)hipStreamDestroy(st);
-    }
-  for (int k = 0; k < 2; k++) {
-    if (b->in_stage[k]) (void)hipFree(b->in_stage[k]);
-    if (b->in_ready[k]) (void)hipEventDestroy(b->in_ready[k]);
-    if (b->in_free[k]) (void)hipEventDestroy(b->in_free[k]);
-  }
-  if (b->out_ready) (void)hipEventDestroy(b->out_ready);
-  for (int k = 0; k < 2; k++) {
-    if (b->acc_pin[k]) (void)hipHostFree(b->acc_pin[k]);
-    if (b->acc_read[k]) (void)hipEventDestroy(b->acc_read[k]);
-  }
-  for (hipEvent_t e : b->pull_done)
-    if (e) (void)hipEventDestroy(e);
-  for (int k = 0; k < kq_bank::kSlots; k++) {
-    if (b->stage_host[k]) (void)hipHostFree(b->stage_host[k]);
-    if (b->stage_ev[k]) (void)hipEventDestroy(b->stage_ev[k]);
-    if (b->stage_t0[k]) (void)hipEventDestroy(b->stage_t0[k]);
-  }
-  for (int k = 0; k < 2; k++)
-    if (b->ev_demod_done[k]) (void)hipEventDestroy(b->ev_demod_done[k]);
-  if (b->stream2 && b->stream2 != b->stream) (void)hipStreamDestroy(b->stream2);
-  if (b->own_stream && b->stream) (void)hipStreamDestroy(b->stream);
+  b->close();
   delete b;
   return 0;
 }
@@ -2063,7 +1969,7 @@ static int pll_admit(kq_bank *b, const kq_channel_config &m) {
   float const binsize = (float)(1. / (65536 * samptime));
   int const nbins = 2 * (int)round((m.square ? 2 : 1) * 300.f / binsize) + 1;
   if (nbins > 4096) {
-    set_err("output rate too low for the PLL search window (%d bins > 4096)", nbins);
+    kq_internal_set_error("output rate too low for the PLL search window (%d bins > 4096)", nbins);
     return -1;
   }
   return 0;
@@ -2076,21 +1982,19 @@ static int pll_admit(kq_bank *b, const kq_channel_config &m) {
 static int pll_acquire(kq_bank *b, int c) {
   size_t const Cmax = b->cfg.max_channels;
   if (!b->list_pll_dev) {
-    if (dev_alloc(&b->list_pll_dev, Cmax) || dev_alloc(&b->pll_slot_dev, Cmax) ||
-        dev_alloc(&b->pll_chunks_dev, (size_t)kq_bank::kMaxPllChunks))
+    if (alloc_cleared(b, &b->list_pll_dev, Cmax) || alloc_cleared(b, &b->pll_slot_dev, Cmax) ||
+        alloc_cleared(b, &b->pll_chunks_dev, (size_t)kq_bank::kMaxPllChunks))
       return -1;
   }
   if (b->pll_free.empty()) {
     if ((int)b->pll_chunks.size() >= kq_bank::kMaxPllChunks) {
-      set_err("at most %d carrier-tracking (pll) channels per bank", kq_bank::kMaxPllChunks * kq::kPllChunk);
+      kq_internal_set_error("at most %d carrier-tracking (pll) channels per bank", kq_bank::kMaxPllChunks * kq::kPllChunk);
       return -1;
     }
     kq::PllChunk ck{};
-    if (dev_alloc(&ck.state, (size_t)kq::kPllChunk) || dev_alloc(&ck.rings, (size_t)kq::kPllChunk * 65536) ||
-        dev_alloc(&ck.side, (size_t)kq::kPllChunk * 4096)) {
-      if (ck.state) (void)hipFree(ck.state);
-      if (ck.rings) (void)hipFree(ck.rings);
-      if (ck.side) (void)hipFree(ck.side);
+    if (alloc_cleared(b, &ck.state, (size_t)kq::kPllChunk) || alloc_cleared(b, &ck.rings, (size_t)kq::kPllChunk * 65536) ||
+        alloc_cleared(b, &ck.side, (size_t)kq::kPllChunk * 4096)) {
+      b->release(&ck.state, &ck.rings, &ck.side);
       return -1;
     }
     int const k = (int)b->pll_chunks.size();
@@ -2122,16 +2026,16 @@ static int check_channel_config(const kq_bank *b, const kq_channel_config &k, in
   char at[32] = "";
   if (entry >= 0) snprintf(at, sizeof at, " (entry %d)", entry);
   if (k.demod_type < KQ_LINEAR_DEMOD || k.demod_type > KQ_FM_DEMOD) {
-    set_err("unknown demod_type %d%s", k.demod_type, at);
+    kq_internal_set_error("unknown demod_type %d%s", k.demod_type, at);
     return -1;
   }
   if (std::isnan(k.low) || std::isnan(k.high)) {  // filter.c:504-505
-    set_err("NaN filter edge%s", at);
+    kq_internal_set_error("NaN filter edge%s", at);
     return -1;
   }
   if (k.demod_type == KQ_FM_DEMOD && !kq::demod64_supported(b->g) && kq::demod_fm_lds_bytes(b->g) > 160 * 1024) {
     // the FM kernels keep one block of samples / the N/D-point audio master in LDS (N/D <= 8192)
-    set_err("FM working set of %zu bytes exceeds the 160 KiB of LDS at this geometry", kq::demod_fm_lds_bytes(b->g));
+    kq_internal_set_error("FM working set of %zu bytes exceeds the 160 KiB of LDS at this geometry", kq::demod_fm_lds_bytes(b->g));
     return -1;
   }
   return 0;
@@ -2149,7 +2053,7 @@ static void set_oscillators(const kq_bank *b, HostChan &h, const kq_channel_conf
 int kq_bank_add_channel(kq_bank *b, const kq_channel_config *cfg) {
   BankScope dev_scope_(b);
   if (!b || !cfg) {
-    set_err("NULL argument");
+    kq_internal_set_error("NULL argument");
     return -1;
   }
   // the lowest hole a removed channel left, else a new slot at the end
@@ -2160,7 +2064,7 @@ int kq_bank_add_channel(kq_bank *b, const kq_channel_config *cfg) {
       break;
     }
   if ((size_t)c >= b->cfg.max_channels) {
-    set_err("bank is full (%u channels)", b->cfg.max_channels);
+    kq_internal_set_error("bank is full (%u channels)", b->cfg.max_channels);
     return -1;
   }
   if (check_channel_config(b, *cfg)) return -1;
@@ -2201,7 +2105,7 @@ int kq_bank_add_channel(kq_bank *b, const kq_channel_config *cfg) {
 int kq_bank_add_channels(kq_bank *b, const kq_channel_config *cfgs, unsigned n, int *indices) {
   BankScope dev_scope_(b);
   if (!b || (!cfgs && n)) {
-    set_err("NULL argument");
+    kq_internal_set_error("NULL argument");
     return -1;
   }
   if (n == 0) return 0;
@@ -2229,7 +2133,7 @@ int kq_bank_add_channels(kq_bank *b, const kq_channel_config *cfgs, unsigned n, 
   kq::Geom const &g = b->g;
   size_t const c0 = b->chans.size();
   if (c0 + n > b->cfg.max_channels) {
-    set_err("bank is full (%u channels): %zu present, %u more asked for", b->cfg.max_channels, c0, n);
+    kq_internal_set_error("bank is full (%u channels): %zu present, %u more asked for", b->cfg.max_channels, c0, n);
     return -1;
   }
   for (unsigned i = 0; i < n; i++)
@@ -2269,7 +2173,7 @@ int kq_bank_add_channels(kq_bank *b, const kq_channel_config *cfgs, unsigned n, 
     std::vector<kq::cfloat> resp;
     std::vector<float> ng;
     if (kq::design_responses(g.N, g.olen, g.Mdec, ot, edges, resp, ng) || resp.size() != edges.size() * (size_t)g.Ndec) {
-      set_err("response design failed");
+      kq_internal_set_error("response design failed");
       return -1;
     }
     for (unsigned i = 0; i < n; i++)
@@ -2290,7 +2194,7 @@ int kq_bank_add_channels(kq_bank *b, const kq_channel_config *cfgs, unsigned n, 
       if (it == aresp_by_beta.end()) {
         std::vector<kq::cfloat> a = kq::design_fm_audio_response(g.olen, g.Mdec, g.dsamprate, k.kaiser_beta);
         if (a.empty()) {
-          set_err("FM audio response design failed");
+          kq_internal_set_error("FM audio response design failed");
           return -1;
         }
         it = aresp_by_beta.emplace(k.kaiser_beta, std::move(a)).first;
@@ -2301,7 +2205,7 @@ int kq_bank_add_channels(kq_bank *b, const kq_channel_config *cfgs, unsigned n, 
   if (ctl_flush_now(b) || sync_all(b)) return -1;  // (what the control plane has queued goes first: the copies below are immediate)
   // per-channel planes of the new range, one copy each
   auto put = [&](auto *dst, auto const &v) -> int {
-    HIP_TRY(hipMemcpy(dst + c0, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice));
+    KQ_TRY(hipMemcpy(dst + c0, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice));
     return 0;
   };
   {
@@ -2328,27 +2232,27 @@ int kq_bank_add_channels(kq_bank *b, const kq_channel_config *cfgs, unsigned n, 
       return -1;
   }
   // demodulator state at its prologue values (fm.c:26,68-69; am.c:26,33; linear.c:33)
-  HIP_TRY(hipMemset(b->chd.lastaudio + c0, 0, n * sizeof(float)));
-  HIP_TRY(hipMemset(b->chd.sq_count + c0, 0, n * sizeof(int)));
-  HIP_TRY(hipMemset(b->chd.hang + c0, 0, n * sizeof(int)));
-  HIP_TRY(hipMemset(b->chd.dc + c0, 0, n * sizeof(float)));
-  HIP_TRY(hipMemset(b->chd.foffset + c0, 0, n * sizeof(float)));
-  HIP_TRY(hipMemset(b->chd.pdev + c0, 0, n * sizeof(float)));
+  KQ_TRY(hipMemset(b->chd.lastaudio + c0, 0, n * sizeof(float)));
+  KQ_TRY(hipMemset(b->chd.sq_count + c0, 0, n * sizeof(int)));
+  KQ_TRY(hipMemset(b->chd.hang + c0, 0, n * sizeof(int)));
+  KQ_TRY(hipMemset(b->chd.dc + c0, 0, n * sizeof(float)));
+  KQ_TRY(hipMemset(b->chd.foffset + c0, 0, n * sizeof(float)));
+  KQ_TRY(hipMemset(b->chd.pdev + c0, 0, n * sizeof(float)));
   if (g.Mdec > 1) {
     size_t const w = (size_t)(g.Mdec - 1);
-    HIP_TRY(hipMemset(b->chd.ahist + c0 * w, 0, n * w * sizeof(float)));
+    KQ_TRY(hipMemset(b->chd.ahist + c0 * w, 0, n * w * sizeof(float)));
     for (int k = 0; k < 2; k++)
-      if (b->fm_hist[k]) HIP_TRY(hipMemset(b->fm_hist[k] + c0 * w, 0, n * w * sizeof(float)));
+      if (b->fm_hist[k]) KQ_TRY(hipMemset(b->fm_hist[k] + c0 * w, 0, n * w * sizeof(float)));
   }
   if (g.pl_n > 0) {
-    HIP_TRY(hipMemset(b->chd.plring + c0 * 16384, 0, (size_t)n * 16384 * sizeof(float)));
-    HIP_TRY(hipMemset(b->chd.pl_ptr + c0, 0, n * sizeof(*b->chd.pl_ptr)));
-    HIP_TRY(hipMemset(b->chd.pl_last + c0, 0, n * sizeof(*b->chd.pl_last)));
+    KQ_TRY(hipMemset(b->chd.plring + c0 * 16384, 0, (size_t)n * 16384 * sizeof(float)));
+    KQ_TRY(hipMemset(b->chd.pl_ptr + c0, 0, n * sizeof(*b->chd.pl_ptr)));
+    KQ_TRY(hipMemset(b->chd.pl_last + c0, 0, n * sizeof(*b->chd.pl_last)));
   }
   {  // responses
     std::vector<float2> resp((size_t)n * g.Ndec);
     for (unsigned i = 0; i < n; i++) memcpy(&resp[(size_t)i * g.Ndec], hs[i].resp.data(), sizeof(float2) * g.Ndec);
-    HIP_TRY(hipMemcpy(b->chd.resp + c0 * g.Ndec, resp.data(), resp.size() * sizeof(float2), hipMemcpyHostToDevice));
+    KQ_TRY(hipMemcpy(b->chd.resp + c0 * g.Ndec, resp.data(), resp.size() * sizeof(float2), hipMemcpyHostToDevice));
     size_t const na = (size_t)g.Ndec / 2 + 1;
     std::vector<float2> ar((size_t)n * na, make_float2(0.f, 0.f));
     bool any = false;
@@ -2357,7 +2261,7 @@ int kq_bank_add_channels(kq_bank *b, const kq_channel_config *cfgs, unsigned n, 
         memcpy(&ar[(size_t)i * na], hs[i].aresp.data(), sizeof(float2) * na);
         any = true;
       }
-    if (any) HIP_TRY(hipMemcpy(b->chd.aresp + c0 * na, ar.data(), ar.size() * sizeof(float2), hipMemcpyHostToDevice));
+    if (any) KQ_TRY(hipMemcpy(b->chd.aresp + c0 * na, ar.data(), ar.size() * sizeof(float2), hipMemcpyHostToDevice));
   }
   if (b->chd.n0lane) {  // compute_n0's lane masks: one set per distinct pair of edges, shared
     int const nsub = b->use64k ? 4 : 1;
@@ -2374,11 +2278,11 @@ int kq_bank_add_channels(kq_bank *b, const kq_channel_config *cfgs, unsigned n, 
           std::vector<unsigned long long> m;
           std::vector<unsigned> meta;
           build_n0mask(b, cfgs[i].low, cfgs[i].high, m, meta);
-          HIP_TRY(hipMemcpy(b->chd.n0lane + (size_t)slot * nsub * 256, m.data(), m.size() * sizeof(m[0]), hipMemcpyHostToDevice));
-          HIP_TRY(hipMemcpy(b->chd.n0meta + (size_t)slot * nsub, meta.data(), meta.size() * sizeof(unsigned), hipMemcpyHostToDevice));
+          KQ_TRY(hipMemcpy(b->chd.n0lane + (size_t)slot * nsub * 256, m.data(), m.size() * sizeof(m[0]), hipMemcpyHostToDevice));
+          KQ_TRY(hipMemcpy(b->chd.n0meta + (size_t)slot * nsub, meta.data(), meta.size() * sizeof(unsigned), hipMemcpyHostToDevice));
         }
       }
-      HIP_TRY(hipMemcpy(b->chd.n0slot + c0, slots.data(), n * sizeof(int), hipMemcpyHostToDevice));
+      KQ_TRY(hipMemcpy(b->chd.n0slot + c0, slots.data(), n * sizeof(int), hipMemcpyHostToDevice));
       return 0;
     };
     if (fill()) {  // all or nothing: the references taken so far go back
@@ -2401,7 +2305,7 @@ int kq_bank_add_channels(kq_bank *b, const kq_channel_config *cfgs, unsigned n, 
 int kq_bank_remove_channel(kq_bank *b, int ch) {
   BankScope dev_scope_(b);
   if (!valid_ch(b, ch)) {
-    set_err("bad channel");
+    kq_internal_set_error("bad channel");
     return -1;
   }
   HostChan &h = b->chans[ch];
@@ -2444,7 +2348,7 @@ unsigned kq_bank_num_channels(const kq_bank *b) {
 int kq_bank_set_mode(kq_bank *b, int ch, const kq_channel_config *m) {
   BankScope dev_scope_(b);
   if (!valid_ch(b, ch) || !m) {
-    set_err("bad channel or NULL mode");
+    kq_internal_set_error("bad channel or NULL mode");
     return -1;
   }
   if (check_channel_config(b, *m)) return -1;
@@ -2497,12 +2401,12 @@ int kq_bank_set_mode(kq_bank *b, int ch, const kq_channel_config *m) {
 int kq_bank_set_linear_options(kq_bank *b, int ch, int isb, int channels) {
   BankScope dev_scope_(b);
   if (!valid_ch(b, ch) || (channels != 1 && channels != 2)) {
-    set_err("bad channel, or channels not 1 or 2");
+    kq_internal_set_error("bad channel, or channels not 1 or 2");
     return -1;
   }
   HostChan &h = b->chans[ch];
   if (h.cfg.demod_type != KQ_LINEAR_DEMOD) {
-    set_err("not a linear channel");
+    kq_internal_set_error("not a linear channel");
     return -1;
   }
   if ((h.cfg.isb != 0) == (isb != 0) && h.cfg.channels == channels) return 0;
@@ -2523,7 +2427,7 @@ int kq_bank_set_linear_options(kq_bank *b, int ch, int isb, int channels) {
 int kq_bank_set_second_lo(kq_bank *b, int ch, double hz) {
   BankScope dev_scope_(b);
   if (!valid_ch(b, ch) || std::isnan(hz)) {
-    set_err("bad channel or NaN");
+    kq_internal_set_error("bad channel or NaN");
     return -1;
   }
   note_retune(b, ch);
@@ -2537,7 +2441,7 @@ int kq_bank_set_second_lo(kq_bank *b, int ch, double hz) {
 int kq_bank_set_doppler(kq_bank *b, int ch, double hz, double hz_per_s) {
   BankScope dev_scope_(b);
   if (!valid_ch(b, ch) || std::isnan(hz) || std::isnan(hz_per_s)) {
-    set_err("bad channel or NaN");
+    kq_internal_set_error("bad channel or NaN");
     return -1;
   }
   double const fs = b->g.samprate;
@@ -2553,7 +2457,7 @@ int kq_bank_set_doppler(kq_bank *b, int ch, double hz, double hz_per_s) {
 int kq_bank_set_shift(kq_bank *b, int ch, double hz) {
   BankScope dev_scope_(b);
   if (!valid_ch(b, ch) || std::isnan(hz)) {
-    set_err("bad channel or NaN");
+    kq_internal_set_error("bad channel or NaN");
     return -1;
   }
   b->chans[ch].cfg.shift = hz;
@@ -2565,7 +2469,7 @@ int kq_bank_set_shift(kq_bank *b, int ch, double hz) {
 int kq_bank_set_n0(kq_bank *b, int ch, float n0) {
   BankScope dev_scope_(b);
   if (!valid_ch(b, ch)) {
-    set_err("bad channel");
+    kq_internal_set_error("bad channel");
     return -1;
   }
   // the demodulators of a call in flight own the state: written behind them, in front of the next call's
@@ -2576,11 +2480,11 @@ int kq_bank_set_n0(kq_bank *b, int ch, float n0) {
 int kq_bank_set_filter(kq_bank *b, int ch, float low, float high, float beta) {
   BankScope dev_scope_(b);
   if (!valid_ch(b, ch)) {
-    set_err("bad channel");
+    kq_internal_set_error("bad channel");
     return -1;
   }
   if (std::isnan(low) || std::isnan(high)) {  // filter.c:504-505
-    set_err("NaN filter edge");
+    kq_internal_set_error("NaN filter edge");
     return -1;
   }
   HostChan &h = b->chans[ch];
@@ -2600,76 +2504,6 @@ int kq_bank_set_filter(kq_bank *b, int ch, float low, float high, float beta) {
 namespace {
 static int acc_flush(kq_bank *b);
 static int acc_append(kq_bank *b, const void *src, size_t nsamples, int format);
-}  // namespace
-
-int kq_bank_push_iq(kq_bank *b, const void *iq, size_t nsamples, int format, int is_device) {
-  BankScope dev_scope_(b);
-  if (!b || (!iq && nsamples)) {
-    set_err("NULL argument");
-    return -1;
-  }
-  if (acc_flush(b)) return -1;  // packet payloads gathered by kq_bank_push_rtp go first
-  if (format < KQ_IQ_CF32 || format > KQ_IQ_S8) {
-    set_err("unknown I/Q format %d", format);
-    return -1;
-  }
-  kq::Geom const &g = b->g;
-  size_t const used = (size_t)(g.M - 1) + b->pending;
-  if (used + nsamples > b->ring_cap) {
-    set_err("ring overflow: %zu pending + %zu pushed > %zu", b->pending, nsamples, b->ring_cap - (g.M - 1));
-    return -1;
-  }
-  size_t const bps = format == KQ_IQ_CF32 ? 8 : format == KQ_IQ_S16 ? 4 : 2;
-  const void *src = iq;
-  if (!is_device) {
-    if (b->stage_cap < nsamples * bps) {
-      if (b->stage_dev) (void)hipFree(b->stage_dev);
-      b->stage_cap = nsamples * bps;
-      HIP_TRY(hipMalloc(&b->stage_dev, b->stage_cap));
-    }
-    HIP_TRY(hipMemcpyAsync(b->stage_dev, iq, nsamples * bps, hipMemcpyHostToDevice, b->stream));
-    src = b->stage_dev;
-  }
-  {
-    Scope t(b, 2, b->stream);
-    kq::launch_ingest(b->stream, src, format, b->ring[b->cur] + used, nsamples, b->cfg.gain_factor);
-  }
-  if (!is_device) HIP_TRY(hipStreamSynchronize(b->stream));  // the caller may reuse iq
-  // block completion bookkeeping for the IF-power rule
-  size_t fill = b->pending % g.L;
-  size_t left = nsamples;
-  while (left) {
-    size_t const take = std::min(left, (size_t)g.L - fill);
-    fill += take;
-    left -= take;
-    if (fill == (size_t)g.L) {
-      b->zero_tail.push_back(0);
-      fill = 0;
-    }
-  }
-  b->pending += nsamples;
-  return 0;
-}
-
-namespace {
-static int host_io_setup(kq_bank *b) {
-  if (b->copy_in) return 0;
-  // Streams share a handful of hardware queues, handed out in creation order, and a queue runs in order: the two copy
-  // streams can land on one queue.  Then an input copy queued BEHIND an output copy waits with it for that call's
-  // demodulators, and every step runs input copy, kernels and output copy one after the other (rocprofv3 timeline,
-  // tools/hostio_trace.sh) -- hence the call order the header asks for: push batch k+1 before pulling the planes of
-  // batch k.  (Streams of different priority come from different queue pools, but with a high-priority output stream
-  // the filter kernel itself ran 40 % slower for the whole step, measured.)
-  HIP_TRY(hipStreamCreateWithFlags(&b->copy_in, hipStreamNonBlocking));
-  HIP_TRY(hipStreamCreateWithFlags(&b->copy_out, hipStreamNonBlocking));
-  for (int k = 0; k < 2; k++) {
-    HIP_TRY(hipEventCreateWithFlags(&b->in_ready[k], hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&b->in_free[k], hipEventDisableTiming));
-  }
-  HIP_TRY(hipEventCreateWithFlags(&b->out_ready, hipEventDisableTiming));
-  for (int k = 0; k < kq_bank::kPullRing; k++) HIP_TRY(hipEventCreateWithFlags(&b->pull_done[k], hipEventDisableTiming));
-  return 0;
-}
 // block completion bookkeeping for the IF-power rule (radio.c:140-146 against radio.c:94-98)
 static void note_pushed(kq_bank *b, size_t nsamples, unsigned char zero) {
   size_t fill = b->pending % b->g.L, left = nsamples;
@@ -2686,6 +2520,58 @@ static void note_pushed(kq_bank *b, size_t nsamples, unsigned char zero) {
 }
 }  // namespace
 
+int kq_bank_push_iq(kq_bank *b, const void *iq, size_t nsamples, int format, int is_device) {
+  BankScope dev_scope_(b);
+  if (!b || (!iq && nsamples)) {
+    kq_internal_set_error("NULL argument");
+    return -1;
+  }
+  if (acc_flush(b)) return -1;  // packet payloads gathered by kq_bank_push_rtp go first
+  if (format < KQ_IQ_CF32 || format > KQ_IQ_S8) {
+    kq_internal_set_error("unknown I/Q format %d", format);
+    return -1;
+  }
+  kq::Geom const &g = b->g;
+  size_t const used = (size_t)(g.M - 1) + b->pending;
+  if (used + nsamples > b->ring_cap) {
+    kq_internal_set_error("ring overflow: %zu pending + %zu pushed > %zu", b->pending, nsamples, b->ring_cap - (g.M - 1));
+    return -1;
+  }
+  size_t const bps = format == KQ_IQ_CF32 ? 8 : format == KQ_IQ_S16 ? 4 : 2;
+  const void *src = iq;
+  if (!is_device) {
+    if (b->grow(&b->stage_dev, &b->stage_cap, nsamples * bps)) return -1;
+    KQ_TRY(hipMemcpyAsync(b->stage_dev, iq, nsamples * bps, hipMemcpyHostToDevice, b->stream));
+    src = b->stage_dev;
+  }
+  {
+    Scope t(b, 2, b->stream);
+    kq::launch_ingest(b->stream, src, format, b->ring[b->cur] + used, nsamples, b->cfg.gain_factor);
+  }
+  if (!is_device) KQ_TRY(hipStreamSynchronize(b->stream));  // the caller may reuse iq
+  note_pushed(b, nsamples, 0);
+  return 0;
+}
+
+namespace {
+static int host_io_setup(kq_bank *b) {
+  if (b->copy_in) return 0;
+  // Streams share a handful of hardware queues, handed out in creation order, and a queue runs in order: the two copy
+  // streams can land on one queue.  Then an input copy queued BEHIND an output copy waits with it for that call's
+  // demodulators, and every step runs input copy, kernels and output copy one after the other (rocprofv3 timeline,
+  // tools/hostio_trace.sh) -- hence the call order the header asks for: push batch k+1 before pulling the planes of
+  // batch k.  (Streams of different priority come from different queue pools, but with a high-priority output stream
+  // the filter kernel itself ran 40 % slower for the whole step, measured.)
+  if (b->new_stream(&b->copy_in) || b->new_stream(&b->copy_out)) return -1;
+  for (int k = 0; k < 2; k++)
+    if (b->new_event(&b->in_ready[k], hipEventDisableTiming) || b->new_event(&b->in_free[k], hipEventDisableTiming)) return -1;
+  if (b->new_event(&b->out_ready, hipEventDisableTiming)) return -1;
+  for (hipEvent_t &e : b->pull_done)
+    if (b->new_event(&e, hipEventDisableTiming)) return -1;
+  return 0;
+}
+}  // namespace
+
 namespace {
 // `nsamples` samples of `format` in pinned host memory -> staging buffer (copy stream) -> conversion kernel (bank's stream)
 // into the ring at sample offset `ring_off`.  Nothing waits on the host but the reuse of a staging buffer two copies later.
@@ -2695,26 +2581,23 @@ static int queue_input_copy(kq_bank *b, const void *iq, size_t nsamples, int for
   int const k = b->in_next;
   b->in_next ^= 1;
   if (b->in_stage_cap[k] < nsamples * bps) {
-    HIP_TRY(hipStreamSynchronize(b->copy_in));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    if (b->in_stage[k]) (void)hipFree(b->in_stage[k]);
-    b->in_stage_cap[k] = nsamples * bps;
-    HIP_TRY(hipMalloc(&b->in_stage[k], b->in_stage_cap[k]));
+    KQ_TRY(hipStreamSynchronize(b->copy_in));  // (grow waits for the main stream: the conversion kernels)
+    if (b->grow(&b->in_stage[k], &b->in_stage_cap[k], nsamples * bps)) return -1;
   }
   // The header's promise -- `iq` may be reused once two more pushes have been queued -- is kept here: the push two
   // back used this staging index, and its host-to-device copy must have READ the caller's buffer before this call
   // returns (a device-side wait alone would let the host run ahead of the copy engine).  Normally long done.
-  if (b->in_used[k]) HIP_TRY(hipEventSynchronize(b->in_ready[k]));
+  if (b->in_used[k]) KQ_TRY(hipEventSynchronize(b->in_ready[k]));
   b->in_used[k] = true;
-  HIP_TRY(hipStreamWaitEvent(b->copy_in, b->in_free[k], 0));  // the conversion kernel that last read this buffer
-  HIP_TRY(hipMemcpyAsync(b->in_stage[k], iq, nsamples * bps, hipMemcpyHostToDevice, b->copy_in));
-  HIP_TRY(hipEventRecord(b->in_ready[k], b->copy_in));
-  HIP_TRY(hipStreamWaitEvent(b->stream, b->in_ready[k], 0));
+  KQ_TRY(hipStreamWaitEvent(b->copy_in, b->in_free[k], 0));  // the conversion kernel that last read this buffer
+  KQ_TRY(hipMemcpyAsync(b->in_stage[k], iq, nsamples * bps, hipMemcpyHostToDevice, b->copy_in));
+  KQ_TRY(hipEventRecord(b->in_ready[k], b->copy_in));
+  KQ_TRY(hipStreamWaitEvent(b->stream, b->in_ready[k], 0));
   {
     Scope t(b, 2, b->stream);
     kq::launch_ingest(b->stream, b->in_stage[k], format, b->ring[b->cur] + ring_off, nsamples, b->cfg.gain_factor);
   }
-  HIP_TRY(hipEventRecord(b->in_free[k], b->stream));
+  KQ_TRY(hipEventRecord(b->in_free[k], b->stream));
   return 0;
 }
 
@@ -2723,12 +2606,12 @@ static int acc_flush(kq_bank *b) {
   if (b->acc_n == 0) return 0;
   int const j = b->acc_cur;
   if (queue_input_copy(b, b->acc_pin[j], b->acc_n, b->acc_fmt, b->acc_ring_off)) return -1;
-  HIP_TRY(hipEventRecord(b->acc_read[j], b->copy_in));
+  KQ_TRY(hipEventRecord(b->acc_read[j], b->copy_in));
   b->acc_read_set[j] = true;
   b->acc_cur ^= 1;
   b->acc_n = 0;
   // the buffer gathered into next was handed to the copy engine two flushes ago
-  if (b->acc_read_set[b->acc_cur]) HIP_TRY(hipEventSynchronize(b->acc_read[b->acc_cur]));
+  if (b->acc_read_set[b->acc_cur]) KQ_TRY(hipEventSynchronize(b->acc_read[b->acc_cur]));
   return 0;
 }
 
@@ -2739,8 +2622,7 @@ static int acc_append(kq_bank *b, const void *src, size_t nsamples, int format) 
   if (!b->acc_pin[0]) {
     b->acc_cap = b->ring_cap * 8;  // the whole ring in the widest format
     for (int k = 0; k < 2; k++) {
-      HIP_TRY(hipHostMalloc((void **)&b->acc_pin[k], b->acc_cap, hipHostMallocDefault));
-      HIP_TRY(hipEventCreateWithFlags(&b->acc_read[k], hipEventDisableTiming));
+      if (b->alloc_pinned(&b->acc_pin[k], b->acc_cap) || b->new_event(&b->acc_read[k], hipEventDisableTiming)) return -1;
     }
   }
   if (b->acc_n && (format != b->acc_fmt || (b->acc_n + nsamples) * bps > b->acc_cap) && acc_flush(b)) return -1;
@@ -2758,17 +2640,17 @@ static int acc_append(kq_bank *b, const void *src, size_t nsamples, int format) 
 int kq_bank_push_iq_async(kq_bank *b, const void *iq, size_t nsamples, int format) {
   BankScope dev_scope_(b);
   if (!b || (!iq && nsamples)) {
-    set_err("NULL argument");
+    kq_internal_set_error("NULL argument");
     return -1;
   }
   if (format < KQ_IQ_CF32 || format > KQ_IQ_S8) {
-    set_err("unknown I/Q format %d", format);
+    kq_internal_set_error("unknown I/Q format %d", format);
     return -1;
   }
   kq::Geom const &g = b->g;
   size_t const used = (size_t)(g.M - 1) + b->pending;
   if (used + nsamples > b->ring_cap) {
-    set_err("ring overflow: %zu pending + %zu pushed > %zu", b->pending, nsamples, b->ring_cap - (g.M - 1));
+    kq_internal_set_error("ring overflow: %zu pending + %zu pushed > %zu", b->pending, nsamples, b->ring_cap - (g.M - 1));
     return -1;
   }
   if (nsamples == 0) return 0;
@@ -2783,22 +2665,22 @@ namespace {
 // on the main stream
 static int pull_prologue(kq_bank *b) {
   if (!b || b->calls == 0) {
-    set_err("nothing processed yet");
+    kq_internal_set_error("nothing processed yet");
     return -1;
   }
   if (host_io_setup(b)) return -1;
   int const last = (int)((b->calls - 1) & 1);
   if (b->demod_overlapped[last]) {
-    HIP_TRY(hipStreamWaitEvent(b->copy_out, b->ev_demod_done[last], 0));
+    KQ_TRY(hipStreamWaitEvent(b->copy_out, b->ev_demod_done[last], 0));
   } else {
-    HIP_TRY(hipEventRecord(b->out_ready, b->stream));
-    HIP_TRY(hipStreamWaitEvent(b->copy_out, b->out_ready, 0));
+    KQ_TRY(hipEventRecord(b->out_ready, b->stream));
+    KQ_TRY(hipStreamWaitEvent(b->copy_out, b->out_ready, 0));
   }
   b->pulled_since_call = true;
   return 0;
 }
 static int pull_epilogue(kq_bank *b) {
-  HIP_TRY(hipEventRecord(b->pull_done[b->pulls % kq_bank::kPullRing], b->copy_out));
+  KQ_TRY(hipEventRecord(b->pull_done[b->pulls % kq_bank::kPullRing], b->copy_out));
   b->pulls++;
   b->out_pending = true;
   return 0;
@@ -2812,21 +2694,21 @@ int kq_bank_pull_planes_async(kq_bank *b, float *audio, kq_chan_status *status) 
   // of every channel-block's 2 * olen floats only the status.nout that hold samples travel (mono: half): the kernel
   // moves 16 bytes per lane, so olen must be a multiple of 4 for it -- other geometries take the plain copy
   size_t const sbytes = n * sizeof(kq_chan_status), s16 = sbytes & ~(size_t)15;
-  // (hipHostMalloc'ed memory is page aligned; anything less than 16 bytes takes the plain copies)
+  // (memory from kq_host_alloc is page aligned; anything less than 16 bytes takes the plain copies)
   bool const aligned = (reinterpret_cast<uintptr_t>(audio) & 15) == 0 && (reinterpret_cast<uintptr_t>(status) & 15) == 0;
   bool const rows_ok = b->g.olen % 4 == 0 && aligned;
   if (!aligned) {
     if (audio)
-      HIP_TRY(hipMemcpyAsync(audio, b->pl.audio, n * 2 * (size_t)b->g.olen * sizeof(float), hipMemcpyDeviceToHost, b->copy_out));
-    if (status) HIP_TRY(hipMemcpyAsync(status, b->pl.status, sbytes, hipMemcpyDeviceToHost, b->copy_out));
+      KQ_TRY(hipMemcpyAsync(audio, b->pl.audio, n * 2 * (size_t)b->g.olen * sizeof(float), hipMemcpyDeviceToHost, b->copy_out));
+    if (status) KQ_TRY(hipMemcpyAsync(status, b->pl.status, sbytes, hipMemcpyDeviceToHost, b->copy_out));
     return pull_epilogue(b);
   }
   kq::launch_copy_to_host(b->copy_out, b->pl.audio, rows_ok ? audio : nullptr, 2 * b->g.olen, b->pl.status, status, n);
   LAUNCH_CHECK("plane copy");
   if (audio && !rows_ok)
-    HIP_TRY(hipMemcpyAsync(audio, b->pl.audio, n * 2 * (size_t)b->g.olen * sizeof(float), hipMemcpyDeviceToHost, b->copy_out));
+    KQ_TRY(hipMemcpyAsync(audio, b->pl.audio, n * 2 * (size_t)b->g.olen * sizeof(float), hipMemcpyDeviceToHost, b->copy_out));
   if (status && sbytes > s16)
-    HIP_TRY(hipMemcpyAsync((char *)status + s16, (const char *)b->pl.status + s16, sbytes - s16, hipMemcpyDeviceToHost, b->copy_out));
+    KQ_TRY(hipMemcpyAsync((char *)status + s16, (const char *)b->pl.status + s16, sbytes - s16, hipMemcpyDeviceToHost, b->copy_out));
   return pull_epilogue(b);
 }
 
@@ -2836,13 +2718,13 @@ int kq_bank_pull_planes_async(kq_bank *b, float *audio, kq_chan_status *status) 
 static int pull_pcm_planes(kq_bank *b, int16_t *pcm, uint32_t *silent_mask, void *status, bool compact) {
   BankScope dev_scope_(b);
   if (!pcm) {
-    set_err("NULL pcm plane");
+    kq_internal_set_error("NULL pcm plane");
     return -1;
   }
   bool const aligned = (reinterpret_cast<uintptr_t>(pcm) & 15) == 0 && (reinterpret_cast<uintptr_t>(status) & 15) == 0 &&
                        (reinterpret_cast<uintptr_t>(silent_mask) & 3) == 0;
   if (b && (b->g.olen % 8 != 0 || !aligned || 2 * (size_t)b->g.olen > 32 * 480)) {
-    set_err("kq_bank_pull_pcm_planes_async: olen must be a multiple of 8 and at most 7680, the planes 16-byte aligned");
+    kq_internal_set_error("kq_bank_pull_pcm_planes_async: olen must be a multiple of 8 and at most 7680, the planes 16-byte aligned");
     return -1;
   }
   if (pull_prologue(b)) return -1;
@@ -2852,7 +2734,7 @@ static int pull_pcm_planes(kq_bank *b, int16_t *pcm, uint32_t *silent_mask, void
                               compact && status ? b->chd.mode : nullptr, b->g.max_blocks);
   LAUNCH_CHECK("PCM plane copy");
   if (status && !compact && sbytes > s16)
-    HIP_TRY(hipMemcpyAsync((char *)status + s16, (const char *)b->pl.status + s16, sbytes - s16, hipMemcpyDeviceToHost, b->copy_out));
+    KQ_TRY(hipMemcpyAsync((char *)status + s16, (const char *)b->pl.status + s16, sbytes - s16, hipMemcpyDeviceToHost, b->copy_out));
   return pull_epilogue(b);
 }
 int kq_bank_pull_pcm_planes_async(kq_bank *b, int16_t *pcm, uint32_t *silent_mask, kq_chan_status *status) {
@@ -2867,14 +2749,14 @@ int kq_bank_pull_wait(kq_bank *b, unsigned lag) {
   BankScope dev_scope_(b);
   if (!b) return -1;
   if (lag >= (unsigned)kq_bank::kPullRing) {
-    set_err("kq_bank_pull_wait: lag %u, at most %d deliveries are remembered", lag, kq_bank::kPullRing - 1);
+    kq_internal_set_error("kq_bank_pull_wait: lag %u, at most %d deliveries are remembered", lag, kq_bank::kPullRing - 1);
     return -1;
   }
   if (b->pulls <= lag) return 0;  // nothing that far back was ever queued
   hipEvent_t const ev = b->pull_done[(b->pulls - 1 - lag) % kq_bank::kPullRing];
   {
     Unlocked u(dev_scope_);  // (the ring holds kPullRing deliveries: the event is not recorded again before this one is long over)
-    HIP_TRY(hipEventSynchronize(ev));
+    KQ_TRY(hipEventSynchronize(ev));
   }
   return report_lost_sibling(b);
 }
@@ -2885,8 +2767,8 @@ int kq_bank_host_io_wait(kq_bank *b) {
   hipStream_t const cin = b->copy_in, cout = b->copy_out;  // (read under the lock: host_io_setup may be creating them)
   {
     Unlocked u(dev_scope_);
-    if (cin) HIP_TRY(hipStreamSynchronize(cin));
-    if (cout) HIP_TRY(hipStreamSynchronize(cout));
+    if (cin) KQ_TRY(hipStreamSynchronize(cin));
+    if (cout) KQ_TRY(hipStreamSynchronize(cout));
   }
   return report_lost_sibling(b);  // the planes just landed come from kernels that have finished
 }
@@ -2894,17 +2776,17 @@ int kq_bank_host_io_wait(kq_bank *b) {
 int kq_bank_push_zeros(kq_bank *b, size_t nsamples) {
   BankScope dev_scope_(b);
   if (!b) {
-    set_err("NULL bank");
+    kq_internal_set_error("NULL bank");
     return -1;
   }
   kq::Geom const &g = b->g;
   size_t const used = (size_t)(g.M - 1) + b->pending;
   if (used + nsamples > b->ring_cap) {
-    set_err("ring overflow");
+    kq_internal_set_error("ring overflow");
     return -1;
   }
   if (acc_flush(b)) return -1;
-  HIP_TRY(hipMemsetAsync(b->ring[b->cur] + used, 0, nsamples * sizeof(float2), b->stream));
+  KQ_TRY(hipMemsetAsync(b->ring[b->cur] + used, 0, nsamples * sizeof(float2), b->stream));
   size_t fill = b->pending % g.L;
   size_t left = nsamples;
   while (left) {
@@ -2925,7 +2807,7 @@ static inline size_t g_M1(const kq_bank *b) { return (size_t)(b->g.M - 1); }
 int kq_bank_push_rtp(kq_bank *b, const void *datagram, size_t size) {
   BankScope dev_scope_(b);
   if (!b || !datagram) {
-    set_err("NULL argument");
+    kq_internal_set_error("NULL argument");
     return -1;
   }
   const unsigned char *p = static_cast<const unsigned char *>(datagram);
@@ -3005,7 +2887,7 @@ int kq_bank_push_rtp(kq_bank *b, const void *datagram, size_t size) {
     };
     if (b->pending >= (size_t)b->g.L) {  // nothing has moved: not the sequence number, not the timestamp, not a counter
       b->rtp_retry = retry;
-      set_err("ring full: %zu samples pending, the packet brings %zu (zero fill %d): run kq_bank_process, then push it again",
+      kq_internal_set_error("ring full: %zu samples pending, the packet brings %zu (zero fill %d): run kq_bank_process, then push it again",
               b->pending, (size_t)time_step + payload, time_step);
       return -2;
     }
@@ -3018,14 +2900,14 @@ int kq_bank_push_rtp(kq_bank *b, const void *datagram, size_t size) {
       r.drops += seq_step;
       r.next_seq = seq;  // the retry is in sequence
       remember();
-      set_err("the gap's zero fill is larger than the ring: %zu of %d samples in, run kq_bank_process, then push it again", z,
+      kq_internal_set_error("the gap's zero fill is larger than the ring: %zu of %d samples in, run kq_bank_process, then push it again", z,
               time_step);
       return -2;
     }
     if (!retry) r.packets++;
     r.drops += seq_step;
     r.next_seq = (uint16_t)(seq + 1);
-    set_err("a packet of %zu samples does not fit a ring of %zu: raise max_blocks", payload, b->ring_cap - (size_t)g_M1(b));
+    kq_internal_set_error("a packet of %zu samples does not fit a ring of %zu: raise max_blocks", payload, b->ring_cap - (size_t)g_M1(b));
     return -1;
   }
   if (!retry) r.packets++;
@@ -3064,7 +2946,7 @@ int slot_prewait(BankScope &scope, kq_bank *b) {
   auto const t0 = std::chrono::steady_clock::now();
   {
     Unlocked u(scope);
-    HIP_TRY(hipEventSynchronize(ev));
+    KQ_TRY(hipEventSynchronize(ev));
   }
   double const w = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   b->host_acc.slot_wait_ms += w;
@@ -3075,7 +2957,7 @@ int slot_prewait(BankScope &scope, kq_bank *b) {
 int kq_bank_process(kq_bank *b) {
   BankScope dev_scope_(b, true);
   if (!b) {
-    set_err("NULL bank");
+    kq_internal_set_error("NULL bank");
     return -1;
   }
   if (slot_prewait(dev_scope_, b)) return -1;
@@ -3092,7 +2974,7 @@ int kq_bank_process(kq_bank *b) {
   // overlap-save history (filter.c:164) plus any unprocessed tail moves to the other ring buffer
   size_t const consumed = (size_t)nb * g.L;
   size_t const keep = (size_t)(g.M - 1) + (b->pending - consumed);
-  HIP_TRY(hipMemcpyAsync(b->ring[b->cur ^ 1], b->ring[b->cur] + consumed, keep * sizeof(float2), hipMemcpyDeviceToDevice,
+  KQ_TRY(hipMemcpyAsync(b->ring[b->cur ^ 1], b->ring[b->cur] + consumed, keep * sizeof(float2), hipMemcpyDeviceToDevice,
                          b->stream));
   b->cur ^= 1;
   b->pending -= consumed;
@@ -3102,11 +2984,11 @@ int kq_bank_process(kq_bank *b) {
 int kq_bank_process_resident(kq_bank *b, const void *iq_dev, unsigned nblocks) {
   BankScope dev_scope_(b, true);
   if (!b || !iq_dev) {
-    set_err("NULL argument");
+    kq_internal_set_error("NULL argument");
     return -1;
   }
   if (nblocks == 0 || nblocks > b->cfg.max_blocks) {
-    set_err("nblocks %u out of range 1..%u", nblocks, b->cfg.max_blocks);
+    kq_internal_set_error("nblocks %u out of range 1..%u", nblocks, b->cfg.max_blocks);
     return -1;
   }
   if (slot_prewait(dev_scope_, b)) return -1;
@@ -3117,18 +2999,18 @@ int kq_bank_process_resident(kq_bank *b, const void *iq_dev, unsigned nblocks) {
 int kq_bank_process_spectrum(kq_bank *b, const void *spectrum_dev, unsigned nblocks) {
   BankScope dev_scope_(b, true);
   if (!b || !spectrum_dev) {
-    set_err("NULL argument");
+    kq_internal_set_error("NULL argument");
     return -1;
   }
   if (nblocks == 0 || nblocks > b->cfg.max_blocks) {
-    set_err("nblocks %u out of range 1..%u", nblocks, b->cfg.max_blocks);
+    kq_internal_set_error("nblocks %u out of range 1..%u", nblocks, b->cfg.max_blocks);
     return -1;
   }
   for (HostChan const &h : b->chans) {
     if (!h.active) continue;
     // the spectrum is what it is: a channel that still has an oscillator to apply cannot be served from it
     if (h.lo2.set_f != 0 || h.dop.set_f != 0) {
-      set_err("kq_bank_process_spectrum: a channel has a second LO or Doppler set; the mix belongs in front of the master");
+      kq_internal_set_error("kq_bank_process_spectrum: a channel has a second LO or Doppler set; the mix belongs in front of the master");
       return -1;
     }
   }
@@ -3144,7 +3026,7 @@ int kq_bank_join(kq_bank *b) {
   if (!b) return -1;
   if (b->calls == 0) return 0;
   int const last = (int)((b->calls - 1) & 1);
-  if (b->demod_overlapped[last]) HIP_TRY(hipStreamWaitEvent(b->stream, b->ev_demod_done[last], 0));
+  if (b->demod_overlapped[last]) KQ_TRY(hipStreamWaitEvent(b->stream, b->ev_demod_done[last], 0));
   return 0;
 }
 
@@ -3157,7 +3039,7 @@ int kq_bank_sync(kq_bank *b) {
   {
     Unlocked u(dev_scope_);
     for (hipStream_t x : st)
-      if (x) HIP_TRY(hipStreamSynchronize(x));
+      if (x) KQ_TRY(hipStreamSynchronize(x));
   }
   return report_lost_sibling(b);
 }
@@ -3168,27 +3050,27 @@ unsigned kq_bank_last_blocks(const kq_bank *b) { return b ? b->last_blocks : 0; 
 int kq_bank_pull_status(kq_bank *b, int ch, unsigned blk, kq_chan_status *st) {
   BankScope dev_scope_(b);
   if (!valid_ch(b, ch) || !st || blk >= b->last_blocks) {
-    set_err("bad channel/block");
+    kq_internal_set_error("bad channel/block");
     return -1;
   }
   if (sync_all(b)) return -1;
-  HIP_TRY(hipMemcpy(st, b->pl.status + (size_t)ch * b->g.max_blocks + blk, sizeof(*st), hipMemcpyDeviceToHost));
+  KQ_TRY(hipMemcpy(st, b->pl.status + (size_t)ch * b->g.max_blocks + blk, sizeof(*st), hipMemcpyDeviceToHost));
   return 0;
 }
 
 int kq_bank_pull_audio(kq_bank *b, int ch, unsigned blk, float *dst, size_t cap, size_t *n) {
   BankScope dev_scope_(b);
   if (!valid_ch(b, ch) || !dst || blk >= b->last_blocks) {
-    set_err("bad channel/block");
+    kq_internal_set_error("bad channel/block");
     return -1;
   }
   kq_chan_status st;
   if (kq_bank_pull_status(b, ch, blk, &st)) return -1;
   if ((size_t)st.nout > cap) {
-    set_err("audio buffer too small: %d > %zu", st.nout, cap);
+    kq_internal_set_error("audio buffer too small: %d > %zu", st.nout, cap);
     return -1;
   }
-  HIP_TRY(hipMemcpy(dst, b->pl.audio + ((size_t)ch * b->g.max_blocks + blk) * 2 * (size_t)b->g.olen, st.nout * sizeof(float),
+  KQ_TRY(hipMemcpy(dst, b->pl.audio + ((size_t)ch * b->g.max_blocks + blk) * 2 * (size_t)b->g.olen, st.nout * sizeof(float),
                     hipMemcpyDeviceToHost));
   if (n) *n = (size_t)st.nout;
   return 0;
@@ -3199,12 +3081,12 @@ int kq_bank_enable_pcm(kq_bank *b, int on) {
   if (!b) return -1;
   if (on && 2 * (size_t)b->g.olen > 32 * 480) {
     // the silent-packet mask of kq_bank_pull_pcm is 32 bits: one per 480-word packet of a block
-    set_err("PCM stage: %d output samples per block make more than 32 packets", b->g.olen);
+    kq_internal_set_error("PCM stage: %d output samples per block make more than 32 packets", b->g.olen);
     return -1;
   }
   if (on && !b->pcm) {
     size_t const CB = (size_t)b->cfg.max_channels * b->cfg.max_blocks;
-    if (dev_alloc(&b->pcm, CB * 2 * (size_t)b->g.olen) || dev_alloc(&b->pcm_mask, CB)) return -1;
+    if (alloc_cleared(b, &b->pcm, CB * 2 * (size_t)b->g.olen) || alloc_cleared(b, &b->pcm_mask, CB)) return -1;
   }
   b->pcm_on = on != 0;
   return 0;
@@ -3213,19 +3095,19 @@ int kq_bank_enable_pcm(kq_bank *b, int on) {
 int kq_bank_pull_pcm(kq_bank *b, int ch, unsigned blk, int16_t *dst, size_t cap, size_t *nwords, uint32_t *silent_mask) {
   BankScope dev_scope_(b);
   if (!valid_ch(b, ch) || !dst || blk >= b->last_blocks || !b->pcm_on) {
-    set_err("bad channel/block, or PCM stage not enabled");
+    kq_internal_set_error("bad channel/block, or PCM stage not enabled");
     return -1;
   }
   kq_chan_status st;
   if (kq_bank_pull_status(b, ch, blk, &st)) return -1;
   if ((size_t)st.nout > cap) {
-    set_err("PCM buffer too small");
+    kq_internal_set_error("PCM buffer too small");
     return -1;
   }
   size_t const cb = (size_t)ch * b->g.max_blocks + blk;
-  HIP_TRY(hipMemcpy(dst, b->pcm + cb * 2 * (size_t)b->g.olen, st.nout * sizeof(int16_t), hipMemcpyDeviceToHost));
+  KQ_TRY(hipMemcpy(dst, b->pcm + cb * 2 * (size_t)b->g.olen, st.nout * sizeof(int16_t), hipMemcpyDeviceToHost));
   uint32_t m = 0;
-  HIP_TRY(hipMemcpy(&m, b->pcm_mask + cb, sizeof(m), hipMemcpyDeviceToHost));
+  KQ_TRY(hipMemcpy(&m, b->pcm_mask + cb, sizeof(m), hipMemcpyDeviceToHost));
   if (nwords) *nwords = (size_t)st.nout;
   if (silent_mask) *silent_mask = m;
   return 0;
@@ -3234,7 +3116,7 @@ int kq_bank_pull_pcm(kq_bank *b, int ch, unsigned blk, int16_t *dst, size_t cap,
 int kq_bank_set_output_ssrc(kq_bank *b, int ch, uint32_t ssrc) {
   BankScope dev_scope_(b);
   if (!valid_ch(b, ch)) {
-    set_err("bad channel");
+    kq_internal_set_error("bad channel");
     return -1;
   }
   b->chans[ch].out_rtp.ssrc = ssrc;
@@ -3273,7 +3155,7 @@ int packetize_block(kq_out_rtp_state &o, const unsigned char *w, size_t nwords, 
       uint16_t const seq = o.seq++;
       size_t const len = 12 + 2 * chunk;
       if (pos + 2 + len > cap) {
-        set_err("packet buffer too small");
+        kq_internal_set_error("packet buffer too small");
         return -1;
       }
       unsigned char *dp = dst + pos;
@@ -3303,7 +3185,7 @@ int packetize_block(kq_out_rtp_state &o, const unsigned char *w, size_t nwords, 
 int kq_bank_pull_rtp_audio(kq_bank *b, int ch, unsigned blk, unsigned char *dst, size_t cap, size_t *used) {
   BankScope dev_scope_(b);
   if (!valid_ch(b, ch) || !dst) {
-    set_err("bad channel or NULL buffer");
+    kq_internal_set_error("bad channel or NULL buffer");
     return -1;
   }
   std::vector<int16_t> words(2 * (size_t)b->g.olen);
@@ -3317,7 +3199,7 @@ int kq_bank_pull_rtp_audio(kq_bank *b, int ch, unsigned blk, unsigned char *dst,
 int kq_bank_rtp_from_planes(kq_bank *b, int ch, unsigned blk, const int16_t *pcm_plane, const kq_chan_status *status_plane,
                             unsigned char *dst, size_t cap, size_t *used) {
   if (!b) {
-    set_err("NULL bank");
+    kq_internal_set_error("NULL bank");
     return -1;
   }
   // Host work only, and meant to be spread over the host's threads by channel range: the bank's lock is held just long
@@ -3329,7 +3211,7 @@ int kq_bank_rtp_from_planes(kq_bank *b, int ch, unsigned blk, const int16_t *pcm
   {
     std::lock_guard<std::recursive_mutex> lk(b->mu);
     if (!valid_ch(b, ch) || !dst || !pcm_plane || !status_plane || blk >= (unsigned)b->g.max_blocks) {
-      set_err("bad channel / block or NULL plane");
+      kq_internal_set_error("bad channel / block or NULL plane");
       return -1;
     }
     o = &b->chans[ch].out_rtp;
@@ -3339,7 +3221,7 @@ int kq_bank_rtp_from_planes(kq_bank *b, int ch, unsigned blk, const int16_t *pcm
   size_t const cb = (size_t)ch * max_blocks + blk;
   int const nout = status_plane[cb].nout;
   if (nout < 0 || nout > 2 * olen) {
-    set_err("status plane: nout %d out of range", nout);
+    kq_internal_set_error("status plane: nout %d out of range", nout);
     return -1;
   }
   return packetize_block(*o, reinterpret_cast<const unsigned char *>(pcm_plane + cb * 2 * (size_t)olen), (size_t)nout,
@@ -3349,11 +3231,11 @@ int kq_bank_rtp_from_planes(kq_bank *b, int ch, unsigned blk, const int16_t *pcm
 int kq_bank_pull_filter_output(kq_bank *b, int ch, unsigned blk, float *dst, size_t cap) {
   BankScope dev_scope_(b);
   if (!valid_ch(b, ch) || !dst || blk >= b->last_blocks || cap < (size_t)b->g.olen) {
-    set_err("bad channel/block/capacity");
+    kq_internal_set_error("bad channel/block/capacity");
     return -1;
   }
   if (sync_all(b)) return -1;
-  HIP_TRY(hipMemcpy(dst, b->pl.filt + ((size_t)ch * b->g.max_blocks + blk) * b->g.olen, b->g.olen * sizeof(float2),
+  KQ_TRY(hipMemcpy(dst, b->pl.filt + ((size_t)ch * b->g.max_blocks + blk) * b->g.olen, b->g.olen * sizeof(float2),
                     hipMemcpyDeviceToHost));
   return 0;
 }
@@ -3361,34 +3243,34 @@ int kq_bank_pull_filter_output(kq_bank *b, int ch, unsigned blk, float *dst, siz
 int kq_bank_pull_spectrum(kq_bank *b, int ch, unsigned blk, float *dst, size_t cap) {
   BankScope dev_scope_(b);
   if (!valid_ch(b, ch) || !dst || cap < (size_t)b->g.N) {
-    set_err("bad channel/capacity");
+    kq_internal_set_error("bad channel/capacity");
     return -1;
   }
   if (b->fwd_mode != KQ_FWD_FULL) {
-    set_err("master spectrum exists only in KQ_FWD_FULL mode");
+    kq_internal_set_error("master spectrum exists only in KQ_FWD_FULL mode");
     return -1;
   }
   // The dump is armed for one channel at a time: the first pull after (re)arming returns -1 with a
   // hint; spectra are captured by the next kq_bank_process call.
   if (b->spec_ch != ch || !b->spec_dump) {
-    if (!b->spec_dump && dev_alloc(&b->spec_dump, (size_t)b->g.max_blocks * b->g.N)) return -1;
+    if (!b->spec_dump && alloc_cleared(b, &b->spec_dump, (size_t)b->g.max_blocks * b->g.N)) return -1;
     b->spec_ch = ch;
-    set_err("spectrum capture armed for channel %d; it is filled by the next process call", ch);
+    kq_internal_set_error("spectrum capture armed for channel %d; it is filled by the next process call", ch);
     return -1;
   }
   if (blk >= b->last_blocks) {
-    set_err("bad block");
+    kq_internal_set_error("bad block");
     return -1;
   }
   if (sync_all(b)) return -1;
-  HIP_TRY(hipMemcpy(dst, b->spec_dump + (size_t)blk * b->g.N, b->g.N * sizeof(float2), hipMemcpyDeviceToHost));
+  KQ_TRY(hipMemcpy(dst, b->spec_dump + (size_t)blk * b->g.N, b->g.N * sizeof(float2), hipMemcpyDeviceToHost));
   return 0;
 }
 
 int kq_bank_get_response(kq_bank *b, int ch, float *dst, size_t cap) {
   BankScope dev_scope_(b);
   if (!valid_ch(b, ch) || !dst || cap < (size_t)b->g.Ndec) {
-    set_err("bad channel/capacity");
+    kq_internal_set_error("bad channel/capacity");
     return -1;
   }
   if (fetch_response(b, ch)) return -1;
@@ -3399,12 +3281,12 @@ int kq_bank_get_response(kq_bank *b, int ch, float *dst, size_t cap) {
 int kq_bank_get_audio_response(kq_bank *b, int ch, float *dst, size_t cap) {
   BankScope dev_scope_(b);
   if (!valid_ch(b, ch) || !dst) {
-    set_err("bad channel");
+    kq_internal_set_error("bad channel");
     return -1;
   }
   auto const &a = b->chans[ch].aresp;
   if (a.empty() || cap < a.size()) {
-    set_err("no audio response (not FM, or flat) or capacity too small");
+    kq_internal_set_error("no audio response (not FM, or flat) or capacity too small");
     return -1;
   }
   memcpy(dst, a.data(), sizeof(float2) * a.size());

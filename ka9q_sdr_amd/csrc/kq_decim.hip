@@ -442,7 +442,7 @@ struct kq_decimator : kq::HostSide {
   int16_t *out16_dev = nullptr;
   unsigned long long *partial = nullptr;  // tagged per-workgroup energies of the last group's launch
   float *energy_dev = nullptr;
-  int *err = nullptr;  // pinned host word the kernel sets when a tile's energy never arrived (hipHostMalloc: freed by hand)
+  int *err = nullptr;  // pinned host word the kernel sets when a tile's energy never arrived
   unsigned epoch = 0;
   size_t n_partial = 0;
   unsigned num_cus = 256;
@@ -480,7 +480,7 @@ static int decim_alloc(kq_decimator *d) {
   }
   d->n_partial = (size_t)d->num_cus * 16 + 1;  // one per workgroup of the last launch
   if (d->alloc(&d->partial, d->n_partial, true)) return -1;  // epoch 0 = never written
-  KQ_TRY(hipHostMalloc((void **)&d->err, sizeof(int), hipHostMallocDefault));
+  if (d->alloc_pinned(&d->err, 1)) return -1;
   *d->err = 0;
   if (d->alloc(&d->energy_dev, 1)) return -1;
   KQ_TRY(hipStreamSynchronize(d->stream));
@@ -521,7 +521,6 @@ int kq_decim_destroy(kq_decimator *d) {
   kq::DeviceScope dev_scope_(d ? d->cfg.device : -1);
   if (!d) return -1;
   d->close();
-  if (d->err) (void)hipHostFree(d->err);
   delete d;
   return 0;
 }

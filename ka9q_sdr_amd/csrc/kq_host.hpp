@@ -1,6 +1,8 @@
-// kq_host.hpp -- the host half that the satellite banks share (kq_afsk, kq_decim, kq_mod, kq_spec, kq_wfm): error
-// reporting, the handle's stream and the device memory the handle owns.  Host only; a handle's struct derives from
-// kq::HostSide.  Every member function wants the handle's device current (the entry point's kq::DeviceScope).
+// kq_host.hpp -- the host half that every handle shares (kq_bank, and the satellite banks kq_afsk, kq_decim, kq_mod, kq_spec,
+// kq_wfm): error reporting, the handle's streams, and whatever the handle owns on the device or for it -- device memory,
+// pinned host memory, events.  Each is named once, where it is made; close() lets go of all of it.  Host only; a handle's
+// struct derives from kq::HostSide.  Every member function wants the handle's device current (the entry point's
+// kq::DeviceScope).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -21,9 +23,11 @@ void kq_internal_set_error(const char *fmt, ...);  // kq_bank.cpp: the text kq_l
 namespace kq {
 
 struct HostSide {
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
-  std::vector<void *> held;  // every device allocation the handle holds, in the order it was made
+  hipStream_t stream = nullptr;      // the handle's main stream: the caller's, or one of `streams`
+  std::vector<void *> held;          // every device allocation the handle holds, in the order it was made
+  std::vector<void *> pinned;        // pinned host memory
+  std::vector<hipEvent_t> events;
+  std::vector<hipStream_t> streams;  // the streams the handle made itself (a stream the caller handed in is never here)
 
   // the caller's stream (kq_*_config::stream), or a non-blocking one of the handle's own
   int open_stream(void *given) {
@@ -31,8 +35,28 @@ struct HostSide {
       stream = (hipStream_t)given;
       return 0;
     }
-    KQ_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    own_stream = true;
+    return new_stream(&stream);
+  }
+
+  // a further non-blocking stream of the handle's own
+  int new_stream(hipStream_t *s) {
+    KQ_TRY(hipStreamCreateWithFlags(s, hipStreamNonBlocking));
+    streams.push_back(*s);
+    return 0;
+  }
+
+  // an event, destroyed by close(); flags as for hipEventCreateWithFlags (hipEventDefault: one that can be timed)
+  int new_event(hipEvent_t *e, unsigned flags) {
+    KQ_TRY(hipEventCreateWithFlags(e, flags));
+    events.push_back(*e);
+    return 0;
+  }
+
+  // `count` elements of pinned host memory, freed by close(); flags as for hipHostMalloc.  Not cleared
+  template <class T>
+  int alloc_pinned(T **p, size_t count, unsigned flags = hipHostMallocDefault) {
+    KQ_TRY(hipHostMalloc((void **)p, count * sizeof(T), flags));
+    pinned.push_back(*p);
     return 0;
   }
 
@@ -72,14 +96,20 @@ struct HostSide {
     return 0;
   }
 
-  // at destroy: waits for the stream, frees what is still held, destroys the stream if it is the handle's own
+  // at destroy: waits for every stream before anything goes (a copy in flight on one may read or write a buffer that work
+  // on another made), then frees device memory, pinned memory, events and, last, the streams of the handle's own
   void close() {
     if (stream) (void)hipStreamSynchronize(stream);
+    for (hipStream_t s : streams) (void)hipStreamSynchronize(s);
     for (void *q : held) (void)hipFree(q);
+    for (void *q : pinned) (void)hipHostFree(q);
+    for (hipEvent_t e : events) (void)hipEventDestroy(e);
+    for (hipStream_t s : streams) (void)hipStreamDestroy(s);
     held.clear();
-    if (own_stream) (void)hipStreamDestroy(stream);
+    pinned.clear();
+    events.clear();
+    streams.clear();
     stream = nullptr;
-    own_stream = false;
   }
 };
 

@@ -10,6 +10,7 @@ import ka9q_sdr_amd as kq
 import kq_oracle as ko
 from common import bank_cfg, rel_rms, run_oracle
 from ka9q_sdr_amd import workload as wl
+from test_rtp_ingest import rtp_packet
 
 pytestmark = pytest.mark.gpu
 
@@ -128,18 +129,40 @@ def test_handles_release_their_device_memory(gpu):
         assert hip.hipMemGetInfo(C.byref(f), C.byref(t)) == 0
         return f.value
 
-    g = wl.GEOMETRY["cfg3"]
-    plan = wl.channel_plan("cfg3", 16)
-    iq = wl.make_iq(g["samprate"], 2 * g["L"], seed=1)
+    # Each bank goes through everything a bank makes after create as well: streaming host I/O on pinned memory (copy streams,
+    # input staging, the event rings), a datagram (the pinned gathering buffers), the PCM planes, a carrier-tracking channel
+    # (a chunk of PLL slots is 33 MiB: a leaked one fails the bound on the second cycle), the timing events, and on the
+    # full path the master spectrum's capture buffer.  cfg 5 with compute_n0 is the N = 65536 path and its own buffers.
+    nb = 2
+    cases = []
+    for name, mode, n0 in (("cfg3", kq.KQ_FWD_PRUNED, False), ("cfg3", kq.KQ_FWD_FULL, True), ("cfg5", kq.KQ_FWD_AUTO, True)):
+        g = wl.GEOMETRY[name]
+        plan = wl.channel_plan(name, 16 if name == "cfg3" else 4)
+        plan.append(dict(demod="linear", low=-5000.0, high=5000.0, second_lo=-20000.0, recovery_rate=50.0, pll=1))
+        cases.append((g, plan, mode, n0, wl.make_iq(g["samprate"], nb * g["L"], seed=1)))
+    hin = kq.HostBuffer(max(iq.nbytes for *_, iq in cases))
+    haudio = kq.HostBuffer(max(len(plan) * nb * 2 * (g["L"] // g["D"]) * 4 for g, plan, *_ in cases))
+    hstatus = kq.HostBuffer(max(len(plan) for _, plan, *_ in cases) * nb * C.sizeof(kq.ChanStatus))
+    packet = rtp_packet(7, 1000, 0x1234, np.zeros((240, 2), "<i2").tobytes())
 
     def cycle():
-        for mode, n0 in ((kq.KQ_FWD_PRUNED, False), (kq.KQ_FWD_FULL, True)):
-            bank = kq.Bank(g["samprate"], g["L"], g["M"], g["D"], len(plan), 2, compute_n0=n0, fwd_mode=mode)
+        for g, plan, mode, n0, iq in cases:
+            bank = kq.Bank(g["samprate"], g["L"], g["M"], g["D"], len(plan), nb, compute_n0=n0, fwd_mode=mode)
             bank.enable_pcm(True)
+            bank.enable_timing(2)
             for p in plan:
                 bank.add_channel(bank_cfg(p))
-            bank.push_iq(iq)
-            assert bank.process() == 2
+            full = bank.fwd_mode == kq.KQ_FWD_FULL
+            if full:
+                bank.arm_spectrum(0)
+            hin.array(np.complex64)[:iq.size] = iq
+            bank.push_iq_async(hin.ptr, iq.size)
+            assert bank.push_rtp(packet) == 240     # (stays in the ring: less than a block)
+            assert bank.process() == nb
+            bank.pull_planes_async(haudio.ptr, hstatus.ptr)
+            bank.pull_wait()
+            if full:
+                assert bank.spectrum(0, 0).size == g["L"] + g["M"] - 1
             bank.sync()
             bank.close()
         dec = kq.Decimator(6, 8, 1, max_out=1024)
@@ -154,6 +177,8 @@ def test_handles_release_their_device_memory(gpu):
     for _ in range(10):
         cycle()
     after = free_bytes()
+    for h in (hin, haudio, hstatus):
+        h.free()
     assert before - after < 8 << 20, (before, after)
 
 
