@@ -1,4 +1,4 @@
-// kq_ctl.hpp -- one write record of the bank's control queues (kq_bank.cpp CtlQueue) and the workgroup-wide routine that applies it:
+// kq_ctl.hpp -- one write record of the bank's control queues (kq_bank.hpp CtlQueue, filled by kq_bank_ctl.cpp) and the workgroup-wide routine that applies it:
 // shared by k_ctl_apply (kq_kernels.hip) and by the response-design kernel (kq_design.hip), whose launch takes the filter side's
 // records along when a call has both (one launch instead of two in front of the call's kernels).
 #pragma once

@@ -46,7 +46,7 @@ FftDim fft_dim(int n, bool *ok);
 bool fft_size_ok(int n);      // n = 2^a 3^b 5^c 7^d, 2 <= n <= 65536, even
 
 // Carrier-tracking channels keep their loop state, 65536-sample ring and search scratch in a SLOT of their own for as long
-// as they exist (kq_bank.cpp pll_acquire): storage grows by chunks of kPllChunk slots, nothing ever moves.
+// as they exist (kq_bank_chan.cpp pll_acquire): storage grows by chunks of kPllChunk slots, nothing ever moves.
 constexpr int kPllChunk = 64;
 struct PllChunk {
   PllState *state;  // [kPllChunk]
@@ -71,7 +71,7 @@ constexpr int kOldLevels = 4;  // retune transitions a window may hold beyond th
 struct ChanDev {
   // configuration
   int *mode;            // enum kq_demod_type
-  int *flags;           // as the demodulators see them (written on their stream, kq_bank.cpp ctl queues)
+  int *flags;           // as the demodulators see them (written on their stream, kq_bank_ctl.cpp's queues)
   int *fflags;          // the same word as the filter kernels see it (FLAG_ISB): written on the main stream
   float *low, *high;    // Hz, for compute_n0's passband exclusion
   float2 *resp;
@@ -172,7 +172,7 @@ void launch_block_energy_sum(hipStream_t s, const float2 *newsamples, int L, int
                              void *params_dev, size_t params_bytes, float2 *paired, int hist, const double *prev_planes = nullptr,
                              unsigned nchan = 0, unsigned cmax = 0, double adv = 0, double adv_out = 0, const void *patch_records_host = nullptr,
                              int npatch = 0, const void *patch_bits_host = nullptr);
-// control-plane writes of a call, gathered by the host in pinned memory (kq_bank.cpp CtlQueue): nrec records {dst, nbytes,
+// control-plane writes of a call, gathered by the host in pinned memory (kq_bank.hpp CtlQueue): nrec records {dst, nbytes,
 // payload offset | fill value}; one workgroup per record copies or fills 4-byte words
 void launch_ctl_apply(hipStream_t s, const void *queue_host, int nrec);
 void launch_block_energy_iir(hipStream_t s, const float *sums, int L, int nblocks, const unsigned char *update, float *energy_state,

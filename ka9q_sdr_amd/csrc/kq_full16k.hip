@@ -661,7 +661,7 @@ __global__ __launch_bounds__(kT, 4) void k_filter_full16k(Geom g, ChanDev ch, Pl
       asm("v_fma_f32 %0, %1, %1, %0" : "+v"(p0) : "v"(ya[k3].y));
       asm("v_fma_f32 %0, %1, %1, %0" : "+v"(p1) : "v"(yb[k3].y));
       // Passband exclusion (radio.c:405-411): the bin counts as 0 from here on.  Which bins lie inside the passband
-      // depends only on the channel's filter edges and is precomputed on the host (kq_bank.cpp upload_n0mask) as one
+      // depends only on the channel's filter edges and is precomputed on the host (kq_bank_ctl.cpp upload_n0mask) as one
       // 64-bit LANE mask per (wave, bin slot): scalar loads, and one v_cndmask with the mask as its condition per bin.
       // (With the reference's 32-bit wrap of k * samprate the "passband" is scattered over the whole spectrum at
       // 10 MS/s -- 6 % of all bins -- so there are no rows to skip; a bit mask per thread took and / compare / select

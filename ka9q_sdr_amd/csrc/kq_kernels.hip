@@ -94,7 +94,7 @@ __global__ void k_block_energy_sum(const float2 *__restrict__ x, int L, float *_
   int const pcol = 2 * (threadIdx.x & 511) + (threadIdx.x >> 9);  // place of sample (row parity, column) within its pair of rows
   int const nsum = nblocks * split;
   if ((int)blockIdx.x >= nsum + copy_wgs + hist_wgs) {
-    // the channels retuned since the last call (kq_bank.cpp: patch_list): their planes as the host staged them, records of
+    // the channels retuned since the last call (kq_bank.hpp: patch_list): their planes as the host staged them, records of
     // (channel index, eight values) in pinned memory.  The advancing threads below leave exactly these channels alone
     // (patch_bits: one bit per channel, staged with the records), so the two never write the same place.
     int const j = ((int)blockIdx.x - nsum - copy_wgs - hist_wgs) * (int)blockDim.x + (int)threadIdx.x;
@@ -197,7 +197,7 @@ void launch_block_energy_sum(hipStream_t s, const float2 *newsamples, int L, int
                      npatch ? static_cast<const unsigned long long *>(patch_bits_host) : nullptr);
 }
 
-// Control-plane writes (kq_bank.cpp CtlQueue): what kq_bank_set_filter / add_channel / set_mode ... change on the device,
+// Control-plane writes (kq_bank.hpp CtlQueue): what kq_bank_set_filter / add_channel / set_mode ... change on the device,
 // gathered by the host in pinned memory since the last call and applied here in ONE launch -- as separate small copies each
 // cost the stream 10-20 us of switching between kernel and copy packets (a kq_bank_set_filter came to 0.8 ms of pipeline
 // time on a bank at real time, tools/soak_realtime.py).  Record r (32 bytes at the front of the buffer): destination, byte

@@ -494,7 +494,7 @@ def test_if_power_recurrence_in_the_filter_launch_is_the_stand_alone_one(gpu, co
 
 @pytest.mark.parametrize("L,D,C", [(8192, 256, 1), (8192, 256, 2), (8192, 256, 9), (32768, 512, 3)])
 def test_full_bank_of_distinct_edges_changes_every_filter(gpu, L, D, C):
-    """compute_n0's passband masks live in max_channels slot sets, one per distinct pair of edges (kq_bank.cpp
+    """compute_n0's passband masks live in max_channels slot sets, one per distinct pair of edges (kq_bank_ctl.cpp
     acquire_n0slot).  A FULL bank in which every channel has its own edges has no free set: a filter change must give the
     channel's old set back before it asks for a new one (asking first wrote one set past the planes -- 2 KiB,
     8 KiB at N = 65536, beyond n0lane and 4 bytes beyond n0meta).  Every channel's filter changes twice between calls, on

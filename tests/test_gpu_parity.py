@@ -1608,7 +1608,7 @@ def _pll_plan(n):
 
 def test_a_thousand_carrier_tracking_channels_in_one_bank(gpu):
     """linear.c:129-246 on 1 024 channels of ONE bank (rounds 1-5 stopped at 64: slot = rank among the PLL channels, fixed
-    allocations; now a slot per channel out of chunks of 64 that are allocated as the count grows, kq_bank.cpp pll_acquire).
+    allocations; now a slot per channel out of chunks of 64 that are allocated as the count grows, kq_bank_chan.cpp pll_acquire).
     Every 93rd channel against the oracle: lock state, lock counter, hang counter block for block, carrier phase and offset,
     audio; all channels: the right number of samples, the carrier found."""
     g = wl.GEOMETRY["cfg1"]

@@ -554,7 +554,7 @@ def test_8192_mixed_channels_two_blocks_per_call_against_the_oracle(gpu):
 
 
 def test_many_filter_changes_between_two_calls(gpu):
-    """Responses are designed on the bank's stream in front of the call that uses them (kq_bank.cpp DesignQueue): 1300
+    """Responses are designed on the bank's stream in front of the call that uses them (kq_bank.hpp DesignQueue): 1300
     kq_bank_set_filter calls between two calls in flight -- more than one design launch holds, so the queue is applied early
     once -- then a second set_filter for some of those channels (the later design of a channel replaces the earlier one),
     nothing drained.  Against a bank that is drained around every single change: responses (fetched from the device when
