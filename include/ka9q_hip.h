@@ -511,6 +511,80 @@ int kq_decim_process(kq_decimator *d, const float *iq_in, int on_device, size_t 
 int kq_decim_sync(kq_decimator *d);
 int kq_decim_reset(kq_decimator *d);
 
+/* --- raw A/D conditioning ahead of the cascade -----------------------------------------------------------------
+ * What the front-end daemons do to every sample that comes off the A/D before the Fs/4 rotation and the cascade
+ * (hackrf.c:122-196 rx_callback, funcube.c:287-390): integer to float, DC removal, I/Q gain balance at constant total
+ * energy, I/Q phase correction, and the running estimates behind them, updated once per block.
+ *
+ * Definition.  The stream is cut into blocks of `block` samples, counted from the first sample after create / reset,
+ * whatever the call boundaries are.  For int8 a raw -128 counts one clip and becomes -127 (hackrf.c:146-153).  With the
+ * float constants DC_i, DC_q, gain_i, gain_q, secphi, tanphi in force at the start of a sample's block, per sample, in
+ * float, unfused, in the reference's operand order:
+ *     x = float(i) * SCALE - DC_i;  y = float(q) * SCALE - DC_q;  x *= gain_i;  y *= gain_q;  y = secphi * y - tanphi * x
+ * SCALE = (float)(1./127) for int8, (float)(1./32767) for int16.  Output cf32 is (x, y); output int16 is
+ * round(v * 32767) (funcube.c:348), saturated to +-32767 ... -32768.
+ * Per block, in double (+ - * / sqrt, no fused operations), from the exact integer moments n = block, SI, SQ, SII, SQQ,
+ * SIQ of the block's samples, S = (double)SCALE and the constants above:
+ *     sum_i = S * SI;  sum_q = S * SQ
+ *     i_energy = S * S * SII - 2 * DC_i * (S * SI) + n * (DC_i * DC_i)           (q_energy alike)
+ *     dotprod  = (gain_i * gain_q) * (S * S * SIQ - DC_q * (S * SI) - DC_i * (S * SQ) + n * (DC_i * DC_q))
+ * then the reference's update (hackrf.c:182-193), every stored value rounded to float:
+ *     DC_i += dc_alpha * (sum_i - n * DC_i)                                       (DC_q alike, with the old DC)
+ *     block_energy = 0.5 * (i_energy + q_energy);  only if block_energy > 0:
+ *       in_power = block_energy / n
+ *       imbalance += r * (i_energy / q_energy - imbalance)      r = block / (adc_samprate * power_alpha)
+ *       sinphi    += r * (dotprod / block_energy - sinphi)
+ *       gain_q = sqrt(0.5 * (1 + imbalance));  gain_i = sqrt(0.5 * (1 + 1 / imbalance))
+ *       secphi = 1 / sqrt(1 - sinphi * sinphi);  tanphi = sinphi * secphi
+ * Initial state: DC = 0, imbalance = 1, sinphi = 0, in_power = 0, gains and secphi 1, tanphi = 0.  The integer sums do
+ * not depend on the order they are formed in, so the result is the same bits on every device and for every way of cutting
+ * the stream into calls; it differs from the reference's literal loop by that loop's own float rounding of its sums
+ * (DESIGN 4.14).  A partial block at the end of a call leaves its moments and clip count in the handle.
+ *
+ * Calls: kq_fe_create checks its arguments before it touches a device.  on_device != 0: every pointer is device memory
+ * (raw 16-byte aligned) and the call is asynchronous on the handle's stream; otherwise host memory, synchronous.  There is
+ * no CPU path. */
+typedef struct kq_frontend kq_frontend;
+enum kq_fe_format { KQ_FE_S8 = 0, KQ_FE_S16 = 1 }; /* interleaved I,Q: int8 (HackRF) or int16 in host byte order (Funcube) */
+typedef struct kq_fe_config {
+  int device;
+  int format;          /* enum kq_fe_format */
+  unsigned block;      /* samples per update, 64 .. 1 << 22 (the int16 second moments then stay below 2^53) */
+  double adc_samprate; /* > 0 */
+  double dc_alpha;     /* > 0, per sample: hackrf.c:74 has 1e-7, funcube.c:65 1e-6 */
+  double power_alpha;  /* > 0, seconds: hackrf.c:75, funcube.c:66 have 1.0 */
+  size_t max_samples;  /* largest n of one call (n_out << log_decimate for kq_fe_process_decim) */
+  void *stream;        /* hipStream_t to run on, NULL = private stream */
+} kq_fe_config;
+/* The state after a completed block. */
+typedef struct kq_fe_status {
+  unsigned long long samples; /* samples in completed blocks since create / reset */
+  unsigned long long blocks;
+  unsigned long long clips;   /* int8 -128 values met in completed blocks, I and Q counted separately */
+  float DC_i, DC_q, imbalance, sinphi, in_power;
+  float gain_i, gain_q, secphi, tanphi; /* in force from the next block on */
+  float reserved_;
+} kq_fe_status;
+kq_frontend *kq_fe_create(const kq_fe_config *cfg);
+int kq_fe_destroy(kq_frontend *fe);
+int kq_fe_reset(kq_frontend *fe);
+int kq_fe_sync(kq_frontend *fe);
+void *kq_fe_stream(kq_frontend *fe); /* the hipStream_t the handle runs on, for a kq_decim_config / kq_bank_config beside it */
+/* Conditions n samples (any n up to max_samples).  raw: n I,Q pairs of the configured format.  out_cf32 (n complex
+ * floats) and out_s16 (n I,Q int16 pairs) may each be NULL.  block_status (may be NULL) receives one record for each block
+ * completed inside the call, in order: at most (n + block - 1) / block of them; the return value is their number, -1 on
+ * error. */
+int kq_fe_process(kq_frontend *fe, const void *raw, int on_device, size_t n, float *out_cf32, int16_t *out_s16,
+                  kq_fe_status *block_status);
+/* Conditions n_out << log_decimate raw samples and runs dec's cascade on them; out_cf32, out_s16, out_energy as for
+ * kq_decim_process.  Outputs and the carried state of both handles are those of kq_fe_process into a buffer followed by
+ * kq_decim_process on that buffer, but no input-rate float buffer is written: the cascade's first kernel reads the raw
+ * samples.  fe and dec must be on the same device and stream. */
+int kq_fe_process_decim(kq_frontend *fe, kq_decimator *dec, const void *raw, int on_device, size_t n_out, float *out_cf32,
+                        int16_t *out_s16, float *out_energy, kq_fe_status *block_status);
+/* The state after the last completed block; waits for the handle's stream. */
+int kq_fe_get_status(kq_frontend *fe, kq_fe_status *out);
+
 /* --- AFSK-1200 / HDLC packet decoder -----------------------------------------------------------
  * What the `packet` program does per RTP session between its PCM input and a decoded AX.25 frame: the REAL master
  * filter of 1000 new samples / 1049 taps (packet.c:41-45,190), the analytic 100..4000 Hz slave (packet.c:272-273),

@@ -29,6 +29,7 @@ from .bank import (  # noqa: F401
     load_library,
 )
 from .decimate import Decimator  # noqa: F401,E402
+from .frontend import FE_STATUS_DTYPE, FrontEnd, KQ_FE_S8, KQ_FE_S16  # noqa: F401,E402
 from .packet import AfskBank, KQ_PCM_F32, KQ_PCM_S16BE  # noqa: F401,E402
 from . import iqfile  # noqa: F401,E402
 from .modulate import KQ_MOD_FM, KQ_MOD_LINEAR, ModBank, StationConfig, station_config  # noqa: F401,E402

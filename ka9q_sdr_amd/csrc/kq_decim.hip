@@ -21,6 +21,7 @@
 
 #include "ka9q_hip.h"
 #include "kq_device.hpp"
+#include "kq_fe.hpp"
 #include "kq_host.hpp"
 
 // hipcc contracts a*b+c into an FMA by default (and its __fmul_rn/__fadd_rn are plain operators), which would change
@@ -59,6 +60,7 @@ struct GroupArgs {
   int final;
   float scale;
   float c0, c1, c2, c3;
+  kq::FeRaw raw;       // RAW instances (first group of kq_fe_process_decim): the raw samples take the place of `in`
 };
 
 // The caller's samples are read once (plus a tile's 98-sample halo): nontemporal loads, which leave the cache to the
@@ -178,7 +180,11 @@ using ic = std::integral_constant<int, N>;
 // filter) the tile starts one sample earlier, which swaps the roles of the planes for stage 0 (`pad` below).
 // EDGE = this workgroup takes the tiles that need care -- the first (history buffer) and a ragged last one -- with
 // clamped indices and a pointer select; the other workgroups share the full tiles in between and need neither.
-template <int G, bool FINAL, bool ROT, bool EDGE>
+// RAW = 1 (int8) or 2 (int16): the group reads raw A/D samples, 16 bytes (kVec samples) per lane, and conditions them in
+// registers (kq_fe.hpp) on the way to the LDS planes.  The vectors are aligned in the caller's buffer, so a full tile
+// fetches up to kVec - 2 samples ahead of its halo and drops them.  The edge workgroup reads sample pairs instead, straight
+// into LDS, and the history it leaves behind is conditioned: the carried state is the same as with complex float input.
+template <int G, bool FINAL, bool ROT, bool EDGE, int RAW = 0>
 __device__ __forceinline__ void hb_group_body(const GroupArgs &a, float2 *lds) {
   // halo_s: history (in level-s samples) that level s must hold ahead of a tile's first output
   int halo[G + 1];
@@ -202,15 +208,31 @@ __device__ __forceinline__ void hb_group_body(const GroupArgs &a, float2 *lds) {
   constexpr int kLoadIters = (kMaxLen0 + kPer * kThreads - 1) / (kPer * kThreads);
   constexpr int kFullIters = (kTileOut << G) / (kPer * kThreads);  // always inside a full tile, whatever the halo
   using LoadT = float4;
-  LoadT v[kLoadIters];
+  LoadT v[RAW ? 1 : kLoadIters];
   int const tid = threadIdx.x;
+  constexpr bool kS16 = RAW == 2;
+  constexpr int kVec = kq::fe_vec<kS16>();
+  constexpr int kRawIters = (kMaxLen0 + 8 + kVec * kThreads - 1) / (kVec * kThreads);
+  uint4 rv[RAW && !EDGE ? kRawIters : 1];
+  // samples fetched ahead of the halo so that every vector is aligned, and a full tile's length with them
+  int const ext = ((halo[0] + pad + kVec - 1) & ~(kVec - 1)) - (halo[0] + pad);
+  int const len0r = (kTileOut << G) + halo[0] + pad + ext;
 
   // Level 0 of tile t as loaded: global input index = t * kTileOut * 2^G - halo[0] - pad + i, i < (tile << G) + halo[0]
   // + pad (an even count from an even index).  All loads of a thread are issued back to back.
   auto fetch = [&](long long t) {
     long long const first_out = t * kTileOut;
     long long const lo0 = (first_out << G) - halo[0] - pad;
-    if constexpr (!EDGE) {
+    if constexpr (RAW != 0) {
+      if constexpr (!EDGE) {
+        const char *base = reinterpret_cast<const char *>(a.raw.raw) + (lo0 - ext) * (kS16 ? 4 : 2);
+#pragma unroll
+        for (int it = 0; it < kRawIters; it++) {
+          int const i = min((it * kThreads + tid) * kVec, len0r - kVec);
+          rv[it] = kq::fe_load_once(reinterpret_cast<const uint4 *>(base + (size_t)i * (kS16 ? 4 : 2)));
+        }
+      }
+    } else if constexpr (!EDGE) {
       int const len0 = (kTileOut << G) + halo[0] + pad;
       const LoadT *src = reinterpret_cast<const LoadT *>(a.in + lo0) + tid;
 #pragma unroll
@@ -253,17 +275,63 @@ __device__ __forceinline__ void hb_group_body(const GroupArgs &a, float2 *lds) {
     // rotation phase of this thread's first sample; later iterations are a multiple of 4 samples further on
     int const ph = a.rot_phase0 + (int)((lo0 + tid * kPer) & 3) * a.rot_step;
     bool const full = !EDGE;
+    if constexpr (RAW != 0 && !EDGE) {
+      // the tile's first vector: one division per tile, uniform; the lanes go on from there
+      kq::FeSpan const span0 = kq::fe_locate(a.raw, (unsigned)(lo0 - ext));
+      float const rcp_block = 1.f / (float)a.raw.block;
 #pragma unroll
-    for (int it = 0; it < kLoadIters; it++) {
-      int const i = (it * kThreads + tid) * kPer;
-      if ((it < kFullIters && full) || i < len[0] + pad) {
-        float2 w0 = make_float2(v[it].x, v[it].y), w1 = make_float2(v[it].z, v[it].w);
-        if constexpr (ROT) {
-          w0 = rot90(w0, ph);
-          w1 = rot90(w1, ph + a.rot_step);
+      for (int it = 0; it < kRawIters; it++) {
+        int const i0 = (it * kThreads + tid) * kVec;
+        if (i0 < len0r) {
+          kq::FeSpan const sp = kq::fe_advance(span0, (unsigned)i0, a.raw.block, rcp_block);
+          kq::fe_vector<kS16>(a.raw, rv[it], sp, [&](int j, float2 w0, float2 w1) {
+            int const li = i0 + j - ext;  // lo0 - ext + i0 is a multiple of 4: sample j has rotation phase j
+            if (li >= 0) {
+              if constexpr (ROT) {
+                w0 = rot90(w0, a.rot_phase0 + j * a.rot_step);
+                w1 = rot90(w1, a.rot_phase0 + (j + 1) * a.rot_step);
+              }
+              lvA.even[li >> 1] = w0;
+              lvA.odd[li >> 1] = w1;
+            }
+          });
         }
-        lvA.even[it * kThreads + tid] = w0;
-        lvA.odd[it * kThreads + tid] = w1;
+      }
+    } else if constexpr (RAW != 0) {
+#pragma unroll 1
+      for (int it = 0; it < kLoadIters; it++) {
+        int const i = (it * kThreads + tid) * kPer;
+        if (i < len[0] + pad) {
+          long long const gi = lo0 + i;
+          float2 w0, w1;
+          if (gi < 0) {
+            w0 = a.hist[a.halo + gi];  // hist[-1] exists (the pad sample, unused)
+            w1 = a.hist[a.halo + gi + 1];
+          } else {
+            w0 = kq::fe_sample<kS16>(a.raw, (unsigned)gi);
+            w1 = kq::fe_sample<kS16>(a.raw, (unsigned)gi + 1);
+          }
+          if constexpr (ROT) {
+            w0 = rot90(w0, ph);
+            w1 = rot90(w1, ph + a.rot_step);
+          }
+          lvA.even[it * kThreads + tid] = w0;
+          lvA.odd[it * kThreads + tid] = w1;
+        }
+      }
+    } else {
+#pragma unroll
+      for (int it = 0; it < kLoadIters; it++) {
+        int const i = (it * kThreads + tid) * kPer;
+        if ((it < kFullIters && full) || i < len[0] + pad) {
+          float2 w0 = make_float2(v[it].x, v[it].y), w1 = make_float2(v[it].z, v[it].w);
+          if constexpr (ROT) {
+            w0 = rot90(w0, ph);
+            w1 = rot90(w1, ph + a.rot_step);
+          }
+          lvA.even[it * kThreads + tid] = w0;
+          lvA.odd[it * kThreads + tid] = w1;
+        }
       }
     }
     __syncthreads();
@@ -349,7 +417,10 @@ __device__ __forceinline__ void hb_group_body(const GroupArgs &a, float2 *lds) {
     float2 hv = make_float2(0.f, 0.f);
     if (tid < a.halo) {
       long long const gi = n_in - a.halo + tid;
-      hv = gi >= 0 ? a.in[gi] : a.hist[a.halo + gi];
+      if constexpr (RAW != 0)
+        hv = gi >= 0 ? kq::fe_sample<kS16>(a.raw, (unsigned)gi) : a.hist[a.halo + gi];
+      else
+        hv = gi >= 0 ? a.in[gi] : a.hist[a.halo + gi];
     }
     __syncthreads();
     if (tid < a.halo) const_cast<float2 *>(a.hist)[tid] = hv;
@@ -391,14 +462,14 @@ __device__ __forceinline__ void hb_group_body(const GroupArgs &a, float2 *lds) {
 
 // six waves per SIMD = three workgroups per CU, which is what the 50 KB tile allows: the FINAL instances otherwise take
 // 86-91 registers and run two (log_decimate 3 and 4: -5 % and -10 %)
-template <int G, bool FINAL, bool ROT>
+template <int G, bool FINAL, bool ROT, int RAW = 0>
 __global__ __launch_bounds__(kThreads, 6) void k_hb_group(GroupArgs a) {
   extern __shared__ float4 lds4[];
   float2 *lds = reinterpret_cast<float2 *>(lds4);
   if (blockIdx.x == 0)
-    hb_group_body<G, FINAL, ROT, true>(a, lds);
+    hb_group_body<G, FINAL, ROT, true, RAW>(a, lds);
   else
-    hb_group_body<G, FINAL, ROT, false>(a, lds);
+    hb_group_body<G, FINAL, ROT, false, RAW>(a, lds);
 }
 
 using GroupKernel = void (*)(GroupArgs);
@@ -407,6 +478,19 @@ template <int G>
 GroupKernel group_kernel_g(bool final, bool rotate) {
   if (final) return rotate ? k_hb_group<G, true, true> : k_hb_group<G, true, false>;
   return rotate ? k_hb_group<G, false, true> : k_hb_group<G, false, false>;
+}
+
+// The raw first group: fewer than four stages means it is also the last one.
+template <int RAW>
+GroupKernel raw_kernel(int nstages, bool final, bool rotate) {
+  switch (nstages) {
+    case 1: return rotate ? k_hb_group<1, true, true, RAW> : k_hb_group<1, true, false, RAW>;
+    case 2: return rotate ? k_hb_group<2, true, true, RAW> : k_hb_group<2, true, false, RAW>;
+    case 3: return rotate ? k_hb_group<3, true, true, RAW> : k_hb_group<3, true, false, RAW>;
+    default:
+      if (final) return rotate ? k_hb_group<4, true, true, RAW> : k_hb_group<4, true, false, RAW>;
+      return rotate ? k_hb_group<4, false, true, RAW> : k_hb_group<4, false, false, RAW>;
+  }
 }
 
 GroupKernel group_kernel(int nstages, bool final, bool rotate) {
@@ -427,6 +511,8 @@ struct Group {
   float2 *out = nullptr;  // intermediate buffer (null for the last group)
   unsigned resident = 0;  // workgroups of this group's kernel that fit on a CU (for resident_for bytes of LDS)
   size_t resident_for = 0;
+  unsigned resident_raw[2] = {0, 0};  // the same for the first group's raw instances, int8 and int16
+  size_t resident_raw_for[2] = {0, 0};
 };
 
 }  // namespace
@@ -532,6 +618,86 @@ int kq_decim_set_coeffs(kq_decimator *d, const float coeffs[4]) {
   return 0;
 }
 
+}  // extern "C"
+
+// The call's launches, device memory throughout: `raw` (kq_fe_process_decim) takes the place of `src` for the first group
+static int decim_launch(kq_decimator *d, const float2 *src, const kq::FeRaw *raw, size_t n_out, float2 *final_out,
+                        int16_t *final16, float *energy) {
+  int const S = d->cfg.log_decimate;
+  size_t const n_in = n_out << S;
+  d->epoch++;
+  if (d->epoch == 0) d->epoch = 1;  // 0 is what a never-written word holds (the bank's tags skip it the same way)
+  size_t n_g_in = n_in;
+  for (size_t gi = 0; gi < d->groups.size(); gi++) {
+    Group &g = d->groups[gi];
+    bool const last = gi + 1 == d->groups.size();
+    bool const is_raw = raw && gi == 0;
+    GroupArgs a{};
+    a.in = src;
+    if (is_raw) a.raw = *raw;
+    a.hist = g.hist;
+    a.out = last ? final_out : g.out;
+    a.out16 = last ? final16 : nullptr;
+    a.partial = last ? d->partial : nullptr;
+    a.energy_out = last ? energy : nullptr;
+    a.err = d->err;
+    a.epoch = d->epoch;
+    a.n_out = (long long)(n_g_in >> g.nstages);
+    a.nstages = g.nstages;
+    a.hb15_mask = g.mask;
+    a.halo = g.halo;
+    a.rotate = gi == 0 && (d->cfg.offset & 3) != 0;
+    a.rot_step = d->cfg.offset & 3;
+    a.rot_phase0 = d->rot_phase;
+    a.in_once = gi == 0;
+    a.final = last;
+    a.scale = d->atten;
+    a.c0 = d->coeffs[0];
+    a.c1 = d->coeffs[1];
+    a.c2 = d->coeffs[2];
+    a.c3 = d->coeffs[3];
+    int const kTileOut = tile_out(g.nstages);
+    unsigned const ntiles = (unsigned)((a.n_out + kTileOut - 1) / kTileOut);
+    // two planes each for level 0 and level 1
+    int const h1 = (g.halo - ((g.mask & 1) ? 14 : 1)) / 2;
+    size_t const lds_elems = 2 * (size_t)plane_cap((kTileOut << g.nstages) + g.halo + (g.halo & 1)) +
+                             (g.nstages > 1 ? 2 * (size_t)plane_cap((kTileOut << (g.nstages - 1)) + h1) : 0);
+    // persistent workgroups: exactly as many as fit on the device at once (registers, wave slots and LDS all count -- an
+    // estimate from the LDS alone once launched half as many again as could run, and the stragglers ran alone)
+    GroupKernel const kern = !is_raw        ? group_kernel(g.nstages, last, a.rotate != 0)
+                             : raw->s16     ? raw_kernel<2>(g.nstages, last, a.rotate != 0)
+                                            : raw_kernel<1>(g.nstages, last, a.rotate != 0);
+    size_t const lds_bytes = sizeof(float2) * lds_elems;
+    unsigned &resident = is_raw ? g.resident_raw[raw->s16 ? 1 : 0] : g.resident;
+    size_t &resident_for = is_raw ? g.resident_raw_for[raw->s16 ? 1 : 0] : g.resident_for;
+    if (resident_for != lds_bytes) {
+      int nb = 0;
+      KQ_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)kern, kThreads, lds_bytes));
+      resident = (unsigned)std::max(1, nb);
+      resident_for = lds_bytes;
+    }
+    unsigned const grid = std::min(ntiles, d->num_cus * resident) + 1;  // + the edge workgroup
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), lds_bytes, d->stream, a);
+    src = g.out;
+    n_g_in >>= g.nstages;
+  }
+  KQ_TRY(hipGetLastError());
+  d->rot_phase = (int)((d->rot_phase + (long long)(n_in & 3) * (d->cfg.offset & 3)) & 3);
+  return 0;
+}
+
+void kq_decim_internal_get_info(kq_decimator *d, kq_decim_internal_info *out) {
+  *out = kq_decim_internal_info{d->cfg.device, (void *)d->stream, d->cfg.log_decimate, d->cfg.max_out};
+}
+
+int kq_decim_internal_process_raw(kq_decimator *d, const kq::FeRaw &raw, size_t n_out, float *out_cf32, int16_t *out_s16,
+                                  float *out_energy) {
+  kq::DeviceScope dev_scope_(d->cfg.device);
+  return decim_launch(d, nullptr, &raw, n_out, (float2 *)out_cf32, out_s16, out_energy);
+}
+
+extern "C" {
+
 int kq_decim_process(kq_decimator *d, const float *iq_in, int on_device, size_t n_out, float *out_cf32,
                      int16_t *out_s16, float *out_energy) {
   kq::DeviceScope dev_scope_(d ? d->cfg.device : -1);
@@ -560,58 +726,9 @@ int kq_decim_process(kq_decimator *d, const float *iq_in, int on_device, size_t 
     final_out = d->out_dev;
     final16 = out_s16 ? d->out16_dev : nullptr;
   }
-  d->epoch++;
-  if (d->epoch == 0) d->epoch = 1;  // 0 is what a never-written word holds (the bank's tags skip it the same way)
-  size_t n_g_in = n_in;
-  for (size_t gi = 0; gi < d->groups.size(); gi++) {
-    Group &g = d->groups[gi];
-    bool const last = gi + 1 == d->groups.size();
-    GroupArgs a{};
-    a.in = src;
-    a.hist = g.hist;
-    a.out = last ? final_out : g.out;
-    a.out16 = last ? final16 : nullptr;
-    a.partial = last ? d->partial : nullptr;
-    a.energy_out = last && out_energy ? (on_device ? out_energy : d->energy_dev) : nullptr;
-    a.err = d->err;
-    a.epoch = d->epoch;
-    a.n_out = (long long)(n_g_in >> g.nstages);
-    a.nstages = g.nstages;
-    a.hb15_mask = g.mask;
-    a.halo = g.halo;
-    a.rotate = gi == 0 && (d->cfg.offset & 3) != 0;
-    a.rot_step = d->cfg.offset & 3;
-    a.rot_phase0 = d->rot_phase;
-    a.in_once = gi == 0;
-    a.final = last;
-    a.scale = d->atten;
-    a.c0 = d->coeffs[0];
-    a.c1 = d->coeffs[1];
-    a.c2 = d->coeffs[2];
-    a.c3 = d->coeffs[3];
-    int const kTileOut = tile_out(g.nstages);
-    unsigned const ntiles = (unsigned)((a.n_out + kTileOut - 1) / kTileOut);
-    // two planes each for level 0 and level 1
-    int const h1 = (g.halo - ((g.mask & 1) ? 14 : 1)) / 2;
-    size_t const lds_elems = 2 * (size_t)plane_cap((kTileOut << g.nstages) + g.halo + (g.halo & 1)) +
-                             (g.nstages > 1 ? 2 * (size_t)plane_cap((kTileOut << (g.nstages - 1)) + h1) : 0);
-    // persistent workgroups: exactly as many as fit on the device at once (registers, wave slots and LDS all count -- an
-    // estimate from the LDS alone once launched half as many again as could run, and the stragglers ran alone)
-    GroupKernel const kern = group_kernel(g.nstages, last, a.rotate != 0);
-    size_t const lds_bytes = sizeof(float2) * lds_elems;
-    if (g.resident_for != lds_bytes) {
-      int nb = 0;
-      KQ_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)kern, kThreads, lds_bytes));
-      g.resident = (unsigned)std::max(1, nb);
-      g.resident_for = lds_bytes;
-    }
-    unsigned const grid = std::min(ntiles, d->num_cus * g.resident) + 1;  // + the edge workgroup
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), lds_bytes, d->stream, a);
-    src = g.out;
-    n_g_in >>= g.nstages;
-  }
-  KQ_TRY(hipGetLastError());
-  d->rot_phase = (int)((d->rot_phase + (long long)(n_in & 3) * (d->cfg.offset & 3)) & 3);
+  if (decim_launch(d, src, nullptr, n_out, final_out, final16,
+                   out_energy ? (on_device ? out_energy : d->energy_dev) : nullptr))
+    return -1;
   if (out_energy && !on_device)
     KQ_TRY(hipMemcpyAsync(out_energy, d->energy_dev, sizeof(float), hipMemcpyDeviceToHost, d->stream));
   if (!on_device) {
