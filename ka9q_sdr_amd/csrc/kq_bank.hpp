@@ -438,7 +438,7 @@ struct Unlocked {
 };
 
 enum { CTL_FILTER = 0, CTL_DEMOD = 1 };
-struct CtlRecHost {  // kq_kernels.hip CtlRec
+struct CtlRecHost {  // kq_ctl.hpp CtlRec
   unsigned long long dst;
   unsigned nbytes, fill, value, payload_off;  // fill: 0 payload, 1 fill with `value`, 2 copy from device address `src`
   unsigned long long src;

@@ -12,36 +12,14 @@
 // to HBM at the end of the launch.
 #include "kq_device.hpp"
 #include <cstdlib>
-#include "kq_lane.hpp"
+#include "kq_ldsfft.hpp"
 
 namespace kq {
 
 namespace {
 
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) {
-  return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ float2 cconj(float2 a) { return make_float2(a.x, -a.y); }
-__device__ __forceinline__ float cnrm(float2 a) { return a.x * a.x + a.y * a.y; }
 __device__ __forceinline__ float2 shfl2(float2 v, int src) {
   return make_float2(__shfl(v.x, src, 64), __shfl(v.y, src, 64));
-}
-template <int M>
-__device__ __forceinline__ float2 xor2(float2 v, int lane) {
-  return make_float2(lane_xor<M>(v.x, lane), lane_xor<M>(v.y, lane));
-}
-// lane ^ (1 << s) with s a constant after unrolling
-__device__ __forceinline__ float2 xor2_pow(float2 v, int s, int lane) {
-  switch (s) {
-    case 0: return xor2<1>(v, lane);
-    case 1: return xor2<2>(v, lane);
-    case 2: return xor2<4>(v, lane);
-    case 3: return xor2<8>(v, lane);
-    case 4: return xor2<16>(v, lane);
-    default: return xor2<32>(v, lane);
-  }
 }
 // value of a wave-uniform lane
 __device__ __forceinline__ float rdlane(float v, int src) {
@@ -223,7 +201,7 @@ __device__ void fm_channel_pair(const Geom &g, const ChanDev &ch, const Planes &
       float2 z = make_float2(h ? xo : hist, out);  // real: [hist | b], imaginary: [b | b+1]
 #pragma unroll
       for (int s = 5; s >= 0; s--) {  // forward, decimation in frequency: natural in, bit-reversed out
-        float2 const r = xor2_pow(z, s, lane);
+        float2 const r = lane_xor_pow2(z, s, lane);
         z = ((lane >> s) & 1) ? cmul(csub(r, z), wf[s]) : cadd(z, r);
       }
       float2 const zm = cconj(shfl2(z, herm_src));  // conj(Z[64 - k])
@@ -236,7 +214,7 @@ __device__ void fm_channel_pair(const Geom &g, const ChanDev &ch, const Planes &
       for (int s = 0; s < 6; s++) {  // backward, decimation in time: bit-reversed in, natural out
         int const bit = (lane >> s) & 1;
         float2 const v = bit ? cmul(z, wi[s]) : z;
-        float2 const r = xor2_pow(v, s, lane);
+        float2 const r = lane_xor_pow2(v, s, lane);
         z = bit ? csub(r, v) : cadd(v, r);
       }
       // lanes 32-63 hold the kept halves: real part block b, imaginary part block b+1 (fm.c:169-170)
@@ -471,7 +449,7 @@ __device__ void fm_channel_four_waves(const Geom &g, const ChanDev &ch, const Pl
         float2 z = make_float2(h ? xo : hist, out);  // real: [hist | b], imaginary: [b | b+1]
 #pragma unroll
         for (int s = 5; s >= 0; s--) {  // forward, decimation in frequency: natural in, bit-reversed out
-          float2 const r = xor2_pow(z, s, lane);
+          float2 const r = lane_xor_pow2(z, s, lane);
           z = ((lane >> s) & 1) ? cmul(csub(r, z), wf[s]) : cadd(z, r);
         }
         float2 const zm = cconj(shfl2(z, herm_src));  // conj(Z[64 - k])
@@ -528,7 +506,7 @@ __device__ void fm_channel_four_waves(const Geom &g, const ChanDev &ch, const Pl
       for (int s = 0; s < 6; s++) {  // backward, decimation in time: bit-reversed in, natural out
         int const bit = (lane >> s) & 1;
         float2 const v = bit ? cmul(z, wi[s]) : z;
-        float2 const r = xor2_pow(v, s, lane);
+        float2 const r = lane_xor_pow2(v, s, lane);
         z = bit ? csub(r, v) : cadd(v, r);
       }
       // lanes 32-63 hold the kept halves: real part block b, imaginary part block b+1 (fm.c:169-170)

@@ -153,7 +153,7 @@ struct DeviceScope {
 // kept per kernel and device: a process may drive banks on several devices).
 void ensure_dynamic_lds(const void *kernel, size_t bytes);
 
-// launchers (kq_kernels.hip)
+// ---- launchers: kq_kernels.hip
 // output planes to pinned host memory (a null host pointer skips its plane): of every audio row of `row` floats the
 // first status.nout, and the status plane up to its last whole 16 bytes
 void launch_copy_to_host(hipStream_t s, const float *audio, float *haudio, int row, const kq_chan_status *status, void *hstatus,
@@ -177,9 +177,17 @@ void launch_block_energy_sum(hipStream_t s, const float2 *newsamples, int L, int
 void launch_ctl_apply(hipStream_t s, const void *queue_host, int nrec);
 void launch_block_energy_iir(hipStream_t s, const float *sums, int L, int nblocks, const unsigned char *update, float *energy_state,
                              float *if_power);
+// chan_list: the active channels when kq_bank_remove_channel has left holes (nchan = its length), else null
+void launch_pcm(hipStream_t s, const Geom &g, const Planes &pl, short *pcm, unsigned *mask, int nchan, int nblocks,
+                const int *chan_list);
+// ---- kq_filter_full.hip
 void launch_filter_full(hipStream_t s, const Geom &g, const ChanDev &ch, const Planes &pl, const float2 *window,
                         const float2 *tw, int nchan, int nblocks, int compute_n0, float2 *spec_dump, int spec_ch,
                         const int *chan_list);
+bool split_supported(const Geom &g);
+void launch_filter_split(hipStream_t s, const Geom &g, const ChanDev &ch, const Planes &pl, const float2 *window,
+                         const float2 *tw, int nchan, int nblocks, const int *chan_list);
+// ---- kq_full16k.hip
 // N = 65536 on the same kernel: four sibling workgroups per channel-block, each the 16384-point transform of one residue
 // class of bins (k = 4 q + r); what they share travels through these planes (kq_full16k.hip)
 struct Big64 {  // (N = 65536's hand-over places -- and, for every full-spectrum launch, what its side job needs: `iir`)
@@ -211,29 +219,27 @@ void launch_filter_full64k(hipStream_t s, const Geom &g, const ChanDev &ch, cons
                            const int *chan_list, bool plain, bool swept, const float2 *window_paired, const Big64 &big);
 double full16k_sweep_limit();  // the same for the N = 16384 steady-state variant of swept channels (plain == 2)
 double full64k_sweep_limit();  // |rate| in cycles per sample^2 up to which the table path's first-order cross term holds
-bool split_supported(const Geom &g);
-void launch_filter_split(hipStream_t s, const Geom &g, const ChanDev &ch, const Planes &pl, const float2 *window,
-                         const float2 *tw, int nchan, int nblocks, const int *chan_list);
+// ---- kq_pruned.hip
 bool pruned_supported(const Geom &g);
 void launch_filter_pruned(hipStream_t s, const Geom &g, const ChanDev &ch, const Planes &pl, const float2 *window,
                           const float2 *chan_tw, int nchan, int nblocks, bool swept, const int *chan_list, const IirArgs &iir = IirArgs{});
 // the geometries whose pruned kernel runs the IF-power recurrence handed to it in `iir` (the others ignore it)
 bool pruned_carries_iir(const Geom &g);
 void launch_pruned_tables(hipStream_t s, const Geom &g, const ChanDev &ch, float2 *chan_tw, int nchan);
+size_t pruned_table_elems(const Geom &g);
+// ---- kq_demod_fm.hip
 size_t demod_fm_lds_bytes(const Geom &g);
 void launch_demod_fm(hipStream_t s, const Geom &g, const ChanDev &ch, const Planes &pl, const float2 *tw, const int *list_fm,
                      int n_fm, int nblocks, int compute_n0, float *fmout, const float *fm_hist_in, float *fm_hist_out);
+void launch_pl_track(hipStream_t s, const Geom &g, const ChanDev &ch, const Planes &pl, const float2 *tw, const int *list_fm,
+                     int n_fm, int nblocks);
+// ---- kq_demod64.hip, kq_pll.hip
 bool demod64_supported(const Geom &g);
 void launch_demod64(hipStream_t s, const Geom &g, const ChanDev &ch, const Planes &pl, const int *list_fm, int n_fm,
                     const int *list_am, int n_am, const int *list_lin, int n_lin, int nblocks, int compute_n0);
 void launch_demod_pll(hipStream_t s, const Geom &g, const ChanDev &ch, const Planes &pl, const float2 *tw, const int *list_pll,
                       int n_pll, const PllChunk *chunks, const int *slot_of, int nblocks, int compute_n0);
-// chan_list (both): the active channels when kq_bank_remove_channel has left holes (nchan = its length), else null
-void launch_pcm(hipStream_t s, const Geom &g, const Planes &pl, short *pcm, unsigned *mask, int nchan, int nblocks,
-                const int *chan_list);
-void launch_pl_track(hipStream_t s, const Geom &g, const ChanDev &ch, const Planes &pl, const float2 *tw, const int *list_fm,
-                     int n_fm, int nblocks);
-// single transforms for the compat surface
+// ---- kq_single.hip: single transforms for the compat surface
 void launch_fft_single(hipStream_t s, const float2 *in, float2 *out, const FftDim &d, int sign, const float2 *tw, int tw_log2);
 // the same for 2^15 .. 2^22 points, through global memory (`tmp`: N elements of scratch)
 int launch_fft_large(hipStream_t s, const float2 *in, float2 *out, float2 *tmp, int N, int sign, const float2 *tw, int tw_log2);
@@ -242,7 +248,6 @@ void launch_slave_single(hipStream_t s, const float2 *fdomain, const float2 *res
                          int in_real, int out_type, const float2 *tw, int tw_log2);
 void launch_slave_bank(hipStream_t s, const float2 *fdomain, const float2 *resp, float2 *out, int N, int Ndec, int olen,
                        int out_type, const float2 *tw, int tw_log2);
-size_t pruned_table_elems(const Geom &g);
 
 
 // ---- compat surface internals shared with the demodulator entry points (kq_compat.cpp, kq_radio.cpp)

@@ -1,6 +1,6 @@
 // kq_full16k.hip -- full-spectrum pre-detection filter for N = 16384, register-resident forward transform.
 //
-// Same contract as k_filter_full (kq_kernels.hip): per (channel, block) NCO mix (radio.c:132-139), the N-point forward
+// Same contract as k_filter_full (kq_filter_full.hip): per (channel, block) NCO mix (radio.c:132-139), the N-point forward
 // transform of execute_filter_input (filter.c:151), compute_n0 over all N bins (radio.c:383-425), response multiply,
 // CROSS_CONJ and the N/D-point inverse transform of execute_filter_output (filter.c:206-250).  It exists because
 // compute_n0 -- which the reference's demodulator threads run on every block -- needs every bin, so the pruned

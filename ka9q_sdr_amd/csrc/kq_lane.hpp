@@ -2,6 +2,8 @@
 // (quad permutes, row shifts with bank masks, row rotate), v_permlane16_swap / v_permlane32_swap (gfx950) above.
 // A ds_bpermute costs an LDS round trip; in the single-wave demodulators forty of them in a dependent chain were
 // the whole block latency.
+// Also the two helpers that kq_pruned.hip shares with the rest but cannot take from kq_ldsfft.hpp, whose cmul would
+// collide with its packed one: the wave-level LDS fence and the unit phasor.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -39,6 +41,32 @@ __device__ __forceinline__ int lane_xor_i(int v, int lane) {
 template <int M>
 __device__ __forceinline__ float lane_xor(float v, int lane) {
   return __int_as_float(lane_xor_i<M>(__float_as_int(v), lane));
+}
+// both halves of a float2 from lane ^ (1 << s), s a constant after unrolling
+__device__ __forceinline__ float2 lane_xor_pow2(float2 v, int s, int lane) {
+  switch (s) {
+    case 0: return make_float2(lane_xor<1>(v.x, lane), lane_xor<1>(v.y, lane));
+    case 1: return make_float2(lane_xor<2>(v.x, lane), lane_xor<2>(v.y, lane));
+    case 2: return make_float2(lane_xor<4>(v.x, lane), lane_xor<4>(v.y, lane));
+    case 3: return make_float2(lane_xor<8>(v.x, lane), lane_xor<8>(v.y, lane));
+    case 4: return make_float2(lane_xor<16>(v.x, lane), lane_xor<16>(v.y, lane));
+    default: return make_float2(lane_xor<32>(v.x, lane), lane_xor<32>(v.y, lane));
+  }
+}
+
+// LDS written by one lane of this wave, read by another
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Unit phasor exp(j*2*pi*turns) from a double phase in turns
+__device__ __forceinline__ float2 phasor_turns(double turns) {
+  turns -= rint(turns);
+  float s, c;
+  sincospif(2.0f * (float)turns, &s, &c);
+  return make_float2(c, s);
 }
 
 }  // namespace kq

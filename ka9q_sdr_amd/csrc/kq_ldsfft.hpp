@@ -1,6 +1,6 @@
 // kq_ldsfft.hpp -- device helpers shared by the kernels: complex arithmetic, wave/block reductions and the
 // in-LDS power-of-two FFT (unnormalised, sign -1 forward / +1 backward: the convention of fftwf_plan_dft_1d that
-// filter.c:84,133 plans with).
+// filter.c:84,133 plans with).  phasor_turns, wave_sync and the lane exchanges come with kq_lane.hpp.
 #pragma once
 #include <type_traits>
 
@@ -18,14 +18,6 @@ __device__ __forceinline__ float2 cconj(float2 a) { return make_float2(a.x, -a.y
 __device__ __forceinline__ float cnrm(float2 a) { return a.x * a.x + a.y * a.y; }
 
 __device__ __forceinline__ unsigned bitrev(unsigned i, int bits) { return bits ? (__brev(i) >> (32 - bits)) : 0u; }
-
-// Unit phasor exp(j*2*pi*turns) from a double phase in turns
-__device__ __forceinline__ float2 phasor_turns(double turns) {
-  turns -= rint(turns);
-  float s, c;
-  sincospif(2.0f * (float)turns, &s, &c);
-  return make_float2(c, s);
-}
 
 // Butterfly reductions over the 64 lanes (every lane gets the result) by DPP / v_permlane exchanges (kq_lane.hpp):
 // same pairing order as the ds_bpermute versions they replace (32, 16, ..., 1), so the same rounding.

@@ -13,54 +13,18 @@
 // The two NCOs are kept as (phase, step) pairs; the reference's sample-by-sample double phasor recurrences are
 // evaluated in closed form inside the block.
 #include "kq_device.hpp"
+#include "kq_ldsfft.hpp"
 
 namespace kq {
 
 namespace {
 
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) {
-  return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ float cnrm(float2 a) { return a.x * a.x + a.y * a.y; }
-__device__ __forceinline__ unsigned bitrev(unsigned i, int bits) { return __brev(i) >> (32 - bits); }
-__device__ __forceinline__ float2 unit(double turns) {
-  turns -= rint(turns);
-  float s, c;
-  sincospif(2.f * (float)turns, &s, &c);
-  return make_float2(c, s);
-}
+// (not kq_ldsfft.hpp's wave_sum: its DPP exchanges pair the lanes in the same order but change the kernel's instruction
+// stream, so the swap belongs to a change that measures it)
 __device__ __forceinline__ float wsum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
-}
-
-// 16384-point forward FFT in LDS (bit-reversed in, natural out), radix 2^2 like kq_kernels.hip
-__device__ void fft16k(float2 *s, const float2 *__restrict__ tw, int tw_log2) {
-  constexpr int LOG = 14, n = 1 << LOG;
-  __syncthreads();
-  for (int stage = 0; stage < LOG; stage += 2) {
-    int const m = 1 << stage;
-    for (int i = threadIdx.x; i < n / 4; i += blockDim.x) {
-      int const j = i & (m - 1);
-      int const base = ((i >> stage) << (stage + 2)) + j;
-      float2 const w2 = tw[(size_t)j << (tw_log2 - stage - 1)];
-      float2 const w4 = tw[(size_t)j << (tw_log2 - stage - 2)];
-      float2 const a0 = s[base], a1 = cmul(s[base + m], w2);
-      float2 const a2 = s[base + 2 * m], a3 = cmul(s[base + 3 * m], w2);
-      float2 const b0 = cadd(a0, a1), b1 = csub(a0, a1), b2 = cadd(a2, a3), b3 = csub(a2, a3);
-      float2 const c2 = cmul(b2, w4);
-      float2 c3 = cmul(b3, w4);
-      c3 = make_float2(c3.y, -c3.x);
-      s[base] = cadd(b0, c2);
-      s[base + 2 * m] = csub(b0, c2);
-      s[base + m] = cadd(b1, c3);
-      s[base + 3 * m] = csub(b1, c3);
-    }
-    __syncthreads();
-  }
 }
 
 }  // namespace
@@ -138,7 +102,7 @@ __global__ void __launch_bounds__(1024) k_demod_linear_pll(Geom g, ChanDev ch, P
       for (int s4 = 0; s4 < 4; s4++) {
         __syncthreads();
         for (int i = tid; i < 16384; i += nthr) lds[bitrev((unsigned)i, 14)] = ring[4 * i + s4];
-        fft16k(lds, tw, g.tw_log2);
+        lds_fft<-1>(lds, 14, tw, g.tw_log2);
         for (int i = tid; i < nbins; i += nthr) {
           int const k = lowlimit + i;                              // signed bin of the 65536-point transform
           int const src = k & 16383;                               // k mod 16384
@@ -196,7 +160,7 @@ __global__ void __launch_bounds__(1024) k_demod_linear_pll(Geom g, ChanDev ch, P
     // spin by coarse*fine and gather the carrier phase (linear.c:208-223)
     float ax = 0, ay = 0;
     for (int i = tid; i < olen; i += nthr) {
-      float2 const rot = unit(st.c_phase + st.f_phase + (st.c_freq + st.f_freq) * (double)i);
+      float2 const rot = phasor_turns(st.c_phase + st.f_phase + (st.c_freq + st.f_freq) * (double)i);
       float2 const s = cmul(S[i], rot);
       S[i] = s;
       float2 const ss = square ? cmul(s, s) : s;
@@ -266,7 +230,7 @@ __global__ void __launch_bounds__(1024) k_demod_linear_pll(Geom g, ChanDev ch, P
     float *aud = pl.audio + ((size_t)c * g.max_blocks + b) * (2 * (size_t)olen);
     for (int i = tid; i < olen; i += nthr) {
       float2 s = S[i];
-      if (sh_f != 0.0) s = cmul(s, unit(sh_ph + sh_f * ((double)b * olen + i)));  // linear.c:283-289
+      if (sh_f != 0.0) s = cmul(s, phasor_turns(sh_ph + sh_f * ((double)b * olen + i)));  // linear.c:283-289
       if (stereo) {
         aud[2 * i] = s.x;
         aud[2 * i + 1] = s.y;

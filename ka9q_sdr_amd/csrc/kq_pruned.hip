@@ -41,7 +41,8 @@ namespace kq {
 
 namespace {
 
-// Complex products and butterflies go through 2-vectors so that they become v_pk_fma_f32 / v_pk_mul_f32
+// Complex products and butterflies go through 2-vectors so that they become v_pk_fma_f32 / v_pk_mul_f32 (this cmul is why
+// the unit stays without kq_ldsfft.hpp, whose plain one it would collide with; phasor_turns and wave_sync: kq_lane.hpp)
 __device__ __forceinline__ rfft::v2f as_v2f(float2 a) { return (rfft::v2f){a.x, a.y}; }
 __device__ __forceinline__ float2 as_f2(rfft::v2f a) { return make_float2(a.x, a.y); }
 __device__ __forceinline__ float2 cmul(float2 a, float2 b) { return as_f2(rfft::pk_cmul(as_v2f(a), as_v2f(b))); }
@@ -95,13 +96,6 @@ __device__ __forceinline__ int signed_bin(int q) {
   return q <= ND / 2 ? q : q - ND;
 }
 
-__device__ __forceinline__ float2 unit(double turns) {
-  turns -= rint(turns);
-  float s, c;
-  sincospif(2.f * (float)turns, &s, &c);
-  return make_float2(c, s);
-}
-
 // Table entry i of the A + T part (i indexes float2 units), for instantaneous step f, sweep r, R columns
 template <int ND>
 __device__ __forceinline__ float2 table_entry_AT(int i, double f, double r, int R, int N) {
@@ -123,7 +117,7 @@ __device__ __forceinline__ float2 table_entry_AT(int i, double f, double r, int 
       extra = -(double)(s * pass) / 8.0 - (double)(ap * pass) / 256.0;
     }
     double const Ra = (double)R * a;
-    return unit(f * Ra + r * (0.5 * Ra * (Ra - 1.0)) + extra);
+    return phasor_turns(f * Ra + r * (0.5 * Ra * (Ra - 1.0)) + extra);
   }
   int const t = i - nA;  // T: [p][q'] -> bin q = P q' + p
   int const p = t >> 5, qp = t & 31;
@@ -131,7 +125,7 @@ __device__ __forceinline__ float2 table_entry_AT(int i, double f, double r, int 
   double turns = 64.0 * f;
   turns -= rint(turns);
   turns -= 64.0 * (double)signed_bin<ND>(q) / (double)N;
-  return unit(turns);
+  return phasor_turns(turns);
 }
 
 __device__ __forceinline__ void swap32(float &a, float &b) {
@@ -164,12 +158,6 @@ __device__ __forceinline__ void pair_dpp(float &e, float &o) {
   }
   e = __int_as_float(lo);
   o = __int_as_float(up);
-}
-
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // ---- one column group, one pass: premultiply + radix-P fold + 32-point FFT.
@@ -426,14 +414,14 @@ __device__ __forceinline__ void fill_tables(float4 *wtab, const float *tc, doubl
     for (int i = lane; i < Tab<ND>::kWaveF4 * 2; i += 64) w2[i] = table_entry_AT<ND>(i, f_blk, r, R, N);
     // the level tables in HBM were built for the call's first block: rotate them by the step difference
 #pragma unroll
-    for (int i = 0; i < 6; i++) th[i] = unit((double)(1 << i) * df);
+    for (int i = 0; i < 6; i++) th[i] = phasor_turns((double)(1 << i) * df);
   } else {
     const float4 *src = reinterpret_cast<const float4 *>(tc);
     for (int i = lane; i < Tab<ND>::kWaveF4; i += 64) wtab[i] = src[i];
 #pragma unroll
     for (int i = 0; i < 6; i++) th[i] = make_float2(1.f, 0.f);
   }
-  wave_lds_sync();
+  wave_sync();
 }
 
 // Epilogue for N_dec > 64: each lane owns the bins q = P q' + p with q' = rev5(lane >> 1) and p = b0, b0+2, ...
@@ -455,7 +443,7 @@ __device__ __forceinline__ void epilogue_lds(float2 *scratch, const float2 (&ypa
     int const q = P * qp + 2 * i + b0;
     scratch[q] = cmul(cmul(y, p0), H[q]);
   }
-  wave_lds_sync();
+  wave_sync();
   epilogue_from_scratch<ND>(scratch, isb, out, olen, lane);
 }
 
@@ -531,7 +519,7 @@ __global__ void k_pruned_tables(Geom g, ChanDev ch, float *__restrict__ tab, int
     double turns = off * f;
     turns -= rint(turns);
     turns -= off * (double)signed_bin<ND>(q) / (double)g.N;
-    t[nAT + i] = unit(turns);
+    t[nAT + i] = phasor_turns(turns);
   }
 }
 
@@ -618,7 +606,7 @@ __global__ void __launch_bounds__(NWAVES * 64) k_pruned_resident(Geom g, ChanDev
     {
       double turns = ch.lo_phase[c] + f0 * m0;
       if (SWEPT) turns += r * (0.5 * m0 * (m0 - 1.0));
-      y = cmul(y, unit(turns));
+      y = cmul(y, phasor_turns(turns));
       y = cmul(y, ch.resp[(size_t)c * 64 + q]);
       if (ch.fflags[c] & FLAG_ISB) {
         int const qp = (64 - q) & 63;
@@ -680,7 +668,7 @@ __global__ void __launch_bounds__(NWAVES * 64) k_pruned_stream(Geom g, ChanDev c
   float4 *wtab = reinterpret_cast<float4 *>(lds + 2 * kSlice) + wave * (Tab<ND>::kWaveF4 + ND / 2);
   float2 *scratch = reinterpret_cast<float2 *>(wtab + Tab<ND>::kWaveF4);  // ND float2
   float2 *wsh = reinterpret_cast<float2 *>(reinterpret_cast<float4 *>(lds + 2 * kSlice) + NWAVES * (Tab<ND>::kWaveF4 + ND / 2));
-  for (int i = threadIdx.x; i < 128; i += NWAVES * 64) wsh[i] = unit(-(double)i / 128.0);  // exp(-2 pi i k / 128)
+  for (int i = threadIdx.x; i < 128; i += NWAVES * 64) wsh[i] = phasor_turns(-(double)i / 128.0);  // exp(-2 pi i k / 128)
   const float2 *win = window + (size_t)blk * g.L;
   double const m0 = (double)blk * g.L;
 
@@ -747,7 +735,7 @@ __global__ void __launch_bounds__(NWAVES * 64) k_pruned_stream(Geom g, ChanDev c
   {
     double turns = ch.lo_phase[c] + f0 * m0;
     if (SWEPT) turns += r * (0.5 * m0 * (m0 - 1.0));
-    epilogue_lds<ND>(scratch, ypass, unit(turns), ch.resp + (size_t)c * ND, (ch.fflags[c] & FLAG_ISB) != 0,
+    epilogue_lds<ND>(scratch, ypass, phasor_turns(turns), ch.resp + (size_t)c * ND, (ch.fflags[c] & FLAG_ISB) != 0,
                      pl.filt + ((size_t)c * g.max_blocks + blk) * g.olen, g.olen, lane);
   }
 }
@@ -789,7 +777,7 @@ __global__ void __launch_bounds__(NWAVES * 64) k_pruned_resident256(Geom g, Chan
     const float *tc = tab + (size_t)c * Tab<ND>::kFloats;
     const float2 *tL = reinterpret_cast<const float2 *>(tc + Tab<ND>::kA + Tab<ND>::kT);
     const float2 *H = ch.resp + (size_t)c * ND;
-    float2 const p0 = unit(ch.lo_phase[c] + ch.lo_freq[c] * m0);
+    float2 const p0 = phasor_turns(ch.lo_phase[c] + ch.lo_freq[c] * m0);
     const float2 *col = lds + lane;
 #pragma unroll 1
     for (int pass = 0; pass < P; pass++) {
@@ -829,10 +817,10 @@ __global__ void __launch_bounds__(NWAVES * 64) k_pruned_resident256(Geom g, Chan
         scratch[q] = cmul(cmul(y, p0), H[q]);
       }
     }
-    wave_lds_sync();
+    wave_sync();
     epilogue_from_scratch<ND>(scratch, (ch.fflags[c] & FLAG_ISB) != 0, pl.filt + ((size_t)c * g.max_blocks + blk) * g.olen,
                               g.olen, lane);
-    wave_lds_sync();
+    wave_sync();
   }
 }
 
