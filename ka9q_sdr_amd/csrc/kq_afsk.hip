@@ -20,6 +20,7 @@
 
 #include "ka9q_hip.h"
 #include "kq_design.hpp"
+#include "kq_device.hpp"
 #include "kq_host.hpp"
 #include "kq_ldsfft.hpp"
 

@@ -242,7 +242,10 @@ static int create_alloc(kq_bank *b) {
   b->ring_cap = (size_t)(g.M - 1) + B * (size_t)g.L + (size_t)(g.L - 1);
   if (b->alloc(&b->ring[0], b->ring_cap, true)) return -1;
   if (b->alloc(&b->ring[1], b->ring_cap, true)) return -1;
-  if (b->alloc(&b->tw, (size_t)1 << (g.tw_log2 - 1), true)) return -1;
+  if (!(b->tw = kq::half_twiddles(g.tw_log2))) {
+    kq_internal_set_error("kq_bank_create: no twiddle table of period 2^%d", g.tw_log2);
+    return -1;
+  }
   if (b->alloc(&b->chd.mode, C, true)) return -1;
   if (b->alloc(&b->chd.flags, C, true)) return -1;
   if (b->alloc(&b->chd.low, C, true)) return -1;
@@ -375,16 +378,6 @@ static int create_alloc(kq_bank *b) {
   {
     std::vector<float> nanv(C, NAN);
     KQ_TRY(hipMemcpy(b->chd.plfreq, nanv.data(), C * sizeof(float), hipMemcpyHostToDevice));
-  }
-  // twiddles exp(-2*pi*i*k/T) in double, rounded once
-  {
-    size_t const T = (size_t)1 << g.tw_log2;
-    std::vector<float2> tw(T / 2);
-    for (size_t k = 0; k < T / 2; k++) {
-      double const a = -2.0 * M_PI * (double)k / (double)T;
-      tw[k] = make_float2((float)std::cos(a), (float)std::sin(a));
-    }
-    KQ_TRY(hipMemcpy(b->tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice));
   }
   return 0;
 }

@@ -141,7 +141,7 @@ struct kq_bank : kq::HostSide {
   unsigned last_blocks = 0;
 
   // ---- the device's tables and planes that outlive a call (made by create_alloc, kq_bank.cpp; launched with by kq_bank_call.cpp)
-  float2 *tw = nullptr;
+  const float2 *tw = nullptr;  // kq::half_twiddles(g.tw_log2): shared, not the bank's to free
   float2 *chan_tw = nullptr;  // pruned path: per-channel twiddle tables
   bool chan_tw_dirty = true;
   kq::ChanDev chd{};  // (what a geometry does not use stays null)

@@ -142,104 +142,6 @@ __global__ void k_design(FftDim dim, int M, int spec, const DesignJob *__restric
 
 }  // namespace
 
-// half-circle twiddle tables exp(-2 pi i k / T), k < T/2, per device and size (built in double, rounded once)
-const float2 *half_twiddles(int log2T) {
-  static std::mutex mu;
-  static std::map<std::pair<int, int>, float2 *> tabs;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = tabs.find({dev, log2T});
-  if (it != tabs.end()) return it->second;
-  size_t const T = (size_t)1 << log2T;
-  std::vector<float2> h(T / 2 ? T / 2 : 1);
-  for (size_t k = 0; k < T / 2; k++) {
-    double const a = -2.0 * M_PI * (double)k / (double)T;
-    h[k] = make_float2((float)std::cos(a), (float)std::sin(a));
-  }
-  float2 *d = nullptr;
-  if (hipMalloc((void **)&d, h.size() * sizeof(float2)) != hipSuccess) return nullptr;
-  if (hipMemcpy(d, h.data(), h.size() * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(d);
-    return nullptr;
-  }
-  tabs[{dev, log2T}] = d;
-  return d;
-}
-
-bool fft_size_ok(int n) {
-  if (n < 2 || n > 65536 || (n & 1)) return false;
-  for (int p : {2, 3, 5, 7})
-    while (n % p == 0) n /= p;
-  return n == 1;
-}
-
-// The plan of an n-point transform on the generic path, tables on the current device (cached per device and size)
-FftDim fft_dim(int n, bool *ok) {
-  FftDim d{};
-  d.n = n;
-  d.log2n = -1;
-  if (ok) *ok = false;
-  if (n >= 1 && (n & (n - 1)) == 0) {
-    d.log2n = 0;
-    while ((1 << d.log2n) < n) d.log2n++;
-    if (ok) *ok = true;
-    return d;
-  }
-  {  // (odd sizes are fine here -- a factor of a two-pass transform may be one; fft_size_ok's evenness is the filters' rule)
-    int m = n;
-    for (int p : {2, 3, 5, 7})
-      while (m % p == 0) m /= p;
-    if (n < 2 || n > 65536 || m != 1) return d;
-  }
-  {  // radices: 4s first (fewest passes), then 2, 3s, 5s, 7s
-    int m = n;
-    while (m % 4 == 0) d.f[d.nf++] = 4, m /= 4;
-    while (m % 2 == 0) d.f[d.nf++] = 2, m /= 2;
-    while (m % 3 == 0) d.f[d.nf++] = 3, m /= 3;
-    while (m % 5 == 0) d.f[d.nf++] = 5, m /= 5;
-    while (m % 7 == 0) d.f[d.nf++] = 7, m /= 7;
-  }
-  static std::mutex mu;
-  static std::map<std::pair<int, int>, std::pair<const unsigned short *, const float2 *>> tabs;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return d;
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = tabs.find({dev, n});
-  if (it == tabs.end()) {
-    std::vector<unsigned short> rev(n);
-    for (int p = 0; p < n; p++) {  // position p = sum_k d_k prod_{j<k} f_j holds index i = sum_k d_k n / prod_{j<=k} f_j
-      int rest = p, weight = n, i = 0;
-      for (int k = 0; k < d.nf; k++) {
-        weight /= d.f[k];
-        i += (rest % d.f[k]) * weight;
-        rest /= d.f[k];
-      }
-      rev[i] = (unsigned short)p;
-    }
-    std::vector<float2> tw(n);
-    for (int k = 0; k < n; k++) {
-      double const a = -2.0 * M_PI * (double)k / (double)n;
-      tw[k] = make_float2((float)std::cos(a), (float)std::sin(a));
-    }
-    unsigned short *drev = nullptr;
-    float2 *dtw = nullptr;
-    if (hipMalloc((void **)&drev, n * sizeof(unsigned short)) != hipSuccess || hipMalloc((void **)&dtw, n * sizeof(float2)) != hipSuccess ||
-        hipMemcpy(drev, rev.data(), n * sizeof(unsigned short), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dtw, tw.data(), n * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess) {
-      if (drev) (void)hipFree(drev);
-      if (dtw) (void)hipFree(dtw);
-      return d;
-    }
-    it = tabs.emplace(std::make_pair(dev, n), std::make_pair((const unsigned short *)drev, (const float2 *)dtw)).first;
-  }
-  d.rev = it->second.first;
-  d.twc = it->second.second;
-  d.tw_n = n;
-  if (ok) *ok = true;
-  return d;
-}
-
 namespace {
 
 // Workspace of the design kernels: per device, grown on demand, never freed.  (hipMalloc / hipFree around every design --

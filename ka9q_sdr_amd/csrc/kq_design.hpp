@@ -49,11 +49,6 @@ int design_launch(void *stream, int L_dec, int M_dec, const DesignJob *jobs, con
                   const void *ctl_queue = nullptr, unsigned ctl_records = 0);
 void design_scales(int N, int out_type, float *gain, float *ng_scale);
 
-// Half-circle twiddle table exp(-2 pi i k / T), k < T / 2, T = 1 << log2T, as lds_fft / fft_any read it: on the current
-// device, built in double and rounded once, cached per (device, size) and never freed (like fft_dim's tables), so it
-// outlives the handle that asked first.  Null when the allocation fails.
-const float2 *half_twiddles(int log2T);
-
 // modified Bessel function I0 in double (power series), for the host-side Kaiser designs of the satellite banks
 inline double i0_double(double x) {
   double const q = 0.25 * x * x;

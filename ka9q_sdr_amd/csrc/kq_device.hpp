@@ -13,6 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <functional>
+
 #include "../../include/ka9q_hip.h"
 
 struct filter_in;  // include/ka9q_hip_compat.h
@@ -29,6 +31,7 @@ struct PllState {
   int lock_count, pll_lock, fft_samples, fft_ptr;
 };
 
+// ---- FFT plans and tables: kq_fftplan.cpp (host only)
 // A transform size on the generic path (kq_ldsfft.hpp lds_fft_mixed): n = f[0] f[1] ... f[nf-1] with radices 2..5, or a
 // power of two (log2n >= 0: then rev / twc are not used and the kernels run lds_fft as ever).  fft_dim() builds one on the
 // current device: the tables are cached per (device, n) and never freed.  ok = false: n has a prime factor beyond 7, or
@@ -44,6 +47,14 @@ struct FftDim {
 };
 FftDim fft_dim(int n, bool *ok);
 bool fft_size_ok(int n);      // n = 2^a 3^b 5^c 7^d, 2 <= n <= 65536, even
+// Half-circle twiddle table exp(-2 pi i k / T), k < T / 2, T = 1 << log2T, as lds_fft / fft_any read it: on the current
+// device, built in double and rounded once, cached per (device, size) and never freed (like fft_dim's tables), so it
+// outlives the handle that asked first.  Null when the allocation fails.
+const float2 *half_twiddles(int log2T);
+// A table that is uploaded once per device and never freed: the device copy of (`table`, `size`) on the current device, made
+// at the first request from the `bytes` of host memory (cleared) that `fill` writes.  Null when the allocation or the upload fails.
+enum { TABLE_HALF_TWIDDLES, TABLE_DIM_REV, TABLE_DIM_TW, TABLE_FULL16K };
+const void *upload_once(int table, int size, size_t bytes, const std::function<void(void *)> &fill);
 
 // Carrier-tracking channels keep their loop state, 65536-sample ring and search scratch in a SLOT of their own for as long
 // as they exist (kq_bank_chan.cpp pll_acquire): storage grows by chunks of kPllChunk slots, nothing ever moves.

@@ -36,9 +36,7 @@
 #include "kq_device.hpp"
 #include "kq_ldsfft.hpp"
 #include <cmath>
-#include <mutex>
 #include <type_traits>
-#include <vector>
 
 #include "kq_lane.hpp"
 #include "kq_regfft.hpp"
@@ -980,36 +978,24 @@ bool full16k_supported(const Geom &g) {
 
 // The twiddle tables depend on nothing but N: one copy per device, built on first use.
 static const float2 *twiddle_tables() {
-  static std::mutex mu;
-  static float2 *tabs[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-  std::lock_guard<std::mutex> lock(mu);
-  if (tabs[dev]) return tabs[dev];
-  std::vector<float2> h(kTabSize);
-  auto w = [](long long e) {
-    double const ang = -2.0 * M_PI * (double)(e % kN) / kN;
-    return make_float2((float)cos(ang), (float)sin(ang));
-  };
-  for (int t = 0; t < kT; t++)
-    for (int e = 0; e < 10; e++)
-      h[kTabP1 + 2 * (kT * (e >> 1) + t) + (e & 1)] = e < 3 ? w((long long)(e + 1) * t) : w(4LL * (e - 2) * t);
-  for (int n3 = 0; n3 < 16; n3++)
-    for (int k2 = 0; k2 < 32; k2++) h[kTabTw2 + 32 * n3 + k2] = w(32LL * n3 * k2);
-  for (int st = 1; st <= 5; st++)
-    for (int t = 0; t < 64; t++) {
-      int const half = 1 << st;
-      double const ang = M_PI * (double)(t & (half - 1)) / half;
-      h[kTabEpi + (st - 1) * 64 + t] = (t & half) ? make_float2((float)cos(ang), (float)sin(ang)) : make_float2(1.f, 0.f);
-    }
-  float2 *d = nullptr;
-  if (hipMalloc(&d, h.size() * sizeof(float2)) != hipSuccess) return nullptr;
-  if (hipMemcpy(d, h.data(), h.size() * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(d);
-    return nullptr;
-  }
-  tabs[dev] = d;
-  return d;
+  return (const float2 *)upload_once(TABLE_FULL16K, kN, kTabSize * sizeof(float2), [](void *bytes) {
+    float2 *h = (float2 *)bytes;
+    auto w = [](long long e) {
+      double const ang = -2.0 * M_PI * (double)(e % kN) / kN;
+      return make_float2((float)cos(ang), (float)sin(ang));
+    };
+    for (int t = 0; t < kT; t++)
+      for (int e = 0; e < 10; e++)
+        h[kTabP1 + 2 * (kT * (e >> 1) + t) + (e & 1)] = e < 3 ? w((long long)(e + 1) * t) : w(4LL * (e - 2) * t);
+    for (int n3 = 0; n3 < 16; n3++)
+      for (int k2 = 0; k2 < 32; k2++) h[kTabTw2 + 32 * n3 + k2] = w(32LL * n3 * k2);
+    for (int st = 1; st <= 5; st++)
+      for (int t = 0; t < 64; t++) {
+        int const half = 1 << st;
+        double const ang = M_PI * (double)(t & (half - 1)) / half;
+        h[kTabEpi + (st - 1) * 64 + t] = (t & half) ? make_float2((float)cos(ang), (float)sin(ang)) : make_float2(1.f, 0.f);
+      }
+  });
 }
 
 // the row-paired copy (see PAIRED) needs whole pairs of rows in every block; k_block_energy_sum writes it

@@ -17,6 +17,7 @@
 #include "../../include/ka9q_hip.h"
 #include "../../include/ka9q_hip_radio.h"
 #include "kq_device.hpp"
+#include "kq_host.hpp"
 
 // The host program provides these two (audio.c); weak so that the library loads without them (tests that never start a
 // demodulator thread, the Python bindings).
@@ -44,6 +45,7 @@ struct Session {
   struct demod *demod = nullptr;
   struct filter_out *slave = nullptr;
   kq_bank *bank = nullptr;
+  kq::HostSide mem;  // holds d_spectrum (no stream of its own: nothing is queued through it)
   float2 *d_spectrum = nullptr;
   int dev = -1;
   unsigned olen = 0;
@@ -58,9 +60,9 @@ struct Session {
 
   ~Session() {
     if (bank) kq_bank_destroy(bank);
-    if (d_spectrum) {
+    {
       kq::DeviceScope scope(dev);
-      (void)hipFree(d_spectrum);
+      mem.close();
     }
     if (slave) delete_filter_output(slave);
   }
@@ -150,7 +152,7 @@ bool start(Session &s, struct demod *demod, int demod_type, enum filtertype out_
   s.channels = cc.channels;
   kq::DeviceScope scope(s.dev);
   size_t const N = (size_t)m->ilen + m->impulse_length - 1;
-  if (hipMalloc((void **)&s.d_spectrum, N * sizeof(float2)) != hipSuccess) {
+  if (s.mem.alloc(&s.d_spectrum, N)) {
     fail(demod, "device allocation failed");
     return false;
   }

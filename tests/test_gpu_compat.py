@@ -219,3 +219,98 @@ def test_fftw_entry_points_outside_the_filter_api(lib):
     s = lib.create_filter_output(m, resp, 1, 3)
     assert s and s.contents.response == resp
     assert lib.delete_filter_output(s) == 0 and lib.delete_filter_input(m) == 0
+
+
+def _fftw_prototypes(lib):
+    lib.fftwf_plan_dft_1d.restype = C.c_void_p
+    lib.fftwf_plan_dft_1d.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_uint]
+    lib.fftwf_plan_dft_r2c_1d.restype = C.c_void_p
+    lib.fftwf_plan_dft_r2c_1d.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint]
+    lib.fftwf_execute.argtypes = [C.c_void_p]
+    lib.fftwf_destroy_plan.argtypes = [C.c_void_p]
+
+
+# n = 64: a power of two in LDS; 120 = 2^3 3 5: mixed radix, fft_dim's tables; 32768: past one LDS block, two passes through
+# device memory and their scratch -- the smallest size on each of the three paths
+@pytest.mark.parametrize("n", [64, 120, 32768])
+@pytest.mark.parametrize("real", [False, True])
+def test_filter_master_and_fftw_plan_are_the_same_transform(lib, n, real):
+    """A filter master's forward transform and an FFTW plan of the same size are one kernel on one set of tables: the same
+    input gives the same bytes (m->fdomain after execute_filter_input against the plan's output after fftwf_execute;
+    COMPLEX master against fftwf_plan_dft_1d(FFTW_FORWARD) over n bins, REAL master against fftwf_plan_dft_r2c_1d over
+    n/2 + 1), and both agree with numpy's float64 transform as in test_fftw_entry_points_outside_the_filter_api."""
+    _fftw_prototypes(lib)
+    rng = np.random.default_rng(1000 + n)
+    Lb, M = n // 2, n // 2 + 1
+    assert Lb + M - 1 == n
+    if real:
+        x = rng.standard_normal(n).astype(np.float32)
+        ref, bins, tol = np.fft.rfft(x.astype(np.float64)), n // 2 + 1, 4e-7
+    else:
+        x = (rng.standard_normal(n) + 1j * rng.standard_normal(n)).astype(np.complex64)
+        ref, bins, tol = np.fft.fft(x.astype(np.complex128)), n, 5e-7
+    m = lib.create_filter_input(Lb, M, 3 if real else 1)
+    assert m
+    _as(m.contents.input_buffer, n, x.dtype)[:] = x          # the whole window: M - 1 samples of history and L new ones
+    assert lib.execute_filter_input(m) == 0
+    master = _as(m.contents.fdomain, bins, np.complex64).copy()
+    assert lib.delete_filter_input(m) == 0
+    src, dst = x.copy(), np.zeros(bins, np.complex64)
+    if real:
+        plan = lib.fftwf_plan_dft_r2c_1d(n, src.ctypes.data, dst.ctypes.data, 0)
+    else:
+        plan = lib.fftwf_plan_dft_1d(n, src.ctypes.data, dst.ctypes.data, -1, 0)
+    assert plan
+    lib.fftwf_execute(plan)
+    lib.fftwf_destroy_plan(plan)
+    assert master.tobytes() == dst.tobytes()
+    for got in (master, dst):
+        e = np.sqrt(np.mean(np.abs(got - ref) ** 2) / np.mean(np.abs(ref) ** 2))
+        print("n", n, "real", real, "error against float64", e)
+        assert e < tol
+
+
+def test_compat_objects_release_their_device_memory(lib):
+    """create / execute / delete of the compat surface's objects in a loop: free device memory must come back.  A cycle is a
+    master of 16384 points with a slave at decimate 1, a master of 32768 points (the two-pass scratch), and a c2c and an r2c
+    plan of 32768 points.  The smallest buffer a cycle allocates is one of the slave's two, 16384 float2 = 128 KiB: 256
+    cycles make one leaked buffer 32 MiB, four times the bound (test_handles_release_their_device_memory's)."""
+    _fftw_prototypes(lib)
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipMemGetInfo.argtypes = [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    libc = C.CDLL(None)
+    libc.malloc.restype = C.c_void_p
+    libc.malloc.argtypes = [C.c_size_t]
+
+    def free_bytes():
+        f, t = C.c_size_t(), C.c_size_t()
+        assert hip.hipMemGetInfo(C.byref(f), C.byref(t)) == 0
+        return f.value
+
+    n = 32768
+    src, dst = np.ones(n, np.complex64), np.zeros(n, np.complex64)
+    rsrc = np.ones(n, np.float32)
+
+    def cycle():
+        m = lib.create_filter_input(8192, 8193, 1)
+        resp = libc.malloc(8 * 16384)                       # (delete_filter_output frees it, filter.c:271)
+        _as(resp, 16384, np.complex64)[:] = 1e-3
+        s = lib.create_filter_output(m, resp, 1, 1)
+        assert m and s
+        assert lib.execute_filter_input(m) == 0 and lib.execute_filter_output(s) == 0
+        assert lib.delete_filter_output(s) == 0 and lib.delete_filter_input(m) == 0
+        m = lib.create_filter_input(16384, 16385, 1)
+        assert m and lib.execute_filter_input(m) == 0
+        assert lib.delete_filter_input(m) == 0
+        for plan in (lib.fftwf_plan_dft_1d(n, src.ctypes.data, dst.ctypes.data, -1, 0),
+                     lib.fftwf_plan_dft_r2c_1d(n, rsrc.ctypes.data, dst.ctypes.data, 0)):
+            assert plan
+            lib.fftwf_execute(plan)
+            lib.fftwf_destroy_plan(plan)
+
+    cycle()                                   # first use pays for one-off tables (twiddles, code objects)
+    before = free_bytes()
+    for _ in range(256):
+        cycle()
+    after = free_bytes()
+    assert before - after < 8 << 20, (before, after)

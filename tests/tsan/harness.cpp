@@ -46,6 +46,10 @@ FftDim fft_dim(int n, bool *ok) {  // (the mock transforms copy: a plan is its s
   return d;
 }
 bool fft_size_ok(int n) { return n >= 2 && (n & 1) == 0; }
+const float2 *half_twiddles(int) {  // (the mock transforms never read it)
+  static float2 const one = {1.f, 0.f};
+  return &one;
+}
 void launch_n0_single(hipStream_t, const float2 *X, int N, int, float, float, float *out) {
   std::lock_guard<std::mutex> lk(mock_stream_mutex());
   float acc = 0;

@@ -1,5 +1,5 @@
 // Device-less stand-in for <hip/hip_runtime.h>, for the ThreadSanitizer build of the library's OWN host protocol code
-// (tests/tsan/Makefile): kq_compat.cpp and kq_radio.cpp compile against it unchanged.  Test infrastructure only.
+// (tests/tsan/Makefile): the kq_compat*.cpp units and kq_radio.cpp compile against it unchanged, kq_host.hpp with them.  Test infrastructure only.
 //
 // What it models of the device: memory is host memory, and a stream is an in-order queue -- every operation that would
 // go through a stream runs to completion under one mutex (mock_stream_mutex), which is the ordering the real stream
@@ -19,7 +19,8 @@ typedef int hipError_t;
 enum { hipSuccess = 0, hipErrorOutOfMemory = 2 };
 typedef struct mock_stream_t *hipStream_t;
 enum hipMemcpyKind { hipMemcpyHostToHost, hipMemcpyHostToDevice, hipMemcpyDeviceToHost, hipMemcpyDeviceToDevice, hipMemcpyDefault };
-enum { hipStreamNonBlocking = 1 };
+typedef struct mock_event_t *hipEvent_t;
+enum { hipStreamNonBlocking = 1, hipHostMallocDefault = 0, hipEventDefault = 0, hipEventDisableTiming = 2 };
 
 inline std::mutex &mock_stream_mutex() {
   static std::mutex m;
@@ -39,6 +40,18 @@ inline hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) {
   *s = reinterpret_cast<hipStream_t>(new char);
   return hipSuccess;
 }
+inline hipError_t hipStreamDestroy(hipStream_t s) {
+  delete reinterpret_cast<char *>(s);
+  return hipSuccess;
+}
+inline hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) {
+  *e = reinterpret_cast<hipEvent_t>(new char);
+  return hipSuccess;
+}
+inline hipError_t hipEventDestroy(hipEvent_t e) {
+  delete reinterpret_cast<char *>(e);
+  return hipSuccess;
+}
 inline hipError_t hipStreamSynchronize(hipStream_t) {
   std::lock_guard<std::mutex> lk(mock_stream_mutex());  // everything queued so far has run
   return hipSuccess;
@@ -50,6 +63,19 @@ inline hipError_t hipMalloc(void **p, size_t n) {
 inline hipError_t hipFree(void *p) {
   std::lock_guard<std::mutex> lk(mock_stream_mutex());  // hipFree waits for the device
   free(p);
+  return hipSuccess;
+}
+inline hipError_t hipHostMalloc(void **p, size_t n, unsigned) {
+  *p = calloc(1, n ? n : 1);
+  return *p ? hipSuccess : hipErrorOutOfMemory;
+}
+inline hipError_t hipHostFree(void *p) {
+  free(p);
+  return hipSuccess;
+}
+inline hipError_t hipMemsetAsync(void *p, int v, size_t n, hipStream_t) {
+  std::lock_guard<std::mutex> lk(mock_stream_mutex());
+  memset(p, v, n);
   return hipSuccess;
 }
 inline hipError_t hipMemset(void *p, int v, size_t n) {
