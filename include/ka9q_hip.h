@@ -846,6 +846,108 @@ int kq_wfm_sync(kq_wfm_bank *bank);
 /* Stream index back to 0; every slot restarts cold with its settings */
 int kq_wfm_reset(kq_wfm_bank *bank);
 
+/* --- RDS / RBDS decoder bank -------------------------------------------------------------------------------------------
+ * Up to 4096 decoder slots, each reading the 57 kHz data subcarrier of one broadcast FM composite (the input of kq_wfm_*:
+ * a flat FM channel's discriminator output in rad/sample at Fc = comp_rate; a receiver bank's audio plane can be decoded
+ * in place on its stream after kq_bank_join) and giving RDS groups: four 16-bit blocks each, with a mask of the blocks
+ * whose checkword held.  There is no error correction.  The reference has no RDS decoder: the algorithm is defined here.
+ * Geometry: Dr = decimate, Fr = Fc / Dr, frames of L new samples, filter length M (odd), N = L + M - 1, Lr = L / Dr,
+ * spb = Fr / 1187.5 (samples of z per bit).  Per slot, x[n] is the composite; n counts samples since create or
+ * kq_rds_reset on a grid shared by every slot, and x[n] = 0 before the slot was set.
+ *   response   h_r: the ideal response R(f) sampled on the N bins and shaped by window_filter's procedure as for kq_wfm_*
+ *              (filter.c:365-413, in double, make_kaiser(M, kaiser_beta), used as float).  With g = f - 57000 and
+ *              t_d = 1 / 1187.5: R = -j sin(pi g t_d / 2) cos(pi g t_d / 4) for |g| <= 2 / t_d = 2375 Hz, 0 elsewhere: the
+ *              matched filter of the shaped biphase symbol of IEC 62106; one-sided, so the taps are complex.
+ *   baseband   z[k] = (h_r * x)[k Dr] exp(-j 2 pi ((57000 k Dr) mod Fc) / Fc), k on the global grid; frame f owns
+ *              k in [f Lr, (f + 1) Lr).
+ *   sums       over the frame's Lr samples: S_f = sum z[k]^2, E_f = sum |z[k]|^2 exp(-j 2 pi ((2375 k) mod 2 Fr) / 2 Fr),
+ *              P_f = sum |z[k]|^2.
+ *   tracker    sequential over frames, state zero when a slot is set.  alpha = 1 - exp(-L / (Fc track_ms 1e-3));
+ *              A_f = A_{f-1} + alpha (S_f - A_{f-1}), B_f likewise from E_f.  Carrier: w = arg A_f - 2 phi_{f-1},
+ *              phi_f = phi_{f-1} + (w - 2 pi rint(w / 2 pi)) / 2, wrapped into (-pi, pi].  Bit clock:
+ *              u = -arg(B_f) / 2 pi - tau_{f-1}, tau_f = tau_{f-1} + u - rint(u): unwrapped, never reduced.
+ *   bits       bit i is sampled at t_i = (i + tau_f) spb, in samples of z.  In frame f, from the next unsampled i, bits are
+ *              taken while t_i + 1 < (f + 1) Lr; consecutive i are neither skipped nor repeated.  The first i of a slot is
+ *              the least with t_i >= f_s Lr, f_s the slot's first frame.  With k0 = floor(t_i), r = t_i - k0:
+ *              y_i = Re((z[k0] + r (z[k0 + 1] - z[k0])) exp(-j phi_f)), c_i = (y_i < 0), data bit b_i = c_i xor c_{i-1}
+ *              (c before the first: 0).
+ *   blocks     crc10(w) = remainder of w x^10 modulo x^10 + x^8 + x^7 + x^5 + x^4 + x^3 + 1 (0x5B9), w of 16 bits.  A 26-bit
+ *              word is (info << 10) | (crc10(info) xor offset); offsets A 0x0FC, B 0x198, C 0x168, C' 0x350, D 0x1B4 at
+ *              positions 0, 1, 2, 2, 3.  Per bit reg = (reg << 1 | b) mod 2^26; once 26 bits are in,
+ *              s = crc10(reg >> 10) xor (reg & 0x3FF), and a "hit" is an offset equal to s.
+ *   unsynced   every hit is remembered (bit count, offset, info word).  Sync is taken when a hit comes exactly 26 bits
+ *              after the remembered one at the remembered position + 1 mod 4: a fresh group record opens, the remembered
+ *              word goes into its place with its ok bit if the new position is above 0, the new word goes in with its ok
+ *              bit, C' sets version_b, and position 3 emits the group.
+ *   synced     every 26 bits the word is stored at the expected position whether good or not; it is good if the hit's
+ *              position is the expected one: that sets its ok bit and zeroes `bad`, anything else increments `bad`.
+ *              Position 3 emits the group and opens a new record.  bad >= lose_after drops sync, the remembered hit and
+ *              the open record.  blocks_ok / blocks_bad count the words stored with / without their ok bit since the set.
+ * Samples that do not complete a frame are carried to the next call, so the same composite split differently into calls
+ * or blocks gives the same bits.
+ * Limits (refused by kq_rds_create with the reason in kq_last_error): Fc >= 128000; Dr divides Fc, L and M - 1; Fr >= 9500;
+ * M odd; N even, 2^a 3^b 5^c 7^d and <= 16384; (57000 N) mod Fc = 0 (the subcarrier sits on a bin, so the mix is a bin shift
+ * and a per-frame phase from integer arithmetic); (M - 1) / Fc >= 3 / 1187.5; 59375 Hz + the transition band
+ * 2 Fc sqrt(1 + kaiser_beta^2) / M <= Fc / 2; max_slots <= 4096.  kq_rds_set refuses track_ms <= 0 and lose_after < 1.
+ * Device memory per slot: Rx 4 + Rz 8 + Fmax 40 bytes, Rx = max_samples + L - 1 + M - 1, Rz = Fmax Lr + ceil(spb) + 2,
+ * Fmax = ceil(max_samples / L).
+ * Calls: kq_rds_create touches no device.  kq_rds_process with device memory is asynchronous on the handle's stream and
+ * reads nothing back; with host memory it is synchronous.  kq_rds_set, kq_rds_remove and kq_rds_reset wait for the stream
+ * and take effect at the first sample of the next kq_rds_process.  One lock per handle. */
+typedef struct kq_rds_bank kq_rds_bank;
+typedef struct kq_rds_config {
+  int device;
+  int comp_rate;             /* Fc: composite samples per second */
+  unsigned decimate;         /* Dr: Fr = Fc / Dr */
+  unsigned L, M;             /* new samples per frame, filter length (odd) */
+  float kaiser_beta;         /* window_filter's beta (make_kaiser convention) */
+  unsigned max_slots;        /* slots 0 .. max_slots - 1 (limit 4096) */
+  size_t max_samples;        /* largest nblocks * block_len of one kq_rds_process call */
+  void *stream;              /* hipStream_t, NULL = own stream; kq_bank_stream(bank) puts it beside a receiver bank */
+} kq_rds_config;
+typedef struct kq_rds_params {
+  unsigned source;           /* input row this slot decodes (a receiver bank's channel index) */
+  float track_ms;            /* time constant of the carrier and bit-clock tracker, 20 by default */
+  int lose_after;            /* consecutive bad blocks that drop sync, 10 by default */
+} kq_rds_params;
+typedef struct kq_rds_group {
+  uint16_t block[4];
+  uint8_t ok;                /* bit p: the block at position p passed its check */
+  uint8_t version_b;         /* the block at position 2 came with offset C' */
+  uint16_t reserved;
+  uint32_t bit;              /* bits decoded since the slot was set, at the group's last bit */
+} kq_rds_group;
+typedef struct kq_rds_status {
+  float phase, timing;       /* phi_f (rad), tau_f (bits) */
+  float level;               /* sqrt(P_f / Lr) */
+  int32_t synced;
+  uint32_t blocks_ok, blocks_bad;
+} kq_rds_status;
+
+kq_rds_bank *kq_rds_create(const kq_rds_config *cfg);
+int kq_rds_destroy(kq_rds_bank *bank);
+/* Put a decoder in `slot` (or replace the one there): a cold start at the next call's first sample */
+int kq_rds_set(kq_rds_bank *bank, unsigned slot, const kq_rds_params *params);
+/* The slot stops from the next call */
+int kq_rds_remove(kq_rds_bank *bank, unsigned slot);
+/* The bound on groups per slot of a call of nsamples (0 and an error for no bank): ceil(nsamples 1187.5 / Fc) / 104 + 2, or
+ * more where a call can emit more.  A call completes F <= (nsamples + L - 1) / L frames, up to L - 1 of whose samples were
+ * carried in, and tau moves by at most half a bit per frame, so it decodes fewer than (nsamples + L - 1) 1187.5 / Fc + F / 2
+ * + 1 bits and emits at most floor(that / 104) + 1 groups: the bound is the larger of the two, and no group is ever dropped. */
+size_t kq_rds_max_groups(const kq_rds_bank *bank, size_t nsamples);
+/* Composite addressed as in kq_wfm_process.  Returns F, the frames completed in this call.  groups[slot groups_stride + g]
+ * holds group g for g < counts[slot] and zeros from there to kq_rds_max_groups(bank, nblocks block_len), below which
+ * groups_stride is refused; status[slot status_stride + f] for f < F (strides in records).  Any output may be NULL; nothing is written for an empty slot.
+ * on_device != 0: every pointer is device memory and the call is asynchronous on the handle's stream. */
+int kq_rds_process(kq_rds_bank *bank, const float *comp, size_t src_stride, size_t row_stride, unsigned block_len,
+                   unsigned nblocks, int on_device, kq_rds_group *groups, size_t groups_stride, uint32_t *counts,
+                   kq_rds_status *status, size_t status_stride);
+/* The last call's z of a slot (F Lr complex samples, cap_complex at most) to host memory; synchronous; returns the count */
+int kq_rds_pull_baseband(kq_rds_bank *bank, unsigned slot, float *dst_re_im, size_t cap_complex);
+int kq_rds_sync(kq_rds_bank *bank);
+/* Stream index back to 0; every slot restarts cold with its settings */
+int kq_rds_reset(kq_rds_bank *bank);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,3 +35,4 @@ from . import iqfile  # noqa: F401,E402
 from .modulate import KQ_MOD_FM, KQ_MOD_LINEAR, ModBank, StationConfig, station_config  # noqa: F401,E402
 from .spectrum import SpecBank, SpecParams, plan, spec_params  # noqa: F401,E402
 from .wfm import STATUS_DTYPE, WfmBank, WfmParams, wfm_params  # noqa: F401,E402
+from .rds import GROUP_DTYPE, RdsBank, RdsParams, RdsStation, rds_params  # noqa: F401,E402  (rds.STATUS_DTYPE: the rds one)
