@@ -948,6 +948,82 @@ int kq_rds_sync(kq_rds_bank *bank);
 /* Stream index back to 0; every slot restarts cold with its settings */
 int kq_rds_reset(kq_rds_bank *bank);
 
+/* --- monitor mixer bank ------------------------------------------------------------------------------------------------
+ * Up to 65536 sessions, each one row of PCM (mono or stereo) with a gain, a stereo position and a mute switch
+ * (monitor.c:433-450), summed into up to 256 stereo buses (monitor.c:475-496 has one).  A receiver bank's audio plane
+ * (kq_bank_audio_device_ptr) is mixed in place on its stream after kq_bank_join(bank); kq_wfm_*'s output likewise.
+ * n counts frames since create or kq_mon_reset, on one grid for all sessions.  Per session, in float:
+ *   gains      gl = gain (1 - pan) / 2, gr = gain (1 + pan) / 2                                      (monitor.c:440-441)
+ *   delays     dl = pan > 0 ? round(pan 0.001 samprate) : 0, dr = pan < 0 ? round(-pan 0.001 samprate) : 0, in double with
+ *              C's round (monitor.c:444-447): the less favoured side comes up to 1 ms late
+ *   samples    xl[n], xr[n]: equal for a mono session, zero before the session was set.  KQ_MON_S16BE words w are
+ *              SCALE * (short)ntohs(w) as a float product, SCALE = 1.f / SHRT_MAX                    (monitor.c:88,492)
+ * The members of bus b are its unmuted sessions in ascending slot order, m_0 .. m_{K-1}.  (monitor.c adds a muted stream
+ * with gain 0; here it is left out, so a NaN from a channel nobody listens to never reaches the bus.)  Chunk c holds
+ * members 64 c .. 64 c + 63; its partial is P_c = the fold acc = fmaf(gl_m, xl_m[n - dl_m], acc) from 0.0f in member order,
+ * and the bus sample is 0.0f + P_0 + P_1 + ... in chunk order, by float additions; the right side likewise with gr, xr, dr.
+ * This order is part of the contract: it makes the bits independent of how the stream is cut into calls and blocks and
+ * of every session in another bus.  An empty bus gives zeros.
+ * H = round(0.001 samprate) frames of every session's input (muted ones too) are carried across calls, so a call may bring
+ * fewer than H frames, or one.
+ * pcm is out through scaleclip (audio.c:22-28: >= 1 gives SHRT_MAX, <= -1 SHRT_MIN, else truncation of SHRT_MAX x; NaN
+ * gives 0) in network byte order.  status, one record per bus and call: peak_* the largest |sample| of the call, clipped
+ * the number of int16 words equal to SHRT_MAX or SHRT_MIN, sessions = K, active the members with any non-zero input
+ * sample in this call (those audio.c:101-104 would not have suppressed).
+ * Limits (refused with -1 / NULL and the reason in kq_last_error, before any device call): samprate 8000 .. 384000,
+ * max_sessions 1 .. 65536, max_buses 1 .. 256, max_samples >= 1; slot < max_sessions, bus < max_buses, channels 1 or 2,
+ * gain finite and >= 0, |pan| <= 1; kq_mon_adjust / kq_mon_remove of an empty slot; nblocks block_len > max_samples;
+ * nblocks > 1 with a block (2 block_len elements where a stereo session is set) longer than row_stride; an unknown format.
+ * Device memory: max_sessions (8 H + 68) bytes of history and tables, and (max_sessions / 64 + max_buses) 8208 bytes of
+ * chunk partials (1024 frames at a time, whatever max_samples is); host-memory calls add their staging buffers.
+ * Calls: kq_mon_create, kq_mon_set, kq_mon_adjust and kq_mon_remove touch no device; they and kq_mon_reset take effect at
+ * the first frame of the next kq_mon_process, which uploads the tables when they changed.  kq_mon_process with device
+ * memory is asynchronous on the handle's stream and reads nothing back; with host memory it is synchronous.  One lock per
+ * handle. */
+enum kq_mon_format { KQ_MON_F32 = 0, KQ_MON_S16BE = 1 };  /* float, or int16 in network byte order (audio.c's PCM) */
+typedef struct kq_mon_bank kq_mon_bank;
+typedef struct kq_mon_config {
+  int device;
+  int samprate;              /* frames per second of every input and of the buses */
+  unsigned max_sessions;     /* slots 0 .. max_sessions - 1 (limit 65536) */
+  unsigned max_buses;        /* buses 0 .. max_buses - 1 (limit 256) */
+  size_t max_samples;        /* largest nblocks * block_len of one kq_mon_process call */
+  void *stream;              /* hipStream_t, NULL = own stream; kq_bank_stream(bank) puts it beside a receiver bank */
+} kq_mon_config;
+typedef struct kq_mon_params {
+  unsigned source;           /* input row this session plays (a receiver bank's channel index) */
+  unsigned bus;
+  int channels;              /* 1: mono, 2: interleaved L, R */
+  float gain;                /* linear, >= 0 */
+  float pan;                 /* -1 (left) .. +1 (right) */
+  int muted;
+} kq_mon_params;
+typedef struct kq_mon_status {
+  float peak_left, peak_right;
+  int32_t clipped, sessions, active;
+} kq_mon_status;
+
+kq_mon_bank *kq_mon_create(const kq_mon_config *cfg);
+int kq_mon_destroy(kq_mon_bank *bank);
+/* Put a session in `slot` (or replace the one there): a cold start, zero history */
+int kq_mon_set(kq_mon_bank *bank, unsigned slot, const kq_mon_params *params);
+/* monitor.c's keys: new gain, position and mute switch of the session in `slot`; its history is kept */
+int kq_mon_adjust(kq_mon_bank *bank, unsigned slot, float gain, float pan, int muted);
+int kq_mon_remove(kq_mon_bank *bank, unsigned slot);
+/* T = nblocks block_len frames per session.  Block k of row r starts at audio[r src_stride + k row_stride]: a mono session
+ * reads block_len values there, a stereo one 2 block_len interleaved L, R (a receiver bank's plane: src_stride =
+ * max_blocks 2 olen, row_stride = 2 olen, block_len = olen; kq_wfm_*'s output is one block of pairs); strides in elements
+ * of `format`.  Returns T.  out[b out_stride + 2 j + {0, 1}] is bus b's L / R for j < T (stride in floats), pcm[b
+ * pcm_stride + 2 j + {0, 1}] the same as int16 in network byte order, status[b] one record per bus; all max_buses buses are
+ * written, and any of the three may be NULL.  on_device != 0: every pointer is device memory and the call is asynchronous
+ * on the handle's stream. */
+int kq_mon_process(kq_mon_bank *bank, const void *audio, int format, size_t src_stride, size_t row_stride,
+                   unsigned block_len, unsigned nblocks, int on_device, float *out, size_t out_stride, int16_t *pcm,
+                   size_t pcm_stride, kq_mon_status *status);
+int kq_mon_sync(kq_mon_bank *bank);
+/* Frame index back to 0; every session restarts with zero history and its settings */
+int kq_mon_reset(kq_mon_bank *bank);
+
 #ifdef __cplusplus
 }
 #endif

@@ -265,18 +265,7 @@ void launch_copy_to_host(hipStream_t s, const float *audio, float *haudio, int r
 // audio.c:22-28; htons at audio.c:48,98 -- the arithmetic of k_pcm below) on the way out, half the bytes over the link.
 // 16 lanes take one row, 8 words (two 16-byte loads, one 16-byte store) per lane and trip; 480 = 60 x 8, so a lane's 8
 // words never straddle one of the 480-word chunks whose all-zero test decides whether the reference sends the packet
-// (audio.c:49,99,105): mask bit k = chunk k of the row is all zero.
-__device__ __forceinline__ unsigned pcm_word_be(float x) {
-  int v;
-  if (x >= 1.0f)
-    v = 32767;
-  else if (x <= -1.0f)
-    v = -32768;
-  else
-    v = (int)(32767.f * x);  // truncation, as the (short) cast of audio.c:27
-  unsigned const h = (unsigned)v & 0xffffu;
-  return ((h << 8) | (h >> 8)) & 0xffffu;
-}
+// (audio.c:49,99,105): mask bit k = chunk k of the row is all zero.  The word itself is kq_lane.hpp's pcm_word_be.
 // COMPACT: instead of the whole 64-byte status records, the 24 bytes a receiver reads per block (kq_chan_status_compact:
 // bb_power, n0, snr, FM foffset / AM + linear agc.gain, FM squelch counter / AM + linear hang counter, nout) -- at real
 // time the status plane is half of the PCM delivery's bytes.  A workgroup packs 256 records into LDS and stores them as

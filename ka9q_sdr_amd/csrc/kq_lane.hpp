@@ -3,7 +3,8 @@
 // A ds_bpermute costs an LDS round trip; in the single-wave demodulators forty of them in a dependent chain were
 // the whole block latency.
 // Also the two helpers that kq_pruned.hip shares with the rest but cannot take from kq_ldsfft.hpp, whose cmul would
-// collide with its packed one: the wave-level LDS fence and the unit phasor.
+// collide with its packed one: the wave-level LDS fence and the unit phasor.  And the PCM word that kq_kernels.hip's
+// delivery and kq_mon.hip's buses share.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -67,6 +68,20 @@ __device__ __forceinline__ float2 phasor_turns(double turns) {
   float s, c;
   sincospif(2.0f * (float)turns, &s, &c);
   return make_float2(c, s);
+}
+
+// float -> clipped int16 in network byte order, in the low half of the word: scaleclip (audio.c:22-28) and htons
+// (audio.c:48,98).  A NaN gives 0
+__device__ __forceinline__ unsigned pcm_word_be(float x) {
+  int v;
+  if (x >= 1.0f)
+    v = 32767;
+  else if (x <= -1.0f)
+    v = -32768;
+  else
+    v = (int)(32767.f * x);  // truncation, as the (short) cast of audio.c:27
+  unsigned const h = (unsigned)v & 0xffffu;
+  return ((h << 8) | (h >> 8)) & 0xffffu;
 }
 
 }  // namespace kq
