@@ -1024,6 +1024,110 @@ int kq_mon_sync(kq_mon_bank *bank);
 /* Frame index back to 0; every session restarts with zero history and its settings */
 int kq_mon_reset(kq_mon_bank *bank);
 
+/* --- baseband FSK / GMSK packet decoder bank ------------------------------------------------------------------------------
+ * Up to 4096 decoder slots, each reading HDLC frames from the discriminator output of one flat FM channel (rad/sample at
+ * Fs = samprate; a receiver bank's audio plane can be decoded in place on its stream after kq_bank_join): 9600 bit/s G3RUH
+ * packet (scrambled, NRZI, AX.25) and AIS (GMSK 9600 bit/s, NRZI, unscrambled, the same framing and 16-bit FCS), or any
+ * other rate with 4 baud <= Fs <= 40 baud.  The reference has no such decoder (packet.c is AFSK-1200): the algorithm is
+ * defined here.  Everything after the quantiser is integer arithmetic, so the bits do not depend on how sums are ordered.
+ * Per slot, x[n] is its input row; n counts samples since create or kq_fsk_reset on a grid shared by every slot, and
+ * x[n] = 0 before the slot was set.  K = taps, W = rint(window_bits Fs / baud).
+ *   quantise   q[n] = clamp(rint(x[n] input_scale), -32767, 32767): one float multiply, round to nearest even; NaN reads
+ *              as 0.  input_scale 4096 suits rad/sample.  A KQ_PCM_S16BE word w (network byte order, two's complement) is
+ *              taken as q itself, -32768 as -32767.
+ *   low-pass   h[k] = sinc(2 cutoff_hz / Fs (k - (K - 1) / 2)) w[k], w = make_kaiser(K, kaiser_beta) (filter.c:337-357), in
+ *              double, scaled to sum h = 1; hq[k] = rint(32768 h[k]) as int16 (kq_fsk_get_taps); y[n] = sum_k hq[k] q[n - k] in
+ *              int32.  A design with sum |hq| > 65535 is refused, so y cannot overflow.
+ *   threshold  c2[n] = max(y[n - W + 1 .. n]) + min(y[n - W + 1 .. n]), d[n] = (2 y[n] > c2[n]) in 64 bits: the mid level of
+ *              the last window_bits bits takes out DC and tuning offset.  d = 0 before the stream starts.
+ *   bit clock  s: int32, 0 when the slot is set; inc = rint(2^32 baud / Fs).  Per sample n in order: if d[n] != d[n - 1],
+ *              s = s - (s >> pll_shift) (arithmetic shift); then t = s + inc; if t >= 2^31, s = t - 2^32 and a channel bit
+ *              c = d[n] is taken, else s = t.
+ *   bits       scrambled slots (G3RUH, 1 + x^12 + x^17, self-synchronising): u = c xor sr<16> xor sr<11>, then
+ *              sr = (sr << 1 | c) & 0x1FFFF; else u = c.  Data bit b = (u == u_prev) (NRZI).  sr = 0, u_prev = 0 at the set.
+ *   HDLC       state ones, in_frame, nbits (saturating at 2^31 - 1) and the open frame of max_frame_bytes bytes, filled LSB
+ *              first; bits beyond it are counted in nbits and not stored.
+ *              b = 1: ones = min(ones + 1, 7); at 7, aborts += in_frame and in_frame = 0; below 7, in a frame, a 1 is appended.
+ *              b = 0: ones == 6 is a flag: if in_frame, nb = nbits - 7 is a candidate when nb >= 8 min_bytes; it is good when
+ *              nb mod 8 == 0, nb / 8 <= max_frame_bytes and the CRC-16/X.25 of its nb / 8 bytes leaves 0xf0b8 (ax25.c:138-156
+ *              crc_good): frames_good += 1 and the frame goes to the slot's arena, or dropped += 1 when that holds
+ *              max_frames; any other candidate: frames_bad += 1.  Then in_frame = 1, nbits = 0.  ones == 5: a stuffed
+ *              zero, dropped.  ones < 5, in a frame: a 0 is appended.  Always ones = 0.
+ *   record     the bytes (body + FCS, as kq_afsk_pull_frame gives them), length, end_sample (n of the sample at which the
+ *              closing flag's last bit was taken: AIS slot timing) and end_bit (bits taken since the set, that one included).
+ * Every sample of a call is consumed in that call; carried are the last K - 1 + W - 1 + 63 values of q, s, sr, u_prev, d
+ * of the last sample, the deframer and the open frame, so the same stream split differently into calls or blocks gives the
+ * same bits, records and status.  d is packed 64 samples to a word on the grid (bit n mod 64 of word n / 64); a call that
+ * starts inside a word computes that word again from the carried q.
+ * Limits (refused by kq_fsk_create / kq_fsk_set with the reason in kq_last_error, before any HIP call): 4 baud <= Fs <=
+ * 40 baud (the algorithm decodes cleanly at 4.07 samples per bit and fails at 2.5); K odd, 3..127; 2 <= W <= 1024;
+ * 0 < cutoff_hz < Fs / 2; kaiser_beta finite and >= 0; 1 <= pll_shift <= 8; input_scale > 0; max_slots 1..4096; max_frames
+ * 1..4096; 8 <= max_frame_bytes <= 1024; max_samples 1..2^28; 4 <= min_bytes <= max_frame_bytes.
+ * Device memory per slot: 4 (K + W + 61) bytes of q (two copies), 8 (max_samples / 64 + 2) of d, max_frame_bytes of open
+ * frame, max_frames (max_frame_bytes + 16) of arena and 96 of state and tables.
+ * Calls: kq_fsk_create touches no device.  kq_fsk_process with device memory is asynchronous on the handle's stream and
+ * reads nothing back; with host memory it is synchronous.  kq_fsk_set, kq_fsk_remove and kq_fsk_reset wait for the stream
+ * and take effect at the first sample of the next kq_fsk_process.  One lock per handle. */
+typedef struct kq_fsk_bank kq_fsk_bank;
+typedef struct kq_fsk_config {
+  int device;
+  int samprate;              /* Fs: input samples per second */
+  int baud;
+  unsigned taps;             /* K: low-pass length (odd) */
+  float cutoff_hz;           /* 0.6 baud is a good choice */
+  float kaiser_beta;         /* make_kaiser convention */
+  float window_bits;         /* threshold window, in bits: W = rint(window_bits Fs / baud) */
+  float input_scale;
+  int pll_shift;
+  unsigned max_slots;        /* slots 0 .. max_slots - 1 (limit 4096) */
+  unsigned max_frames;       /* arena places per slot between kq_fsk_clear_frames calls */
+  unsigned max_frame_bytes;  /* longest frame, FCS included */
+  size_t max_samples;        /* largest nblocks * block_len of one kq_fsk_process call */
+  void *stream;              /* hipStream_t, NULL = own stream; kq_bank_stream(bank) puts it beside a receiver bank */
+} kq_fsk_config;
+typedef struct kq_fsk_params {
+  unsigned source;           /* input row this slot decodes (a receiver bank's channel index) */
+  int scrambled;             /* 1: G3RUH, 0: plain NRZI (AIS) */
+  unsigned min_bytes;        /* shortest candidate, FCS included; 8 by default */
+} kq_fsk_params;
+typedef struct kq_fsk_status {   /* counters since the slot was set */
+  uint32_t bits;
+  uint32_t frames_good, frames_bad, aborts, dropped;
+  int32_t pll_phase;         /* s */
+  int32_t in_frame;
+  uint32_t level;            /* max - min of y over the window at the call's last sample */
+} kq_fsk_status;
+typedef struct kq_fsk_frame_info {
+  uint32_t length;
+  uint32_t end_bit;
+  uint64_t end_sample;
+} kq_fsk_frame_info;
+
+kq_fsk_bank *kq_fsk_create(const kq_fsk_config *cfg);
+int kq_fsk_destroy(kq_fsk_bank *bank);
+/* Put a decoder in `slot` (or replace the one there): a cold start at the next call's first sample, its arena empty */
+int kq_fsk_set(kq_fsk_bank *bank, unsigned slot, const kq_fsk_params *params);
+/* The slot stops from the next call; its arena stays readable */
+int kq_fsk_remove(kq_fsk_bank *bank, unsigned slot);
+/* Input addressed as in kq_wfm_process, in elements of `format` (KQ_PCM_F32 or KQ_PCM_S16BE).  status[slot status_stride]
+ * is the slot's record after the call's last sample (stride in records, may be NULL; nothing is written for an empty
+ * slot).  Returns 0.  on_device != 0: src and status are device memory and the call is asynchronous on the handle's
+ * stream. */
+int kq_fsk_process(kq_fsk_bank *bank, const void *src, int format, size_t src_stride, size_t row_stride, unsigned block_len,
+                   unsigned nblocks, int on_device, kq_fsk_status *status, size_t status_stride);
+/* Frames in every slot's arena, counts[max_slots], in one copy; synchronous */
+int kq_fsk_pull_counts(kq_fsk_bank *bank, uint32_t *counts);
+/* Copies frame `index` of `slot` (at most cap bytes) and its record (info may be NULL); returns its length, or -1 */
+int kq_fsk_pull_frame(kq_fsk_bank *bank, unsigned slot, unsigned index, unsigned char *dst, size_t cap,
+                      kq_fsk_frame_info *info);
+/* Empties every arena (on the handle's stream); the status counters go on */
+int kq_fsk_clear_frames(kq_fsk_bank *bank);
+/* hq (at most cap words); returns K */
+int kq_fsk_get_taps(const kq_fsk_bank *bank, int16_t *dst, size_t cap);
+int kq_fsk_sync(kq_fsk_bank *bank);
+/* Stream index back to 0; every slot restarts cold with its settings */
+int kq_fsk_reset(kq_fsk_bank *bank);
+
 #ifdef __cplusplus
 }
 #endif
