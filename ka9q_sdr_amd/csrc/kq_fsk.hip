@@ -17,7 +17,6 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
-#include <map>
 #include <mutex>
 #include <vector>
 
@@ -25,6 +24,7 @@
 #include "kq_design.hpp"
 #include "kq_device.hpp"
 #include "kq_host.hpp"
+#include "kq_slots.hpp"
 
 namespace {
 
@@ -336,24 +336,18 @@ struct kq_fsk_bank : kq::HostSide {
   uint64_t n_cur = 0;
   int turn = 0;                          // the copy of the carried q the next call reads
   std::vector<short> hq;
-  std::vector<FskPar> par;
-  std::vector<int> all;                  // active slots, ascending
-  FskPar *d_par = nullptr;
-  int *d_list = nullptr;
-  int *d_rowmap = nullptr;
-  short *d_taps = nullptr;
-  short *d_hist[2] = {nullptr, nullptr};
-  unsigned long long *d_dw = nullptr;
-  unsigned *d_level = nullptr;
-  FskState *d_state = nullptr;
-  unsigned char *d_open = nullptr, *d_frames = nullptr;
-  kq_fsk_frame_info *d_info = nullptr;
-  unsigned *d_nframes = nullptr;
-  // host-memory calls
-  char *d_stage = nullptr;
-  size_t stage_cap = 0;                  // bytes: source rows x max_samples x 4
-  kq_fsk_status *d_st = nullptr;
-  std::vector<int> rowmap;
+  struct Dev {  // kq::lazy_device
+    kq::SlotTable<FskPar> slots;
+    short *taps = nullptr;
+    short *hist[2] = {nullptr, nullptr};
+    unsigned long long *dw = nullptr;
+    unsigned *level = nullptr;
+    FskState *state = nullptr;
+    unsigned char *open = nullptr, *frames = nullptr;
+    kq_fsk_frame_info *info = nullptr;
+    unsigned *nframes = nullptr;
+    kq_fsk_status *st = nullptr;         // host-memory calls
+  } d;
 };
 
 namespace {
@@ -361,53 +355,25 @@ namespace {
 int make_device(kq_fsk_bank *b) {
   kq_fsk_config const &c = b->cfg;
   FskGeom const &g = b->g;
+  auto &d = b->d;
   if (b->open_stream(c.stream)) return -1;
   size_t const S = c.max_slots;
-  if (b->alloc(&b->d_par, S, true) || b->alloc(&b->d_list, S) || b->alloc(&b->d_rowmap, S) || b->alloc(&b->d_taps, (size_t)g.K) ||
-      b->alloc(&b->d_hist[0], S * g.HN, true) || b->alloc(&b->d_hist[1], S * g.HN, true) || b->alloc(&b->d_dw, g.words * S) ||
-      b->alloc(&b->d_level, S, true) || b->alloc(&b->d_state, S, true) || b->alloc(&b->d_open, S * g.mfb, true) ||
-      b->alloc(&b->d_frames, S * g.max_frames * g.mfb) || b->alloc(&b->d_info, S * g.max_frames) ||
-      b->alloc(&b->d_nframes, S, true))
+  if (d.slots.alloc(*b, S) || b->alloc(&d.taps, (size_t)g.K) || b->alloc(&d.hist[0], S * g.HN, true) ||
+      b->alloc(&d.hist[1], S * g.HN, true) || b->alloc(&d.dw, g.words * S) || b->alloc(&d.level, S, true) ||
+      b->alloc(&d.state, S, true) || b->alloc(&d.open, S * g.mfb, true) || b->alloc(&d.frames, S * g.max_frames * g.mfb) ||
+      b->alloc(&d.info, S * g.max_frames) || b->alloc(&d.nframes, S, true))
     return -1;
-  KQ_TRY(hipMemcpyAsync(b->d_taps, b->hq.data(), b->hq.size() * sizeof(short), hipMemcpyHostToDevice, b->stream));
+  KQ_TRY(hipMemcpyAsync(d.taps, b->hq.data(), b->hq.size() * sizeof(short), hipMemcpyHostToDevice, b->stream));
   KQ_TRY(hipStreamSynchronize(b->stream));
-  b->dev_ready = true;
   return 0;
-}
-
-// at the first set; a failure half way lets go of what was made, so the next set starts over and destroy owes nothing
-int fsk_device(kq_fsk_bank *b) {
-  if (b->dev_ready) return 0;
-  if (make_device(b) == 0) return 0;
-  b->close();
-  b->d_par = nullptr;
-  b->d_list = b->d_rowmap = nullptr;
-  b->d_taps = b->d_hist[0] = b->d_hist[1] = nullptr;
-  b->d_dw = nullptr;
-  b->d_level = b->d_nframes = nullptr;
-  b->d_state = nullptr;
-  b->d_open = b->d_frames = nullptr;
-  b->d_info = nullptr;
-  return -1;
 }
 
 // zero history, clock, deframer and arena (the stream is idle: callers synchronised it)
 int cold_start(kq_fsk_bank *b, unsigned s) {
-  for (short *h : b->d_hist) KQ_TRY(hipMemsetAsync(h + (size_t)s * b->g.HN, 0, b->g.HN * sizeof(short), b->stream));
-  KQ_TRY(hipMemsetAsync(b->d_state + s, 0, sizeof(FskState), b->stream));
-  KQ_TRY(hipMemsetAsync(b->d_nframes + s, 0, sizeof(unsigned), b->stream));
-  KQ_TRY(hipMemsetAsync(b->d_level + s, 0, sizeof(unsigned), b->stream));
-  return 0;
-}
-
-int upload(kq_fsk_bank *b, unsigned s) {
-  KQ_TRY(hipMemcpyAsync(b->d_par + s, &b->par[s], sizeof(FskPar), hipMemcpyHostToDevice, b->stream));
-  b->all.clear();
-  for (unsigned k = 0; k < b->cfg.max_slots; k++)
-    if (b->par[k].active) b->all.push_back((int)k);
-  if (!b->all.empty())
-    KQ_TRY(hipMemcpyAsync(b->d_list, b->all.data(), b->all.size() * sizeof(int), hipMemcpyHostToDevice, b->stream));
-  KQ_TRY(hipStreamSynchronize(b->stream));
+  for (short *h : b->d.hist) KQ_TRY(hipMemsetAsync(h + (size_t)s * b->g.HN, 0, b->g.HN * sizeof(short), b->stream));
+  KQ_TRY(hipMemsetAsync(b->d.state + s, 0, sizeof(FskState), b->stream));
+  KQ_TRY(hipMemsetAsync(b->d.nframes + s, 0, sizeof(unsigned), b->stream));
+  KQ_TRY(hipMemsetAsync(b->d.level + s, 0, sizeof(unsigned), b->stream));
   return 0;
 }
 
@@ -500,32 +466,13 @@ kq_fsk_bank *kq_fsk_create(const kq_fsk_config *cfg) {
   g.mfb = (int)cfg->max_frame_bytes;
   g.S = (int)cfg->max_slots;
   g.words = cfg->max_samples / 64 + 2;
-  b->par.assign(cfg->max_slots, FskPar{});
   return b;
 }
 
-int kq_fsk_destroy(kq_fsk_bank *b) {
-  if (!b) {
-    kq_internal_set_error("kq_fsk_destroy: null bank");
-    return -1;
-  }
-  if (b->dev_ready) {
-    kq::DeviceScope dev_scope_(b->cfg.device);
-    b->close();
-  }
-  delete b;
-  return 0;
-}
+int kq_fsk_destroy(kq_fsk_bank *b) { return kq::destroy_bank(b, "kq_fsk_destroy"); }
 
 int kq_fsk_set(kq_fsk_bank *b, unsigned slot, const kq_fsk_params *p) {
-  if (slot >= kMaxSlots) {
-    kq_internal_set_error("kq_fsk_set: slot %u is beyond any bank (%u slots at most)", slot, kMaxSlots);
-    return -1;
-  }
-  if (!p) {
-    kq_internal_set_error("kq_fsk_set: null params");
-    return -1;
-  }
+  if (!kq::set_args_ok("kq_fsk_set", slot, p, kMaxSlots)) return -1;
   if (p->min_bytes < 4) {
     kq_internal_set_error("kq_fsk_set: min_bytes %u must be >= 4", p->min_bytes);
     return -1;
@@ -539,38 +486,21 @@ int kq_fsk_set(kq_fsk_bank *b, unsigned slot, const kq_fsk_params *p) {
     kq_internal_set_error("kq_fsk_set: min_bytes %u > max_frame_bytes %u", p->min_bytes, b->cfg.max_frame_bytes);
     return -1;
   }
-  if (slot >= b->cfg.max_slots) {
-    kq_internal_set_error("kq_fsk_set: slot %u >= max_slots %u", slot, b->cfg.max_slots);
-    return -1;
-  }
+  if (!kq::slot_in_bank("kq_fsk_set", slot, b->cfg.max_slots)) return -1;
   kq::DeviceScope dev_scope_(b->cfg.device);
-  if (fsk_device(b)) return -1;
+  if (kq::lazy_device(b, make_device)) return -1;
   KQ_TRY(hipStreamSynchronize(b->stream));
   FskPar np{};
   np.active = 1;
   np.source = p->source;
   np.scrambled = p->scrambled != 0;
   np.min_bytes = (int)p->min_bytes;
-  b->par[slot] = np;
+  b->d.slots.par[slot] = np;
   if (cold_start(b, slot)) return -1;
-  return upload(b, slot);
+  return b->d.slots.upload(*b, slot);
 }
 
-int kq_fsk_remove(kq_fsk_bank *b, unsigned slot) {
-  if (!b) {
-    kq_internal_set_error("kq_fsk_remove: null bank");
-    return -1;
-  }
-  std::lock_guard<std::mutex> lk(b->mu);
-  if (slot >= b->cfg.max_slots || !b->par[slot].active) {
-    kq_internal_set_error("kq_fsk_remove: slot %u holds no decoder", slot);
-    return -1;
-  }
-  kq::DeviceScope dev_scope_(b->cfg.device);
-  KQ_TRY(hipStreamSynchronize(b->stream));
-  b->par[slot] = FskPar{};
-  return upload(b, slot);
-}
+int kq_fsk_remove(kq_fsk_bank *b, unsigned slot) { return kq::remove_slot(b, slot, "kq_fsk_remove"); }
 
 int kq_fsk_process(kq_fsk_bank *b, const void *src, int format, size_t src_stride, size_t row_stride, unsigned block_len,
                    unsigned nblocks, int on_device, kq_fsk_status *status, size_t status_stride) {
@@ -583,46 +513,36 @@ int kq_fsk_process(kq_fsk_bank *b, const void *src, int format, size_t src_strid
     return -1;
   }
   std::lock_guard<std::mutex> lk(b->mu);
+  if (!kq::blocks_ok("kq_fsk_process", b->cfg.max_samples, row_stride, block_len, nblocks)) return -1;
   size_t const ncall = (size_t)block_len * nblocks;
-  if (ncall > b->cfg.max_samples) {
-    kq_internal_set_error("kq_fsk_process: nblocks %u x block_len %u = %zu > max_samples %zu", nblocks, block_len, ncall,
-                          b->cfg.max_samples);
-    return -1;
-  }
-  if (nblocks > 1 && row_stride < block_len) {
-    kq_internal_set_error("kq_fsk_process: row_stride %zu < block_len %u", row_stride, block_len);
-    return -1;
-  }
   if (status && status_stride < 1) {
     kq_internal_set_error("kq_fsk_process: status_stride %zu < 1", status_stride);
     return -1;
   }
-  if (ncall == 0) return 0;
-  if (!src) {
-    kq_internal_set_error("kq_fsk_process: null src");
-    return -1;
-  }
-  if (b->all.empty() || !b->dev_ready) {
+  kq::CallWork const work = kq::call_work(b, "kq_fsk_process", ncall, src, "src");
+  if (work == kq::CALL_IDLE) {
     b->n_cur += ncall;
     return 0;
   }
+  if (work != kq::CALL_RUN) return work;
   kq::DeviceScope dev_scope_(b->cfg.device);
   FskGeom const &g = b->g;
-  size_t const S = b->cfg.max_slots, nlist = b->all.size(), esize = format == KQ_PCM_S16BE ? 2 : 4;
+  auto &d = b->d;
+  size_t const S = b->cfg.max_slots, nlist = d.slots.all.size();
   CallArgs a{};
   a.g = g;
-  a.par = b->d_par;
-  a.list = b->d_list;
-  a.taps = b->d_taps;
-  a.hist_in = b->d_hist[b->turn];
-  a.hist_out = b->d_hist[b->turn ^ 1];
-  a.dw = b->d_dw;
-  a.level = b->d_level;
-  a.state = b->d_state;
-  a.open = b->d_open;
-  a.frames = b->d_frames;
-  a.info = b->d_info;
-  a.nframes = b->d_nframes;
+  a.par = d.slots.d_par;
+  a.list = d.slots.d_list;
+  a.taps = d.taps;
+  a.hist_in = d.hist[b->turn];
+  a.hist_out = d.hist[b->turn ^ 1];
+  a.dw = d.dw;
+  a.level = d.level;
+  a.state = d.state;
+  a.open = d.open;
+  a.frames = d.frames;
+  a.info = d.info;
+  a.nframes = d.nframes;
   a.n0 = (int64_t)b->n_cur;
   a.n1 = a.n0 + (int64_t)ncall;
   a.w0 = a.n0 >> 6;
@@ -636,29 +556,17 @@ int kq_fsk_process(kq_fsk_bank *b, const void *src, int format, size_t src_strid
     a.st = status;
     a.sstride = status_stride;
   } else {
-    // the distinct source rows of the active slots, staged contiguously
-    std::map<unsigned, int> rows;
-    b->rowmap.resize(nlist);
-    for (size_t i = 0; i < nlist; i++) {
-      unsigned const r = b->par[b->all[i]].source;
-      auto it = rows.find(r);
-      if (it == rows.end()) it = rows.emplace(r, (int)rows.size()).first;
-      b->rowmap[i] = it->second;
-    }
-    // (grow waits for the stream, which is idle here: the last host-memory call ended in a synchronise)
-    if (b->grow(&b->d_stage, &b->stage_cap, rows.size() * b->cfg.max_samples * 4)) return -1;
-    const char *hsrc = reinterpret_cast<const char *>(src);
-    for (auto const &kv : rows)
-      KQ_TRY(hipMemcpy2DAsync(b->d_stage + (size_t)kv.second * ncall * esize, block_len * esize,
-                               hsrc + (size_t)kv.first * src_stride * esize, (nblocks > 1 ? row_stride : block_len) * esize,
-                               block_len * esize, nblocks, hipMemcpyHostToDevice, b->stream));
-    KQ_TRY(hipMemcpyAsync(b->d_rowmap, b->rowmap.data(), nlist * sizeof(int), hipMemcpyHostToDevice, b->stream));
-    a.src = b->d_stage;
-    a.src_stride = ncall;
-    a.row_stride = block_len;
-    a.rowmap = b->d_rowmap;
-    if (status && !b->d_st && b->alloc(&b->d_st, S)) return -1;
-    a.st = status ? b->d_st : nullptr;
+    // (the stage holds 4 bytes per sample whatever the format; the rows lie as closely as the format allows)
+    kq::Staged in;
+    if (d.slots.stage_rows(*b, src, format == KQ_PCM_S16BE ? 2 : 4, src_stride, row_stride, block_len, nblocks,
+                           b->cfg.max_samples * 4, &in))
+      return -1;
+    a.src = in.src;
+    a.src_stride = in.src_stride;
+    a.row_stride = in.row_stride;
+    a.rowmap = in.rowmap;
+    if (status && !d.st && b->alloc(&d.st, S)) return -1;
+    a.st = status ? d.st : nullptr;
     a.sstride = 1;
   }
   int64_t const nwords = ((a.n1 - 1) >> 6) - a.w0 + 1;  // <= max_samples / 64 + 2
@@ -670,16 +578,10 @@ int kq_fsk_process(kq_fsk_bank *b, const void *src, int format, size_t src_strid
   b->turn ^= 1;  // from here on the carried q is in the other copy, whatever fails below
   b->n_cur += ncall;
   if (!on_device) {
-    if (status) {  // the records of the active slots, a run of consecutive slots at a time
-      for (size_t i = 0; i < nlist;) {
-        size_t j = i + 1;
-        while (j < nlist && b->all[j] == b->all[j - 1] + 1) j++;
-        size_t const s0 = (size_t)b->all[i], n = j - i;
-        KQ_TRY(hipMemcpy2DAsync(status + s0 * status_stride, status_stride * sizeof(kq_fsk_status), b->d_st + s0,
-                                 sizeof(kq_fsk_status), sizeof(kq_fsk_status), n, hipMemcpyDeviceToHost, b->stream));
-        i = j;
-      }
-    }
+    auto back = [&](size_t s0, size_t n) {  // the records of the active slots
+      return kq::copy_rows_back(*b, status, status_stride, d.st, 1, 1, sizeof(kq_fsk_status), s0, n);
+    };
+    if (status && d.slots.for_runs(back)) return -1;
     KQ_TRY(hipStreamSynchronize(b->stream));
   }
   return 0;
@@ -700,7 +602,7 @@ int kq_fsk_pull_counts(kq_fsk_bank *b, uint32_t *counts) {
     return 0;
   }
   kq::DeviceScope dev_scope_(b->cfg.device);
-  KQ_TRY(hipMemcpyAsync(counts, b->d_nframes, b->cfg.max_slots * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
+  KQ_TRY(hipMemcpyAsync(counts, b->d.nframes, b->cfg.max_slots * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
   KQ_TRY(hipStreamSynchronize(b->stream));
   return 0;
 }
@@ -722,7 +624,7 @@ int kq_fsk_pull_frame(kq_fsk_bank *b, unsigned slot, unsigned index, unsigned ch
   unsigned n = 0;
   kq::DeviceScope dev_scope_(b->cfg.device);
   if (b->dev_ready) {
-    KQ_TRY(hipMemcpyAsync(&n, b->d_nframes + slot, sizeof n, hipMemcpyDeviceToHost, b->stream));
+    KQ_TRY(hipMemcpyAsync(&n, b->d.nframes + slot, sizeof n, hipMemcpyDeviceToHost, b->stream));
     KQ_TRY(hipStreamSynchronize(b->stream));
   }
   if (index >= n) {
@@ -731,11 +633,11 @@ int kq_fsk_pull_frame(kq_fsk_bank *b, unsigned slot, unsigned index, unsigned ch
   }
   size_t const at = (size_t)slot * b->g.max_frames + index;
   kq_fsk_frame_info r;
-  KQ_TRY(hipMemcpyAsync(&r, b->d_info + at, sizeof r, hipMemcpyDeviceToHost, b->stream));
+  KQ_TRY(hipMemcpyAsync(&r, b->d.info + at, sizeof r, hipMemcpyDeviceToHost, b->stream));
   KQ_TRY(hipStreamSynchronize(b->stream));
   size_t const take = std::min(cap, (size_t)r.length);
   if (take) {
-    KQ_TRY(hipMemcpyAsync(dst, b->d_frames + at * b->g.mfb, take, hipMemcpyDeviceToHost, b->stream));
+    KQ_TRY(hipMemcpyAsync(dst, b->d.frames + at * b->g.mfb, take, hipMemcpyDeviceToHost, b->stream));
     KQ_TRY(hipStreamSynchronize(b->stream));
   }
   if (info) *info = r;
@@ -750,7 +652,7 @@ int kq_fsk_clear_frames(kq_fsk_bank *b) {
   std::lock_guard<std::mutex> lk(b->mu);
   if (!b->dev_ready) return 0;
   kq::DeviceScope dev_scope_(b->cfg.device);
-  KQ_TRY(hipMemsetAsync(b->d_nframes, 0, b->cfg.max_slots * sizeof(unsigned), b->stream));
+  KQ_TRY(hipMemsetAsync(b->d.nframes, 0, b->cfg.max_slots * sizeof(unsigned), b->stream));
   return 0;
 }
 
@@ -768,17 +670,7 @@ int kq_fsk_get_taps(const kq_fsk_bank *b, int16_t *dst, size_t cap) {
   return (int)b->hq.size();
 }
 
-int kq_fsk_sync(kq_fsk_bank *b) {
-  if (!b) {
-    kq_internal_set_error("kq_fsk_sync: null bank");
-    return -1;
-  }
-  std::lock_guard<std::mutex> lk(b->mu);
-  if (!b->dev_ready) return 0;
-  kq::DeviceScope dev_scope_(b->cfg.device);
-  KQ_TRY(hipStreamSynchronize(b->stream));
-  return 0;
-}
+int kq_fsk_sync(kq_fsk_bank *b) { return kq::sync_bank(b, "kq_fsk_sync"); }
 
 int kq_fsk_reset(kq_fsk_bank *b) {
   if (!b) {
@@ -790,7 +682,7 @@ int kq_fsk_reset(kq_fsk_bank *b) {
   if (!b->dev_ready) return 0;
   kq::DeviceScope dev_scope_(b->cfg.device);
   KQ_TRY(hipStreamSynchronize(b->stream));
-  for (int s : b->all)
+  for (int s : b->d.slots.all)
     if (cold_start(b, (unsigned)s)) return -1;
   KQ_TRY(hipStreamSynchronize(b->stream));
   return 0;

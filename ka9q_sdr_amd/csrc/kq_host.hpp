@@ -1,8 +1,10 @@
-// kq_host.hpp -- the host half that every handle shares (kq_bank, the satellite banks kq_afsk, kq_decim, kq_mod, kq_spec, kq_rds, kq_mon,
-// kq_wfm, and the compat surface's context, masters, slaves and FFTW plans, kq_compat.hpp): error reporting, the handle's streams, and whatever the handle owns on the device or for it -- device memory,
-// pinned host memory, events.  Each is named once, where it is made; close() lets go of all of it.  Host only; a handle's
-// struct derives from kq::HostSide.  Every member function wants the handle's device current (the entry point's
-// kq::DeviceScope).
+// kq_host.hpp -- the host half that every handle shares (kq_bank, the satellite banks kq_afsk, kq_decim, kq_mod, kq_spec, kq_rds,
+// kq_mon, kq_wfm, kq_fsk, and the compat surface's context, masters, slaves and FFTW plans, kq_compat.hpp): error reporting,
+// the handle's streams, and whatever the handle owns on the device or for it -- device memory, pinned host memory, events.
+// Each is named once, where it is made; close() lets go of all of it.  Host only; a handle's struct derives from
+// kq::HostSide.  Every member function wants the handle's device current (the entry point's kq::DeviceScope).
+// kq::lazy_device() is for the handles that touch no device before their first set.  What the slot banks (kq_wfm, kq_rds,
+// kq_fsk) share beyond this -- slot table, staging, copy-back, entry-point bodies -- is kq_slots.hpp, on top of this file.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -112,5 +114,22 @@ struct HostSide {
     stream = nullptr;
   }
 };
+
+// The device half of a handle that has none until it is first needed (so that create and the argument checks touch no
+// device): the handle keeps `bool dev_ready` and groups every device pointer it holds, with whatever else names device
+// memory, in one member `d` whose default initialisers are the state without a device.  make(b) opens the stream and
+// allocates; when it fails half way everything made so far goes and `d` is as it was before, so the next call starts
+// over and a handle that is not ready holds nothing.
+template <class Handle, class Make>
+int lazy_device(Handle *b, Make make) {
+  if (b->dev_ready) return 0;
+  if (make(b) == 0) {
+    b->dev_ready = true;
+    return 0;
+  }
+  b->close();
+  b->d = {};
+  return -1;
+}
 
 }  // namespace kq

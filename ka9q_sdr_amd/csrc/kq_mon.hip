@@ -222,33 +222,33 @@ struct kq_mon_bank : kq::HostSide {
   std::vector<MonRec> mem, all;  // members by (bus, slot); every session by slot
   std::vector<MonChunk> chunk;
   std::vector<MonBus> bus;
-  MonRec *d_mem = nullptr, *d_all = nullptr;
-  MonChunk *d_chunk = nullptr;
-  MonBus *d_bus = nullptr;
-  float2 *d_part = nullptr, *d_hist = nullptr;
-  unsigned long long *d_act = nullptr;
-  // host-memory calls
-  std::vector<int> rowmap;
-  int *d_rowmap = nullptr;
-  char *d_stage = nullptr;
-  size_t stage_cap = 0;  // bytes
-  float *d_out = nullptr;
-  size_t out_cap = 0;
-  int16_t *d_pcm = nullptr;
-  size_t pcm_cap = 0;
-  kq_mon_status *d_st = nullptr;
+  struct Dev {  // kq::lazy_device
+    MonRec *mem = nullptr, *all = nullptr;
+    MonChunk *chunk = nullptr;
+    MonBus *bus = nullptr;
+    float2 *part = nullptr, *hist = nullptr;
+    unsigned long long *act = nullptr;
+    kq_mon_status *st = nullptr;
+    // host-memory calls
+    int *rowmap = nullptr;
+    char *stage = nullptr;
+    size_t stage_cap = 0;  // bytes
+    float *out = nullptr;
+    size_t out_cap = 0;
+    int16_t *pcm = nullptr;
+    size_t pcm_cap = 0;
+  } d;
+  std::vector<int> rowmap;  // host-memory calls
 };
 
 namespace {
 
-int mon_device(kq_mon_bank *b) {
-  if (b->dev_ready) return 0;
+int make_device(kq_mon_bank *b) {
   if (b->open_stream(b->cfg.stream)) return -1;
   size_t const S = b->cfg.max_sessions, B = b->cfg.max_buses, C = b->max_chunks;
-  if (b->alloc(&b->d_mem, S) || b->alloc(&b->d_all, S) || b->alloc(&b->d_chunk, C) || b->alloc(&b->d_bus, B) ||
-      b->alloc(&b->d_part, C * kTile) || b->alloc(&b->d_act, C) || b->alloc(&b->d_hist, S * b->H) || b->alloc(&b->d_st, B))
+  if (b->alloc(&b->d.mem, S) || b->alloc(&b->d.all, S) || b->alloc(&b->d.chunk, C) || b->alloc(&b->d.bus, B) ||
+      b->alloc(&b->d.part, C * kTile) || b->alloc(&b->d.act, C) || b->alloc(&b->d.hist, S * b->H) || b->alloc(&b->d.st, B))
     return -1;
-  b->dev_ready = true;
   return 0;
 }
 
@@ -300,10 +300,10 @@ int rebuild(kq_mon_bank *b) {
     if (v.empty()) return hipSuccess;
     return hipMemcpyAsync(dst, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice, b->stream);
   };
-  KQ_TRY(up(b->d_mem, b->mem));
-  KQ_TRY(up(b->d_all, b->all));
-  KQ_TRY(up(b->d_chunk, b->chunk));
-  KQ_TRY(up(b->d_bus, b->bus));
+  KQ_TRY(up(b->d.mem, b->mem));
+  KQ_TRY(up(b->d.all, b->all));
+  KQ_TRY(up(b->d.chunk, b->chunk));
+  KQ_TRY(up(b->d.bus, b->bus));
   KQ_TRY(hipStreamSynchronize(b->stream));
   b->dirty = false;
   return 0;
@@ -478,7 +478,7 @@ int kq_mon_process(kq_mon_bank *b, const void *audio, int format, size_t src_str
     return -1;
   }
   kq::DeviceScope dev_scope_(b->cfg.device);
-  if (mon_device(b)) return -1;
+  if (kq::lazy_device(b, make_device)) return -1;
   if (b->dirty && rebuild(b)) return -1;
   unsigned const B = b->cfg.max_buses, H = b->H;
   size_t const nall = b->all.size(), nchunk = b->chunk.size(), es = format == KQ_MON_S16BE ? 2 : 4;
@@ -486,15 +486,15 @@ int kq_mon_process(kq_mon_bank *b, const void *audio, int format, size_t src_str
   a.format = format;
   a.block_len = block_len;
   a.T = (unsigned)T;
-  a.hist = b->d_hist;
+  a.hist = b->d.hist;
   a.H = H;
   a.h0 = (unsigned)(b->n_cur % H);
   a.n0 = b->n_cur;
-  a.mem = b->d_mem;
-  a.chunk = b->d_chunk;
-  a.bus = b->d_bus;
-  a.part = b->d_part;
-  a.act = b->d_act;
+  a.mem = b->d.mem;
+  a.chunk = b->d.chunk;
+  a.bus = b->d.bus;
+  a.part = b->d.part;
+  a.act = b->d.act;
   if (on_device) {
     a.audio = audio;
     a.src_stride = src_stride;
@@ -516,28 +516,28 @@ int kq_mon_process(kq_mon_bank *b, const void *audio, int format, size_t src_str
       b->rowmap[r.slot] = it->second.first;
     }
     // (grow waits for the stream, which is idle here: the last host-memory call ended in a synchronise)
-    if (b->grow(&b->d_stage, &b->stage_cap, std::max<size_t>(rows.size(), 1) * 2 * b->cfg.max_samples * 4)) return -1;
-    if (!b->d_rowmap && b->alloc(&b->d_rowmap, b->cfg.max_sessions)) return -1;
+    if (b->grow(&b->d.stage, &b->d.stage_cap, std::max<size_t>(rows.size(), 1) * 2 * b->cfg.max_samples * 4)) return -1;
+    if (!b->d.rowmap && b->alloc(&b->d.rowmap, b->cfg.max_sessions)) return -1;
     for (auto const &kv : rows) {
       size_t const w = (size_t)kv.second.second * block_len * es;
-      KQ_TRY(hipMemcpy2DAsync(b->d_stage + (size_t)kv.second.first * 2 * T * es, (size_t)2 * block_len * es,
+      KQ_TRY(hipMemcpy2DAsync(b->d.stage + (size_t)kv.second.first * 2 * T * es, (size_t)2 * block_len * es,
                                (const char *)audio + (size_t)kv.first * src_stride * es, (nblocks > 1 ? row_stride * es : w), w,
                                nblocks, hipMemcpyHostToDevice, b->stream));
     }
-    KQ_TRY(hipMemcpyAsync(b->d_rowmap, b->rowmap.data(), b->rowmap.size() * sizeof(int), hipMemcpyHostToDevice, b->stream));
-    a.audio = b->d_stage;
+    KQ_TRY(hipMemcpyAsync(b->d.rowmap, b->rowmap.data(), b->rowmap.size() * sizeof(int), hipMemcpyHostToDevice, b->stream));
+    a.audio = b->d.stage;
     a.src_stride = 2 * T;
     a.row_stride = (size_t)2 * block_len;
-    a.rowmap = b->d_rowmap;
-    if (out && b->grow(&b->d_out, &b->out_cap, (size_t)B * 2 * T)) return -1;
-    if (pcm && b->grow(&b->d_pcm, &b->pcm_cap, (size_t)B * 2 * T)) return -1;
-    a.out = out ? b->d_out : nullptr;
-    a.pcm = pcm ? b->d_pcm : nullptr;
+    a.rowmap = b->d.rowmap;
+    if (out && b->grow(&b->d.out, &b->d.out_cap, (size_t)B * 2 * T)) return -1;
+    if (pcm && b->grow(&b->d.pcm, &b->d.pcm_cap, (size_t)B * 2 * T)) return -1;
+    a.out = out ? b->d.out : nullptr;
+    a.pcm = pcm ? b->d.pcm : nullptr;
     a.out_stride = a.pcm_stride = 2 * T;
-    a.st = status ? b->d_st : nullptr;
+    a.st = status ? b->d.st : nullptr;
   }
   if (a.st) KQ_TRY(hipMemsetAsync(a.st, 0, B * sizeof(kq_mon_status), b->stream));
-  if (nchunk) KQ_TRY(hipMemsetAsync(b->d_act, 0, nchunk * sizeof(unsigned long long), b->stream));
+  if (nchunk) KQ_TRY(hipMemsetAsync(b->d.act, 0, nchunk * sizeof(unsigned long long), b->stream));
   for (size_t t0 = 0; t0 < T; t0 += kTile) {
     unsigned const tn = (unsigned)std::min<size_t>(kTile, T - t0), nthr = tn <= 64 ? 64 : 256, pieces = (tn + nthr - 1) / nthr;
     if (nchunk) {
@@ -556,17 +556,17 @@ int kq_mon_process(kq_mon_bank *b, const void *audio, int format, size_t src_str
   }
   if (nall) {
     unsigned const cnt = (unsigned)std::min<size_t>(T, H), hs = (unsigned)((b->n_cur + (T - cnt)) % H);
-    hipLaunchKernelGGL(k_mon_hist, dim3((unsigned)nall), dim3(64), 0, b->stream, a, b->d_all, cnt, hs);
+    hipLaunchKernelGGL(k_mon_hist, dim3((unsigned)nall), dim3(64), 0, b->stream, a, b->d.all, cnt, hs);
     KQ_TRY(hipGetLastError());
   }
   if (!on_device) {
     if (out)
-      KQ_TRY(hipMemcpy2DAsync(out, out_stride * sizeof(float), b->d_out, 2 * T * sizeof(float), 2 * T * sizeof(float), B,
+      KQ_TRY(hipMemcpy2DAsync(out, out_stride * sizeof(float), b->d.out, 2 * T * sizeof(float), 2 * T * sizeof(float), B,
                                hipMemcpyDeviceToHost, b->stream));
     if (pcm)
-      KQ_TRY(hipMemcpy2DAsync(pcm, pcm_stride * sizeof(int16_t), b->d_pcm, 2 * T * sizeof(int16_t), 2 * T * sizeof(int16_t), B,
+      KQ_TRY(hipMemcpy2DAsync(pcm, pcm_stride * sizeof(int16_t), b->d.pcm, 2 * T * sizeof(int16_t), 2 * T * sizeof(int16_t), B,
                                hipMemcpyDeviceToHost, b->stream));
-    if (status) KQ_TRY(hipMemcpyAsync(status, b->d_st, B * sizeof(kq_mon_status), hipMemcpyDeviceToHost, b->stream));
+    if (status) KQ_TRY(hipMemcpyAsync(status, b->d.st, B * sizeof(kq_mon_status), hipMemcpyDeviceToHost, b->stream));
     KQ_TRY(hipStreamSynchronize(b->stream));
   }
   b->n_cur += T;  // only once everything is queued: a call that fails leaves the frame index where it was

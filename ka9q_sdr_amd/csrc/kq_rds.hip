@@ -30,6 +30,7 @@
 #include "kq_device.hpp"
 #include "kq_host.hpp"
 #include "kq_ldsfft.hpp"
+#include "kq_slots.hpp"
 #include "kq_window.hpp"
 
 namespace {
@@ -430,24 +431,19 @@ struct kq_rds_bank : kq::HostSide {
   uint64_t n_cur = 0;
   uint64_t last_F0 = 0;                  // the last call's first frame and frame count (kq_rds_pull_baseband)
   int last_F = 0;
-  std::vector<RdsPar> par;
-  std::vector<int> all;                  // active slots, ascending
-  RdsPar *d_par = nullptr;
-  int *d_list = nullptr;
-  int *d_rowmap = nullptr;
-  float *d_x = nullptr;
-  float2 *d_z = nullptr;
-  double *d_sums = nullptr;
-  RdsState *d_state = nullptr;
-  float2 *d_hr = nullptr;
-  // host-memory calls
-  float *d_stage = nullptr;
-  size_t stage_cap = 0;  // floats: source rows x max_samples
-  size_t gmax = 0;       // max_groups(max_samples)
-  kq_rds_group *d_groups = nullptr;
-  uint32_t *d_counts = nullptr;
-  kq_rds_status *d_st = nullptr;
-  std::vector<int> rowmap;
+  size_t gmax = 0;                       // max_groups(max_samples)
+  struct Dev {  // kq::lazy_device
+    kq::SlotTable<RdsPar> slots;
+    float *x = nullptr;
+    float2 *z = nullptr;
+    double *sums = nullptr;
+    RdsState *state = nullptr;
+    float2 *hr = nullptr;
+    // host-memory calls
+    kq_rds_group *groups = nullptr;
+    uint32_t *counts = nullptr;
+    kq_rds_status *st = nullptr;
+  } d;
 };
 
 namespace {
@@ -455,6 +451,7 @@ namespace {
 int make_device(kq_rds_bank *b) {
   kq_rds_config const &c = b->cfg;
   RdsGeom &g = b->g;
+  auto &d = b->d;
   bool okN = false, okR = false;
   g.dN = kq::fft_dim(g.N, &okN);
   g.dNr = kq::fft_dim(g.Nr, &okR);
@@ -469,47 +466,20 @@ int make_device(kq_rds_bank *b) {
     return -1;
   }
   std::vector<float2> hr = design_rds(g.N, g.M, c.kaiser_beta, c.comp_rate);
-  if (b->alloc(&b->d_hr, hr.size()) || b->alloc(&b->d_par, S, true) || b->alloc(&b->d_list, S) || b->alloc(&b->d_rowmap, S) ||
-      b->alloc(&b->d_x, S * g.Rx) || b->alloc(&b->d_z, S * g.Rz) || b->alloc(&b->d_sums, S * g.Fmax * kSums) ||
-      b->alloc(&b->d_state, S, true))
+  if (b->alloc(&d.hr, hr.size()) || d.slots.alloc(*b, S) || b->alloc(&d.x, S * g.Rx) || b->alloc(&d.z, S * g.Rz) ||
+      b->alloc(&d.sums, S * g.Fmax * kSums) || b->alloc(&d.state, S, true))
     return -1;
-  KQ_TRY(hipMemcpyAsync(b->d_hr, hr.data(), hr.size() * sizeof(float2), hipMemcpyHostToDevice, b->stream));
+  KQ_TRY(hipMemcpyAsync(d.hr, hr.data(), hr.size() * sizeof(float2), hipMemcpyHostToDevice, b->stream));
   KQ_TRY(hipStreamSynchronize(b->stream));
-  g.hr = b->d_hr;
-  b->dev_ready = true;
+  g.hr = d.hr;
   return 0;
-}
-
-// at the first set; a failure half way lets go of what was made, so the next set starts over and destroy owes nothing
-int rds_device(kq_rds_bank *b) {
-  if (b->dev_ready) return 0;
-  if (make_device(b) == 0) return 0;
-  b->close();
-  b->d_par = nullptr;
-  b->d_list = b->d_rowmap = nullptr;
-  b->d_x = nullptr;
-  b->d_z = b->d_hr = nullptr;
-  b->d_sums = nullptr;
-  b->d_state = nullptr;
-  return -1;
 }
 
 // zero history, zero tracker and machine (the stream is idle: callers synchronised it)
 int cold_start(kq_rds_bank *b, unsigned s) {
-  KQ_TRY(hipMemsetAsync(b->d_x + (size_t)s * b->g.Rx, 0, b->g.Rx * sizeof(float), b->stream));
-  KQ_TRY(hipMemsetAsync(b->d_z + (size_t)s * b->g.Rz, 0, b->g.Rz * sizeof(float2), b->stream));
-  KQ_TRY(hipMemsetAsync(b->d_state + s, 0, sizeof(RdsState), b->stream));
-  return 0;
-}
-
-int upload(kq_rds_bank *b, unsigned s) {
-  KQ_TRY(hipMemcpyAsync(b->d_par + s, &b->par[s], sizeof(RdsPar), hipMemcpyHostToDevice, b->stream));
-  b->all.clear();
-  for (unsigned k = 0; k < b->cfg.max_slots; k++)
-    if (b->par[k].active) b->all.push_back((int)k);
-  if (!b->all.empty())
-    KQ_TRY(hipMemcpyAsync(b->d_list, b->all.data(), b->all.size() * sizeof(int), hipMemcpyHostToDevice, b->stream));
-  KQ_TRY(hipStreamSynchronize(b->stream));
+  KQ_TRY(hipMemsetAsync(b->d.x + (size_t)s * b->g.Rx, 0, b->g.Rx * sizeof(float), b->stream));
+  KQ_TRY(hipMemsetAsync(b->d.z + (size_t)s * b->g.Rz, 0, b->g.Rz * sizeof(float2), b->stream));
+  KQ_TRY(hipMemsetAsync(b->d.state + s, 0, sizeof(RdsState), b->stream));
   return 0;
 }
 
@@ -593,32 +563,13 @@ kq_rds_bank *kq_rds_create(const kq_rds_config *cfg) {
   g.Rx = cfg->max_samples + L - 1 + (M - 1);
   g.Rz = (size_t)g.Fmax * g.Lr + (size_t)std::ceil(g.spb) + 2;
   b->gmax = max_groups(g.Fc, g.L, cfg->max_samples);
-  b->par.assign(cfg->max_slots, RdsPar{});
   return b;
 }
 
-int kq_rds_destroy(kq_rds_bank *b) {
-  if (!b) {
-    kq_internal_set_error("kq_rds_destroy: null bank");
-    return -1;
-  }
-  if (b->dev_ready) {
-    kq::DeviceScope dev_scope_(b->cfg.device);
-    b->close();
-  }
-  delete b;
-  return 0;
-}
+int kq_rds_destroy(kq_rds_bank *b) { return kq::destroy_bank(b, "kq_rds_destroy"); }
 
 int kq_rds_set(kq_rds_bank *b, unsigned slot, const kq_rds_params *p) {
-  if (slot >= kMaxSlots) {
-    kq_internal_set_error("kq_rds_set: slot %u is beyond any bank (%u slots at most)", slot, kMaxSlots);
-    return -1;
-  }
-  if (!p) {
-    kq_internal_set_error("kq_rds_set: null params");
-    return -1;
-  }
+  if (!kq::set_args_ok("kq_rds_set", slot, p, kMaxSlots)) return -1;
   if (!std::isfinite(p->track_ms) || p->track_ms <= 0) {
     kq_internal_set_error("kq_rds_set: track_ms must be finite and positive");
     return -1;
@@ -632,38 +583,21 @@ int kq_rds_set(kq_rds_bank *b, unsigned slot, const kq_rds_params *p) {
     return -1;
   }
   std::lock_guard<std::mutex> lk(b->mu);
-  if (slot >= b->cfg.max_slots) {
-    kq_internal_set_error("kq_rds_set: slot %u >= max_slots %u", slot, b->cfg.max_slots);
-    return -1;
-  }
+  if (!kq::slot_in_bank("kq_rds_set", slot, b->cfg.max_slots)) return -1;
   kq::DeviceScope dev_scope_(b->cfg.device);
-  if (rds_device(b)) return -1;
+  if (kq::lazy_device(b, make_device)) return -1;
   KQ_TRY(hipStreamSynchronize(b->stream));
   RdsPar np{};
   np.active = 1;
   np.source = p->source;
   np.lose_after = p->lose_after;
   np.alpha = 1.0 - std::exp(-(double)b->g.L / ((double)b->g.Fc * (double)p->track_ms * 1e-3));
-  b->par[slot] = np;
+  b->d.slots.par[slot] = np;
   if (cold_start(b, slot)) return -1;
-  return upload(b, slot);
+  return b->d.slots.upload(*b, slot);
 }
 
-int kq_rds_remove(kq_rds_bank *b, unsigned slot) {
-  if (!b) {
-    kq_internal_set_error("kq_rds_remove: null bank");
-    return -1;
-  }
-  std::lock_guard<std::mutex> lk(b->mu);
-  if (slot >= b->cfg.max_slots || !b->par[slot].active) {
-    kq_internal_set_error("kq_rds_remove: slot %u holds no decoder", slot);
-    return -1;
-  }
-  kq::DeviceScope dev_scope_(b->cfg.device);
-  KQ_TRY(hipStreamSynchronize(b->stream));
-  b->par[slot] = RdsPar{};
-  return upload(b, slot);
-}
+int kq_rds_remove(kq_rds_bank *b, unsigned slot) { return kq::remove_slot(b, slot, "kq_rds_remove"); }
 
 size_t kq_rds_max_groups(const kq_rds_bank *b, size_t nsamples) {
   if (!b) {
@@ -681,16 +615,8 @@ int kq_rds_process(kq_rds_bank *b, const float *comp, size_t src_stride, size_t 
     return -1;
   }
   std::lock_guard<std::mutex> lk(b->mu);
+  if (!kq::blocks_ok("kq_rds_process", b->cfg.max_samples, row_stride, block_len, nblocks)) return -1;
   size_t const ncall = (size_t)block_len * nblocks;
-  if (ncall > b->cfg.max_samples) {
-    kq_internal_set_error("kq_rds_process: nblocks %u x block_len %u = %zu > max_samples %zu", nblocks, block_len, ncall,
-                          b->cfg.max_samples);
-    return -1;
-  }
-  if (nblocks > 1 && row_stride < block_len) {
-    kq_internal_set_error("kq_rds_process: row_stride %zu < block_len %u", row_stride, block_len);
-    return -1;
-  }
   RdsGeom &g = b->g;
   uint64_t const n0 = b->n_cur, n1 = n0 + ncall, F0 = n0 / (uint64_t)g.L;
   int const F = (int)(n1 / (uint64_t)g.L - F0);
@@ -703,27 +629,25 @@ int kq_rds_process(kq_rds_bank *b, const float *comp, size_t src_stride, size_t 
     kq_internal_set_error("kq_rds_process: status_stride %zu < F = %d", status_stride, F);
     return -1;
   }
-  if (ncall == 0) return 0;
-  if (!comp) {
-    kq_internal_set_error("kq_rds_process: null comp");
-    return -1;
-  }
-  if (b->all.empty() || !b->dev_ready) {
+  kq::CallWork const work = kq::call_work(b, "kq_rds_process", ncall, comp, "comp");
+  if (work == kq::CALL_IDLE) {
     b->n_cur = n1;
     b->last_F0 = F0;
     b->last_F = F;
     return F;
   }
+  if (work != kq::CALL_RUN) return work;
   kq::DeviceScope dev_scope_(b->cfg.device);
-  size_t const S = b->cfg.max_slots, nlist = b->all.size();
+  auto &d = b->d;
+  size_t const S = b->cfg.max_slots, nlist = d.slots.all.size();
   CallArgs a{};
   a.g = g;
-  a.par = b->d_par;
-  a.list = b->d_list;
-  a.x = b->d_x;
-  a.z = b->d_z;
-  a.sums = b->d_sums;
-  a.state = b->d_state;
+  a.par = d.slots.d_par;
+  a.list = d.slots.d_list;
+  a.x = d.x;
+  a.z = d.z;
+  a.sums = d.sums;
+  a.state = d.state;
   a.n0 = n0;
   a.F0 = F0;
   a.F = F;
@@ -741,33 +665,21 @@ int kq_rds_process(kq_rds_bank *b, const float *comp, size_t src_stride, size_t 
     a.st = status;
     a.sstride = status_stride;
   } else {
-    // the distinct source rows of the active slots, staged contiguously
-    std::map<unsigned, int> rows;
-    b->rowmap.resize(nlist);
-    for (size_t i = 0; i < nlist; i++) {
-      unsigned const src = b->par[b->all[i]].source;
-      auto it = rows.find(src);
-      if (it == rows.end()) it = rows.emplace(src, (int)rows.size()).first;
-      b->rowmap[i] = it->second;
-    }
-    // (grow waits for the stream, which is idle here: the last host-memory call ended in a synchronise, so it returns at once)
-    if (b->grow(&b->d_stage, &b->stage_cap, rows.size() * b->cfg.max_samples)) return -1;
-    for (auto const &kv : rows)
-      KQ_TRY(hipMemcpy2DAsync(b->d_stage + (size_t)kv.second * ncall, block_len * sizeof(float), comp + (size_t)kv.first * src_stride,
-                               (nblocks > 1 ? row_stride : block_len) * sizeof(float), block_len * sizeof(float), nblocks,
-                               hipMemcpyHostToDevice, b->stream));
-    KQ_TRY(hipMemcpyAsync(b->d_rowmap, b->rowmap.data(), nlist * sizeof(int), hipMemcpyHostToDevice, b->stream));
-    a.comp = b->d_stage;
-    a.src_stride = ncall;
-    a.row_stride = block_len;
-    a.rowmap = b->d_rowmap;
-    if (groups && !b->d_groups && b->alloc(&b->d_groups, S * b->gmax)) return -1;
-    if (counts && !b->d_counts && b->alloc(&b->d_counts, S)) return -1;
-    if (status && !b->d_st && b->alloc(&b->d_st, S * (size_t)g.Fmax)) return -1;
-    a.groups = groups ? b->d_groups : nullptr;
+    kq::Staged in;
+    if (d.slots.stage_rows(*b, comp, sizeof(float), src_stride, row_stride, block_len, nblocks,
+                           b->cfg.max_samples * sizeof(float), &in))
+      return -1;
+    a.comp = static_cast<const float *>(in.src);
+    a.src_stride = in.src_stride;
+    a.row_stride = in.row_stride;
+    a.rowmap = in.rowmap;
+    if (groups && !d.groups && b->alloc(&d.groups, S * b->gmax)) return -1;
+    if (counts && !d.counts && b->alloc(&d.counts, S)) return -1;
+    if (status && !d.st && b->alloc(&d.st, S * (size_t)g.Fmax)) return -1;
+    a.groups = groups ? d.groups : nullptr;
     a.gstride = b->gmax;
-    a.counts = counts ? b->d_counts : nullptr;
-    a.st = status ? b->d_st : nullptr;
+    a.counts = counts ? d.counts : nullptr;
+    a.st = status ? d.st : nullptr;
     a.sstride = g.Fmax;
   }
   {
@@ -785,23 +697,16 @@ int kq_rds_process(kq_rds_bank *b, const float *comp, size_t src_stride, size_t 
   hipLaunchKernelGGL(k_rds_track, dim3((unsigned)((nlist + 63) / 64)), dim3(64), 0, b->stream, a, (int)nlist);
   KQ_TRY(hipGetLastError());
   if (!on_device) {
-    // copy back the rows of the active slots, a run of consecutive slots at a time
-    for (size_t i = 0; i < nlist;) {
-      size_t j = i + 1;
-      while (j < nlist && b->all[j] == b->all[j - 1] + 1) j++;
-      size_t const s0 = (size_t)b->all[i], n = j - i;
-      if (groups && F > 0)
-        KQ_TRY(hipMemcpy2DAsync(groups + s0 * groups_stride, groups_stride * sizeof(kq_rds_group), b->d_groups + s0 * a.gstride,
-                                 a.gstride * sizeof(kq_rds_group), gcall * sizeof(kq_rds_group), n, hipMemcpyDeviceToHost,
-                                 b->stream));
-      if (counts)
-        KQ_TRY(hipMemcpyAsync(counts + s0, b->d_counts + s0, n * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
-      if (status && F > 0)
-        KQ_TRY(hipMemcpy2DAsync(status + s0 * status_stride, status_stride * sizeof(kq_rds_status), b->d_st + s0 * a.sstride,
-                                 a.sstride * sizeof(kq_rds_status), (size_t)F * sizeof(kq_rds_status), n, hipMemcpyDeviceToHost,
-                                 b->stream));
-      i = j;
-    }
+    // the rows of the active slots: groups and status when a frame was completed, the counts always
+    auto back = [&](size_t s0, size_t n) {
+      if (groups && F > 0 && kq::copy_rows_back(*b, groups, groups_stride, d.groups, a.gstride, gcall, sizeof(kq_rds_group), s0, n))
+        return -1;
+      if (counts) KQ_TRY(hipMemcpyAsync(counts + s0, d.counts + s0, n * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
+      if (status && F > 0 && kq::copy_rows_back(*b, status, status_stride, d.st, a.sstride, (size_t)F, sizeof(kq_rds_status), s0, n))
+        return -1;
+      return 0;
+    };
+    if (d.slots.for_runs(back)) return -1;
     KQ_TRY(hipStreamSynchronize(b->stream));
   }
   b->n_cur = n1;  // only once everything is queued: a call that fails leaves the stream index where it was
@@ -820,7 +725,7 @@ int kq_rds_pull_baseband(kq_rds_bank *b, unsigned slot, float *dst_re_im, size_t
     return -1;
   }
   std::lock_guard<std::mutex> lk(b->mu);
-  if (slot >= b->cfg.max_slots || !b->par[slot].active) {
+  if (!b->d.slots.active(slot)) {
     kq_internal_set_error("kq_rds_pull_baseband: slot %u holds no decoder", slot);
     return -1;
   }
@@ -828,7 +733,7 @@ int kq_rds_pull_baseband(kq_rds_bank *b, unsigned slot, float *dst_re_im, size_t
   size_t const n = std::min((size_t)b->last_F * g.Lr, cap_complex);
   if (n == 0) return 0;
   kq::DeviceScope dev_scope_(b->cfg.device);
-  const float2 *zr = b->d_z + (size_t)slot * g.Rz;
+  const float2 *zr = b->d.z + (size_t)slot * g.Rz;
   size_t const p0 = (size_t)((b->last_F0 * (uint64_t)g.Lr) % (uint64_t)g.Rz), first = std::min(n, g.Rz - p0);
   KQ_TRY(hipMemcpyAsync(dst_re_im, zr + p0, first * sizeof(float2), hipMemcpyDeviceToHost, b->stream));
   if (n > first)
@@ -837,17 +742,7 @@ int kq_rds_pull_baseband(kq_rds_bank *b, unsigned slot, float *dst_re_im, size_t
   return (int)n;
 }
 
-int kq_rds_sync(kq_rds_bank *b) {
-  if (!b) {
-    kq_internal_set_error("kq_rds_sync: null bank");
-    return -1;
-  }
-  std::lock_guard<std::mutex> lk(b->mu);
-  if (!b->dev_ready) return 0;
-  kq::DeviceScope dev_scope_(b->cfg.device);
-  KQ_TRY(hipStreamSynchronize(b->stream));
-  return 0;
-}
+int kq_rds_sync(kq_rds_bank *b) { return kq::sync_bank(b, "kq_rds_sync"); }
 
 int kq_rds_reset(kq_rds_bank *b) {
   if (!b) {
@@ -861,7 +756,7 @@ int kq_rds_reset(kq_rds_bank *b) {
   if (!b->dev_ready) return 0;
   kq::DeviceScope dev_scope_(b->cfg.device);
   KQ_TRY(hipStreamSynchronize(b->stream));
-  for (int s : b->all)
+  for (int s : b->d.slots.all)
     if (cold_start(b, (unsigned)s)) return -1;
   KQ_TRY(hipStreamSynchronize(b->stream));
   return 0;

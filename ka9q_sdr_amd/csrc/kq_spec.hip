@@ -388,20 +388,20 @@ struct kq_spec_bank : kq::HostSide {
   std::vector<Group> groups;
   std::vector<int> all;  // active slots, ascending
   int maxB = 0;          // widest row among them
-  // device
-  SpecPar *d_par = nullptr;
-  SpecCnt *d_cnt = nullptr;  // [2][S]: k_spec_rows reads one half and writes the other
-  int cnt_half = 0;          // the half the next k_spec_rows reads
-  int *d_list = nullptr;  // [all | group lists]
-  float2 *xbuf[2] = {nullptr, nullptr};
-  float2 *d_raw = nullptr;     // [max_samples] a host-memory call's samples as they came, whatever their format
+  int cnt_half = 0;      // the half of d.cnt the next k_spec_rows reads
   const float2 *tw = nullptr;  // kq::half_twiddles(kTwLog2): shared, not the bank's to free
+  struct Dev {  // kq::lazy_device (the slots' own memory, `mem`, comes and goes with each slot)
+    SpecPar *par = nullptr;
+    SpecCnt *cnt = nullptr;  // [2][S]: k_spec_rows reads one half and writes the other
+    int *list = nullptr;     // [all | group lists]
+    float2 *xbuf[2] = {nullptr, nullptr};
+    float2 *raw = nullptr;   // [max_samples] a host-memory call's samples as they came, whatever their format
+  } d;
 };
 
 namespace {
 
-int spec_device(kq_spec_bank *b) {
-  if (b->dev_ready) return 0;
+int make_device(kq_spec_bank *b) {
   kq_spec_config const &c = b->cfg;
   if (b->open_stream(c.stream)) return -1;
   size_t const S = c.max_specs, X = kHist + c.max_samples;
@@ -409,11 +409,10 @@ int spec_device(kq_spec_bank *b) {
     kq_internal_set_error("kq_spec: no twiddle table of period 2^%d", kTwLog2);
     return -1;
   }
-  if (b->alloc(&b->d_par, S, true) || b->alloc(&b->d_cnt, 2 * S, true) || b->alloc(&b->d_list, 2 * S) ||
-      b->alloc(&b->xbuf[0], X, true) || b->alloc(&b->xbuf[1], X, true) || b->alloc(&b->d_raw, c.max_samples))
+  if (b->alloc(&b->d.par, S, true) || b->alloc(&b->d.cnt, 2 * S, true) || b->alloc(&b->d.list, 2 * S) ||
+      b->alloc(&b->d.xbuf[0], X, true) || b->alloc(&b->d.xbuf[1], X, true) || b->alloc(&b->d.raw, c.max_samples))
     return -1;
   KQ_TRY(hipStreamSynchronize(b->stream));
-  b->dev_ready = true;
   return 0;
 }
 
@@ -457,14 +456,14 @@ int rebuild_lists(kq_spec_bank *b) {
     g.n = (int)g.slots.size();
     list.insert(list.end(), g.slots.begin(), g.slots.end());
   }
-  if (!list.empty()) KQ_TRY(hipMemcpy(b->d_list, list.data(), list.size() * sizeof(int), hipMemcpyHostToDevice));
+  if (!list.empty()) KQ_TRY(hipMemcpy(b->d.list, list.data(), list.size() * sizeof(int), hipMemcpyHostToDevice));
   return 0;
 }
 
 int upload_slot(kq_spec_bank *b, unsigned s) {
-  KQ_TRY(hipMemcpyAsync(b->d_par + s, &b->par[s], sizeof(SpecPar), hipMemcpyHostToDevice, b->stream));
+  KQ_TRY(hipMemcpyAsync(b->d.par + s, &b->par[s], sizeof(SpecPar), hipMemcpyHostToDevice, b->stream));
   for (int h = 0; h < 2; h++)
-    KQ_TRY(hipMemcpyAsync(b->d_cnt + h * b->cfg.max_specs + s, &b->cnt[s], sizeof(SpecCnt), hipMemcpyHostToDevice, b->stream));
+    KQ_TRY(hipMemcpyAsync(b->d.cnt + h * b->cfg.max_specs + s, &b->cnt[s], sizeof(SpecCnt), hipMemcpyHostToDevice, b->stream));
   KQ_TRY(hipStreamSynchronize(b->stream));
   return 0;
 }
@@ -592,7 +591,7 @@ int kq_spec_set(kq_spec_bank *b, unsigned slot, const kq_spec_params *p) {
   }
   bool okN = false;
   kq::DeviceScope dev_scope_(b->cfg.device);
-  if (spec_device(b)) return -1;
+  if (kq::lazy_device(b, make_device)) return -1;
   FftDim const dN = kq::fft_dim((int)p->fft_size, &okN);
   if (!okN) {
     kq_internal_set_error("kq_spec_set: no transform plan for fft_size %u", p->fft_size);
@@ -704,25 +703,25 @@ int kq_spec_process(kq_spec_bank *b, const void *iq, int format, size_t nsamples
     return -1;
   }
   kq::DeviceScope dev_scope_(b->cfg.device);
-  if (spec_device(b)) return -1;
+  if (kq::lazy_device(b, make_device)) return -1;
   size_t const esize = format == KQ_IQ_CF32 ? 8 : format == KQ_IQ_S16 ? 4 : 2;
   const void *src = iq;
   if (!on_device) {
-    KQ_TRY(hipMemcpyAsync(b->d_raw, iq, nsamples * esize, hipMemcpyHostToDevice, b->stream));
-    src = b->d_raw;
+    KQ_TRY(hipMemcpyAsync(b->d.raw, iq, nsamples * esize, hipMemcpyHostToDevice, b->stream));
+    src = b->d.raw;
   }
   int const nxt = b->cur ^ 1;
   {
     size_t const total = kHist + nsamples;
     unsigned const blocks = (unsigned)std::min<size_t>((total + 255) / 256, 4096);
     hipLaunchKernelGGL(k_spec_ingest, dim3(blocks), dim3(256), 0, b->stream, src, format, b->cfg.gain_factor, nsamples,
-                       (const float2 *)b->xbuf[b->cur], b->nprev, b->xbuf[nxt]);
+                       (const float2 *)b->d.xbuf[b->cur], b->nprev, b->d.xbuf[nxt]);
     KQ_TRY(hipGetLastError());
   }
   uint64_t const n0 = b->n_cur, n1 = n0 + nsamples;
   CallArgs a{};
-  a.par = b->d_par;
-  a.x = b->xbuf[nxt];
+  a.par = b->d.par;
+  a.x = b->d.xbuf[nxt];
   a.n0 = n0;
   a.n1 = n1;
   a.tw = b->tw;
@@ -737,7 +736,7 @@ int kq_spec_process(kq_spec_bank *b, const void *iq, int format, size_t nsamples
       rounds = std::max<int>(rounds, (int)((nf + p.fcap - 1) / p.fcap));
     }
     if (!tiles) continue;
-    a.list = b->d_list + g.off;
+    a.list = b->d.list + g.off;
     size_t const lds = decim_lds_bytes(g.Dz, g.Q);
     kq::ensure_dynamic_lds((const void *)k_spec_decim, lds);
     hipLaunchKernelGGL(k_spec_decim, dim3((unsigned)tiles, (unsigned)g.n), dim3(g.dthreads), lds, b->stream, a);
@@ -754,15 +753,15 @@ int kq_spec_process(kq_spec_bank *b, const void *iq, int format, size_t nsamples
         if (nf > done) fr = std::max<uint64_t>(fr, std::min<uint64_t>(nf - done, p.fcap));
       }
       if (!fr) continue;
-      a.list = b->d_list + g.off;
+      a.list = b->d.list + g.off;
       size_t const lds = (size_t)g.Nf * sizeof(float2);
       kq::ensure_dynamic_lds((const void *)k_spec_frames, lds);
       hipLaunchKernelGGL(k_spec_frames, dim3((unsigned)fr, (unsigned)g.n), dim3(g.fthreads), lds, b->stream, a);
       KQ_TRY(hipGetLastError());
     }
-    a.list = b->d_list;
-    a.cnt_in = b->d_cnt + (size_t)b->cnt_half * b->cfg.max_specs;
-    a.cnt_out = b->d_cnt + (size_t)(b->cnt_half ^ 1) * b->cfg.max_specs;
+    a.list = b->d.list;
+    a.cnt_in = b->d.cnt + (size_t)b->cnt_half * b->cfg.max_specs;
+    a.cnt_out = b->d.cnt + (size_t)(b->cnt_half ^ 1) * b->cfg.max_specs;
     hipLaunchKernelGGL(k_spec_rows, dim3((unsigned)((b->maxB + 255) / 256), (unsigned)b->all.size()), dim3(256), 0, b->stream, a);
     KQ_TRY(hipGetLastError());
     b->cnt_half ^= 1;
@@ -813,7 +812,7 @@ int kq_spec_pull(kq_spec_bank *b, unsigned slot, float *rows, unsigned max_rows,
   }
   c.pulled += n;
   for (int h = 0; h < 2; h++)
-    KQ_TRY(hipMemcpyAsync(b->d_cnt + h * b->cfg.max_specs + slot, &c, sizeof c, hipMemcpyHostToDevice, b->stream));
+    KQ_TRY(hipMemcpyAsync(b->d.cnt + h * b->cfg.max_specs + slot, &c, sizeof c, hipMemcpyHostToDevice, b->stream));
   KQ_TRY(hipStreamSynchronize(b->stream));
   return (int)n;
 }
@@ -867,15 +866,15 @@ int kq_spec_reset(kq_spec_bank *b) {
   kq::DeviceScope dev_scope_(b->cfg.device);
   KQ_TRY(hipStreamSynchronize(b->stream));
   size_t const X = kHist + b->cfg.max_samples;
-  for (auto &p : b->xbuf) KQ_TRY(hipMemsetAsync(p, 0, X * sizeof(float2), b->stream));
+  for (auto &p : b->d.xbuf) KQ_TRY(hipMemsetAsync(p, 0, X * sizeof(float2), b->stream));
   for (int s : b->all) {
     b->par[s].s0 = 0;
     b->cnt[s] = SpecCnt{};
     KQ_TRY(hipMemsetAsync(b->mem[s].acc, 0, (size_t)b->par[s].B * sizeof(float), b->stream));
   }
-  KQ_TRY(hipMemcpyAsync(b->d_par, b->par.data(), b->par.size() * sizeof(SpecPar), hipMemcpyHostToDevice, b->stream));
+  KQ_TRY(hipMemcpyAsync(b->d.par, b->par.data(), b->par.size() * sizeof(SpecPar), hipMemcpyHostToDevice, b->stream));
   for (int h = 0; h < 2; h++)
-    KQ_TRY(hipMemcpyAsync(b->d_cnt + h * b->cfg.max_specs, b->cnt.data(), b->cnt.size() * sizeof(SpecCnt), hipMemcpyHostToDevice,
+    KQ_TRY(hipMemcpyAsync(b->d.cnt + h * b->cfg.max_specs, b->cnt.data(), b->cnt.size() * sizeof(SpecCnt), hipMemcpyHostToDevice,
                             b->stream));
   KQ_TRY(hipStreamSynchronize(b->stream));
   return 0;

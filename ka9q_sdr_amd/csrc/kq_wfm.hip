@@ -29,6 +29,7 @@
 #include "kq_device.hpp"
 #include "kq_host.hpp"
 #include "kq_ldsfft.hpp"
+#include "kq_slots.hpp"
 #include "kq_window.hpp"
 
 namespace {
@@ -315,31 +316,25 @@ struct kq_wfm_bank : kq::HostSide {
   bool dev_ready = false;
   WfmGeom g{};
   uint64_t n_cur = 0;
-  std::vector<WfmPar> par;
-  std::vector<kq_wfm_params> prm;
-  std::vector<int> all;                  // active slots, ascending
-  std::map<float, float2 *> hm;          // one H_m per de-emphasis
-  WfmPar *d_par = nullptr;
-  int *d_list = nullptr;
-  int *d_rowmap = nullptr;
-  float *d_x = nullptr, *d_d = nullptr, *d_sig = nullptr;
-  float4 *d_fst = nullptr;
-  int *d_flag = nullptr;
-  float2 *d_hp = nullptr;
-  // host-memory calls
-  float *d_stage = nullptr;
-  size_t stage_cap = 0;  // floats: source rows x max_samples
-  float *d_out = nullptr;
-  kq_wfm_status *d_st = nullptr;
-  std::vector<int> rowmap;
+  struct Dev {  // kq::lazy_device
+    kq::SlotTable<WfmPar> slots;
+    std::map<float, float2 *> hm;        // one H_m per de-emphasis
+    float *x = nullptr, *diff = nullptr, *sig = nullptr;
+    float4 *fst = nullptr;
+    int *flag = nullptr;
+    float2 *hp = nullptr;
+    // host-memory calls
+    float *out = nullptr;
+    kq_wfm_status *st = nullptr;
+  } d;
 };
 
 namespace {
 
-int wfm_device(kq_wfm_bank *b) {
-  if (b->dev_ready) return 0;
+int make_device(kq_wfm_bank *b) {
   kq_wfm_config const &c = b->cfg;
   WfmGeom &g = b->g;
+  auto &d = b->d;
   bool okN = false, okD = false;
   g.dN = kq::fft_dim(g.N, &okN);
   g.dNdec = kq::fft_dim(g.Ndec, &okD);
@@ -354,33 +349,20 @@ int wfm_device(kq_wfm_bank *b) {
     return -1;
   }
   std::vector<float2> hp = design_pilot(g.N, g.M, c.kaiser_beta, c.comp_rate, c.pilot_bw);
-  if (b->alloc(&b->d_hp, hp.size()) || b->alloc(&b->d_par, S, true) || b->alloc(&b->d_list, S) || b->alloc(&b->d_rowmap, S) ||
-      b->alloc(&b->d_x, S * g.Rx) || b->alloc(&b->d_d, S * g.Rd) || b->alloc(&b->d_fst, S * g.Fmax) ||
-      b->alloc(&b->d_sig, S * g.Fmax) || b->alloc(&b->d_flag, S, true))
+  if (b->alloc(&d.hp, hp.size()) || d.slots.alloc(*b, S) || b->alloc(&d.x, S * g.Rx) || b->alloc(&d.diff, S * g.Rd) ||
+      b->alloc(&d.fst, S * g.Fmax) || b->alloc(&d.sig, S * g.Fmax) || b->alloc(&d.flag, S, true))
     return -1;
-  KQ_TRY(hipMemcpyAsync(b->d_hp, hp.data(), hp.size() * sizeof(float2), hipMemcpyHostToDevice, b->stream));
+  KQ_TRY(hipMemcpyAsync(d.hp, hp.data(), hp.size() * sizeof(float2), hipMemcpyHostToDevice, b->stream));
   KQ_TRY(hipStreamSynchronize(b->stream));
-  g.hp = b->d_hp;
-  b->dev_ready = true;
+  g.hp = d.hp;
   return 0;
 }
 
 // zero history, flag off (the stream is idle: callers synchronised it)
 int cold_start(kq_wfm_bank *b, unsigned s) {
-  KQ_TRY(hipMemsetAsync(b->d_x + (size_t)s * b->g.Rx, 0, b->g.Rx * sizeof(float), b->stream));
-  KQ_TRY(hipMemsetAsync(b->d_d + (size_t)s * b->g.Rd, 0, b->g.Rd * sizeof(float), b->stream));
-  KQ_TRY(hipMemsetAsync(b->d_flag + s, 0, sizeof(int), b->stream));
-  return 0;
-}
-
-int upload(kq_wfm_bank *b, unsigned s) {
-  KQ_TRY(hipMemcpyAsync(b->d_par + s, &b->par[s], sizeof(WfmPar), hipMemcpyHostToDevice, b->stream));
-  b->all.clear();
-  for (unsigned k = 0; k < b->cfg.max_slots; k++)
-    if (b->par[k].active) b->all.push_back((int)k);
-  if (!b->all.empty())
-    KQ_TRY(hipMemcpyAsync(b->d_list, b->all.data(), b->all.size() * sizeof(int), hipMemcpyHostToDevice, b->stream));
-  KQ_TRY(hipStreamSynchronize(b->stream));
+  KQ_TRY(hipMemsetAsync(b->d.x + (size_t)s * b->g.Rx, 0, b->g.Rx * sizeof(float), b->stream));
+  KQ_TRY(hipMemsetAsync(b->d.diff + (size_t)s * b->g.Rd, 0, b->g.Rd * sizeof(float), b->stream));
+  KQ_TRY(hipMemsetAsync(b->d.flag + s, 0, sizeof(int), b->stream));
   return 0;
 }
 
@@ -464,33 +446,13 @@ kq_wfm_bank *kq_wfm_create(const kq_wfm_config *cfg) {
   g.Rx = cfg->max_samples + L - 1 + (M - 1) + g.D;
   g.Rd = (size_t)g.Fmax * L + M - 1;
   g.Fc = (float)Fc;
-  b->par.assign(cfg->max_slots, WfmPar{});
-  b->prm.assign(cfg->max_slots, kq_wfm_params{});
   return b;
 }
 
-int kq_wfm_destroy(kq_wfm_bank *b) {
-  if (!b) {
-    kq_internal_set_error("kq_wfm_destroy: null bank");
-    return -1;
-  }
-  if (b->dev_ready) {
-    kq::DeviceScope dev_scope_(b->cfg.device);
-    b->close();
-  }
-  delete b;
-  return 0;
-}
+int kq_wfm_destroy(kq_wfm_bank *b) { return kq::destroy_bank(b, "kq_wfm_destroy"); }
 
 int kq_wfm_set(kq_wfm_bank *b, unsigned slot, const kq_wfm_params *p) {
-  if (slot >= kMaxSlots) {
-    kq_internal_set_error("kq_wfm_set: slot %u is beyond any bank (%u slots at most)", slot, kMaxSlots);
-    return -1;
-  }
-  if (!p) {
-    kq_internal_set_error("kq_wfm_set: null params");
-    return -1;
-  }
+  if (!kq::set_args_ok("kq_wfm_set", slot, p, kMaxSlots)) return -1;
   if (const char *why = check_params(p)) {
     kq_internal_set_error("kq_wfm_set: %s", why);
     return -1;
@@ -500,20 +462,17 @@ int kq_wfm_set(kq_wfm_bank *b, unsigned slot, const kq_wfm_params *p) {
     return -1;
   }
   std::lock_guard<std::mutex> lk(b->mu);
-  if (slot >= b->cfg.max_slots) {
-    kq_internal_set_error("kq_wfm_set: slot %u >= max_slots %u", slot, b->cfg.max_slots);
-    return -1;
-  }
+  if (!kq::slot_in_bank("kq_wfm_set", slot, b->cfg.max_slots)) return -1;
   kq::DeviceScope dev_scope_(b->cfg.device);
-  if (wfm_device(b)) return -1;
+  if (kq::lazy_device(b, make_device)) return -1;
   KQ_TRY(hipStreamSynchronize(b->stream));
-  auto it = b->hm.find(p->deemph_us);
-  if (it == b->hm.end()) {
+  auto it = b->d.hm.find(p->deemph_us);
+  if (it == b->d.hm.end()) {
     std::vector<float2> h = design_mono(b->g.N, b->g.M, b->cfg.kaiser_beta, b->cfg.comp_rate, p->deemph_us);
     float2 *d = nullptr;
     if (b->alloc(&d, h.size())) return -1;
     KQ_TRY(hipMemcpy(d, h.data(), h.size() * sizeof(float2), hipMemcpyHostToDevice));
-    it = b->hm.emplace(p->deemph_us, d).first;
+    it = b->d.hm.emplace(p->deemph_us, d).first;
   }
   WfmPar np{};
   np.active = 1;
@@ -525,27 +484,12 @@ int kq_wfm_set(kq_wfm_bank *b, unsigned slot, const kq_wfm_params *p) {
   np.min_hz = p->pilot_min_hz;
   np.tol_hz = p->pilot_tol_hz;
   np.hm = it->second;
-  b->par[slot] = np;
-  b->prm[slot] = *p;
+  b->d.slots.par[slot] = np;
   if (cold_start(b, slot)) return -1;
-  return upload(b, slot);
+  return b->d.slots.upload(*b, slot);
 }
 
-int kq_wfm_remove(kq_wfm_bank *b, unsigned slot) {
-  if (!b) {
-    kq_internal_set_error("kq_wfm_remove: null bank");
-    return -1;
-  }
-  std::lock_guard<std::mutex> lk(b->mu);
-  if (slot >= b->cfg.max_slots || !b->par[slot].active) {
-    kq_internal_set_error("kq_wfm_remove: slot %u holds no decoder", slot);
-    return -1;
-  }
-  kq::DeviceScope dev_scope_(b->cfg.device);
-  KQ_TRY(hipStreamSynchronize(b->stream));
-  b->par[slot] = WfmPar{};
-  return upload(b, slot);
-}
+int kq_wfm_remove(kq_wfm_bank *b, unsigned slot) { return kq::remove_slot(b, slot, "kq_wfm_remove"); }
 
 int kq_wfm_process(kq_wfm_bank *b, const float *comp, size_t src_stride, size_t row_stride, unsigned block_len,
                    unsigned nblocks, int on_device, float *out, size_t out_stride, kq_wfm_status *status,
@@ -555,16 +499,8 @@ int kq_wfm_process(kq_wfm_bank *b, const float *comp, size_t src_stride, size_t 
     return -1;
   }
   std::lock_guard<std::mutex> lk(b->mu);
+  if (!kq::blocks_ok("kq_wfm_process", b->cfg.max_samples, row_stride, block_len, nblocks)) return -1;
   size_t const ncall = (size_t)block_len * nblocks;
-  if (ncall > b->cfg.max_samples) {
-    kq_internal_set_error("kq_wfm_process: nblocks %u x block_len %u = %zu > max_samples %zu", nblocks, block_len, ncall,
-                          b->cfg.max_samples);
-    return -1;
-  }
-  if (nblocks > 1 && row_stride < block_len) {
-    kq_internal_set_error("kq_wfm_process: row_stride %zu < block_len %u", row_stride, block_len);
-    return -1;
-  }
   WfmGeom &g = b->g;
   uint64_t const n0 = b->n_cur, n1 = n0 + ncall, F0 = n0 / (uint64_t)g.L;
   int const F = (int)(n1 / (uint64_t)g.L - F0);
@@ -576,26 +512,24 @@ int kq_wfm_process(kq_wfm_bank *b, const float *comp, size_t src_stride, size_t 
     kq_internal_set_error("kq_wfm_process: status_stride %zu < F = %d", status_stride, F);
     return -1;
   }
-  if (ncall == 0) return 0;
-  if (!comp) {
-    kq_internal_set_error("kq_wfm_process: null comp");
-    return -1;
-  }
-  if (b->all.empty() || !b->dev_ready) {
+  kq::CallWork const work = kq::call_work(b, "kq_wfm_process", ncall, comp, "comp");
+  if (work == kq::CALL_IDLE) {
     b->n_cur = n1;
     return F;
   }
+  if (work != kq::CALL_RUN) return work;
   kq::DeviceScope dev_scope_(b->cfg.device);
-  size_t const S = b->cfg.max_slots, nlist = b->all.size();
+  auto &d = b->d;
+  size_t const S = b->cfg.max_slots, nlist = d.slots.all.size();
   CallArgs a{};
   a.g = g;
-  a.par = b->d_par;
-  a.list = b->d_list;
-  a.x = b->d_x;
-  a.d = b->d_d;
-  a.fst = b->d_fst;
-  a.sig = b->d_sig;
-  a.flag = b->d_flag;
+  a.par = d.slots.d_par;
+  a.list = d.slots.d_list;
+  a.x = d.x;
+  a.d = d.diff;
+  a.fst = d.fst;
+  a.sig = d.sig;
+  a.flag = d.flag;
   a.n0 = n0;
   a.F0 = F0;
   a.F = F;
@@ -611,31 +545,19 @@ int kq_wfm_process(kq_wfm_bank *b, const float *comp, size_t src_stride, size_t 
     a.st = status;
     a.sstride = status_stride;
   } else {
-    // the distinct source rows of the active slots, staged contiguously
-    std::map<unsigned, int> rows;
-    b->rowmap.resize(nlist);
-    for (size_t i = 0; i < nlist; i++) {
-      unsigned const src = b->par[b->all[i]].source;
-      auto it = rows.find(src);
-      if (it == rows.end()) it = rows.emplace(src, (int)rows.size()).first;
-      b->rowmap[i] = it->second;
-    }
-    // (grow waits for the stream, which is idle here: the last host-memory call ended in a synchronise, so it returns at once)
-    if (b->grow(&b->d_stage, &b->stage_cap, rows.size() * b->cfg.max_samples)) return -1;
-    for (auto const &kv : rows)
-      KQ_TRY(hipMemcpy2DAsync(b->d_stage + (size_t)kv.second * ncall, block_len * sizeof(float), comp + (size_t)kv.first * src_stride,
-                               (nblocks > 1 ? row_stride : block_len) * sizeof(float), block_len * sizeof(float), nblocks,
-                               hipMemcpyHostToDevice, b->stream));
-    KQ_TRY(hipMemcpyAsync(b->d_rowmap, b->rowmap.data(), nlist * sizeof(int), hipMemcpyHostToDevice, b->stream));
-    a.comp = b->d_stage;
-    a.src_stride = ncall;
-    a.row_stride = block_len;
-    a.rowmap = b->d_rowmap;
-    if (out && !b->d_out && b->alloc(&b->d_out, S * 2 * (size_t)g.Fmax * g.Lo)) return -1;
-    if (status && !b->d_st && b->alloc(&b->d_st, S * (size_t)g.Fmax)) return -1;
-    a.out = out ? b->d_out : nullptr;
+    kq::Staged in;
+    if (d.slots.stage_rows(*b, comp, sizeof(float), src_stride, row_stride, block_len, nblocks,
+                           b->cfg.max_samples * sizeof(float), &in))
+      return -1;
+    a.comp = static_cast<const float *>(in.src);
+    a.src_stride = in.src_stride;
+    a.row_stride = in.row_stride;
+    a.rowmap = in.rowmap;
+    if (out && !d.out && b->alloc(&d.out, S * 2 * (size_t)g.Fmax * g.Lo)) return -1;
+    if (status && !d.st && b->alloc(&d.st, S * (size_t)g.Fmax)) return -1;
+    a.out = out ? d.out : nullptr;
     a.ostride = 2 * (size_t)g.Fmax * g.Lo;
-    a.st = status ? b->d_st : nullptr;
+    a.st = status ? d.st : nullptr;
     a.sstride = g.Fmax;
   }
   {
@@ -655,37 +577,21 @@ int kq_wfm_process(kq_wfm_bank *b, const float *comp, size_t src_stride, size_t 
     KQ_TRY(hipGetLastError());
   }
   if (!on_device) {
-    // copy back the rows of the active slots, a run of consecutive slots at a time
-    for (size_t i = 0; i < nlist && F > 0;) {
-      size_t j = i + 1;
-      while (j < nlist && b->all[j] == b->all[j - 1] + 1) j++;
-      size_t const s0 = (size_t)b->all[i], n = j - i;
-      if (out)
-        KQ_TRY(hipMemcpy2DAsync(out + s0 * out_stride, out_stride * sizeof(float), b->d_out + s0 * a.ostride, a.ostride * sizeof(float),
-                                 (size_t)2 * F * g.Lo * sizeof(float), n, hipMemcpyDeviceToHost, b->stream));
-      if (status)
-        KQ_TRY(hipMemcpy2DAsync(status + s0 * status_stride, status_stride * sizeof(kq_wfm_status), b->d_st + s0 * a.sstride,
-                                 a.sstride * sizeof(kq_wfm_status), (size_t)F * sizeof(kq_wfm_status), n, hipMemcpyDeviceToHost,
-                                 b->stream));
-      i = j;
-    }
+    // the rows of the active slots; with no frame completed there is nothing to copy
+    auto back = [&](size_t s0, size_t n) {
+      if (out && kq::copy_rows_back(*b, out, out_stride, d.out, a.ostride, (size_t)2 * F * g.Lo, sizeof(float), s0, n)) return -1;
+      if (status && kq::copy_rows_back(*b, status, status_stride, d.st, a.sstride, (size_t)F, sizeof(kq_wfm_status), s0, n))
+        return -1;
+      return 0;
+    };
+    if (F > 0 && d.slots.for_runs(back)) return -1;
     KQ_TRY(hipStreamSynchronize(b->stream));
   }
   b->n_cur = n1;  // only once everything is queued: a call that fails leaves the stream index where it was
   return F;
 }
 
-int kq_wfm_sync(kq_wfm_bank *b) {
-  if (!b) {
-    kq_internal_set_error("kq_wfm_sync: null bank");
-    return -1;
-  }
-  std::lock_guard<std::mutex> lk(b->mu);
-  if (!b->dev_ready) return 0;
-  kq::DeviceScope dev_scope_(b->cfg.device);
-  KQ_TRY(hipStreamSynchronize(b->stream));
-  return 0;
-}
+int kq_wfm_sync(kq_wfm_bank *b) { return kq::sync_bank(b, "kq_wfm_sync"); }
 
 int kq_wfm_reset(kq_wfm_bank *b) {
   if (!b) {
@@ -697,7 +603,7 @@ int kq_wfm_reset(kq_wfm_bank *b) {
   if (!b->dev_ready) return 0;
   kq::DeviceScope dev_scope_(b->cfg.device);
   KQ_TRY(hipStreamSynchronize(b->stream));
-  for (int s : b->all)
+  for (int s : b->d.slots.all)
     if (cold_start(b, (unsigned)s)) return -1;
   KQ_TRY(hipStreamSynchronize(b->stream));
   return 0;

@@ -322,3 +322,50 @@ def test_loopback_through_the_receiver(gpu):
         assert [f[0] for f in got] == sent(sent_frames[s]), (s, len(got), _status(st[s]))
     for h in (mod, rx, fsk, twin):
         h.close()
+
+
+@pytest.mark.parametrize("fmt", [kq.KQ_PCM_F32, kq.KQ_PCM_S16BE])
+def test_shared_rows_and_gaps_from_host_equal_device(gpu, fmt):
+    """Slots {0, 1, 3, 6} of 8 on source rows {2, 0, 2, 1}: two slots share a row, the active list has gaps, and the blocks
+    lie in rows wider than a block.  Two host-memory calls (distinct rows staged, status copied back a run of slots at a
+    time) give bit for bit what a twin bank gives from device memory, and leave everything else of the host buffer alone."""
+    Fs, baud, K, wb = 48000, 9600, 21, 16.0
+    S, slots, nb, pad = 8, {0: 2, 1: 0, 3: 2, 6: 1}, 3, 5
+    frames, x = _rows(Fs, baud, 3)
+    bl = x.shape[1] // (2 * nb)
+    n = nb * bl
+    if fmt == kq.KQ_PCM_S16BE:
+        x = fm.quantise(x, 4096.0).astype(">i2").view(np.int16)
+        junk = 0x0080
+    else:
+        junk = np.nan
+    host, twin = (FskBank(Fs, baud, K, S, n, window_bits=wb) for _ in range(2))
+    for b in (host, twin):
+        for s, src in slots.items():
+            b.set(s, fsk_params(source=src, scrambled=src % 2 == 0))
+    sw = STATUS_DTYPE.itemsize
+    for c in range(2):
+        buf = np.full((3, nb, bl + pad), junk, x.dtype)
+        buf[:, :, :bl] = x[:, c * n:(c + 1) * n].reshape(3, nb, bl)
+        st = np.full((S, 2 * sw), 0xFF, np.uint8)            # status_stride 2: every second record is not the bank's
+        assert host.lib.kq_fsk_process(host.h, buf.ctypes.data, fmt, nb * (bl + pad), bl + pad, bl, nb, 0, st.ctypes.data, 2) == 0
+        host.n += n
+        dbuf = torch.from_numpy(buf).cuda()
+        dst = torch.from_numpy(np.full_like(st, 0xFF)).cuda()
+        torch.cuda.synchronize()
+        twin.process_device(dbuf.data_ptr(), nb * (bl + pad), bl + pad, bl, nb, dst.data_ptr(), 2, fmt=fmt)
+        twin.sync()
+        dst = dst.cpu().numpy()
+        hc, tc = host.counts(), twin.counts()
+        for s in range(S):
+            if s in slots:
+                assert np.array_equal(st[s, :sw], dst[s, :sw]) and (st[s, sw:] == 0xFF).all(), (c, s)
+                assert hc[s] == tc[s] and host.frames(s, int(hc[s])) == twin.frames(s, int(tc[s])), (c, s)
+            else:
+                assert (st[s] == 0xFF).all() and hc[s] == 0, (c, s)
+    # every frame sent is there, twice for the shared row
+    for s in slots:
+        assert [f[0] for f in host.frames(s)] == sent(frames[slots[s]]), s
+    assert host.frames(0) == host.frames(3)
+    host.close()
+    twin.close()

@@ -327,3 +327,49 @@ def test_loopback_through_the_receiver(gpu):
     assert len(full) - (k0 == 0) >= 4
     st = RdsStation().feed(recs)
     assert st.ps == "KA9Q FM " and st.pi == 0x54A8 and st.pty == 10 and st.tp == 1
+
+
+def test_shared_rows_and_gaps_from_host_equal_device(gpu):
+    """Slots {0, 1, 3, 6} of 8 on source rows {2, 0, 2, 1}: two slots share a row, the active list has gaps, and the blocks
+    lie in rows wider than a block.  Two host-memory calls (distinct rows staged, planes copied back a run of slots at a
+    time) give bit for bit what a twin bank gives from device memory, and leave everything else of the host buffers alone."""
+    Fc, Dr, L, M = 128000, 8, 512, 513
+    S, slots, nb, bl, pad = 8, {0: 2, 1: 0, 3: 2, 6: 1}, 4, 5000, 100
+    n = nb * bl
+    comp, _ = _rows(Fc, L, 3, seed=5)
+    assert comp.shape[1] >= 2 * n
+    host = _bank(Fc, Dr, L, M, S, n, slots)
+    twin = _bank(Fc, Dr, L, M, S, n, slots)
+    for c in range(2):
+        buf = np.full((3, nb, bl + pad), np.nan, np.float32)
+        buf[:, :, :bl] = comp[:, c * n:(c + 1) * n].reshape(3, nb, bl)
+        F = host.frames(n)
+        cap = host.max_groups(n)
+        gw, sw = 16 * cap, 24 * F                            # bytes of a slot's row that the call writes
+        assert F >= 2
+        g, st = np.full((S, gw + 32), 0xFF, np.uint8), np.full((S, sw + 24), 0xFF, np.uint8)
+        cn = np.full(S, 0xFFFFFFFF, np.uint32)
+        assert host.lib.kq_rds_process(host.h, buf.ctypes.data, nb * (bl + pad), bl + pad, bl, nb, 0, g.ctypes.data,
+                                       g.shape[1] // 16, cn.ctypes.data, st.ctypes.data, st.shape[1] // 24) == F
+        host.n += n
+        dbuf = torch.from_numpy(buf).cuda()
+        dg, dst = torch.from_numpy(np.full_like(g, 0xFF)).cuda(), torch.from_numpy(np.full_like(st, 0xFF)).cuda()
+        dcn = torch.from_numpy(np.full(S, -1, np.int32)).cuda()
+        torch.cuda.synchronize()
+        assert twin.process_device(dbuf.data_ptr(), nb * (bl + pad), bl + pad, bl, nb, dg.data_ptr(), g.shape[1] // 16,
+                                   dcn.data_ptr(), dst.data_ptr(), st.shape[1] // 24) == F
+        twin.sync()
+        dg, dst, dcn = dg.cpu().numpy(), dst.cpu().numpy(), dcn.cpu().numpy().view(np.uint32)
+        for s in range(S):
+            if s in slots:
+                assert cn[s] == dcn[s] and cn[s] <= cap, (c, s)
+                assert np.array_equal(g[s, :gw], dg[s, :gw]) and np.array_equal(st[s, :sw], dst[s, :sw]), (c, s)
+                assert np.array_equal(host.pull_baseband(s), twin.pull_baseband(s)), (c, s)
+                assert st[s, :sw].view(STATUS_DTYPE)["level"].min() > 0, (c, s)
+                assert (g[s, gw:] == 0xFF).all() and (st[s, sw:] == 0xFF).all(), (c, s)
+            else:
+                assert cn[s] == 0xFFFFFFFF and (g[s] == 0xFF).all() and (st[s] == 0xFF).all(), (c, s)
+        # the slots that share row 2 decode the same samples
+        assert np.array_equal(st[0, :sw], st[3, :sw]) and not np.array_equal(st[0, :sw], st[1, :sw])
+    host.close()
+    twin.close()

@@ -224,3 +224,45 @@ def test_loopback_through_the_receiver(gpu, overlap):
         print("loopback %s (overlap %d): tone %.3f, separation %.1f dB, pilot %.2f Hz" % (
             side, overlap, want, sep, np.median(st[s]["pilot_hz"][2:])))
         assert want > 0.8 and sep >= SEP_DB
+
+
+def test_shared_rows_and_gaps_from_host_equal_device(gpu):
+    """Slots {0, 1, 3, 6} of 8 on source rows {2, 0, 2, 1}: two slots share a row, the active list has gaps, and the blocks
+    lie in rows wider than a block.  Two host-memory calls (distinct rows staged, planes copied back a run of slots at a
+    time) give bit for bit what a twin bank gives from device memory, and leave everything else of the host buffers alone."""
+    S, slots, nb, bl, pad = 8, {0: 2, 1: 0, 3: 2, 6: 1}, 3, 1500, 200
+    n = nb * bl
+    comp = _composites(3, 2 * n, seed=31).astype(np.float32)
+    host, twin = (WfmBank(FC, DA, L, M, max_slots=S, max_samples=n) for _ in range(2))
+    for b in (host, twin):
+        for s, src in slots.items():
+            b.set(s, wfm_params(source=src))
+    for c in range(2):
+        buf = np.full((3, nb, bl + pad), np.nan, np.float32)
+        buf[:, :, :bl] = comp[:, c * n:(c + 1) * n].reshape(3, nb, bl)
+        F = host.frames(n)
+        ow, sw = 4 * 2 * (F * L // DA), 16 * F               # bytes of a slot's row that the call writes
+        assert F >= 2
+        out, st = np.full((S, ow + 24), 0xFF, np.uint8), np.full((S, sw + 16), 0xFF, np.uint8)
+        assert host.lib.kq_wfm_process(host.h, buf.ctypes.data, nb * (bl + pad), bl + pad, bl, nb, 0, out.ctypes.data,
+                                       out.shape[1] // 4, st.ctypes.data, st.shape[1] // 16) == F
+        host.n += n
+        dbuf = torch.from_numpy(buf).cuda()
+        dout, dst = torch.from_numpy(np.full_like(out, 0xFF)).cuda(), torch.from_numpy(np.full_like(st, 0xFF)).cuda()
+        torch.cuda.synchronize()
+        assert twin.process_device(dbuf.data_ptr(), nb * (bl + pad), bl + pad, bl, nb, dout.data_ptr(), out.shape[1] // 4,
+                                   dst.data_ptr(), st.shape[1] // 16) == F
+        twin.sync()
+        dout, dst = dout.cpu().numpy(), dst.cpu().numpy()
+        for s in range(S):
+            if s in slots:
+                assert np.array_equal(out[s, :ow], dout[s, :ow]) and np.array_equal(st[s, :sw], dst[s, :sw]), (c, s)
+                audio = out[s, :ow].view(np.float32)
+                assert np.isfinite(audio).all() and audio.any(), (c, s)
+                assert (out[s, ow:] == 0xFF).all() and (st[s, sw:] == 0xFF).all(), (c, s)
+            else:
+                assert (out[s] == 0xFF).all() and (st[s] == 0xFF).all(), (c, s)
+        # the slots that share row 2 decode the same samples
+        assert np.array_equal(out[0, :ow], out[3, :ow]) and not np.array_equal(out[0, :ow], out[1, :ow])
+    host.close()
+    twin.close()

@@ -1,0 +1,239 @@
+// AddressSanitizer / UndefinedBehaviorSanitizer run of kq_slots.hpp and kq::lazy_device (kq_host.hpp) on the CPU, against the
+// device-less stand-in for the HIP runtime (mock/hip/hip_runtime.h): a toy slot bank with the shape of kq_wfm / kq_rds /
+// kq_fsk's host halves.  A set-up that fails at every one of its runtime objects in turn, the staging of a host-memory
+// call, the runs of active slots and the copy-back, and the table's upload.  LeakSanitizer has the last word: whatever a
+// failed set-up or a destroy leaves behind fails the run.
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <string>
+#include <utility>
+
+#include "kq_slots.hpp"
+
+static std::string last_error;
+void kq_internal_set_error(const char *fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  last_error = buf;
+}
+
+static int failures = 0;
+#define CHECK(cond)                                                    \
+  do {                                                                 \
+    if (!(cond)) {                                                     \
+      fprintf(stderr, "%s:%d: CHECK(%s) failed\n", __FILE__, __LINE__, #cond); \
+      failures++;                                                      \
+    }                                                                  \
+  } while (0)
+
+namespace {
+
+constexpr unsigned kMaxSlots = 4096;
+constexpr int kObjects = 7;  // what make_device makes: two streams and five allocations
+
+struct ToyPar {
+  int active;
+  unsigned source;
+  int value;
+};
+
+struct toy_config {
+  int device;
+  unsigned max_slots;
+  size_t max_samples;
+  void *stream;
+};
+
+struct toy_bank : kq::HostSide {
+  toy_config cfg;
+  std::mutex mu;
+  bool dev_ready = false;
+  struct Dev {
+    kq::SlotTable<ToyPar> slots;
+    std::map<int, float *> tables;  // as kq_wfm's responses: device memory named from a container
+    float *ring = nullptr;
+    int *flags = nullptr;
+    hipStream_t side = nullptr;
+  } d;
+};
+
+int make_device(toy_bank *b) {
+  auto &d = b->d;
+  size_t const S = b->cfg.max_slots;
+  if (b->open_stream(b->cfg.stream)) return -1;
+  if (d.slots.alloc(*b, S) || b->alloc(&d.ring, S * 16) || b->new_stream(&d.side) || b->alloc(&d.flags, S, true)) return -1;
+  KQ_TRY(hipStreamSynchronize(b->stream));
+  return 0;
+}
+
+toy_bank *toy_create(unsigned max_slots, size_t max_samples) {
+  toy_bank *b = new toy_bank;
+  b->cfg = toy_config{0, max_slots, max_samples, nullptr};
+  return b;
+}
+
+int toy_set(toy_bank *b, unsigned slot, unsigned source, int value) {
+  if (!kq::set_args_ok("toy_set", slot, &value, kMaxSlots)) return -1;
+  std::lock_guard<std::mutex> lk(b->mu);
+  if (!kq::slot_in_bank("toy_set", slot, b->cfg.max_slots)) return -1;
+  kq::DeviceScope dev_scope_(b->cfg.device);
+  if (kq::lazy_device(b, make_device)) return -1;
+  KQ_TRY(hipStreamSynchronize(b->stream));
+  if (!b->d.tables.count(value)) {
+    float *t = nullptr;
+    if (b->alloc(&t, 4)) return -1;
+    b->d.tables[value] = t;
+  }
+  b->d.slots.par[slot] = ToyPar{1, source, value};
+  return b->d.slots.upload(*b, slot);
+}
+
+bool holds_nothing(const toy_bank *b) {
+  auto const &d = b->d;
+  return !b->dev_ready && b->held.empty() && b->streams.empty() && b->pinned.empty() && b->events.empty() && !b->stream &&
+         d.slots.par.empty() && d.slots.all.empty() && !d.slots.d_par && !d.slots.d_list && !d.slots.d_rowmap && !d.slots.d_stage &&
+         d.slots.stage_cap == 0 && d.tables.empty() && !d.ring && !d.flags && !d.side;
+}
+
+void failed_setup() {
+  for (int k = 1; k <= kObjects; k++) {
+    toy_bank *b = toy_create(8, 64);
+    mock_hip().fail_in = k;
+    CHECK(toy_set(b, 2, 0, 7) == -1);
+    CHECK(mock_hip().fail_in == 0);  // the k-th object was reached
+    CHECK(holds_nothing(b));
+    CHECK(kq::remove_slot(b, 2, "toy_remove") == -1 && last_error == "toy_remove: slot 2 holds no decoder");
+    CHECK(kq::sync_bank(b, "toy_sync") == 0);
+    CHECK(toy_set(b, 2, 0, 7) == 0);  // starts over
+    CHECK(b->dev_ready && b->streams.size() == 2 && b->held.size() == 6 && b->d.slots.active(2) && b->d.slots.all == std::vector<int>{2});
+    if (k & 1) CHECK(kq::remove_slot(b, 2, "toy_remove") == 0);
+    CHECK(kq::destroy_bank(b, "toy_destroy") == 0);
+  }
+  // one that never got its device, destroyed as it is
+  toy_bank *b = toy_create(8, 64);
+  mock_hip().fail_in = 3;
+  CHECK(toy_set(b, 0, 0, 1) == -1 && holds_nothing(b));
+  CHECK(kq::destroy_bank(b, "toy_destroy") == 0);
+  mock_hip().fail_in = kObjects + 1;  // past the set-up: toy_set's own allocation fails, the device half stays
+  b = toy_create(8, 64);
+  CHECK(toy_set(b, 0, 0, 1) == -1 && mock_hip().fail_in == 0);
+  CHECK(b->dev_ready && b->held.size() == 5 && b->d.slots.all.empty());
+  CHECK(toy_set(b, 0, 0, 1) == 0);
+  CHECK(kq::destroy_bank(b, "toy_destroy") == 0);
+}
+
+template <class T>
+void staging_of(toy_bank *b, bool first) {
+  unsigned const block_len = 5, nblocks = 3;
+  size_t const row_stride = 7, src_stride = 24, rows = 6, ncall = block_len * nblocks;
+  std::vector<T> src(rows * src_stride);
+  for (size_t i = 0; i < src.size(); i++) src[i] = (T)(1000 + i);
+  auto &t = b->d.slots;
+  int const mallocs = mock_hip().mallocs, copies2d = mock_hip().copies2d;
+  kq::Staged in{};
+  CHECK(t.stage_rows(*b, src.data(), sizeof(T), src_stride, row_stride, block_len, nblocks, b->cfg.max_samples * 4, &in) == 0);
+  CHECK(mock_hip().mallocs == mallocs + (first ? 1 : 0));  // grow: once, and not again at the same size
+  CHECK(mock_hip().copies2d == copies2d + 3);              // one copy per distinct row
+  CHECK((t.rowmap == std::vector<int>{0, 1, 0, 2}));
+  CHECK(t.stage_cap == 3 * b->cfg.max_samples * 4);
+  CHECK(in.src == t.d_stage && in.src_stride == ncall && in.row_stride == block_len && in.rowmap == t.d_rowmap);
+  for (size_t i = 0; i < 4; i++) CHECK(t.d_rowmap[i] == t.rowmap[i]);
+  unsigned const source_of_row[3] = {5, 2, 0};
+  const T *stage = reinterpret_cast<const T *>(t.d_stage);
+  for (size_t r = 0; r < 3; r++)
+    for (size_t k = 0; k < nblocks; k++)
+      for (size_t j = 0; j < block_len; j++)
+        CHECK(stage[r * ncall + k * block_len + j] == src[source_of_row[r] * src_stride + k * row_stride + j]);
+  // one block: the row stride does not count
+  CHECK(t.stage_rows(*b, src.data(), sizeof(T), src_stride, 0, block_len, 1, b->cfg.max_samples * 4, &in) == 0);
+  for (size_t j = 0; j < block_len; j++) CHECK(stage[2 * block_len + j] == src[0 * src_stride + j]);
+}
+
+std::vector<std::pair<size_t, size_t>> runs_of(const toy_bank *b) {
+  std::vector<std::pair<size_t, size_t>> r;
+  CHECK(b->d.slots.for_runs([&](size_t s0, size_t n) {
+    r.emplace_back(s0, n);
+    return 0;
+  }) == 0);
+  return r;
+}
+
+void table_staging_runs() {
+  using Runs = std::vector<std::pair<size_t, size_t>>;
+  unsigned const S = 8;
+  toy_bank *b = toy_create(S, 15);
+  auto &t = b->d.slots;
+  CHECK(runs_of(b).empty());
+  // set, remove, set on mixed slots: {0, 1, 3, 6} on sources {5, 2, 5, 0}
+  CHECK(toy_set(b, 6, 9, 60) == 0 && toy_set(b, 1, 2, 10) == 0 && toy_set(b, 4, 1, 40) == 0 && toy_set(b, 3, 5, 30) == 0);
+  CHECK(kq::remove_slot(b, 4, "toy_remove") == 0 && kq::remove_slot(b, 6, "toy_remove") == 0);
+  CHECK(toy_set(b, 0, 5, 0) == 0 && toy_set(b, 6, 0, 61) == 0);
+  CHECK((t.all == std::vector<int>{0, 1, 3, 6}));
+  for (size_t i = 0; i < t.all.size(); i++) CHECK(t.d_list[i] == t.all[i]);
+  for (unsigned s = 0; s < S; s++) {
+    CHECK(t.d_par[s].active == t.par[s].active && t.d_par[s].source == t.par[s].source && t.d_par[s].value == t.par[s].value);
+    CHECK(t.active(s) == (s == 0 || s == 1 || s == 3 || s == 6));
+  }
+  CHECK(t.par[6].value == 61 && t.par[6].source == 0 && t.par[4].value == 0 && !t.active(S) && !t.active(kMaxSlots));
+  // the entry points' checks, word for word
+  CHECK(toy_set(b, S, 0, 0) == -1 && last_error == "toy_set: slot 8 >= max_slots 8");
+  CHECK(toy_set(b, kMaxSlots, 0, 0) == -1 && last_error == "toy_set: slot 4096 is beyond any bank (4096 slots at most)");
+  CHECK(!kq::set_args_ok("toy_set", 0, nullptr, kMaxSlots) && last_error == "toy_set: null params");
+  CHECK(kq::remove_slot(b, 4, "toy_remove") == -1 && last_error == "toy_remove: slot 4 holds no decoder");
+  CHECK(kq::remove_slot((toy_bank *)nullptr, 4, "toy_remove") == -1 && last_error == "toy_remove: null bank");
+  CHECK(kq::sync_bank((toy_bank *)nullptr, "toy_sync") == -1 && last_error == "toy_sync: null bank");
+  CHECK(kq::destroy_bank((toy_bank *)nullptr, "toy_destroy") == -1 && last_error == "toy_destroy: null bank");
+  CHECK(!kq::blocks_ok("toy_process", 15, 7, 4, 4) && last_error == "toy_process: nblocks 4 x block_len 4 = 16 > max_samples 15");
+  CHECK(!kq::blocks_ok("toy_process", 15, 4, 5, 3) && last_error == "toy_process: row_stride 4 < block_len 5");
+  CHECK(kq::blocks_ok("toy_process", 15, 0, 15, 1) && kq::blocks_ok("toy_process", 15, 5, 5, 3));
+  CHECK(kq::call_work(b, "toy_process", 0, nullptr, "src") == kq::CALL_EMPTY);
+  CHECK(kq::call_work(b, "toy_process", 15, nullptr, "src") == kq::CALL_FAILED && last_error == "toy_process: null src");
+  CHECK(kq::call_work(b, "toy_process", 15, b, "src") == kq::CALL_RUN);
+
+  staging_of<float>(b, true);
+  staging_of<int16_t>(b, false);
+
+  CHECK((runs_of(b) == Runs{{0, 2}, {3, 1}, {6, 1}}));
+  // copy-back: rows of 4 on the device, rows of 6 on the host, 3 elements of each active row
+  {
+    std::vector<uint16_t> dev(S * 4), host(S * 6, 0xFFFF);
+    for (size_t i = 0; i < dev.size(); i++) dev[i] = (uint16_t)i;
+    uint16_t *d_plane = nullptr;
+    CHECK(b->alloc(&d_plane, dev.size()) == 0);
+    memcpy(d_plane, dev.data(), dev.size() * sizeof(uint16_t));
+    CHECK(t.for_runs([&](size_t s0, size_t n) { return kq::copy_rows_back(*b, host.data(), 6, d_plane, 4, 3, sizeof(uint16_t), s0, n); }) == 0);
+    for (size_t s = 0; s < S; s++)
+      for (size_t j = 0; j < 6; j++) CHECK(host[s * 6 + j] == (t.active((unsigned)s) && j < 3 ? dev[s * 4 + j] : 0xFFFF));
+    // a run that fails ends the walk
+    int calls = 0;
+    CHECK(t.for_runs([&](size_t, size_t) { return ++calls == 2 ? -1 : 0; }) == -1 && calls == 2);
+  }
+  for (unsigned s : {2u, 4u, 5u, 7u}) CHECK(toy_set(b, s, s, 0) == 0);
+  CHECK((runs_of(b) == Runs{{0, 8}}));
+  // the last slot to go: its entry is copied, the (empty) list is not
+  for (unsigned s = 0; s < S - 1; s++) CHECK(kq::remove_slot(b, s, "toy_remove") == 0);
+  CHECK((t.all == std::vector<int>{7}) && t.d_list[0] == 7);
+  int const copies = mock_hip().copies;
+  CHECK(kq::remove_slot(b, 7, "toy_remove") == 0);
+  CHECK(mock_hip().copies == copies + 1 && t.all.empty() && t.d_par[7].active == 0 && t.d_list[0] == 7);
+  CHECK(runs_of(b).empty());
+  CHECK(kq::call_work(b, "toy_process", 15, b, "src") == kq::CALL_IDLE);
+  CHECK(kq::destroy_bank(b, "toy_destroy") == 0);
+}
+
+}  // namespace
+
+int main() {
+  failed_setup();
+  table_staging_runs();
+  if (failures) {
+    fprintf(stderr, "slot banks' host layer: %d checks failed\n", failures);
+    return 1;
+  }
+  printf("slot banks' host layer: ok\n");
+  return 0;
+}
