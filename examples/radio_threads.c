@@ -8,14 +8,16 @@
  *
  * By default the thread is the library's own demod_fm / demod_am / demod_linear (include/ka9q_hip_radio.h).  With
  * --ref FILE the entry point is taken from that shared object instead: oracle/Makefile builds
- * oracle/_ref/libref_am.so from the reference's am.c, compiled where it lies and unmodified against
- * ka9q_hip_compat.h -- the reference's demodulator loop running on this library's create_filter_output /
- * set_filter / execute_filter_output (tests/test_gpu_dropin.py).
+ * oracle/_ref/libref_{am,fm,linear}_dropin.so from the reference's am.c, fm.c and linear.c, compiled where they lie and
+ * unmodified against ka9q_hip_compat.h -- the reference's demodulator loop running on this library's
+ * create_filter_output / set_filter / execute_filter_output and fftwf_* calls (tests/test_gpu_dropin.py,
+ * tests/test_gpu_dropin_ref.py).
  *
  *   gcc -std=gnu11 -O2 -Iinclude examples/radio_threads.c -Lka9q_sdr_amd/lib -lka9q_hip \
  *       -Wl,-rpath,$PWD/ka9q_sdr_amd/lib -rdynamic -ldl -lpthread -lm -o radio_threads
  *   radio_threads am 192000 3840 3841 4 -5000 5000 6 in.cf32 out.bin [--lo HZ] [--ref libref_am.so]
  *              [--stereo] [--isb] [--flat] [--shift HZ] [--hang S] [--recovery DBPS] [--time]
+ *              [--pll] [--square] [--loop-bw HZ] [--status12]
  *
  * --time prints, per block (mean over the run, the first four blocks left out): the host's mix loop, execute_filter_input
  * (upload, N-point transform on the GPU, spectrum back to filter.in->fdomain), the demodulator thread's block (from
@@ -25,6 +27,8 @@
  * out.bin, per block: int32 n, float audio[n], then 8 floats read at the hand-off: bb_power, n0, snr, foffset,
  * pdeviation, agc.gain, plfreq, noise_gain.  (FM sets its status before the hand-off, AM and linear after it:
  * fm.c:92-154 / am.c:76-78 / linear.c:302-309, so for those two the record of block b shows block b-1's bb_power.)
+ * With --status12 four more floats follow the eight, in each record and in the tail: cphase, pll_lock, lock_timer, snr
+ * (linear.c:164-170, 219-223; written before the hand-off, so they belong to the record's own block).
  */
 #define _GNU_SOURCE 1
 #include <complex.h>
@@ -47,6 +51,12 @@ static double now_us(void){
 
 static FILE *Out;
 static sem_t Block_done;
+static int Status12;
+
+static void record_more(struct demod *demod){
+  float const more[4] = { demod->sig.cphase, (float)demod->sig.pll_lock, demod->sig.lock_timer, demod->sig.snr };
+  fwrite(more, sizeof more, 1, Out);
+}
 
 static void record(struct demod *demod, const float *buf, int n){
   int32_t const cnt = n;
@@ -55,6 +65,8 @@ static void record(struct demod *demod, const float *buf, int n){
   fwrite(&cnt, sizeof cnt, 1, Out);
   fwrite(buf, sizeof *buf, (size_t)n, Out);
   fwrite(st, sizeof st, 1, Out);
+  if(Status12)
+    record_more(demod);
   sem_post(&Block_done);
 }
 /* audio.c:82 and audio.c:32 take `size` samples per channel */
@@ -85,8 +97,8 @@ int main(int argc, char **argv){
   int const nblocks = atoi(argv[8]);
   const char *in_path = argv[9], *out_path = argv[10], *ref = NULL;
   double lo = 0, shift = 0;
-  float hang = 0, recovery = 0;
-  int stereo = 0, isb = 0, flat = 0, timing = 0;
+  float hang = 0, recovery = 0, loop_bw = 0;
+  int stereo = 0, isb = 0, flat = 0, timing = 0, pll = 0, square = 0;
   for(int i = 11; i < argc; i++){
     if(!strcmp(argv[i], "--lo") && i + 1 < argc) lo = atof(argv[++i]);
     else if(!strcmp(argv[i], "--ref") && i + 1 < argc) ref = argv[++i];
@@ -97,6 +109,10 @@ int main(int argc, char **argv){
     else if(!strcmp(argv[i], "--isb")) isb = 1;
     else if(!strcmp(argv[i], "--flat")) flat = 1;
     else if(!strcmp(argv[i], "--time")) timing = 1;
+    else if(!strcmp(argv[i], "--pll")) pll = 1;
+    else if(!strcmp(argv[i], "--square")) square = 1;
+    else if(!strcmp(argv[i], "--loop-bw") && i + 1 < argc) loop_bw = (float)atof(argv[++i]);
+    else if(!strcmp(argv[i], "--status12")) Status12 = 1;
     else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
   }
   void *(*entry)(void *) = !strcmp(mode, "fm") ? demod_fm : !strcmp(mode, "am") ? demod_am : demod_linear;
@@ -124,6 +140,9 @@ int main(int argc, char **argv){
   demod->filter.kaiser_beta = 3.0f;
   demod->filter.isb = isb;
   demod->opt.flat = flat;
+  demod->opt.pll = pll;
+  demod->opt.square = square;
+  demod->opt.loop_bw = loop_bw;           /* linear.c:26 sets it to 1 itself */
   demod->agc.headroom = powf(10.f, -15.f / 20.f);   /* main.c:117 */
   demod->agc.hangtime = hang;
   demod->agc.recovery_rate = recovery;
@@ -193,6 +212,8 @@ int main(int argc, char **argv){
                         demod->agc.gain, demod->sig.plfreq, NAN };
   fwrite(&tail, sizeof tail, 1, Out);
   fwrite(st, sizeof st, 1, Out);
+  if(Status12)
+    record_more(demod);
   fclose(Out);
   if(rc == 0 && demod->filter.out != NULL){
     fprintf(stderr, "the thread left demod->filter.out set\n");

@@ -30,7 +30,13 @@ extern "C" {
 #define FFTW_FORWARD (-1)
 #define FFTW_BACKWARD (+1)
 #define FFTW_ESTIMATE (1U << 6)
+/* fftw3.h's own rule: where <complex.h> came first, fftwf_complex IS the C99 type -- which fm.c:56,208,227 and
+ * linear.c:90-92 rely on (`complex float *x = fftwf_alloc_complex(n)`); otherwise two floats.  The layout is the same. */
+#if !defined(FFTW_NO_Complex) && defined(_Complex_I) && defined(complex) && defined(I)
+typedef float _Complex fftwf_complex;
+#else
 typedef float fftwf_complex[2];
+#endif
 typedef struct kq_fftwf_plan_s *fftwf_plan;
 #endif
 

@@ -242,6 +242,7 @@ int kqo_afsk_frame(const kqo_afsk *a, int i, unsigned char *dst, int cap);
 const float complex *kqo_afsk_filter_output(const kqo_afsk *a);
 void kqo_afsk_state(const kqo_afsk *a, int *symphase, int *frame_bit, int *flagsync, int *ones, float *last_val,
                     float *mid_val);
+int kqo_afsk_max_frame_bit(const kqo_afsk *a);   /* running maximum of frame_bit since creation */
 
 /* PCM output stage (audio.c:22-28, 45-50, 95-100): float -> clipped int16, network byte order, in chunks of at
  * most 480 words; bit i of *silent_mask is set when chunk i is all zero (the reference then skips the packet but

@@ -69,9 +69,9 @@ def build(force=False):
     stale = force or not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs)
     if stale:
         subprocess.check_call(["make", "-C", _HERE, "libkq_oracle.so"], stdout=subprocess.DEVNULL)
-    ref_so = os.path.join(_HERE, "_ref", "libref_osc.so")
-    ref_dec = os.path.join(_HERE, "_ref", "libref_ax25.so")
-    if os.path.exists("/root/reference/osc.c") and (force or not os.path.exists(ref_so) or not os.path.exists(ref_dec)):
+    ref_all = [os.path.join(_HERE, "_ref", n) for n in ("libref_osc.so", "libref_ax25.so", "libref_fm_dropin.so",
+                                                         "libref_linear_dropin.so", "libref_packet_dropin.so")]
+    if os.path.exists("/root/reference/osc.c") and (force or not all(os.path.exists(p) for p in ref_all)):
         subprocess.check_call(["make", "-C", _HERE, "ref"], stdout=subprocess.DEVNULL)
     return so
 
@@ -144,6 +144,7 @@ def lib():
     L.kqo_afsk_filter_output.argtypes = [C.c_void_p]
     L.kqo_afsk_filter_output.restype = C.c_void_p
     L.kqo_afsk_state.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 4 + [fp, fp]
+    L.kqo_afsk_max_frame_bit.argtypes = [C.c_void_p]
     L.kqo_hb15_init.argtypes = [C.POINTER(Hb15State)]
     L.kqo_hb15_block.argtypes = [C.POINTER(Hb15State), fp, fp, C.c_int]
     L.kqo_hb3_block.argtypes = [fp, fp, fp, C.c_int]
@@ -418,6 +419,10 @@ class Afsk:
         self.L.kqo_afsk_state(self.h, *[C.byref(v) for v in i], *[C.byref(v) for v in f])
         return dict(symphase=i[0].value, frame_bit=i[1].value, flagsync=i[2].value, ones=i[3].value,
                     last_val=f[0].value, mid_val=f[1].value)
+
+    def max_frame_bit(self):
+        """the largest frame_bit the deframer has held so far (packet.c:403 indexes hdlc_frame[1024] with it, unbounded)"""
+        return self.L.kqo_afsk_max_frame_bit(self.h)
 
 
 def notch_run(f, bw, x):

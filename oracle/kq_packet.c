@@ -35,6 +35,7 @@ struct kqo_afsk {
   float last_val, mid_val;
   unsigned char hdlc_frame[KQO_AFSK_FRAME_MAX];
   int frame_bit, flagsync, ones;
+  int max_frame_bit;           /* running maximum of frame_bit: how near a stream came to the end of hdlc_frame[] */
   int decoded_packets;
   /* decoded frames, back to back */
   unsigned char *frames;
@@ -128,6 +129,8 @@ static void decode_block(kqo_afsk *a){
         if(a->flagsync)
           a->frame_bit++;
       }
+      if(a->frame_bit > a->max_frame_bit)
+        a->max_frame_bit = a->frame_bit;
       a->ones = 0;
     } else {
       /* NRZI one */
@@ -141,6 +144,8 @@ static void decode_block(kqo_afsk *a){
         if(a->frame_bit >= 0 && a->frame_bit < 8 * KQO_AFSK_FRAME_MAX)
           a->hdlc_frame[a->frame_bit / 8] |= 1 << (a->frame_bit % 8);
         a->frame_bit++;
+        if(a->frame_bit > a->max_frame_bit)
+          a->max_frame_bit = a->frame_bit;
       }
     }
     a->last_val = cur_val;
@@ -187,3 +192,4 @@ void kqo_afsk_state(const kqo_afsk *a, int *symphase, int *frame_bit, int *flags
   *symphase = a->symphase; *frame_bit = a->frame_bit; *flagsync = a->flagsync; *ones = a->ones;
   *last_val = a->last_val; *mid_val = a->mid_val;
 }
+int kqo_afsk_max_frame_bit(const kqo_afsk *a){ return a->max_frame_bit; }

@@ -164,6 +164,27 @@ def test_headers_are_valid_c():
         assert r.returncode == 0, r.stderr
 
 
+def test_fftw_header_follows_fftw3s_complex_rule():
+    """fftw3.h makes fftwf_complex the C99 `float _Complex` where <complex.h> was included first, two floats otherwise.  The
+    reference relies on the first form (`complex float *x = fftwf_alloc_complex(n)` at fm.c:56,208,227, plans over such
+    pointers at fm.c:228 and linear.c:92): both forms must compile without a pointer-type diagnostic."""
+    import subprocess
+    import tempfile
+    inc = os.path.join(ROOT, "include")
+    for body in ('#include <complex.h>\n#include "ka9q_hip_fftw.h"\n#undef I\n'
+                 'int f(void){ complex float *a = fftwf_alloc_complex(8), *b = fftwf_alloc_complex(8); float *r = fftwf_alloc_real(8);\n'
+                 '  fftwf_plan p = fftwf_plan_dft_r2c_1d(8, r, a, FFTW_ESTIMATE), q = fftwf_plan_dft_1d(8, a, b, FFTW_FORWARD, FFTW_ESTIMATE);\n'
+                 '  fftwf_execute(p); fftwf_destroy_plan(p); fftwf_destroy_plan(q); fftwf_free(a); fftwf_free(b); fftwf_free(r);\n'
+                 '  return sizeof(fftwf_complex) == 2 * sizeof(float) ? 0 : 1; }\n',
+                 '#include "ka9q_hip_fftw.h"\nint f(void){ float (*a)[2] = fftwf_alloc_complex(8); a[0][1] = 0; fftwf_free(a); return 0; }\n'):
+        with tempfile.NamedTemporaryFile("w", suffix=".c", delete=False) as t:
+            t.write(body)
+        r = subprocess.run(["gcc", "-std=gnu11", "-Wall", "-Werror", "-Werror=incompatible-pointer-types", "-I", inc,
+                            "-fsyntax-only", t.name], capture_output=True, text=True)
+        os.unlink(t.name)
+        assert r.returncode == 0, r.stderr
+
+
 def test_c_example_builds_against_the_library():
     """examples/radio_bank.c compiles and links against libka9q_hip.so with gcc (running it needs the GPU)."""
     import subprocess

@@ -39,10 +39,10 @@ def harness(gpu):
     os.unlink(exe)
 
 
-def _signal(kind, seed, geom=None):
+def _signal(kind, seed, geom=None, nb=NB):
     rng = np.random.default_rng(seed)
     fs_, l_ = (geom or (FS, L, M, D))[:2]
-    n = NB * l_
+    n = nb * l_
     t = np.arange(n) / fs_
     fc = 20000.0
     if kind == "am":
@@ -56,13 +56,24 @@ def _signal(kind, seed, geom=None):
     return s.astype(np.complex64)
 
 
-def _run(exe, mode, iq, low, high, extra=(), geom=None):
+STATUS8 = ("bb_power", "n0", "snr", "foffset", "pdeviation", "gain", "plfreq", "noise_gain")
+# what --status12 appends (radio_threads.c); "snr12" is sig.snr again, the same field read at the same moment as "snr"
+STATUS12 = STATUS8 + ("cphase", "pll_lock", "lock_timer", "snr12")
+
+
+def _run(exe, mode, iq, low, high, extra=(), geom=None, nb=NB, timeout=300):
+    """-> (records of the first nb blocks, tail).  _run.last_rc is the child's exit status (negative: a signal), None
+    while it runs or after a timeout."""
     fs_, l_, m_, d_ = geom or (FS, L, M, D)
+    names = STATUS12 if "--status12" in extra else STATUS8
+    ns = len(names)
+    _run.last_rc = None
     with tempfile.TemporaryDirectory() as d:
         fin, fout = os.path.join(d, "in.cf32"), os.path.join(d, "out.bin")
         iq.tofile(fin)
-        cmd = [exe, mode, str(fs_), str(l_), str(m_), str(d_), str(low), str(high), str(NB), fin, fout, "--lo", "-20000"]
-        r = subprocess.run(cmd + list(extra), capture_output=True, text=True, timeout=300)
+        cmd = [exe, mode, str(fs_), str(l_), str(m_), str(d_), str(low), str(high), str(nb), fin, fout, "--lo", "-20000"]
+        r = subprocess.run(cmd + list(extra), capture_output=True, text=True, timeout=timeout)
+        _run.last_rc = r.returncode
         assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout + r.stderr
         blob = open(fout, "rb").read()
     recs, pos, tail = [], 0, None
@@ -70,21 +81,24 @@ def _run(exe, mode, iq, low, high, extra=(), geom=None):
         (n,) = struct.unpack_from("<i", blob, pos)
         pos += 4
         if n < 0:
-            tail = np.frombuffer(blob, np.float32, 8, pos)
+            tail = np.frombuffer(blob, np.float32, ns, pos)
             break
         audio = np.frombuffer(blob, np.float32, n, pos)
         pos += 4 * n
-        st = np.frombuffer(blob, np.float32, 8, pos)
-        pos += 32
-        recs.append((audio, dict(zip(("bb_power", "n0", "snr", "foffset", "pdeviation", "gain", "plfreq", "noise_gain"), st))))
-    assert tail is not None and len(recs) >= NB      # the thread may hand over one more (zero) block while it winds down
-    return recs[:NB], tail
+        st = np.frombuffer(blob, np.float32, ns, pos)
+        pos += 4 * ns
+        recs.append((audio, dict(zip(names, st))))
+    assert tail is not None and len(recs) >= nb      # the thread may hand over one more (zero) block while it winds down
+    return recs[:nb], tail
 
 
-def _oracle(p, iq, geom=None):
+_run.last_rc = None
+
+
+def _oracle(p, iq, geom=None, nb=NB, want_filt=False):
     fs_, l_, m_, d_ = geom or (FS, L, M, D)
     cfg = oracle_cfg(p, fs_, l_, m_, d_, compute_n0=1)
-    return ko.run_chain(cfg, iq.reshape(NB, l_), want_filt=False)
+    return ko.run_chain(cfg, iq.reshape(nb, l_), want_filt=want_filt)
 
 
 AM = dict(demod="am", low=-5000.0, high=5000.0, second_lo=-20000.0, hangtime=0.0, recovery_rate=50.0)

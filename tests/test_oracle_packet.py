@@ -105,3 +105,16 @@ def test_pcm_ingest_keeps_the_unsigned_quirk():
     a.push(np.zeros(2000, np.float32))
     b.push(np.zeros(2000, np.float32))
     assert a.frames() == b.frames()
+
+
+def test_running_maximum_of_frame_bit():
+    """packet.c:403 indexes hdlc_frame[1024] with frame_bit and no bound; the oracle keeps the largest value it has held so
+    that a test can show an input stays far from 8192 before the reference itself is run on it."""
+    d = ko.Afsk()
+    assert d.max_frame_bit() == 0
+    d.push(afsk_audio(afsk_bits([FRAME_B, FRAME_A])))
+    d.push(np.zeros(2000, np.float32))
+    assert d.frames() == [FRAME_B + ax25_fcs(FRAME_B), FRAME_A + ax25_fcs(FRAME_A)]
+    # the closing flag's 0111111 is counted before packet.c:340 takes it off again
+    assert d.max_frame_bit() == 8 * (len(FRAME_B) + 2) + 7
+    assert d.state()["frame_bit"] <= d.max_frame_bit()
