@@ -1128,6 +1128,92 @@ int kq_fsk_sync(kq_fsk_bank *bank);
 /* Stream index back to 0; every slot restarts cold with its settings */
 int kq_fsk_reset(kq_fsk_bank *bank);
 
+/* --- rational resampler bank ----------------------------------------------------------------------------------------------
+ * Up to 65536 slots, each one row of PCM (mono or stereo) resampled from Fi = in_rate_num / in_rate_den Hz (a receiver
+ * bank's samprate and decimate, so 39 062.5 Hz is exact) to Fo = out_rate Hz: kq_afsk_*, RTP PCM and the players are 48 kHz,
+ * kq_mon_* wants one rate on a bus, kq_fsk_* 4 to 40 samples per bit, and a receiver channel runs at samprate / decimate.  A
+ * receiver bank's audio plane (kq_bank_audio_device_ptr) is resampled on its stream after kq_bank_join(bank); the outputs
+ * can go on to kq_afsk_push (session_stride = out_stride, on_device = 1), kq_mon_process (one block of J) and
+ * kq_fsk_process without leaving the device.  The reference has no resampler (its front ends are multiples of 48 kHz): the
+ * algorithm is defined here.
+ *   rates      P / Q = Fo in_rate_den / in_rate_num in lowest terms.
+ *   indices    n counts input samples since create or kq_rsmp_reset, j outputs; both are 64-bit and lie on one grid shared
+ *              by every slot.  x[n] = 0 before a slot was set.  A KQ_PCM_S16BE word w (network byte order, two's
+ *              complement) is SCALE * (short)ntohs(w) as a float product, SCALE = 1.f / SHRT_MAX, as kq_mon_* reads it.
+ *   prototype  K = P T taps (T = taps per phase) at rate P Fi, in double: h[m] = sinc(2 cutoff_hz / (P Fi) (m - (K - 1) / 2))
+ *              w[m], w = make_kaiser(K, kaiser_beta) (filter.c:337-357), scaled to sum h = P.  g[phi][k] = (float)h[k P + phi]
+ *              (kq_rsmp_get_taps).
+ *   output j   n_j = floor(j Q / P), phi_j = (j Q) mod P in 64-bit integers; y[j] is the fold acc = fmaf(g[phi_j][k],
+ *              x[n_j - k], acc) from 0.0f for k = 0, 1, ..., T - 1 in that order.  This order is part of the contract: it
+ *              makes the bits independent of how the stream is cut into calls, blocks and tiles.  A stereo slot filters
+ *              its L and R sides separately and writes them interleaved.
+ *   delay      the group delay is (K - 1) / (2 P) input samples (kq_rsmp_info::delay_in_samples).
+ *   per call   a call that brings the input samples [n0, n0 + S) produces the outputs with n0 <= n_j < n0 + S: J = ceil((n0 +
+ *              S) P / Q) - ceil(n0 P / Q) of them, the same for every slot, known without the device, possibly 0.  The last
+ *              T - 1 samples of every slot and side are carried across calls, so a call may bring fewer than T, or one.
+ *   pcm        the call's own out through scaleclip (audio.c:22-28: >= 1 gives SHRT_MAX, <= -1 SHRT_MIN, else truncation of
+ *              SHRT_MAX x; NaN gives 0) in network byte order.
+ * NaN and infinity propagate as the float arithmetic gives them: one bad input sample reaches T outputs and no more.
+ * Transition band: about 2 Fi sqrt(1 + kaiser_beta^2) / T wide, the window's main lobe (as for kq_wfm_*); a design with no
+ * aliasing has cutoff_hz = min(Fi, Fo) / 2 minus half of that.  This is not enforced.
+ * Limits (refused with -1 / NULL and the reason in kq_last_error, before any HIP call): 8000 <= Fi, Fo <= 384000; 1/16 <= P / Q
+ * <= 16; P <= 4096; 4 <= taps <= 256; P taps <= 2^18; 0 < cutoff_hz < min(Fi, Fo) / 2; kaiser_beta finite and >= 0; max_slots
+ * 1..65536; max_samples 1..2^28; channels 1 or 2; kq_rsmp_remove of an empty slot; nblocks block_len > max_samples; nblocks > 1
+ * with a block (2 block_len elements where a stereo slot is set) longer than row_stride; out_stride or pcm_stride below c J
+ * (c = 2 where a stereo slot is set, else 1); J beyond INT_MAX; an unknown format.
+ * Device memory: 16 (taps - 1) + 24 bytes per slot of max_slots (the carried samples of both sides, two copies, and the
+ * slot's record) and 4 P taps of coefficients; host-memory calls add their staging buffers.
+ * Calls: kq_rsmp_create, kq_rsmp_set and kq_rsmp_remove touch no device; they and kq_rsmp_reset take effect at the first sample
+ * of the next kq_rsmp_process, which makes the device half and uploads the slot table when it changed.  A newly set slot
+ * starts with zero history on the shared grid, not on a grid of its own.  kq_rsmp_process with device memory is asynchronous
+ * on the handle's stream and reads nothing back; with host memory it is synchronous.  A call with no slot set only moves n
+ * and j.  One lock per handle. */
+typedef struct kq_rsmp_bank kq_rsmp_bank;
+typedef struct kq_rsmp_config {
+  int device;
+  int in_rate_num;           /* Fi = in_rate_num / in_rate_den Hz: a receiver bank's samprate ... */
+  int in_rate_den;           /* ... and decimate */
+  int out_rate;              /* Fo, Hz */
+  unsigned taps;             /* T: taps per phase */
+  float cutoff_hz;
+  float kaiser_beta;         /* make_kaiser convention */
+  unsigned max_slots;        /* slots 0 .. max_slots - 1 (limit 65536) */
+  size_t max_samples;        /* largest nblocks * block_len of one kq_rsmp_process call */
+  void *stream;              /* hipStream_t, NULL = own stream; kq_bank_stream(bank) puts it beside a receiver bank */
+} kq_rsmp_config;
+typedef struct kq_rsmp_params {
+  unsigned source;           /* input row this slot resamples (a receiver bank's channel index) */
+  int channels;              /* 1: mono, 2: interleaved L, R */
+} kq_rsmp_params;
+typedef struct kq_rsmp_info {
+  uint32_t P, Q, taps;
+  double delay_in_samples;   /* (P taps - 1) / (2 P) */
+  uint64_t next_in, next_out; /* n and j of the next call's first input sample and output */
+} kq_rsmp_info;
+
+kq_rsmp_bank *kq_rsmp_create(const kq_rsmp_config *cfg);
+int kq_rsmp_destroy(kq_rsmp_bank *bank);
+/* Put a resampler in `slot` (or replace the one there): zero history from the next call's first sample */
+int kq_rsmp_set(kq_rsmp_bank *bank, unsigned slot, const kq_rsmp_params *params);
+/* The slot stops from the next call: its rows are no longer written */
+int kq_rsmp_remove(kq_rsmp_bank *bank, unsigned slot);
+/* ceil(nsamples P / Q): the J of a call of nsamples never exceeds it (0 and an error for no bank) */
+size_t kq_rsmp_max_out(const kq_rsmp_bank *bank, size_t nsamples);
+int kq_rsmp_get_info(kq_rsmp_bank *bank, kq_rsmp_info *info);
+/* g[phi][k] as used, row by row (at most cap floats); returns P taps */
+int kq_rsmp_get_taps(const kq_rsmp_bank *bank, float *dst, size_t cap);
+/* Input addressed as in kq_mon_process, in elements of `format` (KQ_PCM_F32 or KQ_PCM_S16BE): block k of row r starts at
+ * src[r src_stride + k row_stride]; a mono slot reads block_len values there, a stereo one 2 block_len interleaved L, R.
+ * Returns J, or -1.  Slot s writes out[s out_stride + c j + side] for the call's j < J, c = its channels (stride in floats),
+ * and pcm[s pcm_stride + c j + side] the same as int16 in network byte order; either may be NULL; nothing is written for an
+ * empty slot.  on_device != 0: every pointer is device memory and the call is asynchronous on the handle's stream. */
+int kq_rsmp_process(kq_rsmp_bank *bank, const void *src, int format, size_t src_stride, size_t row_stride,
+                    unsigned block_len, unsigned nblocks, int on_device, float *out, size_t out_stride, int16_t *pcm,
+                    size_t pcm_stride);
+int kq_rsmp_sync(kq_rsmp_bank *bank);
+/* n and j back to 0; every slot restarts with zero history and its settings */
+int kq_rsmp_reset(kq_rsmp_bank *bank);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,5 @@
-// kq_slots.hpp -- the host half that the slot banks share (kq_wfm, kq_rds, kq_fsk: up to max_slots decoders, each on a source
-// row of the call's input, set and removed one at a time, processed together): the slot table and its device copy, the
+// kq_slots.hpp -- the host half that the slot banks share (kq_wfm, kq_rds, kq_fsk, kq_rsmp: up to max_slots decoders, each on
+// a source row of the call's input, set and removed one at a time, processed together): the slot table and its device copy, the
 // staging of a host-memory call's distinct source rows, the copy-back of the active slots' rows, and the bodies of the entry
 // points that do not differ from bank to bank.  On top of kq::HostSide (kq_host.hpp); host only.  The kernels, their
 // argument blocks and the launches stay with each bank.
@@ -60,21 +60,34 @@ struct SlotTable {
   // synchronise, so it returns at once)
   int stage_rows(HostSide &h, const void *src, size_t esize, size_t src_stride, size_t row_stride, unsigned block_len,
                  unsigned nblocks, size_t cap_bytes_per_row, Staged *out) {
-    size_t const ncall = (size_t)block_len * nblocks;
-    std::map<unsigned, int> rows;
+    return stage_rows(h, src, esize, src_stride, row_stride, block_len, nblocks, cap_bytes_per_row, out, 1u,
+                      [](Par const &) { return 1u; });
+  }
+
+  // The same where a slot reads width(par) <= wmax elements per sample (interleaved sides): a staged block is wmax block_len
+  // elements apart from the next, and of each block of a row what its widest reader takes is copied, no more (the caller's
+  // rows of narrow readers need not be longer than those read).
+  template <class W>
+  int stage_rows(HostSide &h, const void *src, size_t esize, size_t src_stride, size_t row_stride, unsigned block_len,
+                 unsigned nblocks, size_t cap_bytes_per_row, Staged *out, unsigned wmax, W width) {
+    size_t const ncall = (size_t)block_len * nblocks * wmax, blk = (size_t)block_len * wmax;
+    std::map<unsigned, std::pair<int, unsigned>> rows;  // source -> (staged row, elements per sample)
     rowmap.resize(all.size());
     for (size_t i = 0; i < all.size(); i++) {
-      auto const it = rows.emplace(par[all[i]].source, (int)rows.size()).first;
-      rowmap[i] = it->second;
+      Par const &p = par[all[i]];
+      auto const it = rows.emplace(p.source, std::make_pair((int)rows.size(), 1u)).first;
+      it->second.second = std::max(it->second.second, (unsigned)width(p));
+      rowmap[i] = it->second.first;
     }
     if (h.grow(&d_stage, &stage_cap, rows.size() * cap_bytes_per_row)) return -1;
-    for (auto const &kv : rows)
-      KQ_TRY(hipMemcpy2DAsync(d_stage + (size_t)kv.second * ncall * esize, block_len * esize,
+    for (auto const &kv : rows) {
+      size_t const w = (size_t)block_len * kv.second.second * esize;
+      KQ_TRY(hipMemcpy2DAsync(d_stage + (size_t)kv.second.first * ncall * esize, blk * esize,
                                static_cast<const char *>(src) + (size_t)kv.first * src_stride * esize,
-                               (nblocks > 1 ? row_stride : block_len) * esize, block_len * esize, nblocks, hipMemcpyHostToDevice,
-                               h.stream));
+                               nblocks > 1 ? row_stride * esize : w, w, nblocks, hipMemcpyHostToDevice, h.stream));
+    }
     KQ_TRY(hipMemcpyAsync(d_rowmap, rowmap.data(), rowmap.size() * sizeof(int), hipMemcpyHostToDevice, h.stream));
-    *out = Staged{d_stage, ncall, block_len, d_rowmap};
+    *out = Staged{d_stage, ncall, blk, d_rowmap};
     return 0;
   }
 
