@@ -375,6 +375,10 @@ int kq_bank_rtp_from_planes(kq_bank *bank, int ch, unsigned blk, const int16_t *
 int kq_bank_output_rtp_state(const kq_bank *bank, int ch, kq_out_rtp_state *out);
 /* Pre-detection filter output (filter.out->output.c, olen complex) before demodulation */
 int kq_bank_pull_filter_output(kq_bank *bank, int ch, unsigned blk, float *dst_re_im, size_t cap_complex);
+/* The PL slave's output of one FM channel-block of the last call (pltask's pl_filter->output.r, fm.c:234,239: PL_L =
+ * floor(olen / 32) floats, what the tone tracker appends to its ring); *n = PL_L.  -1 with a text when the PL measurement is
+ * off (pl_tone_off, or a geometry without a PL slave), the channel is not FM, or cap < PL_L. */
+int kq_bank_pull_pl_samples(kq_bank *bank, int ch, unsigned blk, float *dst, size_t cap, size_t *n);
 /* Master spectrum fdomain[N] of one channel/block (only in KQ_FWD_FULL mode; radio.c:396) */
 int kq_bank_pull_spectrum(kq_bank *bank, int ch, unsigned blk, float *dst_re_im, size_t cap_complex);
 /* Designed responses (filter.out->response, N/D complex; FM audio response N/D/2+1).  The pre-detection response of a

@@ -153,6 +153,7 @@ def load_library():
     L.kq_bank_pull_audio.argtypes = [C.c_void_p, C.c_int, C.c_uint, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.kq_bank_pull_status.argtypes = [C.c_void_p, C.c_int, C.c_uint, C.POINTER(ChanStatus)]
     L.kq_bank_pull_filter_output.argtypes = [C.c_void_p, C.c_int, C.c_uint, C.c_void_p, C.c_size_t]
+    L.kq_bank_pull_pl_samples.argtypes = [C.c_void_p, C.c_int, C.c_uint, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.kq_bank_pull_spectrum.argtypes = [C.c_void_p, C.c_int, C.c_uint, C.c_void_p, C.c_size_t]
     L.kq_bank_get_response.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
     L.kq_bank_get_audio_response.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
@@ -476,6 +477,13 @@ class Bank(Handle):
         buf = np.zeros(self.olen, np.complex64)
         self._chk(self.lib.kq_bank_pull_filter_output(self.h, ch, blk, buf.ctypes.data, buf.size), "kq_bank_pull_filter_output")
         return buf
+
+    def pl_samples(self, ch, blk):
+        """The PL slave's output of an FM channel-block of the last call (olen // 32 floats)"""
+        buf = np.zeros(max(1, self.olen // 32), np.float32)
+        n = C.c_size_t()
+        self._chk(self.lib.kq_bank_pull_pl_samples(self.h, ch, blk, buf.ctypes.data, buf.size, C.byref(n)), "kq_bank_pull_pl_samples")
+        return buf[:n.value].copy()
 
     def arm_spectrum(self, ch):
         buf = np.zeros(self.N, np.complex64)

@@ -613,6 +613,31 @@ int kq_bank_pull_filter_output(kq_bank *b, int ch, unsigned blk, float *dst, siz
   return 0;
 }
 
+int kq_bank_pull_pl_samples(kq_bank *b, int ch, unsigned blk, float *dst, size_t cap, size_t *n) {
+  BankScope dev_scope_(b);
+  if (!valid_ch(b, ch) || !dst || blk >= b->last_blocks) {
+    kq_internal_set_error("bad channel/block");
+    return -1;
+  }
+  if (b->g.pl_n <= 0 || !b->pl.plout) {
+    kq_internal_set_error("no PL samples: the PL measurement is off (pl_tone_off, or N/decimate / 32 is no size with a transform)");
+    return -1;
+  }
+  if (b->chans[ch].cfg.demod_type != KQ_FM_DEMOD) {
+    kq_internal_set_error("no PL samples: channel %d is not an FM channel", ch);
+    return -1;
+  }
+  if (cap < (size_t)b->g.pl_l) {
+    kq_internal_set_error("PL sample buffer too small: %d > %zu", b->g.pl_l, cap);
+    return -1;
+  }
+  if (sync_all(b)) return -1;
+  KQ_TRY(hipMemcpy(dst, b->pl.plout + ((size_t)ch * b->g.max_blocks + blk) * b->g.pl_l, b->g.pl_l * sizeof(float),
+                    hipMemcpyDeviceToHost));
+  if (n) *n = (size_t)b->g.pl_l;
+  return 0;
+}
+
 int kq_bank_pull_spectrum(kq_bank *b, int ch, unsigned blk, float *dst, size_t cap) {
   BankScope dev_scope_(b);
   if (!valid_ch(b, ch) || !dst || cap < (size_t)b->g.N) {

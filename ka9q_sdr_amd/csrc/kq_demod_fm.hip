@@ -328,8 +328,6 @@ __global__ void __launch_bounds__(256) k_fm_audio(Geom g, ChanDev ch, Planes pl,
   if (pl_on) {
     // PL slave: REAL -> REAL, decimate 32 (fm.c:219,234; filter.c:206-208 then c2r of pl_n points)
     int const PN = g.pl_n;
-    int log2pl = 0;
-    while ((1 << log2pl) < PN) log2pl++;
     for (int k = lane; k <= PN / 2; k += nthr) {
       float2 gk = cmul(ch.plresp[k], F[k]);
       if (k == 0 || k == PN / 2) {
@@ -339,10 +337,15 @@ __global__ void __launch_bounds__(256) k_fm_audio(Geom g, ChanDev ch, Planes pl,
       }
       PLB[fft_pos((unsigned)k, g.dPl)] = gk;
     }
-    if (mixed)
+    // by the slave's own plan, not the master's: floor(AN / 32) of an AN with a factor 3, 5 or 7 may be a power of two (270 -> 8,
+    // 1050 -> 32), whose mixed plan has no stages.  TWL is filled for a power-of-two master only (F2 lies there otherwise), so
+    // such a slave takes its few twiddles from the bank's half-circle table in memory
+    if (g.dPl.log2n < 0)
       lds_fft_mixed<+1>(PLB, g.dPl);
+    else if (mixed)
+      lds_fft<+1>(PLB, g.dPl.log2n, tw, g.tw_log2);
     else
-      lds_fft<+1>(PLB, log2pl, TWL, g.log2Ndec);
+      lds_fft<+1>(PLB, g.dPl.log2n, TWL, g.log2Ndec);
     float *po = pl.plout + ((size_t)c * g.max_blocks + b) * g.pl_l;
     for (int n = lane; n < g.pl_l; n += nthr) po[n] = PLB[PN - g.pl_l + n].x;  // filter.c:140
     __syncthreads();

@@ -325,6 +325,14 @@ const float complex *kqo_chan_audio_response(const kqo_chan *c, unsigned *n){
     *n = c->audio_filter->n_dec / 2 + 1;
   return c->audio_filter->response;
 }
+/* the PL slave's output of the block just run (pl_filter->output.r, fm.c:239); NULL where the channel has no PL slave */
+const float *kqo_chan_pl_output(const kqo_chan *c, unsigned *n){
+  if(!c->pl_filter)
+    return NULL;
+  if(n)
+    *n = c->pl_filter->olen;
+  return c->pl_filter->output_r;
+}
 
 /* --- demodulators, one block each --- */
 

@@ -187,6 +187,7 @@ unsigned kqo_chan_olen(const kqo_chan *c);
 float kqo_chan_noise_gain(const kqo_chan *c);
 const float complex *kqo_chan_response(const kqo_chan *c, unsigned *n);
 const float complex *kqo_chan_audio_response(const kqo_chan *c, unsigned *n);
+const float *kqo_chan_pl_output(const kqo_chan *c, unsigned *n);
 
 /* Half-band decimators of the front-end daemons (decimate.c:108-160, decimate.h:4-9) */
 typedef struct {

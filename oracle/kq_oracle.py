@@ -101,6 +101,8 @@ def lib():
     L.kqo_chan_response.restype = C.c_void_p
     L.kqo_chan_audio_response.argtypes = [C.c_void_p, C.POINTER(C.c_uint)]
     L.kqo_chan_audio_response.restype = C.c_void_p
+    L.kqo_chan_pl_output.argtypes = [C.c_void_p, C.POINTER(C.c_uint)]
+    L.kqo_chan_pl_output.restype = C.c_void_p
     L.kqo_chan_set_lo2.argtypes = [C.c_void_p, C.c_double]
     L.kqo_chan_set_mode.argtypes = [C.c_void_p, C.c_void_p]
     L.kqo_chan_set_shift.argtypes = [C.c_void_p, C.c_double]
@@ -301,18 +303,29 @@ class Channel:
     def noise_gain(self):
         return self.L.kqo_chan_noise_gain(self.h)
 
+    def pl_output(self):
+        """the PL slave's output of the block just run (pl_filter->output.r, fm.c:239); None without a PL slave"""
+        n = C.c_uint()
+        p = self.L.kqo_chan_pl_output(self.h, C.byref(n))
+        if not p:
+            return None
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_float)), (n.value,)).copy()
 
-def run_chain(cfg, iq_blocks, want_filt=False):
-    """Run nblocks through one channel; returns (audio list, status list, filt list)."""
+
+def run_chain(cfg, iq_blocks, want_filt=False, want_pl=False):
+    """Run nblocks through one channel; returns (audio list, status list, filt list), with want_pl a fourth list: the PL
+    slave's output of every block."""
     ch = Channel(cfg)
-    auds, sts, filts = [], [], []
+    auds, sts, filts, pls = [], [], [], []
     for blk in iq_blocks:
         a, s, f, _ = ch.block(blk, want_filt=want_filt)
         auds.append(a)
         sts.append(s)
         filts.append(f)
+        if want_pl:
+            pls.append(ch.pl_output())
     ch.close()
-    return auds, sts, filts
+    return (auds, sts, filts, pls) if want_pl else (auds, sts, filts)
 
 
 def fft_c2c(x, sign=-1):

@@ -50,7 +50,10 @@ def lib(gpu):
                                                     (3, 3, 1, 512), (3, 1, 1, 512), (1, 1, 512, 32768), (1, 2, 64, 65536),
                                                     (1, 3, 5, 4800), (1, 1, 5, 4800), (1, 2, 8, 7680), (3, 3, 1, 1920),
                                                     (3, 1, 2, 1920), (1, 1, 25, 24000),
-                                                    (1, 1, 7, 6720), (1, 3, 4, 3584), (3, 3, 1, 896), (1, 2, 14, 23520)]] + [
+                                                    (1, 1, 7, 6720), (1, 3, 4, 3584), (3, 3, 1, 896), (1, 2, 14, 23520),
+                                                    # a master whose first pass is a power of two inside a mixed N (18432 = 256 x 72)
+                                                    # over power-of-two slaves; a mixed master in one LDS block over one (15360 / 15)
+                                                    (1, 1, 9, 9216), (1, 1, 18, 9216), (1, 1, 15, 7680)]] + [
     # L and M apart (filter.c:78: N = L + M - 1 whatever they are): the reference's default -L 3840 -M 4353 in every output type
     # (the history is longer than a block: filter.c:168's memmove overlaps), an impulse response of three blocks, a short one,
     # the FM audio filter of such a geometry (fm.c:64: 640 samples per block, 1409 taps), decimate 1

@@ -1125,11 +1125,12 @@ def test_pl_tone_at_geometries_drawn_at_random(gpu, seed):
     assert np.isnan(tones[0]) and abs(tones[-1] - 100.0) < 0.5, (N, L, M, D, tones[0], tones[-1])
 
 
-@pytest.mark.parametrize("nd,D,k", [(400, 4, 160), (900, 2, 400), (270, 8, 110), (1350, 4, 600), (2000, 2, 900)])
+@pytest.mark.parametrize("nd,D,k", [(400, 4, 160), (900, 2, 400), (270, 8, 110), (1350, 4, 600), (2000, 2, 900),
+                                    (280, 8, 120), (540, 4, 220)])
 def test_pl_tone_where_32_does_not_divide_the_sizes(gpu, nd, D, k):
     """fm.c:201-205 with N/decimate or the block length no multiple of 32: create_filter_output warns and truncates
     (filter.c:103-107,116), the PL slave then resamples by N_dec / PL_N instead of 32 and the reference reads the tone that much
-    off (100 Hz as 104.2 at N/decimate = 400).  The library does what the reference does: tone and peak bin equal to the
+    off (100 Hz as 104.2 at N/decimate = 900).  The library does what the reference does: tone and peak bin equal to the
     oracle's -- whose create_filter_output truncates the same way -- in every block."""
     N, M, L, fs = nd * D, k * D + 1, (nd - k) * D, 48000 * D
     g = dict(samprate=fs, L=L, M=M, D=D)
