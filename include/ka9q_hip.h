@@ -1132,6 +1132,136 @@ int kq_fsk_sync(kq_fsk_bank *bank);
 /* Stream index back to 0; every slot restarts cold with its settings */
 int kq_fsk_reset(kq_fsk_bank *bank);
 
+/* --- POCSAG pager decoder bank -------------------------------------------------------------------------------------------
+ * Up to 4096 decoder slots, each reading POCSAG pages (direct FSK at 512, 1200 or 2400 bit/s on 12.5 / 25 kHz channels;
+ * the amateur DAPNET transmitters use it too) from the discriminator output of one flat FM channel, as kq_fsk_* reads
+ * packet: a receiver bank's audio plane can be decoded in place on its stream after kq_bank_join.  The bit rate is per
+ * bank, as in kq_fsk_*: a channel that carries 512, 1200 and 2400 bit/s traffic is read by three banks on the same plane
+ * and stream.  The reference has no such decoder: the algorithm is defined here.  All integer after the quantiser.
+ * Front end: quantise, low-pass, threshold and bit clock exactly as kq_fsk_* defines them above (the same code), with
+ * K = taps, W = rint(window_bits Fs / baud), Fs = samprate (a double, so that 39 062.5 is exact).  There is no
+ * descrambler and no NRZI: the channel bit c that the bit clock takes goes to the deframer as it is.
+ *   constants  FSC = 0x7CD215D8 (frame sync), IDLE = 0x7A89C197, generator g(x) = x^10 + x^9 + x^8 + x^6 + x^5 + x^3 + 1
+ *              (0x769).  A codeword is 32 bits, sent MSB first: bit 31 flag, bits 30..11 payload, bits 10..1 the BCH check
+ *              over bits 31..11 (bits 31..1 as a polynomial are a multiple of g), bit 0 even parity over the whole word.
+ *              FSC and IDLE are codewords.
+ *   correct    For a 32-bit word x: syn = bits 31..1 of x as a polynomial modulo g (10 bits), par = popcount(x) & 1.  A
+ *              table of 2048 words maps (syn << 1 | par) to the error pattern of weight <= 2 over the 32 bits that gives
+ *              that pair (1 + 32 + 496 patterns, distinct because the extended code has minimum distance 6), every other
+ *              entry to "uncorrectable".  (v, e) = (x xor pattern, its weight); kq_pag_correct is this on the host, from
+ *              the table the device gets.  Every word with three flipped bits is uncorrectable.
+ *   state      sh (32 bits), synced, inv, cnt, pos, miss and the open page; all zero at the set.
+ *   hunting    (synced == 0) per channel bit c: sh = (sh << 1) | c.  If popcount(sh ^ FSC) <= 2: synced = 1, inv = 0; else
+ *              if popcount(~sh ^ FSC) <= 2: synced = 1, inv = 1.  On either: cnt = pos = miss = 0, syncs += 1, batches += 1.
+ *   synced     sh shifts as above and cnt += 1; at cnt == 32 the word x = inv ? ~sh : sh is taken and cnt = 0.
+ *   sync word  (pos == 16) popcount(x ^ FSC) <= 2: batches += 1, miss = 0.  Else sync_missed += 1, miss += 1, and at
+ *              miss == 2 sync is dropped: synced = 0 (inv stays as it is until the next sync), and an open page closes
+ *              with flag LOST.  Then pos = 0.
+ *   codeword   (pos 0..15) x is corrected to (v, e), then pos += 1 (pos_before is pos ahead of that).
+ *              Uncorrectable: words_bad += 1; if a page is open and holds fewer than max_page_words words, bits 30..11 of
+ *              x are appended with error code 3 and the page gets flag BAD; else nothing more.
+ *              Otherwise words_good += 1 (e == 0) or words_fixed += 1 (e = 1, 2), and
+ *                v == IDLE: an open page closes.
+ *                bit 31 of v clear (address): an open page closes; then one opens with ric = ((v >> 13) & 0x3FFFF) << 3 |
+ *                  (pos_before >> 1), function = (v >> 11) & 3, nwords = 0, flags = 0, errors = e.
+ *                bit 31 set (message): with no open page, orphans += 1.  Else, if the page holds fewer than
+ *                  max_page_words, bits 30..11 of v are appended with error code e and errors += e; if it is full it
+ *                  closes with flag FULL at this word, and the word counts in orphans.
+ *   record     each message word as 3 bytes, big-endian: bits 19..0 the payload, bits 21..20 the error code (0, 1, 2, or
+ *              3 for uncorrectable); ric, function, nwords, flags (LOST = 1, FULL = 2, BAD = 4), errors (the sum of e
+ *              over the address and the corrected message words) and end_sample (n of the sample at which the last bit
+ *              of the page's last stored codeword -- the address, or the last word appended -- was taken).
+ *   closing    pages += 1 and the page goes to the slot's arena, or dropped += 1 when that holds max_pages.  A page open
+ *              at the end of a call is carried.
+ * Every sample of a call is consumed in that call, and what is carried is the front end's, the state above and the open
+ * page, so the same stream split differently into calls or blocks -- calls that start inside a 64-sample word, that end
+ * inside a codeword, a batch or a page -- gives the same records and status.
+ * Run lengths: the threshold is the mid level of the last window_bits bits, so a run of equal bits longer than the window
+ * loses it.  Traffic keeps its runs short (21 bits at most in the trains this was tried on, against windows of 20 to 24
+ * bits); the 96 ones of three message words 0xFFFFF in a row cannot be decoded at any window the limits allow.  W <= 1024
+ * leaves at most 25 bits of window at 40 samples per bit: 20 samples per bit or fewer are recommended, and 512 bit/s from a
+ * 48 kHz plane goes through kq_rsmp_*.  cutoff_hz 0.75 baud, pll_shift 3 and window_bits min(24, 1024 baud / Fs - 0.5)
+ * are good choices.
+ * Limits (refused by kq_pag_create / kq_pag_set with the reason in kq_last_error, before any HIP call): those of
+ * kq_fsk_* (4 baud <= Fs <= 40 baud; K odd, 3..127; 2 <= W <= 1024; 0 < cutoff_hz < Fs / 2; kaiser_beta finite and >= 0;
+ * 1 <= pll_shift <= 8; input_scale > 0; max_slots 1..4096; max_samples 1..2^28; sum |hq| <= 65535), max_pages 1..4096,
+ * max_page_words 1..256.
+ * Device memory per slot: 4 (K + W + 61) bytes of q (two copies), 8 (max_samples / 64 + 2) of d, 3 max_page_words of open
+ * page, max_pages (3 max_page_words + 32) of arena and 128 of state and tables; 8 KiB of correction table per bank.
+ * Calls: as kq_fsk_*.  kq_pag_create touches no device; kq_pag_correct never does. */
+#define KQ_PAG_FSC 0x7CD215D8u
+#define KQ_PAG_IDLE 0x7A89C197u
+#define KQ_PAG_LOST 1u
+#define KQ_PAG_FULL 2u
+#define KQ_PAG_BAD 4u
+typedef struct kq_pag_bank kq_pag_bank;
+typedef struct kq_pag_config {
+  int device;
+  double samprate;           /* Fs: input samples per second; a double, so that 39 062.5 is exact */
+  int baud;                  /* 512, 1200 or 2400 */
+  unsigned taps;             /* K: low-pass length (odd) */
+  float cutoff_hz;           /* 0.75 baud is a good choice */
+  float kaiser_beta;         /* make_kaiser convention */
+  float window_bits;         /* threshold window, in bits: W = rint(window_bits Fs / baud) */
+  float input_scale;
+  int pll_shift;
+  unsigned max_slots;        /* slots 0 .. max_slots - 1 (limit 4096) */
+  unsigned max_pages;        /* arena places per slot between kq_pag_clear_pages calls */
+  unsigned max_page_words;   /* message words a page can hold */
+  size_t max_samples;        /* largest nblocks * block_len of one kq_pag_process call */
+  void *stream;              /* hipStream_t, NULL = own stream; kq_bank_stream(bank) puts it beside a receiver bank */
+} kq_pag_config;
+typedef struct kq_pag_params {
+  unsigned source;           /* input row this slot decodes (a receiver bank's channel index) */
+} kq_pag_params;
+typedef struct kq_pag_status {   /* counters since the slot was set */
+  uint32_t bits;
+  uint32_t syncs;            /* times sync was found while hunting */
+  uint32_t batches;          /* sync words accepted, those included */
+  uint32_t sync_missed;
+  uint32_t words_good, words_fixed, words_bad;
+  uint32_t orphans, pages, dropped;
+  int32_t pll_phase;         /* s */
+  int32_t synced;
+  int32_t inverted;          /* inv */
+  uint32_t level;            /* max - min of y over the window at the call's last sample */
+} kq_pag_status;
+typedef struct kq_pag_page_info {
+  uint32_t ric;
+  uint32_t function;
+  uint32_t nwords;
+  uint32_t flags;
+  uint32_t errors;
+  uint32_t reserved;         /* 0 */
+  uint64_t end_sample;
+} kq_pag_page_info;
+
+kq_pag_bank *kq_pag_create(const kq_pag_config *cfg);
+int kq_pag_destroy(kq_pag_bank *bank);
+/* Put a decoder in `slot` (or replace the one there): a cold start at the next call's first sample, its arena empty */
+int kq_pag_set(kq_pag_bank *bank, unsigned slot, const kq_pag_params *params);
+/* The slot stops from the next call; its arena stays readable */
+int kq_pag_remove(kq_pag_bank *bank, unsigned slot);
+/* Input, status and on_device as in kq_fsk_process */
+int kq_pag_process(kq_pag_bank *bank, const void *src, int format, size_t src_stride, size_t row_stride, unsigned block_len,
+                   unsigned nblocks, int on_device, kq_pag_status *status, size_t status_stride);
+/* Pages in every slot's arena, counts[max_slots], in one copy; synchronous */
+int kq_pag_pull_counts(kq_pag_bank *bank, uint32_t *counts);
+/* Copies the words of page `index` of `slot` (3 bytes each, at most cap bytes) and its record (info may be NULL); returns
+ * 3 nwords, or -1 */
+int kq_pag_pull_page(kq_pag_bank *bank, unsigned slot, unsigned index, unsigned char *dst, size_t cap,
+                     kq_pag_page_info *info);
+/* Empties every arena (on the handle's stream); the status counters go on */
+int kq_pag_clear_pages(kq_pag_bank *bank);
+/* hq (at most cap words); returns K */
+int kq_pag_get_taps(const kq_pag_bank *bank, int16_t *dst, size_t cap);
+int kq_pag_sync(kq_pag_bank *bank);
+/* Stream index back to 0; every slot restarts cold with its settings */
+int kq_pag_reset(kq_pag_bank *bank);
+/* Host only: the correction of one received word by the table the device gets.  Returns the number of bits changed (0, 1
+ * or 2) with the codeword in *fixed (may be NULL), or -1 (uncorrectable; *fixed is left alone) */
+int kq_pag_correct(uint32_t word, uint32_t *fixed);
+
 /* --- rational resampler bank ----------------------------------------------------------------------------------------------
  * Up to 65536 slots, each one row of PCM (mono or stereo) resampled from Fi = in_rate_num / in_rate_den Hz (a receiver
  * bank's samprate and decimate, so 39 062.5 Hz is exact) to Fo = out_rate Hz: kq_afsk_*, RTP PCM and the players are 48 kHz,

@@ -38,5 +38,7 @@ from .wfm import STATUS_DTYPE, WfmBank, WfmParams, wfm_params  # noqa: F401,E402
 from .rds import GROUP_DTYPE, RdsBank, RdsParams, RdsStation, rds_params  # noqa: F401,E402  (rds.STATUS_DTYPE: the rds one)
 from .fsk import FskBank, FskParams, fsk_params  # noqa: F401,E402  (fsk.STATUS_DTYPE: the fsk one)
 from .ais import ais_nmea, ais_payload_bits, ais_position  # noqa: F401,E402
+from .pag import PagBank, PagParams, pag_params  # noqa: F401,E402  (pag.STATUS_DTYPE: the pager one)
+from . import pocsag  # noqa: F401,E402
 from .monitor import KQ_MON_F32, KQ_MON_S16BE, MonBank, MonParams, mon_params  # noqa: F401,E402  (monitor.STATUS_DTYPE: the mixer's)
 from .resample import RsmpBank, RsmpParams, rsmp_params  # noqa: F401,E402

@@ -7,9 +7,8 @@
 // per slot: the last HN = K - 1 + W - 1 + 63 values of q (two copies, written in turn: a call reads one and writes the other),
 // the call's d packed 64 samples to a word, FskState, the open frame, the arena of good frames.
 //
-// k_fsk_front  one workgroup per (slot, tile of kTile samples on the grid of 64-sample words): tile and halo quantised into
-//              LDS, the FIR, running max / min over W by doubling (log2 W steps whatever W is), the compare packed with
-//              __ballot: one wave, one word.  The first tile of a slot also writes the q the next call starts from
+// k_fsk_front  kq_fskfront.hpp, shared with kq_pag: quantiser, FIR, threshold, the decisions packed 64 to a word; so is
+//              the step of the bit clock
 // k_fsk_track  one lane per slot: the call's words in order through DPLL, descrambler, NRZI and deframer; frames and status
 //              out.  Serial by nature, as k_rds_track is; the open frame lives in global memory, written a byte at a time
 #include <hip/hip_runtime.h>
@@ -21,20 +20,16 @@
 #include <vector>
 
 #include "ka9q_hip.h"
-#include "kq_design.hpp"
 #include "kq_device.hpp"
+#include "kq_fskfront.hpp"
 #include "kq_host.hpp"
 #include "kq_slots.hpp"
 
 namespace {
 
-constexpr unsigned kMaxSlots = 4096;
-constexpr int kMaxK = 127, kMaxW = 1024;
-constexpr int kTile = 1024;                     // samples per workgroup of k_fsk_front: 16 words
-constexpr int kThreads = 256;
-constexpr int kMaxH = kMaxK - 1 + kMaxW - 1;    // halo
-constexpr int kMaxY = kTile + kMaxW - 1;        // values of y a tile needs
-constexpr int kPer = (kMaxY + kThreads - 1) / kThreads;
+using kq::fskfront::kMaxSlots;
+using kq::fskfront::pll_step;
+using FskGeom = kq::fskfront::Geom;
 
 struct FskPar {  // per slot, written by the host at kq_fsk_set
   int active;
@@ -54,134 +49,22 @@ struct FskState {  // per slot, carried from call to call; all zero when a slot 
   int pad;
 };
 
-struct FskGeom {
-  int K, W, H, HN;               // H = K - 1 + W - 1, HN = H + 63
-  int P, off;                    // 2^P <= W < 2^(P + 1), off = W - 2^P
-  unsigned inc;
-  int pll_shift;
-  float scale;
+struct FskLim {  // the arena's sizes
   int max_frames, mfb;
-  int S;                         // max_slots
-  size_t words;                  // per slot: max_samples / 64 + 2
 };
 
 struct CallArgs {
-  FskGeom g;
-  const FskPar *par;
-  const int *list;               // active slots, ascending
-  const short *taps;             // [K]
-  const short *hist_in;          // [S][HN]: q[n0 - HN .. n0 - 1]
-  short *hist_out;               // [S][HN]: q[n1 - HN .. n1 - 1]
-  unsigned long long *dw;        // [words][S]: word w0 + i of slot s at i S + s
-  unsigned *level;               // [S]
+  kq::fskfront::FrontArgs<FskPar> f;   // the front end's; k_fsk_track reads its geometry, list, dw, level, n0, n1, w0
+  FskLim lim;
   FskState *state;               // [S]
   unsigned char *open;           // [S][mfb]
   unsigned char *frames;         // [S][max_frames][mfb]
   kq_fsk_frame_info *info;       // [S][max_frames]
   unsigned *nframes;             // [S]
-  int64_t n0, n1;                // the call's samples
-  int64_t w0;                    // n0 / 64
-  // input
-  const void *src;
-  int format;
-  size_t src_stride, row_stride;
-  unsigned block_len;
-  const int *rowmap;             // per list entry: the row of `src` (host input, staged) or null (par.source)
   // output
   kq_fsk_status *st;
   size_t sstride;
 };
-
-// q of the call's i-th sample
-__device__ __forceinline__ int load_q(CallArgs const &a, size_t row, size_t i) {
-  size_t const k = i / a.block_len, j = i - k * a.block_len;
-  size_t const idx = row * a.src_stride + k * a.row_stride + j;
-  if (a.format == KQ_PCM_S16BE) {
-    const unsigned char *p = reinterpret_cast<const unsigned char *>(a.src) + 2 * idx;
-    int const w = (int)(short)(unsigned short)(((unsigned)p[0] << 8) | p[1]);
-    return w < -32767 ? -32767 : w;
-  }
-  float const v = rintf(reinterpret_cast<const float *>(a.src)[idx] * a.g.scale);
-  if (!(v == v)) return 0;
-  return (int)fminf(fmaxf(v, -32767.f), 32767.f);
-}
-
-__global__ __launch_bounds__(kThreads) void k_fsk_front(CallArgs a) {
-  __shared__ short q[kTile + kMaxH];
-  __shared__ int mx[kMaxY], mn[kMaxY];
-  __shared__ int ys[kTile];
-  __shared__ int hs[kMaxK + 1];
-  FskGeom const &g = a.g;
-  int const li = blockIdx.y, slot = a.list[li], tid = threadIdx.x;
-  size_t const row = a.rowmap ? (size_t)a.rowmap[li] : (size_t)a.par[slot].source;
-  const short *hin = a.hist_in + (size_t)slot * g.HN;
-  int64_t const t0 = 64 * a.w0 + (int64_t)blockIdx.x * kTile;     // the tile's first sample
-  int64_t const wend = 64 * (((a.n1 - 1) >> 6) + 1);              // the end of the call's last word
-  int const nT = (int)(wend - t0 < kTile ? wend - t0 : kTile);    // whole words
-  int const nq = nT + g.H, ny = nT + g.W - 1;
-  // q[i] = q of sample t0 - H + i: before the call from the carried ones, beyond it (the rest of the last word) zero
-  for (int i = tid; i < nq; i += kThreads) {
-    int64_t const n = t0 - g.H + i;
-    int v = 0;
-    if (n < a.n0) v = hin[g.HN - (int)(a.n0 - n)];
-    else if (n < a.n1) v = load_q(a, row, (size_t)(n - a.n0));
-    q[i] = (short)v;
-  }
-  for (int k = tid; k < g.K; k += kThreads) hs[k] = a.taps[k];
-  if (blockIdx.x == 0) {  // the next call's carried q (the other copy: the tiles of this call still read this one)
-    short *hout = a.hist_out + (size_t)slot * g.HN;
-    int64_t const ncall = a.n1 - a.n0;
-    for (int i = tid; i < g.HN; i += kThreads) {
-      int64_t const n = a.n1 - g.HN + i;
-      hout[i] = n < a.n0 ? hin[i + ncall] : (short)load_q(a, row, (size_t)(n - a.n0));
-    }
-  }
-  __syncthreads();
-  // y of sample t0 - (W - 1) + i
-  for (int i = tid; i < ny; i += kThreads) {
-    int acc = 0;
-    const short *qi = q + i + g.K - 1;
-    for (int k = 0; k < g.K; k++) acc += hs[k] * (int)qi[-k];
-    mx[i] = mn[i] = acc;
-    if (i >= g.W - 1) ys[i - (g.W - 1)] = acc;
-  }
-  __syncthreads();
-  // after step j, mx[i] = max y over the 2^(j + 1) samples ending at i (where that many exist; the others are not read)
-  for (int j = 0; j < g.P; j++) {
-    int const step = 1 << j;
-    int hi[kPer], lo[kPer];
-#pragma unroll
-    for (int t = 0; t < kPer; t++) {
-      int const i = tid + t * kThreads;
-      if (i < ny) {
-        int const b = i >= step ? i - step : i;
-        hi[t] = max(mx[i], mx[b]);
-        lo[t] = min(mn[i], mn[b]);
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int t = 0; t < kPer; t++) {
-      int const i = tid + t * kThreads;
-      if (i < ny) {
-        mx[i] = hi[t];
-        mn[i] = lo[t];
-      }
-    }
-    __syncthreads();
-  }
-  // one wave, one word
-  int const lane = tid & 63, nwords = nT >> 6;
-  for (int w = tid >> 6; w < nwords; w += kThreads / 64) {
-    int const j = 64 * w + lane, i = j + g.W - 1;
-    int64_t const n = t0 + j;
-    long long const top = max(mx[i], mx[i - g.off]), bot = min(mn[i], mn[i - g.off]);
-    bool const d = n < a.n1 && 2 * (long long)ys[j] > top + bot;
-    unsigned long long const word = __ballot(d);
-    if (lane == 0) a.dw[(size_t)((t0 >> 6) + w - a.w0) * g.S + slot] = word;
-    if (n == a.n1 - 1) a.level[slot] = (unsigned)(top - bot);
-  }
-}
 
 struct FrameOut {
   unsigned char *open;
@@ -204,7 +87,7 @@ __device__ __forceinline__ void append(FskState &s, unsigned bit, int mfb, unsig
 }
 
 // one data bit through the deframer (the header's "HDLC")
-__device__ __forceinline__ void push_bit(FskState &s, unsigned b, FskPar const &p, FskGeom const &g, FrameOut &o, int64_t n) {
+__device__ __forceinline__ void push_bit(FskState &s, unsigned b, FskPar const &p, FskLim const &g, FrameOut &o, int64_t n) {
   if (b) {
     if (s.ones < 7) s.ones++;
     if (s.ones == 7) {
@@ -248,18 +131,19 @@ __device__ __forceinline__ void push_bit(FskState &s, unsigned b, FskPar const &
 }
 
 // one lane per slot: the call's samples in order
-__global__ __launch_bounds__(64) void k_fsk_track(CallArgs a, int nlist) {
+__global__ __launch_bounds__(64) void k_fsk_track(CallArgs c, int nlist) {
   int const li = blockIdx.x * blockDim.x + threadIdx.x;
   if (li >= nlist) return;
+  kq::fskfront::FrontArgs<FskPar> const &a = c.f;
   int const slot = a.list[li];
   FskGeom const &g = a.g;
   FskPar const p = a.par[slot];
-  FskState s = a.state[slot];
+  FskState s = c.state[slot];
   FrameOut o;
-  o.open = a.open + (size_t)slot * g.mfb;
-  o.frames = a.frames + (size_t)slot * g.max_frames * g.mfb;
-  o.info = a.info + (size_t)slot * g.max_frames;
-  o.n = a.nframes[slot];
+  o.open = c.open + (size_t)slot * c.lim.mfb;
+  o.frames = c.frames + (size_t)slot * c.lim.max_frames * c.lim.mfb;
+  o.info = c.info + (size_t)slot * c.lim.max_frames;
+  o.n = c.nframes[slot];
   int64_t n = a.n0;
   while (n < a.n1) {
     int const b0 = (int)(n & 63);
@@ -268,29 +152,22 @@ __global__ __launch_bounds__(64) void k_fsk_track(CallArgs a, int nlist) {
     unsigned long long word = a.dw[(size_t)((n >> 6) - a.w0) * g.S + slot] >> b0;
     for (int k = 0; k < cnt; k++, word >>= 1, n++) {
       int const d = (int)(word & 1u);
-      if (d != s.dprev) s.s -= s.s >> g.pll_shift;
-      s.dprev = d;
-      long long const t = (long long)s.s + (long long)g.inc;
-      if (t < 0x80000000LL) {
-        s.s = (int)t;
-        continue;
-      }
-      s.s = (int)(t - 0x100000000LL);
+      if (!pll_step(s.s, s.dprev, d, g)) continue;
       s.bits++;
-      unsigned const c = (unsigned)d;
-      unsigned u = c;
+      unsigned const cb = (unsigned)d;
+      unsigned u = cb;
       if (p.scrambled) {
-        u = c ^ ((s.sr >> 16) & 1u) ^ ((s.sr >> 11) & 1u);
-        s.sr = ((s.sr << 1) | c) & 0x1FFFFu;
+        u = cb ^ ((s.sr >> 16) & 1u) ^ ((s.sr >> 11) & 1u);
+        s.sr = ((s.sr << 1) | cb) & 0x1FFFFu;
       }
       unsigned const b = u == (unsigned)s.uprev;
       s.uprev = (int)u;
-      push_bit(s, b, p, g, o, n);
+      push_bit(s, b, p, c.lim, o, n);
     }
   }
-  a.state[slot] = s;
-  a.nframes[slot] = o.n;
-  if (a.st) {
+  c.state[slot] = s;
+  c.nframes[slot] = o.n;
+  if (c.st) {
     kq_fsk_status r;
     r.bits = s.bits;
     r.frames_good = s.frames_good;
@@ -300,30 +177,8 @@ __global__ __launch_bounds__(64) void k_fsk_track(CallArgs a, int nlist) {
     r.pll_phase = s.s;
     r.in_frame = s.in_frame;
     r.level = a.level[slot];
-    a.st[(size_t)slot * a.sstride] = r;
+    c.st[(size_t)slot * c.sstride] = r;
   }
-}
-
-// hq: the Kaiser-windowed sinc in double, sum 1, times 32768 and rounded
-std::vector<short> design_taps(int K, double cutoff, double Fs, double beta, long *sum_abs) {
-  std::vector<double> h((size_t)K);
-  double const den = kq::i0_double(M_PI * beta), c = 0.5 * (K - 1);
-  double sum = 0;
-  for (int k = 0; k < K; k++) {
-    double const pp = 2.0 * k / (K - 1) - 1.0;  // make_kaiser, filter.c:337-357
-    double const w = kq::i0_double(M_PI * beta * std::sqrt(std::max(0.0, 1.0 - pp * pp))) / den;
-    double const t = 2.0 * cutoff / Fs * (k - c);
-    h[k] = (t == 0.0 ? 1.0 : std::sin(M_PI * t) / (M_PI * t)) * w;
-    sum += h[k];
-  }
-  std::vector<short> hq((size_t)K);
-  *sum_abs = 0;
-  for (int k = 0; k < K; k++) {
-    long const v = std::lrint(h[k] / sum * 32768.0);
-    *sum_abs += std::labs(v);
-    hq[k] = (short)std::max(-32768L, std::min(32767L, v));
-  }
-  return hq;
 }
 
 }  // namespace
@@ -333,15 +188,13 @@ struct kq_fsk_bank : kq::HostSide {
   std::mutex mu;
   bool dev_ready = false;
   FskGeom g{};
+  int max_frames = 0, mfb = 0;
   uint64_t n_cur = 0;
   int turn = 0;                          // the copy of the carried q the next call reads
   std::vector<short> hq;
   struct Dev {  // kq::lazy_device
     kq::SlotTable<FskPar> slots;
-    short *taps = nullptr;
-    short *hist[2] = {nullptr, nullptr};
-    unsigned long long *dw = nullptr;
-    unsigned *level = nullptr;
+    kq::fskfront::FrontDev front;
     FskState *state = nullptr;
     unsigned char *open = nullptr, *frames = nullptr;
     kq_fsk_frame_info *info = nullptr;
@@ -358,22 +211,19 @@ int make_device(kq_fsk_bank *b) {
   auto &d = b->d;
   if (b->open_stream(c.stream)) return -1;
   size_t const S = c.max_slots;
-  if (d.slots.alloc(*b, S) || b->alloc(&d.taps, (size_t)g.K) || b->alloc(&d.hist[0], S * g.HN, true) ||
-      b->alloc(&d.hist[1], S * g.HN, true) || b->alloc(&d.dw, g.words * S) || b->alloc(&d.level, S, true) ||
-      b->alloc(&d.state, S, true) || b->alloc(&d.open, S * g.mfb, true) || b->alloc(&d.frames, S * g.max_frames * g.mfb) ||
-      b->alloc(&d.info, S * g.max_frames) || b->alloc(&d.nframes, S, true))
+  size_t const mf = (size_t)b->max_frames, mfb = (size_t)b->mfb;
+  if (d.slots.alloc(*b, S) || d.front.alloc(*b, g, b->hq) || b->alloc(&d.state, S, true) || b->alloc(&d.open, S * mfb, true) ||
+      b->alloc(&d.frames, S * mf * mfb) || b->alloc(&d.info, S * mf) || b->alloc(&d.nframes, S, true))
     return -1;
-  KQ_TRY(hipMemcpyAsync(d.taps, b->hq.data(), b->hq.size() * sizeof(short), hipMemcpyHostToDevice, b->stream));
   KQ_TRY(hipStreamSynchronize(b->stream));
   return 0;
 }
 
 // zero history, clock, deframer and arena (the stream is idle: callers synchronised it)
 int cold_start(kq_fsk_bank *b, unsigned s) {
-  for (short *h : b->d.hist) KQ_TRY(hipMemsetAsync(h + (size_t)s * b->g.HN, 0, b->g.HN * sizeof(short), b->stream));
+  if (b->d.front.cold_start(*b, b->g, s)) return -1;
   KQ_TRY(hipMemsetAsync(b->d.state + s, 0, sizeof(FskState), b->stream));
   KQ_TRY(hipMemsetAsync(b->d.nframes + s, 0, sizeof(unsigned), b->stream));
-  KQ_TRY(hipMemsetAsync(b->d.level + s, 0, sizeof(unsigned), b->stream));
   return 0;
 }
 
@@ -386,49 +236,11 @@ kq_fsk_bank *kq_fsk_create(const kq_fsk_config *cfg) {
     kq_internal_set_error("kq_fsk_create: null config");
     return nullptr;
   }
-  if (cfg->baud <= 0 || cfg->samprate <= 0) {
-    kq_internal_set_error("kq_fsk_create: samprate %d and baud %d must be positive", cfg->samprate, cfg->baud);
-    return nullptr;
-  }
-  long long const Fs = cfg->samprate, baud = cfg->baud;
-  if (Fs < 4 * baud || Fs > 40 * baud) {
-    kq_internal_set_error("kq_fsk_create: samprate %d must be 4 .. 40 times baud %d", cfg->samprate, cfg->baud);
-    return nullptr;
-  }
-  unsigned const K = cfg->taps;
-  if (K < 3 || K > (unsigned)kMaxK || !(K & 1)) {
-    kq_internal_set_error("kq_fsk_create: taps %u must be odd and 3..%d", K, kMaxK);
-    return nullptr;
-  }
-  if (!std::isfinite(cfg->window_bits) || cfg->window_bits <= 0) {
-    kq_internal_set_error("kq_fsk_create: window_bits must be finite and positive");
-    return nullptr;
-  }
-  double const Wd = std::rint((double)cfg->window_bits * (double)Fs / (double)baud);
-  if (Wd < 2 || Wd > kMaxW) {
-    kq_internal_set_error("kq_fsk_create: window_bits %g gives W = %.0f samples, must be 2..%d", (double)cfg->window_bits, Wd, kMaxW);
-    return nullptr;
-  }
-  if (!(cfg->cutoff_hz > 0) || !(cfg->cutoff_hz < 0.5 * (double)Fs)) {
-    kq_internal_set_error("kq_fsk_create: cutoff_hz %g must be above 0 and below samprate / 2", (double)cfg->cutoff_hz);
-    return nullptr;
-  }
-  if (!std::isfinite(cfg->kaiser_beta) || cfg->kaiser_beta < 0) {
-    kq_internal_set_error("kq_fsk_create: kaiser_beta must be finite and >= 0");
-    return nullptr;
-  }
-  if (cfg->pll_shift < 1 || cfg->pll_shift > 8) {
-    kq_internal_set_error("kq_fsk_create: pll_shift %d must be 1..8", cfg->pll_shift);
-    return nullptr;
-  }
-  if (!std::isfinite(cfg->input_scale) || !(cfg->input_scale > 0)) {
-    kq_internal_set_error("kq_fsk_create: input_scale must be finite and positive");
-    return nullptr;
-  }
-  if (cfg->max_slots == 0 || cfg->max_slots > kMaxSlots) {
-    kq_internal_set_error("kq_fsk_create: max_slots %u must be 1..%u", cfg->max_slots, kMaxSlots);
-    return nullptr;
-  }
+  kq::fskfront::FrontConfig const fc{(double)cfg->samprate, cfg->baud,        cfg->taps,      cfg->cutoff_hz,  cfg->kaiser_beta,
+                                     cfg->window_bits,      cfg->input_scale, cfg->pll_shift, cfg->max_slots, cfg->max_samples};
+  FskGeom g{};
+  std::vector<short> hq;
+  if (!kq::fskfront::front_config("kq_fsk_create", fc, &g, &hq)) return nullptr;
   if (cfg->max_frames == 0 || cfg->max_frames > 4096) {
     kq_internal_set_error("kq_fsk_create: max_frames %u must be 1..4096", cfg->max_frames);
     return nullptr;
@@ -437,35 +249,12 @@ kq_fsk_bank *kq_fsk_create(const kq_fsk_config *cfg) {
     kq_internal_set_error("kq_fsk_create: max_frame_bytes %u must be 8..1024", cfg->max_frame_bytes);
     return nullptr;
   }
-  if (cfg->max_samples == 0 || cfg->max_samples > ((size_t)1 << 28)) {
-    kq_internal_set_error("kq_fsk_create: max_samples %zu must be 1..2^28", cfg->max_samples);
-    return nullptr;
-  }
-  long sum_abs = 0;
-  std::vector<short> hq = design_taps((int)K, cfg->cutoff_hz, (double)Fs, cfg->kaiser_beta, &sum_abs);
-  if (sum_abs > 65535) {
-    kq_internal_set_error("kq_fsk_create: taps %u, cutoff_hz %g, kaiser_beta %g give sum |hq| = %ld > 65535: the filter could overflow",
-                          K, (double)cfg->cutoff_hz, (double)cfg->kaiser_beta, sum_abs);
-    return nullptr;
-  }
   kq_fsk_bank *b = new kq_fsk_bank;
   b->cfg = *cfg;
   b->hq = std::move(hq);
-  FskGeom &g = b->g;
-  g.K = (int)K;
-  g.W = (int)Wd;
-  g.H = g.K - 1 + g.W - 1;
-  g.HN = g.H + 63;
-  g.P = 0;
-  while ((2 << g.P) <= g.W) g.P++;
-  g.off = g.W - (1 << g.P);
-  g.inc = (unsigned)std::llrint(4294967296.0 * (double)baud / (double)Fs);
-  g.pll_shift = cfg->pll_shift;
-  g.scale = cfg->input_scale;
-  g.max_frames = (int)cfg->max_frames;
-  g.mfb = (int)cfg->max_frame_bytes;
-  g.S = (int)cfg->max_slots;
-  g.words = cfg->max_samples / 64 + 2;
+  b->g = g;
+  b->max_frames = (int)cfg->max_frames;
+  b->mfb = (int)cfg->max_frame_bytes;
   return b;
 }
 
@@ -530,49 +319,25 @@ int kq_fsk_process(kq_fsk_bank *b, const void *src, int format, size_t src_strid
   auto &d = b->d;
   size_t const S = b->cfg.max_slots, nlist = d.slots.all.size();
   CallArgs a{};
-  a.g = g;
-  a.par = d.slots.d_par;
-  a.list = d.slots.d_list;
-  a.taps = d.taps;
-  a.hist_in = d.hist[b->turn];
-  a.hist_out = d.hist[b->turn ^ 1];
-  a.dw = d.dw;
-  a.level = d.level;
+  if (kq::fskfront::bind_front(&a.f, *b, d.slots, d.front, g, b->turn, b->n_cur, b->cfg.max_samples, src, format, src_stride,
+                               row_stride, block_len, nblocks, on_device))
+    return -1;
+  a.lim.max_frames = b->max_frames;
+  a.lim.mfb = b->mfb;
   a.state = d.state;
   a.open = d.open;
   a.frames = d.frames;
   a.info = d.info;
   a.nframes = d.nframes;
-  a.n0 = (int64_t)b->n_cur;
-  a.n1 = a.n0 + (int64_t)ncall;
-  a.w0 = a.n0 >> 6;
-  a.format = format;
-  a.block_len = block_len;
   if (on_device) {
-    a.src = src;
-    a.src_stride = src_stride;
-    a.row_stride = row_stride;
-    a.rowmap = nullptr;
     a.st = status;
     a.sstride = status_stride;
   } else {
-    // (the stage holds 4 bytes per sample whatever the format; the rows lie as closely as the format allows)
-    kq::Staged in;
-    if (d.slots.stage_rows(*b, src, format == KQ_PCM_S16BE ? 2 : 4, src_stride, row_stride, block_len, nblocks,
-                           b->cfg.max_samples * 4, &in))
-      return -1;
-    a.src = in.src;
-    a.src_stride = in.src_stride;
-    a.row_stride = in.row_stride;
-    a.rowmap = in.rowmap;
     if (status && !d.st && b->alloc(&d.st, S)) return -1;
     a.st = status ? d.st : nullptr;
     a.sstride = 1;
   }
-  int64_t const nwords = ((a.n1 - 1) >> 6) - a.w0 + 1;  // <= max_samples / 64 + 2
-  unsigned const tiles = (unsigned)((nwords * 64 + kTile - 1) / kTile);
-  hipLaunchKernelGGL(k_fsk_front, dim3(tiles, (unsigned)nlist), dim3(kThreads), 0, b->stream, a);
-  KQ_TRY(hipGetLastError());
+  if (kq::fskfront::launch_front(a.f, nlist, b->stream)) return -1;
   hipLaunchKernelGGL(k_fsk_track, dim3((unsigned)((nlist + 63) / 64)), dim3(64), 0, b->stream, a, (int)nlist);
   KQ_TRY(hipGetLastError());
   b->turn ^= 1;  // from here on the carried q is in the other copy, whatever fails below
@@ -631,13 +396,13 @@ int kq_fsk_pull_frame(kq_fsk_bank *b, unsigned slot, unsigned index, unsigned ch
     kq_internal_set_error("kq_fsk_pull_frame: slot %u has %u frames", slot, n);
     return -1;
   }
-  size_t const at = (size_t)slot * b->g.max_frames + index;
+  size_t const at = (size_t)slot * b->max_frames + index;
   kq_fsk_frame_info r;
   KQ_TRY(hipMemcpyAsync(&r, b->d.info + at, sizeof r, hipMemcpyDeviceToHost, b->stream));
   KQ_TRY(hipStreamSynchronize(b->stream));
   size_t const take = std::min(cap, (size_t)r.length);
   if (take) {
-    KQ_TRY(hipMemcpyAsync(dst, b->d.frames + at * b->g.mfb, take, hipMemcpyDeviceToHost, b->stream));
+    KQ_TRY(hipMemcpyAsync(dst, b->d.frames + at * b->mfb, take, hipMemcpyDeviceToHost, b->stream));
     KQ_TRY(hipStreamSynchronize(b->stream));
   }
   if (info) *info = r;
