@@ -1262,6 +1262,113 @@ int kq_pag_reset(kq_pag_bank *bank);
  * or 2) with the codeword in *fixed (may be NULL), or -1 (uncorrectable; *fixed is left alone) */
 int kq_pag_correct(uint32_t word, uint32_t *fixed);
 
+/* --- tone signalling decoder bank -----------------------------------------------------------------------------------------
+ * Up to 4096 decoder slots, each reading the in-band tone signalling of one voice channel from its audio row (a receiver
+ * bank's audio plane can be decoded in place on its stream after kq_bank_join): DTMF, the sequential five-tone selective
+ * calls (ZVEI, CCIR, EIA ...), two-tone sequential paging.  One bank decodes one tone plan: a channel that carries DTMF
+ * and ZVEI is read by two banks on the same plane and stream, as kq_fsk_* and kq_pag_* read several bit rates.  The
+ * reference has no such decoder: the algorithm is defined here.  Everything after the quantiser is exact integer
+ * arithmetic, so no result depends on how sums are ordered or how the stream is cut into calls.
+ * Per slot, x[n] is its input row; n counts samples since create or kq_tone_reset on a grid shared by every slot, and
+ * x[n] = 0 before the slot was set.  Fs = samprate, B = block_len, T = ntones; block k is the samples [k B, (k + 1) B).
+ *   quantise   as kq_fsk_*: q[n] = clamp(rint(x[n] input_scale), -32767, 32767), one float multiply, round to nearest even,
+ *              NaN reads as 0; a KQ_PCM_S16BE word is taken as q itself, -32768 as -32767.
+ *   table      C[j] = rint(32767 cos(2 pi j / 1024)) as int16, j = 0..1023, made once on the host in double
+ *              (kq_tone_get_table).
+ *   correlate  tone t: inc_t = rint(f_t 2^32 / Fs) in double, f_t the float of the config (kq_tone_get_incs);
+ *              ph_t(n) = (n inc_t) mod 2^32 -- no oscillator state is carried -- and j = ph_t(n) >> 22.  Per block
+ *              I_t = sum q[n] C[j], Q_t = sum q[n] C[(j - 256) & 1023], E = sum q[n]^2: exact integers in 64 bits.
+ *              a = I_t >> 15, b = Q_t >> 15 (arithmetic shifts), P_t = a^2 + b^2 as uint64.  With B <= 4096: |I| < 2^42,
+ *              P < 2^55, R = E B < 2^54.
+ *   decide     at every completed block.  The tones are one or two groups of consecutive entries: the first group0, then
+ *              group1 (DTMF: low and high; selective calling: one group).  Per group: best = the lowest index that attains
+ *              the largest P, P2 = the largest P of the group's other tones, 0 if it has no other.  The block is valid
+ *              iff E >= min_ms B; in every group P_best >= (R >> 8) frac and P_best >= (P2 >> 4) ratio; and with two groups
+ *              max(P_best0, P_best1) <= (min(P_best0, P_best1) >> 4) twist.  Every compare in uint64.  frac is in 1/256 of
+ *              R: a pure tone gives about 128, each tone of an equal pair about 64; ratio and twist are in sixteenths.
+ *              Symbol s = i0 | i1 << 8, i the best tone's index within its group, i1 = 0 with one group; an invalid block
+ *              gives s = -1.
+ *   runs       per slot cur (-1 at the set), run, start, peak.  Per block with symbol s: if s == cur, run += 1 (saturating
+ *              at 2^32 - 1) and peak = max(peak, E).  Otherwise the old run closes: if cur >= 0 and run >= min_blocks,
+ *              events += 1 and the run goes to the slot's arena as an event, or dropped += 1 when that holds max_events;
+ *              then cur = s, run = 1, start = k, peak = E.
+ *   event      symbol, blocks = run, start_sample = start B, peak.
+ * An open run is no event until it ends; the status shows cur and run, so a client sees a long tone while it lasts.
+ * kq_tone_remove and kq_tone_reset discard the open run.  Carried between calls: the I, Q and E of the open block, the
+ * run, the counters and the last completed block's P and E; so the same stream split differently into calls or blocks
+ * gives the same events, status and powers.
+ * Limits (refused by kq_tone_create / kq_tone_set with the reason in kq_last_error, before any HIP call): samprate
+ * positive and finite; 8 <= B <= 4096; 1..32 tones in group0 >= 1 and group1 >= 0 with group0 + group1 = ntones;
+ * 0 < f_t < Fs / 2; frac 1..128; ratio and twist 16..4095; min_blocks 1..65535; input_scale > 0; max_slots 1..4096;
+ * max_events 1..4096; max_samples 1..2^28.
+ * Device memory per slot: 24 max_events of arena, 24 (T + 1) + 64 of accumulators, powers and state; 2 KiB of table per
+ * bank.
+ * Talk-off (speech taken for tones) has not been measured.
+ * Calls: as kq_fsk_*.  kq_tone_create touches no device. */
+typedef struct kq_tone_bank kq_tone_bank;
+typedef struct kq_tone_config {
+  int device;
+  double samprate;           /* Fs: input samples per second; a double, so that 39 062.5 is exact */
+  unsigned block_len;        /* B: samples per decision block */
+  unsigned ntones;           /* T */
+  const float *freqs;        /* [T], Hz: the first group's tones, then the second's; copied by kq_tone_create */
+  unsigned group0, group1;   /* tones in the first and second group; group1 = 0: one group */
+  unsigned min_ms;           /* least mean square of q over a valid block */
+  unsigned frac;             /* least P_best, in 1/256 of E B */
+  unsigned ratio;            /* least P_best / P2, in sixteenths */
+  unsigned twist;            /* largest ratio of the two groups' P_best, in sixteenths */
+  unsigned min_blocks;       /* shortest run that makes an event */
+  float input_scale;         /* 32767 suits audio of full scale 1 */
+  unsigned max_slots;        /* slots 0 .. max_slots - 1 (limit 4096) */
+  unsigned max_events;       /* arena places per slot between kq_tone_clear_events calls */
+  size_t max_samples;        /* largest nblocks * block_len of one kq_tone_process call */
+  void *stream;              /* hipStream_t, NULL = own stream; kq_bank_stream(bank) puts it beside a receiver bank */
+} kq_tone_config;
+typedef struct kq_tone_params {
+  unsigned source;           /* input row this slot decodes (a receiver bank's channel index) */
+} kq_tone_params;
+typedef struct kq_tone_status {  /* counters since the slot was set */
+  uint32_t blocks;           /* completed */
+  uint32_t valid_blocks;
+  uint32_t events;           /* runs of min_blocks or more that ended, those dropped included */
+  uint32_t dropped;
+  int32_t cur;               /* the open run's symbol, -1: none */
+  uint32_t run;              /* its blocks so far */
+  uint64_t energy;           /* E of the last completed block */
+} kq_tone_status;
+typedef struct kq_tone_event {
+  int32_t symbol;
+  uint32_t blocks;
+  uint64_t start_sample;
+  uint64_t peak;             /* the largest E of the run's blocks */
+} kq_tone_event;
+
+kq_tone_bank *kq_tone_create(const kq_tone_config *cfg);
+int kq_tone_destroy(kq_tone_bank *bank);
+/* Put a decoder in `slot` (or replace the one there): a cold start at the next call's first sample, its arena empty */
+int kq_tone_set(kq_tone_bank *bank, unsigned slot, const kq_tone_params *params);
+/* The slot stops from the next call; its arena stays readable */
+int kq_tone_remove(kq_tone_bank *bank, unsigned slot);
+/* Input, status and on_device as in kq_fsk_process.  powers[slot powers_stride + t] is P_t of the slot's last completed
+ * block for t < T, and at t = T its E (stride in values, >= T + 1; may be NULL; nothing is written for an empty slot; all
+ * zero until a block has completed).  on_device != 0: powers too is device memory. */
+int kq_tone_process(kq_tone_bank *bank, const void *src, int format, size_t src_stride, size_t row_stride, unsigned block_len,
+                    unsigned nblocks, int on_device, kq_tone_status *status, size_t status_stride, uint64_t *powers,
+                    size_t powers_stride);
+/* Events in every slot's arena, counts[max_slots], in one copy; synchronous */
+int kq_tone_pull_counts(kq_tone_bank *bank, uint32_t *counts);
+/* Copies event `index` of `slot`; returns 0, or -1 */
+int kq_tone_pull_event(kq_tone_bank *bank, unsigned slot, unsigned index, kq_tone_event *event);
+/* Empties every arena (on the handle's stream); the status counters and the open runs go on */
+int kq_tone_clear_events(kq_tone_bank *bank);
+/* C (at most cap words); returns 1024 */
+int kq_tone_get_table(const kq_tone_bank *bank, int16_t *dst, size_t cap);
+/* inc_t (at most cap words); returns T */
+int kq_tone_get_incs(const kq_tone_bank *bank, uint32_t *dst, size_t cap);
+int kq_tone_sync(kq_tone_bank *bank);
+/* Stream index back to 0; every slot restarts cold with its settings */
+int kq_tone_reset(kq_tone_bank *bank);
+
 /* --- rational resampler bank ----------------------------------------------------------------------------------------------
  * Up to 65536 slots, each one row of PCM (mono or stereo) resampled from Fi = in_rate_num / in_rate_den Hz (a receiver
  * bank's samprate and decimate, so 39 062.5 Hz is exact) to Fo = out_rate Hz: kq_afsk_*, RTP PCM and the players are 48 kHz,

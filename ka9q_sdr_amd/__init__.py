@@ -40,5 +40,7 @@ from .fsk import FskBank, FskParams, fsk_params  # noqa: F401,E402  (fsk.STATUS_
 from .ais import ais_nmea, ais_payload_bits, ais_position  # noqa: F401,E402
 from .pag import PagBank, PagParams, pag_params  # noqa: F401,E402  (pag.STATUS_DTYPE: the pager one)
 from . import pocsag  # noqa: F401,E402
+from .tone import ToneBank, ToneParams, tone_params  # noqa: F401,E402  (tone.STATUS_DTYPE: the tone decoder's)
+from . import selcall  # noqa: F401,E402
 from .monitor import KQ_MON_F32, KQ_MON_S16BE, MonBank, MonParams, mon_params  # noqa: F401,E402  (monitor.STATUS_DTYPE: the mixer's)
 from .resample import RsmpBank, RsmpParams, rsmp_params  # noqa: F401,E402
