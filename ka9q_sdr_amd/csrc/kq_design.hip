@@ -6,8 +6,10 @@
 // rotated so that the impulse response sits in the first M taps, shaped by a Kaiser window, zero padded and taken
 // back.  Here one workgroup designs one response in LDS: target spectrum -> inverse transform -> taps -> forward
 // transform -> response + sum |H|^2 for noise_gain; a launch designs a batch (every channel of a bank retuning at
-// once costs one launch).  Arithmetic is float, like the reference's; the responses agree with the oracle's to a few
-// 1e-12 absolute (response peak 1/N ~ 6e-5).
+// once costs one launch).  Arithmetic is float, like the reference's.  Measured bin by bin against a float64 statement of the
+// procedure (tests/design_model.py, tests/test_gpu_design.py; N = 2 .. 16384, every error relative to the response peak): the
+// responses are within 6e-7 of it at beta <= 3 and 1.2e-6 at beta = 9, Kaiser taps within 2.6e-6 absolute (beta = 10) -- the
+// distance the oracle's float code keeps from it as well -- and within 3.3e-7 of the oracle's.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -46,7 +48,7 @@ __device__ float kaiser_tap(int n, int M, float beta) {
 #pragma clang fp contract(off)
   int const m = min(n, M - 1 - n);
   if ((M & 1) && m == (M - 1) / 2) return 1.f;
-  float const arg = 3.14159265358979323846f * beta;
+  float const arg = (float)(3.14159265358979323846 * (double)beta);  // filter.c:342: the double product, rounded once
   float const pos = (2.0f / (float)(M - 1)) * (float)m - 1.f;  // -1 at the edge .. 0 at the middle
   return bessel_i0(arg * sqrtf(1.f - pos * pos)) * (1.f / bessel_i0(arg));
 }
