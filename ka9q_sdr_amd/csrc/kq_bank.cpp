@@ -363,6 +363,7 @@ static int create_alloc(kq_bank *b) {
   if (b->alloc(&b->list_unswept_dev, C, true)) return -1;
   if (b->alloc(&b->list_swept_dev, C, true)) return -1;
   if (b->fwd_mode == KQ_FWD_PRUNED && b->alloc(&b->chan_tw, C * kq::pruned_table_elems(g), true)) return -1;
+  if (b->fwd_mode != KQ_FWD_PRUNED && kq::full16k_supported(g) && b->alloc(&b->chd.row_ph, C * 32, true)) return -1;
   KQ_TRY(hipStreamSynchronize(b->stream));  // the clears are over: the blocking copies below do not meet them
   if (g.pl_n > 0) {
     // PL low-pass: bins with 0 < f < 300 Hz, Kaiser beta 2.0 (fm.c:207-218)

@@ -144,6 +144,10 @@ struct kq_bank : kq::HostSide {
   const float2 *tw = nullptr;  // kq::half_twiddles(g.tw_log2): shared, not the bank's to free
   float2 *chan_tw = nullptr;  // pruned path: per-channel twiddle tables
   bool chan_tw_dirty = true;
+  // full-spectrum path, N = 16384: chd.row_ph (the unswept steady-state variant's row phasors, one row per channel slot) no
+  // longer matches some channel's frequency step -- set wherever chan_tw_dirty is; the next call that launches that variant
+  // rebuilds the plane in front of it, as does every call that stages the oscillator planes afresh
+  bool row_ph_dirty = true;
   kq::ChanDev chd{};  // (what a geometry does not use stays null)
   kq::Planes pl{};
   float *energy_state = nullptr;

@@ -461,6 +461,14 @@ void launch_filter(kq_bank *b, Call &k) {
     kq::launch_filter_split(b->stream, g, k.chd, k.pl, k.window, b->tw, k.C, nblocks, nullptr);
   } else {
     int const steady_variant = k.swept_steady ? 2 : k.plain ? 1 : 0;  // (of a launch whose channels all sweep, or none)
+    // The unswept steady-state variant of the N = 16384 kernel takes its row phasors from chd.row_ph, which depends on the
+    // channels' frequency steps only: rebuilt, from the planes this call's launches read, after a step has changed
+    // (row_ph_dirty) and whenever the planes were staged afresh.  (A swept channel's row is never read: its step moves
+    // from call to call, and the setter that ends the sweep marks the plane.)
+    if (k.use16k && (k.plain || k.mixed) && (b->row_ph_dirty || !k.steady)) {
+      kq::launch_full16k_rows(b->stream, k.chd, k.C);
+      b->row_ph_dirty = false;
+    }
     if (k.mixed) {
       full_launch(b, k, (int)b->list_unswept_host.size(), nblocks, b->list_unswept_dev, 1);
       full_launch(b, k, (int)b->list_swept_host.size(), nblocks, b->list_swept_dev, steady_variant);

@@ -146,6 +146,7 @@ int kq_bank_add_channel(kq_bank *b, const kq_channel_config *cfg) {
   }
   if (lists_add(b, c)) return -1;
   b->chan_tw_dirty = true;
+  b->row_ph_dirty = true;
   // a channel more leaves the steady state of the others alone: its planes are patched in by the next call
   b->chans[c].r_eff = 0;
   b->n_active++;
@@ -345,6 +346,7 @@ int kq_bank_add_channels(kq_bank *b, const kq_channel_config *cfgs, unsigned n, 
   b->lists_dirty = true;
   b->osc_dirty = true;
   b->chan_tw_dirty = true;
+  b->row_ph_dirty = true;
   return (int)n;
 }
 
@@ -478,6 +480,7 @@ int kq_bank_set_second_lo(kq_bank *b, int ch, double hz) {
   b->chans[ch].cfg.second_lo = hz;
   b->chans[ch].lo2.set(hz == 0 ? 0.0 : hz / b->g.samprate, 0.0, b->n_abs);
   b->chan_tw_dirty = true;
+  b->row_ph_dirty = true;
   note_patch(b, ch);
   return 0;
 }
@@ -494,6 +497,7 @@ int kq_bank_set_doppler(kq_bank *b, int ch, double hz, double hz_per_s) {
   b->chans[ch].cfg.doppler_rate = hz_per_s;
   b->chans[ch].dop.set(-hz / fs, -hz_per_s / (fs * fs), b->n_abs);
   b->chan_tw_dirty = true;
+  b->row_ph_dirty = true;
   note_patch(b, ch);
   return 0;
 }

@@ -101,6 +101,10 @@ struct ChanDev {
   // oscillator phase (turns), step (cycles/sample) and sweep (cycles/sample^2) at sample 0 of the
   // first window of the call; second LO and Doppler already summed (they multiply, so phases add)
   double *lo_phase, *lo_freq, *lo_rate;
+  // N = 16384 full-spectrum kernel, steady-state variant of unswept channels: [C][32] the phasors of the window's 32 rows,
+  // row_ph[32 c + n1] = exp(j 2 pi 512 n1 lo_freq[c]) (kq_full16k.hip k_full16k_rows).  They depend on the channel's step
+  // alone: rebuilt by the call that follows a change of it (kq_bank::row_ph_dirty).  Null where that kernel cannot run.
+  float2 *row_ph;
   // the same for the M-1 history samples of the call's first block: they were mixed before a retune took effect
   // and keep the old oscillator (radio.c:132-139 mixes sample by sample; osc.c:22-36 only changes what follows)
   double *hist_phase, *hist_freq, *hist_rate;
@@ -222,6 +226,8 @@ void launch_filter_full16k(hipStream_t s, const Geom &g, const ChanDev &ch, cons
                            const float2 *tw, int nchan, int nblocks, int compute_n0, float2 *spec_dump, int spec_ch,
                            const int *chan_list, int plain, const float2 *window_paired, const Big64 &big);
 bool full16k_paired_supported(const Geom &g);
+// fills ch.row_ph for channel slots 0 .. nchan - 1 from ch.lo_freq; the plain == 1 launches that follow on `s` read it
+void launch_full16k_rows(hipStream_t s, const ChanDev &ch, int nchan);
 bool full64k_supported(const Geom &g);
 // plain: no channel of the launch was retuned since the last call and every sweep rate is inside full64k_sweep_limit();
 // swept: some channel sweeps

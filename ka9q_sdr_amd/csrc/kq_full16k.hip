@@ -19,6 +19,9 @@
 // NCO: without sweep the phasor of sample 512 n1 + t is P_t S^{n1}; S^{n1} is built from S, S^2, S^4, S^8, S^16
 // (each from the double-precision phase), at most four products deep.  Swept channels and the first block after a
 // retune (history still on the old oscillator) evaluate the closed-form phase per sample, as k_filter_full does.
+// The S^{n1} depend on the channel's frequency step and on nothing else -- not the block, not the wave, not the call: the
+// steady-state variant (PLAIN == 1) takes them from a per-channel plane (ChanDev::row_ph, k_full16k_rows), rebuilt when a
+// step changes, through scalar loads.
 //
 // N = 65536 (BIG; cfg 5: compute_n0 needs every bin there too, linear.c:123-126).  64 Ki complex values are 512 KiB -- more
 // than a CU's LDS, as much as its whole register file -- so the transform is split by decimation in frequency over the
@@ -142,10 +145,22 @@ __device__ __forceinline__ void twiddle32_fetch(v2f (&tlo)[3], v2f (&thi)[7], rs
   for (int h = 0; h < 7; h++) thi[h] = e[3 + h];
 }
 
+// a * b with b in scalar registers: pk_cmul's two instructions with one scalar source each.  (rfft::pk_cmul_any leaves the
+// encodings to the compiler, which then builds {-a.y, a.y} in registers: a v_xor_b32 and a v_mov_b32 per product.)
+__device__ __forceinline__ v2f pk_cmul_s(v2f a, v2f b) {
+  v2f t, d;
+  asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[0,1]" : "=v"(t) : "v"(a), "s"(b));
+  asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]" : "=v"(d) : "v"(a), "s"(b), "v"(t));
+  return d;
+}
+
 __device__ __forceinline__ v2f phasor2(double turns) {
   float2 const p = phasor_turns(turns);
   return (v2f){p.x, p.y};
 }
+// N = 16384, unswept: the phasor S^{n1} of window row n1 (its first sample is 512 n1) for the frequency step f0.  One
+// expression for the kernel's own table (PLAIN == 0) and for the per-channel plane (k_full16k_rows): the same bits
+__device__ __forceinline__ float2 row_phasor(double f0, int n1) { return phasor_turns(f0 * (double)(512 * n1)); }
 
 // N = 65536: largest sweep (cycles per sample^2) the table path takes.  The lane part of the cross term,
 // theta = 2 pi rate R lane with R <= 65024 and lane <= 63, is applied as 1 + i theta: its error theta^2 / 2 stays below 5e-8.
@@ -201,8 +216,10 @@ __global__ __launch_bounds__(kT, 4) void k_filter_full16k(Geom g, ChanDev ch, Pl
                                                        float2 *__restrict__ spec_dump, int spec_ch,
                                                        const int *__restrict__ chan_list, Big64 big) {
   extern __shared__ __attribute__((aligned(16))) float2 xch[];
-  // per wave: S^{n1}, see the mix (BIG: the 128 row phasors T[j][n1])
-  __shared__ __attribute__((aligned(16))) float2 stab[(kT / 64) * (BIG ? 128 : 32)];
+  // per wave: S^{n1}, see the mix (BIG: the 128 row phasors T[j][n1]; the unswept steady-state variant has them in scalar
+  // registers instead, kRowPlane)
+  constexpr bool kRowPlane = PLAIN == 1 && BIG == 0;
+  __shared__ __attribute__((aligned(16))) float2 stab[kRowPlane ? 1 : (kT / 64) * (BIG ? 128 : 32)];
   __shared__ float sib_f[BIG ? 12 : 1];  // BIG: what the siblings published, see sibling_exchange
   constexpr int kNfull = BIG ? 4 * kN : kN;
   int const r4 = BIG ? (int)(blockIdx.x & 3) : 0;  // residue class of this workgroup's bins
@@ -358,13 +375,18 @@ __global__ __launch_bounds__(kT, 4) void k_filter_full16k(Geom g, ChanDev ch, Pl
       }
     }
   }
+  // PLAIN == 1, N = 16384: the row phasors S^{n1}, n1 = 1..31 (S^0 = 1 is not applied), in scalar registers
+  v2f srow[kRowPlane ? 32 : 1];
   if constexpr (PLAIN && BIG == 0) {
     // The channel's two parameters are asked for before the samples, and the oscillator's table and phasor -- two
     // double-precision evaluations, the only arithmetic a wave has before its samples arrive -- sit between the batches
     // of loads: the memory pipeline takes the workgroup's 350 load instructions at about one per 14 cycles and a wave
     // cannot run ahead of a load it cannot issue yet, so they cost nothing there (-1 % against parameters, table and
-    // phasor behind the last load).  The phasor of sample 512 n1 + t is P_t S^{n1}, S = exp(j 2 pi 512 f0): lane n1 of
-    // each wave evaluates S^{n1} from the double-precision phase into the wave's own LDS slot.
+    // phasor behind the last load).  The phasor of sample 512 n1 + t is P_t S^{n1}, S = exp(j 2 pi 512 f0).
+    // PLAIN == 1: the channel's 32 S^{n1} come from its row of ChanDev::row_ph, asked for with the two parameters -- scalar
+    // loads (c is uniform; read through the constant address space, as the compute_n0 masks are: nothing writes the plane
+    // while a filter kernel runs), so no vector instruction, no LDS slot and no fence is spent on them.
+    // PLAIN == 2: lane n1 of each wave evaluates its entry from the double-precision phase into the wave's own LDS slot.
     // PLAIN == 2: every channel of the launch sweeps (rate inside kSweepLimit16k), none was retuned since the last call.
     // With u = A + R, A = b L + t and R = 512 n1, the phase ph0 + f0 u + rs u (u - 1) / 2 is
     //   [ph0 + f0 A + rs A (A - 1) / 2]  +  [f0 R + rs R (R - 1) / 2 + rs R (b L + 64 w)]  +  rs R lane
@@ -372,14 +394,22 @@ __global__ __launch_bounds__(kT, 4) void k_filter_full16k(Geom g, ChanDev ch, Pl
     // in the mix below (as the N = 65536 path does).
     double const ph0 = ch.lo_phase[c], f0 = ch.lo_freq[c];
     double const rs = PLAIN == 2 ? ch.lo_rate[c] : 0.0;
+    if constexpr (kRowPlane) {
+      typedef const float2 __attribute__((address_space(4))) *row_plane;
+      row_plane const rp = (row_plane)(ch.row_ph + (size_t)__builtin_amdgcn_readfirstlane(c) * 32);
+#pragma unroll
+      for (int n1 = 1; n1 < 32; n1++) srow[n1] = (v2f){rp[n1].x, rp[n1].y};
+    }
     load_rows(0, 12);
     __builtin_amdgcn_sched_barrier(0);
-    float2 *const sw = stab + (t >> 6) * 32;
-    if ((t & 63) < 32) {
-      double const R = (double)(512 * (t & 63));
-      double turns = f0 * R;
-      if constexpr (PLAIN == 2) turns += rs * (0.5 * R * (R - 1.0) + R * ((double)b * g.L + (double)(t & ~63)));
-      sw[t & 63] = phasor_turns(turns);
+    if constexpr (PLAIN == 2) {
+      float2 *const sw = stab + (t >> 6) * 32;
+      if ((t & 63) < 32) {
+        double const R = (double)(512 * (t & 63));
+        double turns = f0 * R;
+        turns += rs * (0.5 * R * (R - 1.0) + R * ((double)b * g.L + (double)(t & ~63)));
+        sw[t & 63] = phasor_turns(turns);
+      }
     }
     __builtin_amdgcn_sched_barrier(0);
     load_rows(12, 22);
@@ -406,20 +436,26 @@ __global__ __launch_bounds__(kT, 4) void k_filter_full16k(Geom g, ChanDev ch, Pl
     int const n_old = (hp0 != ph0 || hf0 != f0 || hr != r) ? ch.hist_len[c] - b * g.L : 0;  // (as above)
     bool const retuned = n_old > 0;
     if (PLAIN || (r == 0.0 && !retuned)) {
-      float2 *const sw = stab + (t >> 6) * 32;
+      float2 *const sw = stab + (kRowPlane ? 0 : (t >> 6) * 32);
       if constexpr (!PLAIN) {
         load_window();
-        if ((t & 63) < 32) sw[t & 63] = phasor_turns(f0 * (double)(512 * (t & 63)));
+        if ((t & 63) < 32) sw[t & 63] = row_phasor(f0, t & 63);
         pt = phasor2(ph0 + f0 * (mbase + t));
       }
       // One phasor evaluation and one product per sample, each power exact to float rounding; every lane reads entry n1
-      // of its wave's table (a broadcast read).  P_t, the same for the thread's 32 samples, commutes with the transform
-      // over n1: it rides on pass 1's twiddles below.
+      // of its wave's table (a broadcast read; PLAIN == 1: the entry is a scalar operand of the product).  P_t, the same
+      // for the thread's 32 samples, commutes with the transform over n1: it rides on pass 1's twiddles below.
       KQ_STAMP(11);  // oscillator table and P_t evaluated
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      if constexpr (PLAIN == 2) {
+      if constexpr (!kRowPlane) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      }
+      if constexpr (kRowPlane) {
+        // the same complex product, operand for operand, as pk_cmul forms it below: the same bits
+#pragma unroll
+        for (int n1 = 1; n1 < 32; n1++) v[rfft::bitrev5(n1)] = pk_cmul_s(v[rfft::bitrev5(n1)], srow[n1]);
+      } else if constexpr (PLAIN == 2) {
         // y (1 + i theta), theta = kb n1: one packed add for theta, one packed fma with the operand swizzle of the N = 65536 path
         float const kbf = (float)(2.0 * M_PI * 512.0 * r * (double)(t & 63));
         v2f const kb = (v2f){kbf, kbf};
@@ -699,8 +735,11 @@ __global__ __launch_bounds__(kT, 4) void k_filter_full16k(Geom g, ChanDev ch, Pl
     // float s < thr (the difference is at least 2^16 after scaling; the fused multiply-add rounds once, so its sign is
     // that of thr - s), exactly 0 for s >= thr.  A passband bin, held as 0, adds nothing to the sum and 1 to the count: the
     // count is put right by their known number at the end.  Three packed instructions per pair of
-    // bins instead of compare / select / add per bin.  Anything else -- a NaN or inf bin, an all-zero or denormal
-    // spectrum, an empty bin set -- takes the loop that spells the reference's comparisons out.
+    // bins instead of compare / select / add per bin.  (One compare and one add under its mask per bin, the count taken
+    // from the masks on the scalar unit, is 64 plain instructions for these 48 packed ones -- but as the compiler forms it,
+    // s_and_saveexec / branch / add / s_or per bin, it took the kernel from -3.0 % to -1.3 % against the commit before the
+    // row-phasor plane, tools/ab_libs.sh: DESIGN_DIARY.md I, A.1.)  Anything else -- a NaN or inf bin, an all-zero or
+    // denormal spectrum, an empty bin set -- takes the loop that spells the reference's comparisons out.
     n0_fast = total < INFINITY && thr < INFINITY && thr >= 1e-26f;
     if (n0_fast) {
       int const e = (__float_as_int(thr) >> 23) & 0xff;  // biased exponent, 1..254 here
@@ -971,6 +1010,16 @@ __global__ void k_epilogue64k(Geom g, ChanDev ch, Planes pl, const float2 *__res
   for (int i = t; i < g.olen; i += blockDim.x) o[i] = G[Ndec - g.olen + i];  // filter.c:131
 }
 
+// ChanDev::row_ph: row c = S^{n1}, n1 = 0..31, for channel slot c's frequency step as the launch's oscillator planes hold it
+__global__ void __launch_bounds__(256) k_full16k_rows(ChanDev ch, int nchan) {
+  int const i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= 32 * nchan) return;
+  ch.row_ph[i] = row_phasor(ch.lo_freq[i >> 5], i & 31);
+}
+void launch_full16k_rows(hipStream_t s, const ChanDev &ch, int nchan) {
+  if (nchan > 0 && ch.row_ph) hipLaunchKernelGGL(k_full16k_rows, dim3((32 * nchan + 255) / 256), dim3(256), 0, s, ch, nchan);
+}
+
 bool full16k_supported(const Geom &g) {
   // the epilogue keeps Xs[N_dec] and G[N_dec] in the exchange buffer
   return g.N == kN && 2 * g.Ndec <= kXchElems && g.Ndec >= 4;
@@ -1020,6 +1069,7 @@ void launch_filter_full16k(hipStream_t s, const Geom &g, const ChanDev &ch, cons
   }
   bool const n0 = compute_n0 && ch.n0lane && ch.n0meta;  // the bank uploads both whenever it was created with compute_n0
   bool const dump = spec_dump != nullptr;
+  if (plain == 1 && !ch.row_ph) plain = 0;  // (no row-phasor plane: the general variant builds its table itself)
   bool const paired = plain && window_paired != nullptr;  // only the steady-state variant reads the row-paired copy
   auto go = [&](auto kernel) {
     ensure_dynamic_lds((const void *)kernel, lds_bytes);
