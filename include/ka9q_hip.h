@@ -1369,6 +1369,131 @@ int kq_tone_sync(kq_tone_bank *bank);
 /* Stream index back to 0; every slot restarts cold with its settings */
 int kq_tone_reset(kq_tone_bank *bank);
 
+/* --- CW (Morse) decoder bank ------------------------------------------------------------------------------------------------
+ * Up to 16384 decoder slots (the slot scaffold takes that number unchanged), each reading on/off keyed Morse at one audio
+ * pitch from one audio row, as characters: a receiver bank's CWU / CWL channels (LINEAR, +-200 Hz, the carrier on a 700 Hz
+ * tone) can be decoded in place on its stream after kq_bank_join, and several slots may read one row at different pitches,
+ * so that an SSB passband is skimmed with a slot every 100 Hz or so.  The reference has no Morse decoder: the algorithm is
+ * defined here.  Everything after the quantiser is exact integer arithmetic, so no result depends on how sums are ordered
+ * or how the stream is cut into calls.
+ * Per slot, x[n] is its input row; n counts samples since create or kq_cw_reset on a grid shared by every slot, and
+ * x[n] = 0 before the slot was set.  Fs = samprate, B = block_len; frame k is the samples [k B, (k + 1) B).
+ *   quantise   as kq_fsk_* / kq_tone_*: q[n] = clamp(rint(x[n] input_scale), -32767, 32767), one float multiply, round to
+ *              nearest even, NaN reads as 0; a KQ_PCM_S16BE word is taken as q itself, -32768 as -32767.
+ *   table      kq_tone_*'s: C[j] = rint(32767 cos(2 pi j / 1024)) as int16 (kq_cw_get_table).
+ *   correlate  inc = rint(pitch 2^32 / Fs) in double, pitch the float of the params (kq_cw_get_inc); ph(n) = (n inc) mod
+ *              2^32 -- no oscillator state is carried -- and j = ph(n) >> 22.  Per frame I = sum q[n] C[j], Q = sum q[n]
+ *              C[(j - 256) & 1023]: exact integers in 64 bits.  a = I >> 15, b = Q >> 15 (arithmetic shifts), P[k] = a^2 +
+ *              b^2 as uint64.  With B <= 4096: |I|, |Q| < 2^42, |a| < 2^27, P < 2^55.
+ *   speeds     a dot of w words per minute lasts 1.2 / w seconds, 19.2 Fs / (B w) sixteenths of a frame.  In double, the
+ *              speeds the floats of the config and the params: u_min = floor(19.2 Fs / (B max_wpm)), u_max = ceil(19.2 Fs /
+ *              (B min_wpm)), and a slot starts at u = rint(19.2 Fs / (B wpm)).
+ *   state      hi, lo (uint64), key, cand, run, u (the dot in 1/16 frame), code, nelem, the flags closed and worded, first
+ *              and last (frame numbers), frames.  At the set: all zero but u, code = 1, closed = worded = 1.
+ *   tracker    one step per completed frame k with P = P[k], in this order (frames += 1 first, saturating):
+ *     1 peak      if P > hi: hi = P, else hi -= hi >> 8.
+ *     2 validity  valid = frames >= warm and hi >= min_p and hi >= (lo >> 4) snr (snr in sixteenths; < 2^63).
+ *     3 threshold d = hi > lo ? hi - lo : 0; thr = lo + (d >> 2) with the key up, lo + (d >> 3) with the key down (half and
+ *                 about a third of the amplitude: hysteresis).  lev = valid and P >= thr.
+ *     4 floor     if lev == 0, or key == 1 and 16 run > 8 u (a carrier, not keying): lo += (P - lo) >> 5, an arithmetic
+ *                 shift of the signed difference.  lo does not follow P through the debounce frames of a rising mark.
+ *     5 debounce  if lev == key: run = min(run + 1 + cand, 2^28 - 1), cand = 0 (a glitch shorter than deb is absorbed).
+ *                 Else cand += 1, and once cand >= deb the old state closes with length run: a mark is classified (6) and
+ *                 last = k + 1 - cand; a space that ends with nelem == 0 sets first = k + 1 - cand.  Then key = lev,
+ *                 run = cand, cand = 0.
+ *     6 mark      m = 16 run.  m > 8 u: a carrier, code = 0.  m < 2 u: a dot, code = 2 code, u += (m - u) >> 2.  Otherwise a
+ *                 dash, code = 2 code + 1 (code 0 stays 0), u += (floor(m / 3) - u) >> 2.  The shifts are arithmetic, on
+ *                 signed differences.  Then u is clamped to [u_min, u_max], nelem += 1, code = 0 once nelem > 8, and
+ *                 closed = worded = 0.
+ *     7 space     with the key up (after step 5, so at the frame where the count is reached, not at the next mark): if not
+ *                 closed and 16 run >= 2 u, the character is filed as an event (code, nelem, u, first B, last B, hi) and
+ *                 code = 1, nelem = 0, closed = 1.  If not worded and 16 run >= 5 u, a word gap is filed (code 1, nelem 0,
+ *                 u, last B, (k + 1) B, hi) and worded = 1.
+ *   event      code: the elements behind a leading 1, the first sent in the highest place, dot 0 and dash 1 (A is 0b101);
+ *              1: a word gap; 0: undecodable (a mark beyond 8 dots, or a ninth element).  events += 1 for each; it goes to
+ *              the slot's arena, or dropped += 1 when that holds max_events.
+ * kq_cw_remove and kq_cw_reset discard the open character.  Carried between calls: the open frame's I and Q and the
+ * whole tracker state; so the same stream split differently into calls or blocks gives the same events and status.
+ * Limits (refused by kq_cw_create / kq_cw_set with the reason in kq_last_error, before any HIP call): samprate positive
+ * and finite; 8 <= B <= 4096; 0 < min_wpm <= max_wpm, finite, with u_min >= 48 (three frames in a dot at max_wpm) and
+ * u_max <= 2^20; deb 1..16; warm 0..65535; snr 16..4095; min_p <= 2^55; input_scale > 0; max_slots 1..16384; max_events
+ * 1..4096; max_samples 1..2^28; per slot 0 < pitch < Fs / 2 and min_wpm <= wpm <= max_wpm.
+ * Device memory per slot: 40 max_events of arena, 112 of state and parameters; 2 KiB of table per bank.
+ * Copying accuracy on hand-keyed, off-air signals has not been measured; there is no AFC on the pitch (a frame's
+ * bandwidth is Fs / B, 250 Hz at 12 kHz and B = 48) and no weighting for hand-sent code.
+ * Calls: as kq_fsk_*.  kq_cw_create touches no device. */
+typedef struct kq_cw_bank kq_cw_bank;
+typedef struct kq_cw_config {
+  int device;
+  double samprate;           /* Fs: input samples per second; a double, so that 39 062.5 is exact */
+  unsigned block_len;        /* B: samples per frame */
+  float min_wpm, max_wpm;    /* the speeds the tracker may follow */
+  unsigned deb;              /* frames a level must last to change the key (2) */
+  unsigned warm;             /* frames after the set in which the key is held up while lo trains (64) */
+  unsigned snr;              /* least hi / lo, in sixteenths (256: 12 dB) */
+  uint64_t min_p;            /* least hi */
+  float input_scale;         /* 32767 suits audio of full scale 1 */
+  unsigned max_slots;        /* slots 0 .. max_slots - 1 (limit 16384) */
+  unsigned max_events;       /* arena places per slot between kq_cw_clear_events calls */
+  size_t max_samples;        /* largest nblocks * block_len of one kq_cw_process call */
+  void *stream;              /* hipStream_t, NULL = own stream; kq_bank_stream(bank) puts it beside a receiver bank */
+} kq_cw_config;
+typedef struct kq_cw_params {
+  unsigned source;           /* input row this slot decodes (a receiver bank's channel index) */
+  float pitch;               /* Hz */
+  float wpm;                 /* the speed the tracker starts from */
+} kq_cw_params;
+typedef struct kq_cw_status {
+  uint32_t frames;           /* completed since the slot was set */
+  uint32_t key;              /* 1: down */
+  uint32_t run;              /* frames in the present state of the key */
+  uint32_t unit;             /* u */
+  uint32_t events;           /* filed since the set, those dropped included */
+  uint32_t dropped;
+  uint32_t cand;             /* the rest is the open character and the open frame, as carried to the next call */
+  uint32_t code;
+  uint32_t nelem;
+  uint32_t flags;            /* closed | worded << 1 */
+  uint64_t hi, lo;           /* peak and floor: of neighbouring slots on one signal the largest hi / lo is on it */
+  uint64_t first, last;      /* frame numbers */
+  int64_t acc_i, acc_q;      /* I and Q of the open frame */
+} kq_cw_status;
+typedef struct kq_cw_event {
+  uint32_t code;
+  uint32_t nelem;
+  uint32_t unit;             /* u at the close: the sender's speed is 19.2 Fs / (B unit) WPM */
+  uint32_t reserved;         /* 0 */
+  uint64_t start_sample;     /* the first mark's first frame, times B (word gap: the last mark's end) */
+  uint64_t end_sample;       /* the last mark's end (word gap: the end of the frame that decided it) */
+  uint64_t peak;             /* hi at the close */
+} kq_cw_event;
+
+kq_cw_bank *kq_cw_create(const kq_cw_config *cfg);
+int kq_cw_destroy(kq_cw_bank *bank);
+/* Put a decoder in `slot` (or replace the one there): a cold start at the next call's first sample, its arena empty.
+ * Touches no device: the next kq_cw_process, kq_cw_pull_counts or kq_cw_pull_event brings every slot set or removed since
+ * the last one there, and waits for the handle's stream to do so (once, however many slots changed). */
+int kq_cw_set(kq_cw_bank *bank, unsigned slot, const kq_cw_params *params);
+/* The slot stops from the next call; its arena stays readable.  Touches no device either */
+int kq_cw_remove(kq_cw_bank *bank, unsigned slot);
+/* Input, status and on_device as in kq_fsk_process / kq_tone_process (status may be NULL; nothing is written for an empty
+ * slot). */
+int kq_cw_process(kq_cw_bank *bank, const void *src, int format, size_t src_stride, size_t row_stride, unsigned block_len,
+                  unsigned nblocks, int on_device, kq_cw_status *status, size_t status_stride);
+/* Events in every slot's arena, counts[max_slots], in one copy; synchronous */
+int kq_cw_pull_counts(kq_cw_bank *bank, uint32_t *counts);
+/* Copies event `index` of `slot`; returns 0, or -1 */
+int kq_cw_pull_event(kq_cw_bank *bank, unsigned slot, unsigned index, kq_cw_event *event);
+/* Empties every arena (on the handle's stream); the status counters and the open characters go on */
+int kq_cw_clear_events(kq_cw_bank *bank);
+/* C (at most cap words); returns 1024 */
+int kq_cw_get_table(const kq_cw_bank *bank, int16_t *dst, size_t cap);
+/* inc of `slot` in *inc; -1 when the slot holds no decoder */
+int kq_cw_get_inc(kq_cw_bank *bank, unsigned slot, uint32_t *inc);
+int kq_cw_sync(kq_cw_bank *bank);
+/* Stream index back to 0; every slot restarts cold with its settings at the next call, as if set again */
+int kq_cw_reset(kq_cw_bank *bank);
+
 /* --- rational resampler bank ----------------------------------------------------------------------------------------------
  * Up to 65536 slots, each one row of PCM (mono or stereo) resampled from Fi = in_rate_num / in_rate_den Hz (a receiver
  * bank's samprate and decimate, so 39 062.5 Hz is exact) to Fo = out_rate Hz: kq_afsk_*, RTP PCM and the players are 48 kHz,

@@ -42,5 +42,7 @@ from .pag import PagBank, PagParams, pag_params  # noqa: F401,E402  (pag.STATUS_
 from . import pocsag  # noqa: F401,E402
 from .tone import ToneBank, ToneParams, tone_params  # noqa: F401,E402  (tone.STATUS_DTYPE: the tone decoder's)
 from . import selcall  # noqa: F401,E402
+from .cw import CwBank, CwParams, cw_params  # noqa: F401,E402  (cw.STATUS_DTYPE: the Morse decoder's)
+from . import morse  # noqa: F401,E402
 from .monitor import KQ_MON_F32, KQ_MON_S16BE, MonBank, MonParams, mon_params  # noqa: F401,E402  (monitor.STATUS_DTYPE: the mixer's)
 from .resample import RsmpBank, RsmpParams, rsmp_params  # noqa: F401,E402
