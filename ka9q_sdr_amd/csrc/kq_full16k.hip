@@ -76,6 +76,9 @@ constexpr int kRow2 = 513;    //   16 consecutive lanes over 32 banks (16 eight-
 constexpr int kXchElems = 16 * kRow1;  // float2 elements; 16 * kRow2 fits as well
 
 using rfft::pk_cmul;
+using rfft::pk_cmul2;
+using rfft::pk_cmul4;
+using rfft::pk_cmul_s;
 using rfft::v2f;
 
 __device__ __forceinline__ v2f ld2(const float2 *p) {
@@ -121,16 +124,19 @@ constexpr int kTw2Pitch = 34;  // LDS row pitch (elements): lane n3 reads 16 byt
 // cost 31.
 // v[q] *= c W^{q}, q = 0..31, W^{q} = lo[q & 3] * hi[q >> 2]; tlo = W^1..W^3, thi = W^4, W^8 .. W^28 of the thread's column.
 __device__ __forceinline__ void twiddle32(v2f (&v)[32], const v2f (&tlo)[3], const v2f (&thi)[7], v2f c) {
+  // In blocks of four independent products (rfft::pk_cmul4): the four W^{4 h} lo[l] of a row h first, then their four
+  // applications -- as single products each v[4 h + l] was a chain of four instructions waiting for one another.
   v2f lo[4];
   lo[0] = c;
-#pragma unroll
-  for (int l = 1; l < 4; l++) lo[l] = pk_cmul(c, tlo[l - 1]);
-#pragma unroll
-  for (int l = 0; l < 4; l++) v[l] = pk_cmul(v[l], lo[l]);
+  pk_cmul2(lo[1], lo[2], c, tlo[0], c, tlo[1]);
+  lo[3] = pk_cmul(c, tlo[2]);
+  pk_cmul4(v[0], v[1], v[2], v[3], v[0], lo[0], v[1], lo[1], v[2], lo[2], v[3], lo[3]);
 #pragma unroll
   for (int h = 1; h < 8; h++) {
-#pragma unroll
-    for (int l = 0; l < 4; l++) v[4 * h + l] = pk_cmul(v[4 * h + l], pk_cmul(thi[h - 1], lo[l]));
+    v2f w[4];
+    pk_cmul4(w[0], w[1], w[2], w[3], thi[h - 1], lo[0], thi[h - 1], lo[1], thi[h - 1], lo[2], thi[h - 1], lo[3]);
+    pk_cmul4(v[4 * h], v[4 * h + 1], v[4 * h + 2], v[4 * h + 3], v[4 * h], w[0], v[4 * h + 1], w[1], v[4 * h + 2], w[2],
+             v[4 * h + 3], w[3]);
   }
 }
 // its ten table entries: requested right behind the window loads -- asked for where they are used, after the transform,
@@ -143,15 +149,6 @@ __device__ __forceinline__ void twiddle32_fetch(v2f (&tlo)[3], v2f (&thi)[7], rs
   for (int l = 0; l < 3; l++) tlo[l] = e[l];
 #pragma unroll
   for (int h = 0; h < 7; h++) thi[h] = e[3 + h];
-}
-
-// a * b with b in scalar registers: pk_cmul's two instructions with one scalar source each.  (rfft::pk_cmul_any leaves the
-// encodings to the compiler, which then builds {-a.y, a.y} in registers: a v_xor_b32 and a v_mov_b32 per product.)
-__device__ __forceinline__ v2f pk_cmul_s(v2f a, v2f b) {
-  v2f t, d;
-  asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[0,1]" : "=v"(t) : "v"(a), "s"(b));
-  asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]" : "=v"(d) : "v"(a), "s"(b), "v"(t));
-  return d;
 }
 
 __device__ __forceinline__ v2f phasor2(double turns) {
@@ -323,6 +320,15 @@ __global__ __launch_bounds__(kT, 4) void k_filter_full16k(Geom g, ChanDev ch, Pl
         float4 tt[4];
 #pragma unroll
         for (int j = 0; j < 4; j++) tt[j] = tp[16 * j + i];
+        // unswept: each row's sum over j is a chain, so the block forms pair the two rows of the step
+        v2f zz[2];
+        if constexpr (!kSwept) {
+          v2f const w0[4] = {{tt[0].x, tt[0].y}, {tt[1].x, tt[1].y}, {tt[2].x, tt[2].y}, {tt[3].x, tt[3].y}};
+          v2f const w1[4] = {{tt[0].z, tt[0].w}, {tt[1].z, tt[1].w}, {tt[2].z, tt[2].w}, {tt[3].z, tt[3].w}};
+          pk_cmul2(zz[0], zz[1], sa[slot][0], w0[0], sb[slot][0], w1[0]);
+#pragma unroll
+          for (int j = 1; j < 4; j++) rfft::pk_cmadd2(zz[0], zz[1], sa[slot][j], w0[j], zz[0], sb[slot][j], w1[j], zz[1]);
+        }
 #pragma unroll
         for (int e = 0; e < 2; e++) {
           int const n1 = 2 * i + e;
@@ -335,17 +341,15 @@ __global__ __launch_bounds__(kT, 4) void k_filter_full16k(Geom g, ChanDev ch, Pl
           v2f z;
           if constexpr (kSwept) {
             // sum_j y_j (1 + i kappa R_j), R_j = 16384 j + 512 n1:  S + i kb (W + n1 / 32 S), W = y1 + 2 y2 + 3 y3
-            v2f const y0 = pk_cmul(x[0], w[0]), y1 = pk_cmul(x[1], w[1]), y2 = pk_cmul(x[2], w[2]), y3 = pk_cmul(x[3], w[3]);
+            v2f y0, y1, y2, y3;
+            pk_cmul4(y0, y1, y2, y3, x[0], w[0], x[1], w[1], x[2], w[2], x[3], w[3]);
             v2f const a = y1 + y3, bb = y2 + y3;
             v2f const S = (y0 + y2) + a;
             v2f const W = rfft::pk_fma(bb, (v2f){2.f, 2.f}, a);
             v2f const Uu = n1 ? rfft::pk_fma(S, (v2f){n1 / 32.f, n1 / 32.f}, W) : W;
             asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[0,1,1] neg_lo:[0,1,0]" : "=v"(z) : "v"(Uu), "v"(kb), "v"(S));
           } else {
-            z = pk_cmul(x[0], w[0]);
-            z = rfft::pk_cmadd(x[1], w[1], z);
-            z = rfft::pk_cmadd(x[2], w[2], z);
-            z = rfft::pk_cmadd(x[3], w[3], z);
+            z = zz[e];
           }
           v[rfft::bitrev5(n1)] = z;
         }
@@ -451,27 +455,67 @@ __global__ __launch_bounds__(kT, 4) void k_filter_full16k(Geom g, ChanDev ch, Pl
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       }
-      if constexpr (kRowPlane) {
-        // the same complex product, operand for operand, as pk_cmul forms it below: the same bits
-#pragma unroll
-        for (int n1 = 1; n1 < 32; n1++) v[rfft::bitrev5(n1)] = pk_cmul_s(v[rfft::bitrev5(n1)], srow[n1]);
-      } else if constexpr (PLAIN == 2) {
-        // y (1 + i theta), theta = kb n1: one packed add for theta, one packed fma with the operand swizzle of the N = 65536 path
-        float const kbf = (float)(2.0 * M_PI * 512.0 * r * (double)(t & 63));
-        v2f const kb = (v2f){kbf, kbf};
-        v2f th = (v2f){0.f, 0.f};
-#pragma unroll
-        for (int n1 = 1; n1 < 32; n1++) {
-          v2f const y = pk_cmul(v[rfft::bitrev5(n1)], ld2(sw + n1));
-          th = th + kb;
-          v2f z;
-          asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[0,1,1] neg_lo:[0,1,0]" : "=v"(z) : "v"(y), "v"(th), "v"(y));
-          v[rfft::bitrev5(n1)] = z;
+      // The 31 products go out in blocks of independent ones (rfft::pk_cmul4 and kin), cut where the load batches end (rows
+      // 0-11, 12-21, 22-31; a paired load brings rows 2 r and 2 r + 1), so that each block starts as its rows land:
+      //   1 | 2 3 | 4-7 | 8-11 || 12-15 | 16-19 | 20 21 || 22 23 | 24-27 | 28-31
+      // `mul(first, count)` forms v[n1] *= (row phasor n1) for n1 = first .. first + count - 1 into y[].
+      auto row = [&](int n1) -> v2f & { return v[rfft::bitrev5(n1)]; };
+      auto mul = [&](auto firstc, auto countc, v2f(&y)[4]) {
+        constexpr int n1 = decltype(firstc)::value, K = decltype(countc)::value;
+        if constexpr (kRowPlane) {
+          // the same complex product, operand for operand, as pk_cmul forms it: the same bits
+          if constexpr (K == 4)
+            rfft::pk_cmul_s4(y[0], y[1], y[2], y[3], row(n1), srow[n1], row(n1 + 1), srow[n1 + 1], row(n1 + 2), srow[n1 + 2],
+                             row(n1 + 3), srow[n1 + 3]);
+          else if constexpr (K == 2)
+            rfft::pk_cmul_s2(y[0], y[1], row(n1), srow[n1], row(n1 + 1), srow[n1 + 1]);
+          else
+            y[0] = pk_cmul_s(row(n1), srow[n1]);
+        } else {
+          if constexpr (K == 4)
+            pk_cmul4(y[0], y[1], y[2], y[3], row(n1), ld2(sw + n1), row(n1 + 1), ld2(sw + n1 + 1), row(n1 + 2), ld2(sw + n1 + 2),
+                     row(n1 + 3), ld2(sw + n1 + 3));
+          else if constexpr (K == 2)
+            pk_cmul2(y[0], y[1], row(n1), ld2(sw + n1), row(n1 + 1), ld2(sw + n1 + 1));
+          else
+            y[0] = pk_cmul(row(n1), ld2(sw + n1));
         }
-      } else {
+      };
+      // PLAIN == 2: y (1 + i theta), theta = kb n1: one packed add for theta, one packed fma with the operand swizzle of the
+      // N = 65536 path
+      float const kbf = PLAIN == 2 ? (float)(2.0 * M_PI * 512.0 * r * (double)(t & 63)) : 0.f;
+      v2f const kb = (v2f){kbf, kbf};
+      v2f th = (v2f){0.f, 0.f};
+      auto mix = [&](auto firstc, auto countc) {
+        constexpr int n1 = decltype(firstc)::value, K = decltype(countc)::value;
+        v2f y[4];
+        mul(firstc, countc, y);
 #pragma unroll
-        for (int n1 = 1; n1 < 32; n1++) v[rfft::bitrev5(n1)] = pk_cmul(v[rfft::bitrev5(n1)], ld2(sw + n1));
-      }
+        for (int i = 0; i < K; i++) {
+          if constexpr (PLAIN == 2) {
+            th = th + kb;
+            v2f z;
+            asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[0,1,1] neg_lo:[0,1,0]" : "=v"(z) : "v"(y[i]), "v"(th), "v"(y[i]));
+            row(n1 + i) = z;
+          } else {
+            row(n1 + i) = y[i];
+          }
+        }
+      };
+      using std::integral_constant;
+      constexpr integral_constant<int, 1> k1{};
+      constexpr integral_constant<int, 2> k2{};
+      constexpr integral_constant<int, 4> k4{};
+      mix(integral_constant<int, 1>{}, k1);
+      mix(integral_constant<int, 2>{}, k2);
+      mix(integral_constant<int, 4>{}, k4);
+      mix(integral_constant<int, 8>{}, k4);
+      mix(integral_constant<int, 12>{}, k4);
+      mix(integral_constant<int, 16>{}, k4);
+      mix(integral_constant<int, 20>{}, k2);
+      mix(integral_constant<int, 22>{}, k2);
+      mix(integral_constant<int, 24>{}, k4);
+      mix(integral_constant<int, 28>{}, k4);
     } else if constexpr (!PLAIN) {
       // swept channels, and the first block after a retune (history still on the old oscillator): closed-form phase
       // per sample
@@ -535,11 +579,17 @@ __global__ __launch_bounds__(kT, 4) void k_filter_full16k(Geom g, ChanDev ch, Pl
   {
     // all 31 from the workgroup's LDS copy of the table (two per 16-byte read): no products of table entries
     const float4 *row = reinterpret_cast<const float4 *>(tw2 + (t & 15) * kTw2Pitch);
+    // in blocks of four independent products (rfft::pk_cmul4), two 16-byte reads each; k2 = 0 has no twiddle
 #pragma unroll
-    for (int k2 = 0; k2 < 32; k2 += 2) {
-      float4 const w = row[k2 / 2];
-      if (k2) u[k2] = pk_cmul(u[k2], (v2f){w.x, w.y});
-      u[k2 + 1] = pk_cmul(u[k2 + 1], (v2f){w.z, w.w});
+    for (int k2 = 0; k2 < 32; k2 += 4) {
+      float4 const w = row[k2 / 2], x = row[k2 / 2 + 1];
+      v2f const w0 = (v2f){w.x, w.y}, w1 = (v2f){w.z, w.w}, w2 = (v2f){x.x, x.y}, w3 = (v2f){x.z, x.w};
+      if (k2) {
+        pk_cmul4(u[k2], u[k2 + 1], u[k2 + 2], u[k2 + 3], u[k2], w0, u[k2 + 1], w1, u[k2 + 2], w2, u[k2 + 3], w3);
+      } else {
+        u[1] = pk_cmul(u[1], w1);
+        pk_cmul2(u[2], u[3], u[2], w2, u[3], w3);
+      }
     }
   }
 

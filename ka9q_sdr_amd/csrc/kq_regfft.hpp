@@ -115,6 +115,76 @@ __device__ __forceinline__ v2f pk_cmadd(v2f a, v2f b, v2f c) {
   return d;
 }
 
+// a * b with b in scalar registers: pk_cmul's two instructions with one scalar source each.  (pk_cmul_any leaves the
+// encodings to the compiler, which then builds {-a.y, a.y} in registers: a v_xor_b32 and a v_mov_b32 per product.)
+__device__ __forceinline__ v2f pk_cmul_s(v2f a, v2f b) {
+  v2f t, d;
+  asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[0,1]" : "=v"(t) : "v"(a), "s"(b));
+  asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]" : "=v"(d) : "v"(a), "s"(b), "v"(t));
+  return d;
+}
+
+// ---- block forms: K independent products in ONE asm statement, all first halves, then all second halves.
+// The compiler knows no latency for an asm statement and schedules around none: a run of single products comes out as
+// mul, fma, mul, fma ..., every instruction waiting for the one before it, with an s_nop 0 between the two statements of
+// a product (its hazard recogniser's answer to a register written by one statement and read by the next).  Inside one
+// statement a half's neighbours are the other products' halves and nothing is inserted.  Each product is pk_cmul's (or
+// pk_cmadd's) two instructions on the same operands with the same modifiers -- the same bits; the first half lands in
+// the destination itself, which is early-clobber (the other products' operands are still to be read), so a block holds
+// no registers beyond its results.
+#define KQ_CM_LO "op_sel_hi:[0,1]"
+#define KQ_CM_HI "op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]"
+#define KQ_CMA_LO "op_sel_hi:[0,1,1]"
+#define KQ_DEFINE_CMUL_BLOCKS(NAME, BC)                                                                                      \
+  __device__ __forceinline__ void NAME##2(v2f &d0, v2f &d1, v2f a0, v2f b0, v2f a1, v2f b1) {                                \
+    v2f x0, x1;                                                                                                              \
+    asm("v_pk_mul_f32 %0, %2, %4 " KQ_CM_LO "\n\t"                                                                           \
+        "v_pk_mul_f32 %1, %3, %5 " KQ_CM_LO "\n\t"                                                                           \
+        "v_pk_fma_f32 %0, %2, %4, %0 " KQ_CM_HI "\n\t"                                                                       \
+        "v_pk_fma_f32 %1, %3, %5, %1 " KQ_CM_HI                                                                              \
+        : "=&v"(x0), "=&v"(x1)                                                                                               \
+        : "v"(a0), "v"(a1), BC(b0), BC(b1));                                                                                 \
+    d0 = x0, d1 = x1;                                                                                                        \
+  }                                                                                                                          \
+  __device__ __forceinline__ void NAME##4(v2f &d0, v2f &d1, v2f &d2, v2f &d3, v2f a0, v2f b0, v2f a1, v2f b1, v2f a2,       \
+                                          v2f b2, v2f a3, v2f b3) {                                                          \
+    v2f x0, x1, x2, x3;                                                                                                      \
+    asm("v_pk_mul_f32 %0, %4, %8 " KQ_CM_LO "\n\t"                                                                           \
+        "v_pk_mul_f32 %1, %5, %9 " KQ_CM_LO "\n\t"                                                                           \
+        "v_pk_mul_f32 %2, %6, %10 " KQ_CM_LO "\n\t"                                                                          \
+        "v_pk_mul_f32 %3, %7, %11 " KQ_CM_LO "\n\t"                                                                          \
+        "v_pk_fma_f32 %0, %4, %8, %0 " KQ_CM_HI "\n\t"                                                                       \
+        "v_pk_fma_f32 %1, %5, %9, %1 " KQ_CM_HI "\n\t"                                                                       \
+        "v_pk_fma_f32 %2, %6, %10, %2 " KQ_CM_HI "\n\t"                                                                      \
+        "v_pk_fma_f32 %3, %7, %11, %3 " KQ_CM_HI                                                                             \
+        : "=&v"(x0), "=&v"(x1), "=&v"(x2), "=&v"(x3)                                                                         \
+        : "v"(a0), "v"(a1), "v"(a2), "v"(a3), BC(b0), BC(b1), BC(b2), BC(b3));                                               \
+    d0 = x0, d1 = x1, d2 = x2, d3 = x3;                                                                                      \
+  }
+#define KQ_BC_V(x) "v"(x)
+#define KQ_BC_S(x) "s"(x)
+KQ_DEFINE_CMUL_BLOCKS(pk_cmul, KQ_BC_V)    // pk_cmul2, pk_cmul4:     d_i = a_i * b_i
+KQ_DEFINE_CMUL_BLOCKS(pk_cmul_s, KQ_BC_S)  // pk_cmul_s2, pk_cmul_s4: the same with the b_i in scalar registers
+#undef KQ_DEFINE_CMUL_BLOCKS
+#undef KQ_BC_V
+#undef KQ_BC_S
+// d_i = c_i + a_i * b_i (pk_cmadd); c_i may be the variable d_i refers to
+__device__ __forceinline__ void pk_cmadd2(v2f &d0, v2f &d1, v2f a0, v2f b0, v2f c0, v2f a1, v2f b1, v2f c1) {
+  v2f x0, x1;
+  asm("v_pk_fma_f32 %0, %2, %4, %6 " KQ_CMA_LO "\n\t"
+      "v_pk_fma_f32 %1, %3, %5, %7 " KQ_CMA_LO "\n\t"
+      "v_pk_fma_f32 %0, %2, %4, %0 " KQ_CM_HI "\n\t"
+      "v_pk_fma_f32 %1, %3, %5, %1 " KQ_CM_HI
+      : "=&v"(x0), "=&v"(x1)
+      : "v"(a0), "v"(a1), "v"(b0), "v"(b1), "v"(c0), "v"(c1));
+  d0 = x0, d1 = x1;
+}
+// (No pk_cmadd4: the only run of accumulating products, the unswept N = 65536 mix, is a chain of four per row with two
+// rows in hand.)
+#undef KQ_CM_LO
+#undef KQ_CM_HI
+#undef KQ_CMA_LO
+
 template <int NP, int LEN, int I>
 __device__ __forceinline__ void bfly_pk(v2f (&v)[NP]) {
   constexpr int half = LEN / 2, base = (I / half) * LEN, j = I % half;
@@ -125,6 +195,7 @@ __device__ __forceinline__ void bfly_pk(v2f (&v)[NP]) {
     v[base + j + half] = a - b;
   } else if constexpr (t == 16) {  // w = -i: a +- (b.y, -b.x).  The swap and the sign ride on the operand modifiers; given the
     // vector expression the compiler builds (b.y, -b.x) in registers first (a v_xor_b32 and a v_mov_b32 per butterfly)
+    // (The two as ONE statement -- they are independent of each other -- measured no faster: DESIGN_DIARY.md I, A.1.)
     v2f x, y;
     asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]" : "=v"(x) : "v"(a), "v"(b));
     asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1]" : "=v"(y) : "v"(a), "v"(b));

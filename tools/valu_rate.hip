@@ -1,7 +1,8 @@
 // valu_rate.hip -- issue rate of the vector instructions the FFT kernels are made of, per SIMD, on the device at hand.
 //   hipcc -O3 --offload-arch=gfx950 tools/valu_rate.hip -o /tmp/valu_rate && /tmp/valu_rate
 // Every wave runs a loop of 8 independent instructions of one kind (no dependent issue stalls); one workgroup per CU with
-// 1, 2 or 4 waves per SIMD.  Cycles are counted by the shader's own clock counter (s_memtime) inside every wave -- mean
+// 1, 2 or 4 waves per SIMD.  The first ten kinds issue every instruction as an asm statement of its own, the "one statement"
+// kinds put the same 8 into a single statement, and the cmul kinds time the complex product as the kernels write it.  Cycles are counted by the shader's own clock counter (s_memtime) inside every wave -- mean
 // (min-max) over the waves of [cycles the wave ran / instructions its SIMD issued meanwhile] -- and the frequency the
 // counter ran at comes from the constant 100 MHz counter (s_memrealtime) beside it.
 #include <hip/hip_runtime.h>
@@ -32,6 +33,67 @@ __global__ __launch_bounds__(1024) void k(float *out, int iters, float seed, uns
       if (KIND == 7) asm volatile("v_add_f32 %0, %0, %1" : "+v"(f[i]) : "v"(b.x));
       if (KIND == 8) asm volatile("v_mov_b32 %0, %1" : "+v"(f[i]) : "v"(b.x));
       if (KIND == 9) asm volatile("v_pk_add_f32 %0, %1, %2" : "+v"(a[i]) : "v"(a[(i + 1) & 7]), "v"(a[(i + 3) & 7]));
+    }
+    // The same 8 independent instructions inside ONE asm statement: the compiler's hazard recogniser does not look into a
+    // statement, so nothing stands between them (between two statements it puts an s_nop 0 wherever the second one reads a
+    // register the first one wrote -- as every in-place kind above does from one iteration to the next, 8 statements apart).
+#define KQ_RATE8(INS, TAIL)                                                                                                    \
+  asm volatile(INS " %0, %0, " TAIL "\n\t" INS " %1, %1, " TAIL "\n\t" INS " %2, %2, " TAIL "\n\t" INS " %3, %3, " TAIL "\n\t" \
+               INS " %4, %4, " TAIL "\n\t" INS " %5, %5, " TAIL "\n\t" INS " %6, %6, " TAIL "\n\t" INS " %7, %7, " TAIL        \
+               : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]), "+v"(x[7])                \
+               : "v"(y), "v"(z))
+    if (KIND == 10) {
+      auto &x = f;
+      float const y = b.x, z = c.x;
+      KQ_RATE8("v_fma_f32", "%8, %9");
+    }
+    if (KIND == 11) {
+      auto &x = a;
+      v2f const y = b, z = c;
+      KQ_RATE8("v_pk_fma_f32", "%8, %9");
+    }
+    if (KIND == 12) {
+      auto &x = a;
+      v2f const y = b, z = c;
+      KQ_RATE8("v_pk_fma_f32", "%8, %9 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]");
+    }
+    if (KIND == 13) {
+      auto &x = a;
+      v2f const y = b, z = c;
+      KQ_RATE8("v_pk_mul_f32", "%8 op_sel_hi:[0,1]");
+      (void)z;
+    }
+#undef KQ_RATE8
+    // The complex product a[i] *= b itself, 8 instructions per iteration both ways.
+    if (KIND == 14) {  // as rfft::pk_cmul stands: two statements, the second reads the first one's result, product after product
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        v2f t;
+        asm volatile("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[0,1]" : "=v"(t) : "v"(a[i]), "v"(b));
+        asm volatile("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]" : "=v"(a[i]) : "v"(a[i]), "v"(b), "v"(t));
+      }
+    }
+    if (KIND == 15) {  // the same four products with every a[i] depending on the one before: twiddle32's chain
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        v2f t;
+        asm volatile("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[0,1]" : "=v"(t) : "v"(a[0]), "v"(b));
+        asm volatile("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]" : "=v"(a[0]) : "v"(a[0]), "v"(b), "v"(t));
+      }
+    }
+    if (KIND == 16) {  // rfft::pk_cmul4: four products in one statement, the four first halves, then the four second halves
+      // (in place with early-clobber temporaries here, so that the loop carries no register moves)
+      v2f t0, t1, t2, t3;
+      asm volatile("v_pk_mul_f32 %4, %0, %8 op_sel_hi:[0,1]\n\t"
+                   "v_pk_mul_f32 %5, %1, %8 op_sel_hi:[0,1]\n\t"
+                   "v_pk_mul_f32 %6, %2, %8 op_sel_hi:[0,1]\n\t"
+                   "v_pk_mul_f32 %7, %3, %8 op_sel_hi:[0,1]\n\t"
+                   "v_pk_fma_f32 %0, %0, %8, %4 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]\n\t"
+                   "v_pk_fma_f32 %1, %1, %8, %5 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]\n\t"
+                   "v_pk_fma_f32 %2, %2, %8, %6 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]\n\t"
+                   "v_pk_fma_f32 %3, %3, %8, %7 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]"
+                   : "+&v"(a[0]), "+&v"(a[1]), "+&v"(a[2]), "+&v"(a[3]), "=&v"(t0), "=&v"(t1), "=&v"(t2), "=&v"(t3)
+                   : "v"(b));
     }
   }
   float s = 0;
@@ -88,5 +150,12 @@ int main() {
   run<3>("v_pk_mul_f32 op_sel_hi (cmul form)");
   run<4>("v_pk_add_f32 acc,b");
   run<9>("v_pk_add_f32 two other VGPR pairs");
+  run<10>("one statement: 8 v_fma_f32");
+  run<11>("one statement: 8 v_pk_fma_f32");
+  run<12>("one statement: 8 v_pk_fma_f32 (cmul form)");
+  run<13>("one statement: 8 v_pk_mul_f32 (cmul form)");
+  run<14>("cmul, two statements each, 4 independent");
+  run<15>("cmul, two statements each, 4 in a chain");
+  run<16>("cmul, 4 per statement: 4 mul, then 4 fma");
   return 0;
 }
