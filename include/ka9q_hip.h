@@ -1494,6 +1494,136 @@ int kq_cw_sync(kq_cw_bank *bank);
 /* Stream index back to 0; every slot restarts cold with its settings at the next call, as if set again */
 int kq_cw_reset(kq_cw_bank *bank);
 
+/* --- RTTY (start-stop FSK teleprinter) decoder bank -----------------------------------------------------------------------
+ * Up to 16384 decoder slots, each reading two-tone FSK with asynchronous framing (one start bit, 5 to 8 data bits, a stop
+ * element) from one audio row, as characters: amateur RTTY (45.45 baud, 170 Hz shift), the weather services' 50 baud with
+ * 450 Hz, 75 baud links with 850 Hz.  A receiver bank's USB / LSB channels can be decoded in place on its stream after
+ * kq_bank_join, and several slots may read one row at different tone pairs.  The reference has no RTTY decoder: the
+ * algorithm is defined here.  Everything after the quantiser is exact integer arithmetic, so no result depends on how sums
+ * are ordered or how the stream is cut into calls.
+ * Per slot, x[n] is its input row; n counts samples since create or kq_rtty_reset on a grid shared by every slot, and
+ * x[n] = 0 before the slot was set.  Fs = samprate, B = block_len (8..256); frame k is the samples [k B, (k + 1) B).
+ *   quantise   kq_cw_*'s: q[n] = clamp(rint(x[n] input_scale), -32767, 32767), one float multiply, round to nearest even,
+ *              NaN reads as 0; a KQ_PCM_S16BE word is taken as q itself, -32768 as -32767.
+ *   table      kq_cw_*'s: C[j] = rint(32767 cos(2 pi j / 1024)) as int16 (kq_rtty_get_table).
+ *   correlate  per tone inc = rint(f 2^32 / Fs) in double, f the float of the params (inc_m of mark, inc_s of space:
+ *              kq_rtty_get_slot); ph(n) = (n inc) mod 2^32 -- no oscillator state is carried -- and j = ph(n) >> 22.  Per
+ *              frame and tone I = sum q[n] C[j], Q = sum q[n] C[(j - 256) & 1023]: exact integers in 64 bits, |I|, |Q| <
+ *              2^38.  They are reduced as a = I >> 12, b = Q >> 12 (arithmetic shifts): |a|, |b| < 2^26.
+ *   bit        tb = rint(256 Fs / (B baud)) in double, baud the float of the params: the bit in 1/256 frame, 2048 <= tb <=
+ *              8192 (8 to 32 frames in a bit).  W = (tb + 128) >> 8 frames, 8..32.
+ *   window     per tone SI[k], SQ[k]: the sums of a and b over the frames k - W + 1 .. k, zeros before the set; below 2^31
+ *              in magnitude.  Pm = SIm^2 + SQm^2, Ps likewise, as uint64 (below 2^63): a matched filter one bit long, read
+ *              out every frame, coherent because the reference phase depends on n alone.
+ *   state      sig, nse (uint64), state (0 WAIT, 1 IDLE, 2 CHAR), t (signed, in 1/256 frame), bit, code, start (a frame
+ *              number), the counters.  At the set all of it is zero.
+ *   step       one per completed frame k, in this order:
+ *     1 count     frames += 1, saturating.  hi = max(Pm, Ps), lo = min(Pm, Ps), lev = Pm >= Ps (1 is mark).
+ *     2 levels    samp = state == CHAR and t - 256 < 128: this frame samples a bit.  If state != CHAR: sig += (hi - sig)
+ *                 >> 6, nse += (lo - nse) >> 6.  If samp: the same with >> 4.  Otherwise (inside a character, between its
+ *                 sampling points, where the window straddles two bits) they stand.  Arithmetic shifts of signed
+ *                 differences.
+ *     3 validity  valid = frames >= warm and sig >= min_p and 16 sig >= nse snr, the products taken exactly (they need up
+ *                 to 75 bits: two words).  If not valid: state = WAIT, and the step ends (t, bit, code stand).
+ *     4 framer    WAIT: if lev == 1, state = IDLE.
+ *                 IDLE: if lev == 0, state = CHAR, t = tb >> 1, bit = -1, code = 0, start = k (the window's output
+ *                 crosses half a bit behind the edge and is best a whole bit behind it).
+ *                 CHAR: t -= 256; if samp, t += tb and the bit is read: with bit == -1 (the start bit) lev == 1 counts
+ *                 false_starts += 1 and state = IDLE, lev == 0 makes bit = 0; with bit < nbits, code |= lev << bit and
+ *                 bit += 1 (the first data bit sent is the lowest); with bit == nbits (the stop element, one bit behind
+ *                 the last data bit) the character is filed: lev == 1 with flags 0 and state = IDLE, lev == 0 with flags 1
+ *                 (framing error), ferr += 1 and state = WAIT, so that a long space (a break) files once.
+ *   event      code, flags, start_sample = start B, sig, nse.  events += 1 for each; it goes to the slot's arena, or
+ *              dropped += 1 when that holds max_events.  The device hands out raw codes: letters / figures, unshift on
+ *              space and the alphabets are the client's (ka9q_sdr_amd/baudot.py).  events, dropped, ferr and false_starts
+ *              saturate at 2^32 - 1, as frames does.
+ * kq_rtty_remove and kq_rtty_reset discard the open character.  Carried between calls: per tone the open frame's I and Q,
+ * the reduced sums of the last 31 frames (W - 1 at the most), the four window sums, and the level and framer state; so the
+ * same stream split differently into calls or blocks gives the same events and status.  kq_rtty_status holds all of it but
+ * the past frames.
+ * A reversed signal is served by swapping mark and space in the params; there is no device flag for it.
+ * Limits (refused by kq_rtty_create / kq_rtty_set with the reason in kq_last_error, before any HIP call): samprate positive
+ * and finite; 8 <= B <= 256; warm 0..65535; snr 16..4095; min_p <= 2^55; input_scale > 0; max_slots 1..16384; max_events
+ * 1..4096; max_samples 1..2^28; per slot 0 < mark, space < Fs / 2, mark != space, nbits 5..8, baud positive and finite
+ * with 2048 <= tb <= 8192.
+ * Device memory per slot: 32 max_events of arena, 640 of state, history and parameters; 2 KiB of table per bank.
+ * Copying off-air signals has not been measured.  There is no AFC on the tone pair, no per-tone threshold correction under
+ * selective fading, and a start bit is found from a single frame's level: at an Eb/N0 of 12 dB and below the model loses
+ * characters by the tens of per cent.
+ * Calls: as kq_cw_*.  kq_rtty_create, kq_rtty_set and kq_rtty_remove touch no device. */
+typedef struct kq_rtty_bank kq_rtty_bank;
+typedef struct kq_rtty_config {
+  int device;
+  double samprate;           /* Fs: input samples per second; a double, so that 39 062.5 is exact */
+  unsigned block_len;        /* B: samples per frame, 8..256 */
+  unsigned warm;             /* frames after the set in which nothing is read while the levels train (64) */
+  unsigned snr;              /* least sig / nse, in sixteenths (96: a ratio of 6; noise alone gives about 3) */
+  uint64_t min_p;            /* least sig (65536) */
+  float input_scale;         /* 32767 suits audio of full scale 1 */
+  unsigned max_slots;        /* slots 0 .. max_slots - 1 (limit 16384) */
+  unsigned max_events;       /* arena places per slot between kq_rtty_clear_events calls */
+  size_t max_samples;        /* largest nblocks * block_len of one kq_rtty_process call */
+  void *stream;              /* hipStream_t, NULL = own stream; kq_bank_stream(bank) puts it beside a receiver bank */
+} kq_rtty_config;
+typedef struct kq_rtty_params {
+  unsigned source;           /* input row this slot decodes (a receiver bank's channel index) */
+  float mark, space;         /* Hz */
+  float baud;
+  unsigned nbits;            /* data bits in a character, 5..8 */
+} kq_rtty_params;
+typedef struct kq_rtty_status {
+  uint32_t frames;           /* completed since the slot was set */
+  uint32_t state;            /* 0 WAIT, 1 IDLE, 2 CHAR */
+  int32_t bit;               /* the next to be read: -1 the start bit, nbits the stop element */
+  uint32_t code;             /* of the open character */
+  int32_t t;                 /* 1/256 frame to the next sampling point */
+  uint32_t events;           /* filed since the set, those dropped included */
+  uint32_t dropped;
+  uint32_t ferr;             /* characters filed with a framing error */
+  uint32_t false_starts;
+  uint32_t reserved;         /* 0 */
+  uint64_t sig, nse;         /* the levels: of slots on one row the largest sig / nse is on the signal */
+  uint64_t start;            /* frame number at which the open (or last) character began */
+  int32_t sum_im, sum_qm, sum_is, sum_qs;   /* the window sums at the last completed frame */
+  int64_t acc_im, acc_qm, acc_is, acc_qs;   /* I and Q of the open frame */
+} kq_rtty_status;
+typedef struct kq_rtty_event {
+  uint32_t code;
+  uint32_t flags;            /* bit 0: framing error (the stop element read space) */
+  uint64_t start_sample;     /* the frame at which the start bit was seen, times B: half a bit behind its edge */
+  uint64_t sig, nse;         /* the levels at the stop element */
+} kq_rtty_event;
+typedef struct kq_rtty_slot {
+  uint32_t inc_m, inc_s;     /* the phase increments of mark and space */
+  uint32_t tb;               /* the bit in 1/256 frame */
+  uint32_t W;                /* the window in frames */
+} kq_rtty_slot;
+
+kq_rtty_bank *kq_rtty_create(const kq_rtty_config *cfg);
+int kq_rtty_destroy(kq_rtty_bank *bank);
+/* Put a decoder in `slot` (or replace the one there): a cold start at the next call's first sample, its arena empty.
+ * Touches no device: the next kq_rtty_process, kq_rtty_pull_counts or kq_rtty_pull_event brings every slot set or removed
+ * since the last one there, and waits for the handle's stream to do so (once, however many slots changed). */
+int kq_rtty_set(kq_rtty_bank *bank, unsigned slot, const kq_rtty_params *params);
+/* The slot stops from the next call; its arena stays readable.  Touches no device either */
+int kq_rtty_remove(kq_rtty_bank *bank, unsigned slot);
+/* Input, status and on_device as in kq_cw_process (status may be NULL; nothing is written for an empty slot). */
+int kq_rtty_process(kq_rtty_bank *bank, const void *src, int format, size_t src_stride, size_t row_stride, unsigned block_len,
+                    unsigned nblocks, int on_device, kq_rtty_status *status, size_t status_stride);
+/* Events in every slot's arena, counts[max_slots], in one copy; synchronous */
+int kq_rtty_pull_counts(kq_rtty_bank *bank, uint32_t *counts);
+/* Copies event `index` of `slot`; returns 0, or -1 */
+int kq_rtty_pull_event(kq_rtty_bank *bank, unsigned slot, unsigned index, kq_rtty_event *event);
+/* Empties every arena (on the handle's stream); the status counters and the open characters go on */
+int kq_rtty_clear_events(kq_rtty_bank *bank);
+/* C (at most cap words); returns 1024 */
+int kq_rtty_get_table(const kq_rtty_bank *bank, int16_t *dst, size_t cap);
+/* inc_m, inc_s, tb and W of `slot`, without a device; -1 when the slot holds no decoder */
+int kq_rtty_get_slot(kq_rtty_bank *bank, unsigned slot, kq_rtty_slot *out);
+int kq_rtty_sync(kq_rtty_bank *bank);
+/* Stream index back to 0; every slot restarts cold with its settings at the next call, as if set again */
+int kq_rtty_reset(kq_rtty_bank *bank);
+
 /* --- rational resampler bank ----------------------------------------------------------------------------------------------
  * Up to 65536 slots, each one row of PCM (mono or stereo) resampled from Fi = in_rate_num / in_rate_den Hz (a receiver
  * bank's samprate and decimate, so 39 062.5 Hz is exact) to Fo = out_rate Hz: kq_afsk_*, RTP PCM and the players are 48 kHz,

@@ -44,5 +44,7 @@ from .tone import ToneBank, ToneParams, tone_params  # noqa: F401,E402  (tone.ST
 from . import selcall  # noqa: F401,E402
 from .cw import CwBank, CwParams, cw_params  # noqa: F401,E402  (cw.STATUS_DTYPE: the Morse decoder's)
 from . import morse  # noqa: F401,E402
+from .rtty import RttyBank, RttyParams, rtty_params  # noqa: F401,E402  (rtty.STATUS_DTYPE: the RTTY decoder's)
+from . import baudot  # noqa: F401,E402
 from .monitor import KQ_MON_F32, KQ_MON_S16BE, MonBank, MonParams, mon_params  # noqa: F401,E402  (monitor.STATUS_DTYPE: the mixer's)
 from .resample import RsmpBank, RsmpParams, rsmp_params  # noqa: F401,E402

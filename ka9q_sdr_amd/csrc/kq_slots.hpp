@@ -1,4 +1,4 @@
-// kq_slots.hpp -- the host half that the slot banks share (kq_wfm, kq_rds, kq_fsk, kq_pag, kq_tone, kq_cw, kq_rsmp: up to max_slots decoders, each on
+// kq_slots.hpp -- the host half that the slot banks share (kq_wfm, kq_rds, kq_fsk, kq_pag, kq_tone, kq_cw, kq_rtty, kq_rsmp: up to max_slots decoders, each on
 // a source row of the call's input, set and removed one at a time, processed together): the slot table and its device copy, the
 // staging of a host-memory call's distinct source rows, the copy-back of the active slots' rows, and the bodies of the entry
 // points that do not differ from bank to bank.  On top of kq::HostSide (kq_host.hpp); host only.  The kernels, their
