@@ -31,22 +31,21 @@
 #include "kq_device.hpp"
 #include "kq_host.hpp"
 #include "kq_slots.hpp"
+#include "kq_tonecorr.hpp"
 
 namespace {
 
+using kq::tonecorr::kTable;
 constexpr unsigned kMaxSlots = 16384;
-constexpr int kTable = 1024;
 constexpr int kThreads = 256, kWaves = kThreads / 64;
 constexpr int kTile = 4288;                     // samples a wave keeps in LDS: 64 frames of B = 64 at stride 66, and a few more
 constexpr unsigned kRunMax = 0x0FFFFFFFu;
 
 struct CwGeom {
-  int B, Bs;                     // Bs: a frame's stride in LDS, >= B, Bs / 2 odd
-  unsigned magic;                // ceil(2^32 / B): x / B = umulhi(x, magic) for x < 2^16
+  kq::tonecorr::FrameGrid grid;
   unsigned deb, warm, snr, u_min, u_max;
   unsigned long long min_p;
   int max_events;
-  float scale;
 };
 
 struct CwPar {  // per slot, written by the host when a call finds the slot set anew
@@ -59,7 +58,7 @@ struct CallArgs {
   CwGeom g;
   const CwPar *par;
   const int *list;               // active slots, ascending
-  const int *rowmap;             // per list entry: the row of `src` (host input, staged) or null (par.source)
+  const int *rowmap;             // per list entry: the row of in.src (host input, staged) or null (par.source)
   const short *table;            // [1024]
   kq_cw_status *state;           // [S]
   kq_cw_event *ev;               // [S][max_events]
@@ -67,29 +66,11 @@ struct CallArgs {
   int nlist;
   int L;                         // lanes to a frame, a power of two <= 64
   int64_t n0, n1;                // the call's samples
-  // input
-  const void *src;
-  int format;
-  size_t src_stride, row_stride;
-  unsigned block_len;
+  kq::PcmIn in;
   // output
   kq_cw_status *st;
   size_t sstride;
 };
-
-// q of the call's i-th sample (i < 2^28)
-__device__ __forceinline__ int load_q(CallArgs const &a, size_t row, unsigned i) {
-  unsigned const k = i / a.block_len, j = i - k * a.block_len;
-  size_t const idx = row * a.src_stride + (size_t)k * a.row_stride + j;
-  if (a.format == KQ_PCM_S16BE) {
-    const unsigned char *p = reinterpret_cast<const unsigned char *>(a.src) + 2 * idx;
-    int const w = (int)(short)(unsigned short)(((unsigned)p[0] << 8) | p[1]);
-    return w < -32767 ? -32767 : w;
-  }
-  float const v = rintf(reinterpret_cast<const float *>(a.src)[idx] * a.g.scale);
-  if (!(v == v)) return 0;
-  return (int)fminf(fmaxf(v, -32767.f), 32767.f);
-}
 
 __device__ __forceinline__ void file_event(CwGeom const &g, kq_cw_status &s, unsigned code, unsigned nelem,
                                            unsigned long long start, unsigned long long end, kq_cw_event *ev, unsigned &nev) {
@@ -103,8 +84,8 @@ __device__ __forceinline__ void file_event(CwGeom const &g, kq_cw_status &s, uns
   r.nelem = nelem;
   r.unit = s.unit;
   r.reserved = 0;
-  r.start_sample = start * (unsigned long long)g.B;
-  r.end_sample = end * (unsigned long long)g.B;
+  r.start_sample = start * (unsigned long long)g.grid.B;
+  r.end_sample = end * (unsigned long long)g.grid.B;
   r.peak = s.hi;
   ev[nev++] = r;
 }
@@ -181,12 +162,11 @@ __global__ __launch_bounds__(kThreads) void k_cw(CallArgs c) {
   int const tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = (int)blockIdx.x * kWaves + wave;
   bool const live = li < c.nlist;
   int const slot = live ? c.list[li] : 0;
-  for (int i = tid; i < kTable; i += kThreads)
-    CS[i] = ((int)c.table[i] & 0xFFFF) | ((int)c.table[(i - 256) & (kTable - 1)] << 16);
+  kq::tonecorr::load_packed_table(CS, c.table, tid, kThreads);
   CwPar const par = c.par[slot];
   size_t const row = live && c.rowmap ? (size_t)c.rowmap[li] : (size_t)par.source;
-  int const B = g.B, L = c.L, F = 64 / L, f = lane / L, p = lane & (L - 1);
-  unsigned const inc = par.inc, step = (unsigned)L * inc;
+  int const B = g.grid.B, L = c.L, F = 64 / L, f = lane / L, p = lane & (L - 1);
+  unsigned const inc[1] = {par.inc};
   // carried: lane 0 holds the record, the open frame's I and Q in it
   kq_cw_status s{};
   unsigned nev = 0;
@@ -195,78 +175,41 @@ __global__ __launch_bounds__(kThreads) void k_cw(CallArgs c) {
     s = c.state[slot];
     nev = c.nev[slot];
   }
-  long long cI = s.acc_i, cQ = s.acc_q;
-  short *q = qs[wave];
+  long long cy[2] = {s.acc_i, s.acc_q};
   int64_t n = c.n0, k0 = c.n0 / B;
   while (n < c.n1) {  // one piece: the frames k0 .. k0 + F - 1, from n to their end or the call's; x counts from k0 B
     int64_t const pe = (k0 + F) * (int64_t)B, e = pe < c.n1 ? pe : c.n1;
     int const x0 = (int)(n - k0 * B), x1 = x0 + (int)(e - n);  // x1 <= F B
-    __syncthreads();  // the piece before is done with q, Pb and carry (and the first finds CS loaded)
-    if (live) {
-      for (int x = x0 + lane; x < x1; x += 64) {
-        unsigned const fr = __umulhi((unsigned)x, g.magic);
-        q[fr * g.Bs + ((unsigned)x - fr * (unsigned)B)] = (short)load_q(c, row, (unsigned)(n - c.n0) + (unsigned)(x - x0));
-      }
-    }
-    __syncthreads();
-    long long sI = 0, sQ = 0;
-    int const xa = x0 > f * B ? x0 : f * B, xb = x1 < (f + 1) * B ? x1 : (f + 1) * B;
-    if (live) {
-      unsigned ph = ((unsigned)(k0 * B) + (unsigned)(xa + p)) * inc;  // (n inc) mod 2^32 needs n mod 2^32 only
-      const short *qf = q + f * (g.Bs - B);
-      for (int x = xa + p; x < xb; x += L, ph += step) {
-        int const v = qf[x], cs = CS[ph >> 22];
-        sI += (long long)v * (short)cs;
-        sQ += (long long)v * (cs >> 16);
-      }
-    }
-    for (int off = L >> 1; off; off >>= 1) {
-      sI += __shfl_xor(sI, off);
-      sQ += __shfl_xor(sQ, off);
-    }
-    if (lane == 0) {  // frame 0 of the call's first piece goes on from the carried sums
-      sI += cI;
-      sQ += cQ;
-      cI = cQ = 0;
-    }
-    int const done = (int)__umulhi((unsigned)x1, g.magic);  // frames of the piece that are complete
+    long long sm[2];  // (its first barrier: the piece before is done with q, Pb and carry)
+    kq::tonecorr::correlate_piece<1>(g.grid, c.in, row, live, lane, L, c.n0, n, k0, x0, x1, qs[wave], CS, inc, sm, cy);
+    int const done = (int)__umulhi((unsigned)x1, g.grid.magic);  // frames of the piece that are complete
     if (p == 0 && f * B < x1) {
       if (f < done) {
-        long long const a = sI >> 15, b = sQ >> 15;
+        long long const a = sm[0] >> 15, b = sm[1] >> 15;
         Pb[wave][f] = (unsigned long long)(a * a) + (unsigned long long)(b * b);
       } else {  // the call ends inside frame f
-        carry[wave][0] = sI;
-        carry[wave][1] = sQ;
+        carry[wave][0] = sm[0];
+        carry[wave][1] = sm[1];
       }
     }
     __syncthreads();
     if (live && lane == 0) {
       for (int i = 0; i < done; i++) track(g, s, Pb[wave][i], (unsigned long long)(k0 + i), ev, nev);
       if (done * B < x1) {
-        cI = carry[wave][0];
-        cQ = carry[wave][1];
+        cy[0] = carry[wave][0];
+        cy[1] = carry[wave][1];
       }
     }
     n = e;
     k0 += F;
   }
   if (live && lane == 0) {
-    s.acc_i = cI;
-    s.acc_q = cQ;
+    s.acc_i = cy[0];
+    s.acc_q = cy[1];
     c.state[slot] = s;
     c.nev[slot] = nev;
     if (c.st) c.st[(size_t)slot * c.sstride] = s;
   }
-}
-
-// C[j] = rint(32767 cos(2 pi j / 1024)), made once
-std::vector<short> const &cos_table() {
-  static std::vector<short> const table = [] {
-    std::vector<short> t((size_t)kTable);
-    for (int j = 0; j < kTable; j++) t[j] = (short)std::lrint(32767.0 * std::cos(2.0 * M_PI * j / kTable));
-    return t;
-  }();
-  return table;
 }
 
 // the dot of `wpm` in sixteenths of a frame
@@ -275,35 +218,23 @@ double unit_of(double Fs, unsigned B, float wpm) { return 19.2 * Fs / ((double)B
 }  // namespace
 
 struct kq_cw_bank : kq::HostSide {
+  static constexpr bool kDeferred = true;
   kq_cw_config cfg;
   std::mutex mu;
   bool dev_ready = false;
   CwGeom g{};
   int Lmin = 1;                  // the least lanes to a frame whose piece fits kTile
   uint64_t n_cur = 0;
-  // kq_cw_set and kq_cw_remove touch no device: they change `want`, and the next call that needs the device brings the
-  // slots in `dirty` there (a cold start for each that is set)
-  std::vector<CwPar> want;
-  std::vector<unsigned> dirty;
-  std::vector<char> is_dirty;
-  size_t nwant = 0;              // active entries of `want`
+  kq::DeferredSlots<CwPar> def;
   struct Dev {  // kq::lazy_device
     kq::SlotTable<CwPar> slots;
     short *table = nullptr;
     kq_cw_status *state = nullptr;
-    kq_cw_event *ev = nullptr;
-    unsigned *nev = nullptr;
+    kq::EventArena<kq_cw_event> arena;
     kq_cw_status *st = nullptr;          // host-memory calls
   } d;
 
-  // no device yet and no slot that wants one: the entry points then ask for none
-  bool deviceless() const { return !dev_ready && nwant == 0; }
-
-  void touch(unsigned slot) {
-    if (is_dirty[slot]) return;
-    is_dirty[slot] = 1;
-    dirty.push_back(slot);
-  }
+  int to_device();
 };
 
 namespace {
@@ -312,54 +243,32 @@ int make_device(kq_cw_bank *b) {
   auto &d = b->d;
   if (b->open_stream(b->cfg.stream)) return -1;
   size_t const S = b->cfg.max_slots;
-  if (d.slots.alloc(*b, S) || b->alloc(&d.table, (size_t)kTable) || b->alloc(&d.state, S, true) ||
-      b->alloc(&d.ev, S * (size_t)b->g.max_events) || b->alloc(&d.nev, S, true))
+  if (d.slots.alloc(*b, S) || kq::tonecorr::alloc_table(*b, &d.table) || b->alloc(&d.state, S, true) ||
+      d.arena.alloc(*b, S, b->cfg.max_events))
     return -1;
-  KQ_TRY(hipMemcpyAsync(d.table, cos_table().data(), kTable * sizeof(short), hipMemcpyHostToDevice, b->stream));
   KQ_TRY(hipStreamSynchronize(b->stream));
   return 0;
 }
-
-// The slots that were set or removed since the last call, to the device: the record of a slot that is set starts cold
-// (the header's state at the set) and its arena empty.  Waits for the stream first and last.  Without a device and
-// without a slot that wants one nothing happens.
-int flush(kq_cw_bank *b) {
-  if (b->dirty.empty()) return 0;
-  auto forget = [b] {
-    for (unsigned s : b->dirty) b->is_dirty[s] = 0;
-    b->dirty.clear();
-  };
-  if (b->deviceless()) {
-    forget();
-    return 0;
-  }
-  if (kq::lazy_device(b, make_device)) return -1;
-  KQ_TRY(hipStreamSynchronize(b->stream));
-  auto &t = b->d.slots;
-  std::vector<kq_cw_status> cold(b->dirty.size());  // lives until upload() has waited
-  for (size_t i = 0; i < b->dirty.size(); i++) {
-    unsigned const s = b->dirty[i];
-    t.par[s] = b->want[s];
-    if (t.par[s].active) {
-      kq_cw_status &r = cold[i];
-      std::memset(&r, 0, sizeof r);
-      r.unit = t.par[s].u0;
-      r.code = 1;
-      r.flags = 3;
-      KQ_TRY(hipMemcpyAsync(b->d.state + s, &r, sizeof r, hipMemcpyHostToDevice, b->stream));
-      KQ_TRY(hipMemsetAsync(b->d.nev + s, 0, sizeof(unsigned), b->stream));
-    }
-    if (i + 1 < b->dirty.size())
-      KQ_TRY(hipMemcpyAsync(t.d_par + s, &t.par[s], sizeof(CwPar), hipMemcpyHostToDevice, b->stream));
-  }
-  if (t.upload(*b, b->dirty.back())) return -1;  // the last record, the active list, and the wait
-  forget();
-  return 0;
-}
-
-bool in_range(unsigned v, unsigned lo, unsigned hi) { return v >= lo && v <= hi; }
 
 }  // namespace
+
+// kq::DeferredSlots::flush; the record of a slot that is set starts cold (the header's state at the set: its own u0, an
+// empty character, both gaps reported) and its arena empty
+int kq_cw_bank::to_device() {
+  std::vector<kq_cw_status> cold(def.dirty.size());  // all zero; a run's records are copied from here
+  size_t used = 0;
+  return def.flush(this, make_device, [&](size_t s0, size_t n) {
+    kq_cw_status *r = cold.data() + used;
+    used += n;
+    for (size_t i = 0; i < n; i++) {
+      r[i].unit = d.slots.par[s0 + i].u0;
+      r[i].code = 1;
+      r[i].flags = 3;
+    }
+    KQ_TRY(hipMemcpyAsync(d.state + s0, r, n * sizeof *r, hipMemcpyHostToDevice, stream));
+    return d.arena.clear(*this, s0, n);
+  });
+}
 
 extern "C" {
 
@@ -370,14 +279,7 @@ kq_cw_bank *kq_cw_create(const kq_cw_config *cfg) {
     return nullptr;
   }
   double const Fs = cfg->samprate;
-  if (!(Fs > 0) || !std::isfinite(Fs)) {
-    kq_internal_set_error("%s: samprate %.10g must be positive and finite", fn, Fs);
-    return nullptr;
-  }
-  if (!in_range(cfg->block_len, 8, 4096)) {
-    kq_internal_set_error("%s: block_len %u must be 8..4096", fn, cfg->block_len);
-    return nullptr;
-  }
+  if (!kq::samprate_ok(fn, Fs) || !kq::field_in_range(fn, "block_len", cfg->block_len, 8, 4096)) return nullptr;
   if (!(cfg->min_wpm > 0) || !std::isfinite(cfg->max_wpm) || !(cfg->min_wpm <= cfg->max_wpm)) {
     kq_internal_set_error("%s: speeds %g..%g WPM must be positive, finite and in order", fn, (double)cfg->min_wpm,
                           (double)cfg->max_wpm);
@@ -394,48 +296,17 @@ kq_cw_bank *kq_cw_create(const kq_cw_config *cfg) {
                           (double)cfg->min_wpm, hi, cfg->block_len);
     return nullptr;
   }
-  if (!in_range(cfg->deb, 1, 16)) {
-    kq_internal_set_error("%s: deb %u must be 1..16", fn, cfg->deb);
+  if (!kq::field_in_range(fn, "deb", cfg->deb, 1, 16) || !kq::field_in_range(fn, "warm", cfg->warm, 0, 65535) ||
+      !kq::field_in_range(fn, "snr", cfg->snr, 16, 4095) || !kq::min_p_ok(fn, cfg->min_p) ||
+      !kq::input_scale_ok(fn, cfg->input_scale) || !kq::field_in_range(fn, "max_slots", cfg->max_slots, 1, kMaxSlots) ||
+      !kq::field_in_range(fn, "max_events", cfg->max_events, 1, 4096) || !kq::max_samples_ok(fn, cfg->max_samples))
     return nullptr;
-  }
-  if (cfg->warm > 65535) {
-    kq_internal_set_error("%s: warm %u must be 0..65535", fn, cfg->warm);
-    return nullptr;
-  }
-  if (!in_range(cfg->snr, 16, 4095)) {
-    kq_internal_set_error("%s: snr %u must be 16..4095", fn, cfg->snr);
-    return nullptr;
-  }
-  if (cfg->min_p > (1ull << 55)) {
-    kq_internal_set_error("%s: min_p %llu must be 0..2^55", fn, (unsigned long long)cfg->min_p);
-    return nullptr;
-  }
-  if (!std::isfinite(cfg->input_scale) || !(cfg->input_scale > 0)) {
-    kq_internal_set_error("%s: input_scale must be finite and positive", fn);
-    return nullptr;
-  }
-  if (!in_range(cfg->max_slots, 1, kMaxSlots)) {
-    kq_internal_set_error("%s: max_slots %u must be 1..%u", fn, cfg->max_slots, kMaxSlots);
-    return nullptr;
-  }
-  if (!in_range(cfg->max_events, 1, 4096)) {
-    kq_internal_set_error("%s: max_events %u must be 1..4096", fn, cfg->max_events);
-    return nullptr;
-  }
-  if (cfg->max_samples == 0 || cfg->max_samples > ((size_t)1 << 28)) {
-    kq_internal_set_error("%s: max_samples %zu must be 1..2^28", fn, cfg->max_samples);
-    return nullptr;
-  }
-  (void)cos_table();  // the table exists from here on
+  (void)kq::tonecorr::cos_table();  // the table exists from here on
   kq_cw_bank *b = new kq_cw_bank;
   b->cfg = *cfg;
-  b->want.assign(cfg->max_slots, CwPar{});
-  b->is_dirty.assign(cfg->max_slots, 0);
+  b->def.init(cfg->max_slots);
   CwGeom &g = b->g;
-  g.B = (int)cfg->block_len;
-  g.Bs = g.B + ((g.B & 1) ? 1 : 0);  // even
-  if ((g.Bs & 3) == 0) g.Bs += 2;    // and Bs / 2 odd
-  g.magic = (unsigned)((0x100000000ull + cfg->block_len - 1) / cfg->block_len);
+  g.grid = kq::tonecorr::frame_grid(cfg->block_len);
   g.deb = cfg->deb;
   g.warm = cfg->warm;
   g.snr = cfg->snr;
@@ -443,8 +314,7 @@ kq_cw_bank *kq_cw_create(const kq_cw_config *cfg) {
   g.u_max = (unsigned)hi;
   g.min_p = cfg->min_p;
   g.max_events = (int)cfg->max_events;
-  g.scale = cfg->input_scale;
-  while ((64 / b->Lmin) * g.Bs > kTile) b->Lmin *= 2;  // ends at 64 at the latest: Bs <= 4098
+  b->Lmin = kq::tonecorr::least_lanes(g.grid, kTile);  // 64 at the most: Bs <= 4098
   return b;
 }
 
@@ -474,196 +344,58 @@ int kq_cw_set(kq_cw_bank *b, unsigned slot, const kq_cw_params *p) {
   np.source = p->source;
   np.inc = (unsigned)std::llrint(f * 4294967296.0 / Fs);
   np.u0 = std::min(std::max((unsigned)std::llrint(unit_of(Fs, b->cfg.block_len, p->wpm)), b->g.u_min), b->g.u_max);
-  b->nwant += !b->want[slot].active;
-  b->want[slot] = np;
-  b->touch(slot);
+  b->def.set(slot, np);
   return 0;
 }
 
-int kq_cw_remove(kq_cw_bank *b, unsigned slot) {
-  if (!b) {
-    kq_internal_set_error("kq_cw_remove: null bank");
-    return -1;
-  }
-  std::lock_guard<std::mutex> lk(b->mu);
-  if (slot >= b->cfg.max_slots || !b->want[slot].active) {
-    kq_internal_set_error("kq_cw_remove: slot %u holds no decoder", slot);
-    return -1;
-  }
-  b->want[slot] = CwPar{};
-  b->nwant--;
-  b->touch(slot);
-  return 0;
-}
+int kq_cw_remove(kq_cw_bank *b, unsigned slot) { return kq::deferred_remove(b, slot, "kq_cw_remove"); }
 
 int kq_cw_process(kq_cw_bank *b, const void *src, int format, size_t src_stride, size_t row_stride, unsigned block_len,
                   unsigned nblocks, int on_device, kq_cw_status *status, size_t status_stride) {
+  const char *fn = "kq_cw_process";
   if (!b) {
-    kq_internal_set_error("kq_cw_process: null bank");
-    return -1;
-  }
-  if (format != KQ_PCM_F32 && format != KQ_PCM_S16BE) {
-    kq_internal_set_error("kq_cw_process: unknown sample format %d", format);
+    kq_internal_set_error("%s: null bank", fn);
     return -1;
   }
   std::lock_guard<std::mutex> lk(b->mu);
-  if (!kq::blocks_ok("kq_cw_process", b->cfg.max_samples, row_stride, block_len, nblocks)) return -1;
+  if (!kq::call_args_ok(fn, format, b->cfg.max_samples, row_stride, block_len, nblocks, status, status_stride)) return -1;
   size_t const ncall = (size_t)block_len * nblocks;
-  if (status && status_stride < 1) {
-    kq_internal_set_error("kq_cw_process: status_stride %zu < 1", status_stride);
-    return -1;
-  }
-  if (ncall == 0) return 0;
-  if (!src) {
-    kq_internal_set_error("kq_cw_process: null src");
-    return -1;
-  }
-  if (b->deviceless()) {
-    (void)flush(b);
-    b->n_cur += ncall;
-    return 0;
-  }
-  kq::DeviceScope dev_scope_(b->cfg.device);
-  if (flush(b)) return -1;
-  kq::CallWork const work = kq::call_work(b, "kq_cw_process", ncall, src, "src");
-  if (work == kq::CALL_IDLE) {
-    b->n_cur += ncall;
-    return 0;
-  }
-  if (work != kq::CALL_RUN) return work;
+  std::optional<kq::DeviceScope> scope;
+  kq::CallWork const work = kq::begin_call(b, fn, ncall, src, scope);
+  if (work != kq::CALL_RUN) return work == kq::CALL_FAILED ? -1 : 0;
   auto &d = b->d;
-  size_t const S = b->cfg.max_slots, nlist = d.slots.all.size();
+  size_t const nlist = d.slots.all.size();
   CallArgs a{};
   a.g = b->g;
   a.par = d.slots.d_par;
   a.list = d.slots.d_list;
   a.table = d.table;
   a.state = d.state;
-  a.ev = d.ev;
-  a.nev = d.nev;
+  a.ev = d.arena.ev;
+  a.nev = d.arena.n;
   a.nlist = (int)nlist;
   a.n0 = (int64_t)b->n_cur;
   a.n1 = a.n0 + (int64_t)ncall;
-  // lanes to a frame: what the piece needs, and more where the call's frames (at most nf) do not fill a wave
-  size_t const nf = (ncall + (size_t)b->g.B - 2) / (size_t)b->g.B + 1;
-  a.L = b->Lmin;
-  while (a.L < 64 && (size_t)(2 * a.L) * nf <= 64) a.L *= 2;
-  a.format = format;
-  a.block_len = block_len;
-  if (on_device) {
-    a.src = src;
-    a.src_stride = src_stride;
-    a.row_stride = row_stride;
-    a.rowmap = nullptr;
-    a.st = status;
-    a.sstride = status_stride;
-  } else {
-    kq::Staged in;
-    if (d.slots.stage_rows(*b, src, format == KQ_PCM_S16BE ? 2 : 4, src_stride, row_stride, block_len, nblocks,
-                           b->cfg.max_samples * 4, &in))
-      return -1;
-    a.src = in.src;
-    a.src_stride = in.src_stride;
-    a.row_stride = in.row_stride;
-    a.rowmap = in.rowmap;
-    if (status && !d.st && b->alloc(&d.st, S)) return -1;
-    a.st = status ? d.st : nullptr;
-    a.sstride = 1;
-  }
+  a.L = kq::tonecorr::lanes_for_call(b->g.grid, b->Lmin, ncall);
+  if (kq::bind_pcm(&a.in, &a.rowmap, *b, d.slots, b->cfg.max_samples, b->cfg.input_scale, src, format, src_stride, row_stride, block_len,
+                   nblocks, on_device) ||
+      kq::bind_status(b, on_device, status, status_stride, &a.st, &a.sstride))
+    return -1;
   hipLaunchKernelGGL(k_cw, dim3((unsigned)((nlist + kWaves - 1) / kWaves)), dim3(kThreads), 0, b->stream, a);
   KQ_TRY(hipGetLastError());
   b->n_cur += ncall;
-  if (!on_device) {
-    auto back = [&](size_t s0, size_t n) {  // the records of the active slots
-      return kq::copy_rows_back(*b, status, status_stride, d.st, 1, 1, sizeof(kq_cw_status), s0, n);
-    };
-    if (status && d.slots.for_runs(back)) return -1;
-    KQ_TRY(hipStreamSynchronize(b->stream));
-  }
-  return 0;
+  return on_device ? 0 : kq::end_host_call(b, status, status_stride, nullptr);
 }
 
-int kq_cw_pull_counts(kq_cw_bank *b, uint32_t *counts) {
-  if (!b) {
-    kq_internal_set_error("kq_cw_pull_counts: null bank");
-    return -1;
-  }
-  if (!counts) {
-    kq_internal_set_error("kq_cw_pull_counts: null counts");
-    return -1;
-  }
-  std::lock_guard<std::mutex> lk(b->mu);
-  if (b->deviceless()) {
-    (void)flush(b);
-    std::memset(counts, 0, b->cfg.max_slots * sizeof(uint32_t));
-    return 0;
-  }
-  kq::DeviceScope dev_scope_(b->cfg.device);
-  if (flush(b)) return -1;  // a slot set since the last call shows its empty arena
-  KQ_TRY(hipMemcpyAsync(counts, b->d.nev, b->cfg.max_slots * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
-  KQ_TRY(hipStreamSynchronize(b->stream));
-  return 0;
-}
+int kq_cw_pull_counts(kq_cw_bank *b, uint32_t *counts) { return kq::pull_counts(b, "kq_cw_pull_counts", counts); }
 
 int kq_cw_pull_event(kq_cw_bank *b, unsigned slot, unsigned index, kq_cw_event *event) {
-  if (!b) {
-    kq_internal_set_error("kq_cw_pull_event: null bank");
-    return -1;
-  }
-  if (!event) {
-    kq_internal_set_error("kq_cw_pull_event: null event");
-    return -1;
-  }
-  std::lock_guard<std::mutex> lk(b->mu);
-  if (slot >= b->cfg.max_slots) {
-    kq_internal_set_error("kq_cw_pull_event: slot %u >= max_slots %u", slot, b->cfg.max_slots);
-    return -1;
-  }
-  unsigned n = 0;
-  if (b->deviceless()) {
-    (void)flush(b);
-    kq_internal_set_error("kq_cw_pull_event: slot %u has %u events", slot, n);
-    return -1;
-  }
-  kq::DeviceScope dev_scope_(b->cfg.device);
-  if (flush(b)) return -1;
-  KQ_TRY(hipMemcpyAsync(&n, b->d.nev + slot, sizeof n, hipMemcpyDeviceToHost, b->stream));
-  KQ_TRY(hipStreamSynchronize(b->stream));
-  if (index >= n) {
-    kq_internal_set_error("kq_cw_pull_event: slot %u has %u events", slot, n);
-    return -1;
-  }
-  size_t const at = (size_t)slot * b->cfg.max_events + index;
-  KQ_TRY(hipMemcpyAsync(event, b->d.ev + at, sizeof *event, hipMemcpyDeviceToHost, b->stream));
-  KQ_TRY(hipStreamSynchronize(b->stream));
-  return 0;
+  return kq::pull_event(b, "kq_cw_pull_event", slot, index, event);
 }
 
-int kq_cw_clear_events(kq_cw_bank *b) {
-  if (!b) {
-    kq_internal_set_error("kq_cw_clear_events: null bank");
-    return -1;
-  }
-  std::lock_guard<std::mutex> lk(b->mu);
-  if (!b->dev_ready) return 0;
-  kq::DeviceScope dev_scope_(b->cfg.device);
-  KQ_TRY(hipMemsetAsync(b->d.nev, 0, b->cfg.max_slots * sizeof(unsigned), b->stream));
-  return 0;
-}
+int kq_cw_clear_events(kq_cw_bank *b) { return kq::clear_arena(b, "kq_cw_clear_events"); }
 
-int kq_cw_get_table(const kq_cw_bank *b, int16_t *dst, size_t cap) {
-  if (!b) {
-    kq_internal_set_error("kq_cw_get_table: null bank");
-    return -1;
-  }
-  if (!dst && cap) {
-    kq_internal_set_error("kq_cw_get_table: null dst");
-    return -1;
-  }
-  size_t const n = std::min(cap, (size_t)kTable);
-  if (n) std::memcpy(dst, cos_table().data(), n * sizeof(int16_t));
-  return kTable;
-}
+int kq_cw_get_table(const kq_cw_bank *b, int16_t *dst, size_t cap) { return kq::tonecorr::get_table(b, "kq_cw_get_table", dst, cap); }
 
 int kq_cw_get_inc(kq_cw_bank *b, unsigned slot, uint32_t *inc) {
   if (!b) {
@@ -675,26 +407,16 @@ int kq_cw_get_inc(kq_cw_bank *b, unsigned slot, uint32_t *inc) {
     return -1;
   }
   std::lock_guard<std::mutex> lk(b->mu);
-  if (slot >= b->cfg.max_slots || !b->want[slot].active) {
+  if (!b->def.is_set(slot)) {
     kq_internal_set_error("kq_cw_get_inc: slot %u holds no decoder", slot);
     return -1;
   }
-  *inc = b->want[slot].inc;
+  *inc = b->def.want[slot].inc;
   return 0;
 }
 
 int kq_cw_sync(kq_cw_bank *b) { return kq::sync_bank(b, "kq_cw_sync"); }
 
-int kq_cw_reset(kq_cw_bank *b) {
-  if (!b) {
-    kq_internal_set_error("kq_cw_reset: null bank");
-    return -1;
-  }
-  std::lock_guard<std::mutex> lk(b->mu);
-  b->n_cur = 0;
-  for (unsigned s = 0; s < b->cfg.max_slots; s++)  // every slot that is set starts cold at the next call
-    if (b->want[s].active) b->touch(s);
-  return 0;
-}
+int kq_cw_reset(kq_cw_bank *b) { return kq::deferred_reset(b, "kq_cw_reset"); }
 
 }  // extern "C"

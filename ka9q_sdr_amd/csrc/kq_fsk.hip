@@ -184,6 +184,7 @@ __global__ __launch_bounds__(64) void k_fsk_track(CallArgs c, int nlist) {
 }  // namespace
 
 struct kq_fsk_bank : kq::HostSide {
+  static constexpr bool kDeferred = false;
   kq_fsk_config cfg;
   std::mutex mu;
   bool dev_ready = false;
@@ -197,8 +198,7 @@ struct kq_fsk_bank : kq::HostSide {
     kq::fskfront::FrontDev front;
     FskState *state = nullptr;
     unsigned char *open = nullptr, *frames = nullptr;
-    kq_fsk_frame_info *info = nullptr;
-    unsigned *nframes = nullptr;
+    kq::EventArena<kq_fsk_frame_info> arena;  // the frames' infos and how many there are
     kq_fsk_status *st = nullptr;         // host-memory calls
   } d;
 };
@@ -213,7 +213,7 @@ int make_device(kq_fsk_bank *b) {
   size_t const S = c.max_slots;
   size_t const mf = (size_t)b->max_frames, mfb = (size_t)b->mfb;
   if (d.slots.alloc(*b, S) || d.front.alloc(*b, g, b->hq) || b->alloc(&d.state, S, true) || b->alloc(&d.open, S * mfb, true) ||
-      b->alloc(&d.frames, S * mf * mfb) || b->alloc(&d.info, S * mf) || b->alloc(&d.nframes, S, true))
+      b->alloc(&d.frames, S * mf * mfb) || d.arena.alloc(*b, S, mf))
     return -1;
   KQ_TRY(hipStreamSynchronize(b->stream));
   return 0;
@@ -223,8 +223,7 @@ int make_device(kq_fsk_bank *b) {
 int cold_start(kq_fsk_bank *b, unsigned s) {
   if (b->d.front.cold_start(*b, b->g, s)) return -1;
   KQ_TRY(hipMemsetAsync(b->d.state + s, 0, sizeof(FskState), b->stream));
-  KQ_TRY(hipMemsetAsync(b->d.nframes + s, 0, sizeof(unsigned), b->stream));
-  return 0;
+  return b->d.arena.clear(*b, s, 1);
 }
 
 }  // namespace
@@ -241,14 +240,9 @@ kq_fsk_bank *kq_fsk_create(const kq_fsk_config *cfg) {
   FskGeom g{};
   std::vector<short> hq;
   if (!kq::fskfront::front_config("kq_fsk_create", fc, &g, &hq)) return nullptr;
-  if (cfg->max_frames == 0 || cfg->max_frames > 4096) {
-    kq_internal_set_error("kq_fsk_create: max_frames %u must be 1..4096", cfg->max_frames);
+  if (!kq::field_in_range("kq_fsk_create", "max_frames", cfg->max_frames, 1, 4096) ||
+      !kq::field_in_range("kq_fsk_create", "max_frame_bytes", cfg->max_frame_bytes, 8, 1024))
     return nullptr;
-  }
-  if (cfg->max_frame_bytes < 8 || cfg->max_frame_bytes > 1024) {
-    kq_internal_set_error("kq_fsk_create: max_frame_bytes %u must be 8..1024", cfg->max_frame_bytes);
-    return nullptr;
-  }
   kq_fsk_bank *b = new kq_fsk_bank;
   b->cfg = *cfg;
   b->hq = std::move(hq);
@@ -293,113 +287,56 @@ int kq_fsk_remove(kq_fsk_bank *b, unsigned slot) { return kq::remove_slot(b, slo
 
 int kq_fsk_process(kq_fsk_bank *b, const void *src, int format, size_t src_stride, size_t row_stride, unsigned block_len,
                    unsigned nblocks, int on_device, kq_fsk_status *status, size_t status_stride) {
+  const char *fn = "kq_fsk_process";
   if (!b) {
-    kq_internal_set_error("kq_fsk_process: null bank");
-    return -1;
-  }
-  if (format != KQ_PCM_F32 && format != KQ_PCM_S16BE) {
-    kq_internal_set_error("kq_fsk_process: unknown sample format %d", format);
+    kq_internal_set_error("%s: null bank", fn);
     return -1;
   }
   std::lock_guard<std::mutex> lk(b->mu);
-  if (!kq::blocks_ok("kq_fsk_process", b->cfg.max_samples, row_stride, block_len, nblocks)) return -1;
+  if (!kq::call_args_ok(fn, format, b->cfg.max_samples, row_stride, block_len, nblocks, status, status_stride)) return -1;
   size_t const ncall = (size_t)block_len * nblocks;
-  if (status && status_stride < 1) {
-    kq_internal_set_error("kq_fsk_process: status_stride %zu < 1", status_stride);
-    return -1;
-  }
-  kq::CallWork const work = kq::call_work(b, "kq_fsk_process", ncall, src, "src");
-  if (work == kq::CALL_IDLE) {
-    b->n_cur += ncall;
-    return 0;
-  }
-  if (work != kq::CALL_RUN) return work;
-  kq::DeviceScope dev_scope_(b->cfg.device);
-  FskGeom const &g = b->g;
+  std::optional<kq::DeviceScope> scope;
+  kq::CallWork const work = kq::begin_call(b, fn, ncall, src, scope);
+  if (work != kq::CALL_RUN) return work == kq::CALL_FAILED ? -1 : 0;
   auto &d = b->d;
-  size_t const S = b->cfg.max_slots, nlist = d.slots.all.size();
+  size_t const nlist = d.slots.all.size();
   CallArgs a{};
-  if (kq::fskfront::bind_front(&a.f, *b, d.slots, d.front, g, b->turn, b->n_cur, b->cfg.max_samples, src, format, src_stride,
-                               row_stride, block_len, nblocks, on_device))
+  if (kq::fskfront::bind_front(&a.f, *b, d.slots, d.front, b->g, b->turn, b->n_cur, b->cfg.max_samples, src, format, src_stride,
+                               row_stride, block_len, nblocks, on_device) ||
+      kq::bind_status(b, on_device, status, status_stride, &a.st, &a.sstride))
     return -1;
   a.lim.max_frames = b->max_frames;
   a.lim.mfb = b->mfb;
   a.state = d.state;
   a.open = d.open;
   a.frames = d.frames;
-  a.info = d.info;
-  a.nframes = d.nframes;
-  if (on_device) {
-    a.st = status;
-    a.sstride = status_stride;
-  } else {
-    if (status && !d.st && b->alloc(&d.st, S)) return -1;
-    a.st = status ? d.st : nullptr;
-    a.sstride = 1;
-  }
+  a.info = d.arena.ev;
+  a.nframes = d.arena.n;
   if (kq::fskfront::launch_front(a.f, nlist, b->stream)) return -1;
   hipLaunchKernelGGL(k_fsk_track, dim3((unsigned)((nlist + 63) / 64)), dim3(64), 0, b->stream, a, (int)nlist);
   KQ_TRY(hipGetLastError());
   b->turn ^= 1;  // from here on the carried q is in the other copy, whatever fails below
   b->n_cur += ncall;
-  if (!on_device) {
-    auto back = [&](size_t s0, size_t n) {  // the records of the active slots
-      return kq::copy_rows_back(*b, status, status_stride, d.st, 1, 1, sizeof(kq_fsk_status), s0, n);
-    };
-    if (status && d.slots.for_runs(back)) return -1;
-    KQ_TRY(hipStreamSynchronize(b->stream));
-  }
-  return 0;
+  return on_device ? 0 : kq::end_host_call(b, status, status_stride, nullptr);
 }
 
-int kq_fsk_pull_counts(kq_fsk_bank *b, uint32_t *counts) {
-  if (!b) {
-    kq_internal_set_error("kq_fsk_pull_counts: null bank");
-    return -1;
-  }
-  if (!counts) {
-    kq_internal_set_error("kq_fsk_pull_counts: null counts");
-    return -1;
-  }
-  std::lock_guard<std::mutex> lk(b->mu);
-  if (!b->dev_ready) {
-    std::memset(counts, 0, b->cfg.max_slots * sizeof(uint32_t));
-    return 0;
-  }
-  kq::DeviceScope dev_scope_(b->cfg.device);
-  KQ_TRY(hipMemcpyAsync(counts, b->d.nframes, b->cfg.max_slots * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
-  KQ_TRY(hipStreamSynchronize(b->stream));
-  return 0;
-}
+int kq_fsk_pull_counts(kq_fsk_bank *b, uint32_t *counts) { return kq::pull_counts(b, "kq_fsk_pull_counts", counts); }
 
 int kq_fsk_pull_frame(kq_fsk_bank *b, unsigned slot, unsigned index, unsigned char *dst, size_t cap, kq_fsk_frame_info *info) {
+  const char *fn = "kq_fsk_pull_frame";
   if (!b) {
-    kq_internal_set_error("kq_fsk_pull_frame: null bank");
+    kq_internal_set_error("%s: null bank", fn);
     return -1;
   }
   if (!dst) {
-    kq_internal_set_error("kq_fsk_pull_frame: null dst");
+    kq_internal_set_error("%s: null dst", fn);
     return -1;
   }
   std::lock_guard<std::mutex> lk(b->mu);
-  if (slot >= b->cfg.max_slots) {
-    kq_internal_set_error("kq_fsk_pull_frame: slot %u >= max_slots %u", slot, b->cfg.max_slots);
-    return -1;
-  }
-  unsigned n = 0;
-  kq::DeviceScope dev_scope_(b->cfg.device);
-  if (b->dev_ready) {
-    KQ_TRY(hipMemcpyAsync(&n, b->d.nframes + slot, sizeof n, hipMemcpyDeviceToHost, b->stream));
-    KQ_TRY(hipStreamSynchronize(b->stream));
-  }
-  if (index >= n) {
-    kq_internal_set_error("kq_fsk_pull_frame: slot %u has %u frames", slot, n);
-    return -1;
-  }
-  size_t const at = (size_t)slot * b->max_frames + index;
+  std::optional<kq::DeviceScope> scope;
   kq_fsk_frame_info r;
-  KQ_TRY(hipMemcpyAsync(&r, b->d.info + at, sizeof r, hipMemcpyDeviceToHost, b->stream));
-  KQ_TRY(hipStreamSynchronize(b->stream));
+  size_t at;
+  if (kq::pull_record(b, fn, slot, index, "frames", &r, &at, scope)) return -1;
   size_t const take = std::min(cap, (size_t)r.length);
   if (take) {
     KQ_TRY(hipMemcpyAsync(dst, b->d.frames + at * b->mfb, take, hipMemcpyDeviceToHost, b->stream));
@@ -409,17 +346,7 @@ int kq_fsk_pull_frame(kq_fsk_bank *b, unsigned slot, unsigned index, unsigned ch
   return (int)r.length;
 }
 
-int kq_fsk_clear_frames(kq_fsk_bank *b) {
-  if (!b) {
-    kq_internal_set_error("kq_fsk_clear_frames: null bank");
-    return -1;
-  }
-  std::lock_guard<std::mutex> lk(b->mu);
-  if (!b->dev_ready) return 0;
-  kq::DeviceScope dev_scope_(b->cfg.device);
-  KQ_TRY(hipMemsetAsync(b->d.nframes, 0, b->cfg.max_slots * sizeof(unsigned), b->stream));
-  return 0;
-}
+int kq_fsk_clear_frames(kq_fsk_bank *b) { return kq::clear_arena(b, "kq_fsk_clear_frames"); }
 
 int kq_fsk_get_taps(const kq_fsk_bank *b, int16_t *dst, size_t cap) {
   if (!b) {
@@ -438,19 +365,7 @@ int kq_fsk_get_taps(const kq_fsk_bank *b, int16_t *dst, size_t cap) {
 int kq_fsk_sync(kq_fsk_bank *b) { return kq::sync_bank(b, "kq_fsk_sync"); }
 
 int kq_fsk_reset(kq_fsk_bank *b) {
-  if (!b) {
-    kq_internal_set_error("kq_fsk_reset: null bank");
-    return -1;
-  }
-  std::lock_guard<std::mutex> lk(b->mu);
-  b->n_cur = 0;
-  if (!b->dev_ready) return 0;
-  kq::DeviceScope dev_scope_(b->cfg.device);
-  KQ_TRY(hipStreamSynchronize(b->stream));
-  for (int s : b->d.slots.all)
-    if (cold_start(b, (unsigned)s)) return -1;
-  KQ_TRY(hipStreamSynchronize(b->stream));
-  return 0;
+  return kq::reset_slots(b, "kq_fsk_reset", [b](unsigned s) { return cold_start(b, s); });
 }
 
 }  // extern "C"

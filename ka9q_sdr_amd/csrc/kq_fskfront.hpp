@@ -3,7 +3,9 @@
 // symbol.  The algorithm is the header's (include/ka9q_hip.h, kq_fsk_*: quantise, low-pass, threshold, bit clock); what a
 // bank does with the channel bits -- its tracker kernel, its state and records -- stays with the bank.
 //
-// Device: FrontArgs<Par> (what k_fsk_front reads and writes of a call), load_q, k_fsk_front, pll_step.
+// Device: FrontArgs<Par> (what k_fsk_front reads and writes of a call), k_fsk_front, pll_step; the quantiser is
+// kq::load_q (kq_tonecorr.hpp), whose 32-bit sample index holds every sample of a call: front_config keeps max_samples
+// within 2^28.
 //   k_fsk_front  one workgroup per (slot, tile of kTile samples on the grid of 64-sample words): tile and halo quantised into
 //                LDS, the FIR, running max / min over W by doubling (log2 W steps whatever W is), the compare packed with
 //                __ballot: one wave, one word.  The first tile of a slot also writes the q the next call starts from
@@ -20,6 +22,7 @@
 #include "kq_design.hpp"
 #include "kq_host.hpp"
 #include "kq_slots.hpp"
+#include "kq_tonecorr.hpp"
 
 namespace kq {
 namespace fskfront {
@@ -55,28 +58,9 @@ struct FrontArgs {
   unsigned *level;               // [S]
   int64_t n0, n1;                // the call's samples
   int64_t w0;                    // n0 / 64
-  // input
-  const void *src;
-  int format;
-  size_t src_stride, row_stride;
-  unsigned block_len;
-  const int *rowmap;             // per list entry: the row of `src` (host input, staged) or null (par.source)
+  PcmIn in;
+  const int *rowmap;             // per list entry: the row of in.src (host input, staged) or null (par.source)
 };
-
-// q of the call's i-th sample
-template <class Par>
-__device__ __forceinline__ int load_q(FrontArgs<Par> const &a, size_t row, size_t i) {
-  size_t const k = i / a.block_len, j = i - k * a.block_len;
-  size_t const idx = row * a.src_stride + k * a.row_stride + j;
-  if (a.format == KQ_PCM_S16BE) {
-    const unsigned char *p = reinterpret_cast<const unsigned char *>(a.src) + 2 * idx;
-    int const w = (int)(short)(unsigned short)(((unsigned)p[0] << 8) | p[1]);
-    return w < -32767 ? -32767 : w;
-  }
-  float const v = rintf(reinterpret_cast<const float *>(a.src)[idx] * a.g.scale);
-  if (!(v == v)) return 0;
-  return (int)fminf(fmaxf(v, -32767.f), 32767.f);
-}
 
 template <class Par>
 __global__ __launch_bounds__(kThreads) void k_fsk_front(FrontArgs<Par> a) {
@@ -97,7 +81,7 @@ __global__ __launch_bounds__(kThreads) void k_fsk_front(FrontArgs<Par> a) {
     int64_t const n = t0 - g.H + i;
     int v = 0;
     if (n < a.n0) v = hin[g.HN - (int)(a.n0 - n)];
-    else if (n < a.n1) v = load_q(a, row, (size_t)(n - a.n0));
+    else if (n < a.n1) v = load_q(a.in, row, (unsigned)(n - a.n0));  // (below max_samples <= 2^28)
     q[i] = (short)v;
   }
   for (int k = tid; k < g.K; k += kThreads) hs[k] = a.taps[k];
@@ -106,7 +90,7 @@ __global__ __launch_bounds__(kThreads) void k_fsk_front(FrontArgs<Par> a) {
     int64_t const ncall = a.n1 - a.n0;
     for (int i = tid; i < g.HN; i += kThreads) {
       int64_t const n = a.n1 - g.HN + i;
-      hout[i] = n < a.n0 ? hin[i + ncall] : (short)load_q(a, row, (size_t)(n - a.n0));
+      hout[i] = n < a.n0 ? hin[i + ncall] : (short)load_q(a.in, row, (unsigned)(n - a.n0));
     }
   }
   __syncthreads();
@@ -241,18 +225,9 @@ inline bool front_config(const char *fn, FrontConfig const &c, Geom *g, std::vec
     kq_internal_set_error("%s: pll_shift %d must be 1..8", fn, c.pll_shift);
     return false;
   }
-  if (!std::isfinite(c.input_scale) || !(c.input_scale > 0)) {
-    kq_internal_set_error("%s: input_scale must be finite and positive", fn);
+  if (!input_scale_ok(fn, c.input_scale) || !field_in_range(fn, "max_slots", c.max_slots, 1, kMaxSlots) ||
+      !max_samples_ok(fn, c.max_samples))
     return false;
-  }
-  if (c.max_slots == 0 || c.max_slots > kMaxSlots) {
-    kq_internal_set_error("%s: max_slots %u must be 1..%u", fn, c.max_slots, kMaxSlots);
-    return false;
-  }
-  if (c.max_samples == 0 || c.max_samples > ((size_t)1 << 28)) {
-    kq_internal_set_error("%s: max_samples %zu must be 1..2^28", fn, c.max_samples);
-    return false;
-  }
   long sum_abs = 0;
   *hq = design_taps((int)K, c.cutoff_hz, Fs, c.kaiser_beta, &sum_abs);
   if (sum_abs > 65535) {
@@ -300,8 +275,7 @@ struct FrontDev {
   }
 };
 
-// A call's FrontArgs: `turn` is the copy of the carried q the call reads; a host-memory call's distinct rows are staged
-// (the stage holds 4 bytes per sample whatever the format; the rows lie as closely as the format allows).
+// A call's FrontArgs: `turn` is the copy of the carried q the call reads; the input as kq::bind_pcm binds it
 template <class Par>
 int bind_front(FrontArgs<Par> *a, HostSide &h, SlotTable<Par> &slots, FrontDev const &d, Geom const &g, int turn, uint64_t n_cur,
                size_t max_samples, const void *src, int format, size_t src_stride, size_t row_stride, unsigned block_len,
@@ -317,23 +291,7 @@ int bind_front(FrontArgs<Par> *a, HostSide &h, SlotTable<Par> &slots, FrontDev c
   a->n0 = (int64_t)n_cur;
   a->n1 = a->n0 + (int64_t)block_len * nblocks;
   a->w0 = a->n0 >> 6;
-  a->format = format;
-  a->block_len = block_len;
-  if (on_device) {
-    a->src = src;
-    a->src_stride = src_stride;
-    a->row_stride = row_stride;
-    a->rowmap = nullptr;
-    return 0;
-  }
-  Staged in;
-  if (slots.stage_rows(h, src, format == KQ_PCM_S16BE ? 2 : 4, src_stride, row_stride, block_len, nblocks, max_samples * 4, &in))
-    return -1;
-  a->src = in.src;
-  a->src_stride = in.src_stride;
-  a->row_stride = in.row_stride;
-  a->rowmap = in.rowmap;
-  return 0;
+  return bind_pcm(&a->in, &a->rowmap, h, slots, max_samples, g.scale, src, format, src_stride, row_stride, block_len, nblocks, on_device);
 }
 
 template <class Par>

@@ -1,10 +1,11 @@
-// kq_host.hpp -- the host half that every handle shares (kq_bank, the satellite banks kq_afsk, kq_decim, kq_mod, kq_spec, kq_rds,
-// kq_mon, kq_wfm, kq_fsk, kq_pag, kq_tone, kq_cw, kq_rtty, kq_rsmp, and the compat surface's context, masters, slaves and FFTW plans, kq_compat.hpp): error reporting,
-// the handle's streams, and whatever the handle owns on the device or for it -- device memory, pinned host memory, events.
-// Each is named once, where it is made; close() lets go of all of it.  Host only; a handle's struct derives from
-// kq::HostSide.  Every member function wants the handle's device current (the entry point's kq::DeviceScope).
-// kq::lazy_device() is for the handles that touch no device before their first set.  What the slot banks (kq_wfm, kq_rds,
-// kq_fsk, kq_pag, kq_tone, kq_cw, kq_rtty, kq_rsmp) share beyond this -- slot table, staging, copy-back, entry-point bodies -- is kq_slots.hpp, on top of this file.
+// kq_host.hpp -- the host half that every handle shares (kq_bank; the satellite banks kq_afsk, kq_decim, kq_mod, kq_spec,
+// kq_mon and the slot banks; the compat surface's context, masters, slaves and FFTW plans, kq_compat.hpp): error
+// reporting, the handle's streams, and whatever the handle owns on the device or for it -- device memory, pinned host
+// memory, events.  Each is named once, where it is made; close() lets go of all of it.  Host only; a handle's struct
+// derives from kq::HostSide.  Every member function wants the handle's device current (the entry point's
+// kq::DeviceScope).  kq::lazy_device() is for the handles that touch no device before their first set.  What the slot
+// banks (kq_wfm, kq_rds, kq_fsk, kq_pag, kq_tone, kq_cw, kq_rtty, kq_rsmp) share beyond this is kq_slots.hpp, on top of
+// this file; it lists what each kind of them takes.
 #pragma once
 #include <hip/hip_runtime.h>
 

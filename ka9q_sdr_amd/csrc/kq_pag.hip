@@ -262,6 +262,7 @@ std::vector<uint32_t> const &fix_table() {
 }  // namespace
 
 struct kq_pag_bank : kq::HostSide {
+  static constexpr bool kDeferred = false;
   kq_pag_config cfg;
   std::mutex mu;
   bool dev_ready = false;
@@ -276,8 +277,7 @@ struct kq_pag_bank : kq::HostSide {
     uint32_t *fix = nullptr;
     PagState *state = nullptr;
     unsigned char *open = nullptr, *pages = nullptr;
-    kq_pag_page_info *info = nullptr;
-    unsigned *npages = nullptr;
+    kq::EventArena<kq_pag_page_info> arena;  // the pages' infos and how many there are
     kq_pag_status *st = nullptr;         // host-memory calls
   } d;
 };
@@ -290,7 +290,7 @@ int make_device(kq_pag_bank *b) {
   size_t const S = b->cfg.max_slots, mp = (size_t)b->max_pages, pb = 3 * (size_t)b->mpw;
   if (d.slots.alloc(*b, S) || d.front.alloc(*b, b->g, b->hq) || b->alloc(&d.fix, (size_t)kFixEntries) ||
       b->alloc(&d.state, S, true) || b->alloc(&d.open, S * pb, true) || b->alloc(&d.pages, S * mp * pb) ||
-      b->alloc(&d.info, S * mp) || b->alloc(&d.npages, S, true))
+      d.arena.alloc(*b, S, mp))
     return -1;
   KQ_TRY(hipMemcpyAsync(d.fix, fix_table().data(), kFixEntries * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream));
   KQ_TRY(hipStreamSynchronize(b->stream));
@@ -301,8 +301,7 @@ int make_device(kq_pag_bank *b) {
 int cold_start(kq_pag_bank *b, unsigned s) {
   if (b->d.front.cold_start(*b, b->g, s)) return -1;
   KQ_TRY(hipMemsetAsync(b->d.state + s, 0, sizeof(PagState), b->stream));
-  KQ_TRY(hipMemsetAsync(b->d.npages + s, 0, sizeof(unsigned), b->stream));
-  return 0;
+  return b->d.arena.clear(*b, s, 1);
 }
 
 }  // namespace
@@ -326,14 +325,9 @@ kq_pag_bank *kq_pag_create(const kq_pag_config *cfg) {
   PagGeom g{};
   std::vector<short> hq;
   if (!kq::fskfront::front_config("kq_pag_create", fc, &g, &hq)) return nullptr;
-  if (cfg->max_pages == 0 || cfg->max_pages > 4096) {
-    kq_internal_set_error("kq_pag_create: max_pages %u must be 1..4096", cfg->max_pages);
+  if (!kq::field_in_range("kq_pag_create", "max_pages", cfg->max_pages, 1, 4096) ||
+      !kq::field_in_range("kq_pag_create", "max_page_words", cfg->max_page_words, 1, 256))
     return nullptr;
-  }
-  if (cfg->max_page_words == 0 || cfg->max_page_words > 256) {
-    kq_internal_set_error("kq_pag_create: max_page_words %u must be 1..256", cfg->max_page_words);
-    return nullptr;
-  }
   (void)fix_table();  // the correction table exists from here on
   kq_pag_bank *b = new kq_pag_bank;
   b->cfg = *cfg;
@@ -369,33 +363,23 @@ int kq_pag_remove(kq_pag_bank *b, unsigned slot) { return kq::remove_slot(b, slo
 
 int kq_pag_process(kq_pag_bank *b, const void *src, int format, size_t src_stride, size_t row_stride, unsigned block_len,
                    unsigned nblocks, int on_device, kq_pag_status *status, size_t status_stride) {
+  const char *fn = "kq_pag_process";
   if (!b) {
-    kq_internal_set_error("kq_pag_process: null bank");
-    return -1;
-  }
-  if (format != KQ_PCM_F32 && format != KQ_PCM_S16BE) {
-    kq_internal_set_error("kq_pag_process: unknown sample format %d", format);
+    kq_internal_set_error("%s: null bank", fn);
     return -1;
   }
   std::lock_guard<std::mutex> lk(b->mu);
-  if (!kq::blocks_ok("kq_pag_process", b->cfg.max_samples, row_stride, block_len, nblocks)) return -1;
+  if (!kq::call_args_ok(fn, format, b->cfg.max_samples, row_stride, block_len, nblocks, status, status_stride)) return -1;
   size_t const ncall = (size_t)block_len * nblocks;
-  if (status && status_stride < 1) {
-    kq_internal_set_error("kq_pag_process: status_stride %zu < 1", status_stride);
-    return -1;
-  }
-  kq::CallWork const work = kq::call_work(b, "kq_pag_process", ncall, src, "src");
-  if (work == kq::CALL_IDLE) {
-    b->n_cur += ncall;
-    return 0;
-  }
-  if (work != kq::CALL_RUN) return work;
-  kq::DeviceScope dev_scope_(b->cfg.device);
+  std::optional<kq::DeviceScope> scope;
+  kq::CallWork const work = kq::begin_call(b, fn, ncall, src, scope);
+  if (work != kq::CALL_RUN) return work == kq::CALL_FAILED ? -1 : 0;
   auto &d = b->d;
-  size_t const S = b->cfg.max_slots, nlist = d.slots.all.size();
+  size_t const nlist = d.slots.all.size();
   CallArgs a{};
   if (kq::fskfront::bind_front(&a.f, *b, d.slots, d.front, b->g, b->turn, b->n_cur, b->cfg.max_samples, src, format, src_stride,
-                               row_stride, block_len, nblocks, on_device))
+                               row_stride, block_len, nblocks, on_device) ||
+      kq::bind_status(b, on_device, status, status_stride, &a.st, &a.sstride))
     return -1;
   a.max_pages = b->max_pages;
   a.mpw = b->mpw;
@@ -403,79 +387,33 @@ int kq_pag_process(kq_pag_bank *b, const void *src, int format, size_t src_strid
   a.state = d.state;
   a.open = d.open;
   a.pages = d.pages;
-  a.info = d.info;
-  a.npages = d.npages;
-  if (on_device) {
-    a.st = status;
-    a.sstride = status_stride;
-  } else {
-    if (status && !d.st && b->alloc(&d.st, S)) return -1;
-    a.st = status ? d.st : nullptr;
-    a.sstride = 1;
-  }
+  a.info = d.arena.ev;
+  a.npages = d.arena.n;
   if (kq::fskfront::launch_front(a.f, nlist, b->stream)) return -1;
   hipLaunchKernelGGL(k_pag_track, dim3((unsigned)((nlist + 63) / 64)), dim3(64), 0, b->stream, a, (int)nlist);
   KQ_TRY(hipGetLastError());
   b->turn ^= 1;  // from here on the carried q is in the other copy, whatever fails below
   b->n_cur += ncall;
-  if (!on_device) {
-    auto back = [&](size_t s0, size_t n) {  // the records of the active slots
-      return kq::copy_rows_back(*b, status, status_stride, d.st, 1, 1, sizeof(kq_pag_status), s0, n);
-    };
-    if (status && d.slots.for_runs(back)) return -1;
-    KQ_TRY(hipStreamSynchronize(b->stream));
-  }
-  return 0;
+  return on_device ? 0 : kq::end_host_call(b, status, status_stride, nullptr);
 }
 
-int kq_pag_pull_counts(kq_pag_bank *b, uint32_t *counts) {
-  if (!b) {
-    kq_internal_set_error("kq_pag_pull_counts: null bank");
-    return -1;
-  }
-  if (!counts) {
-    kq_internal_set_error("kq_pag_pull_counts: null counts");
-    return -1;
-  }
-  std::lock_guard<std::mutex> lk(b->mu);
-  if (!b->dev_ready) {
-    std::memset(counts, 0, b->cfg.max_slots * sizeof(uint32_t));
-    return 0;
-  }
-  kq::DeviceScope dev_scope_(b->cfg.device);
-  KQ_TRY(hipMemcpyAsync(counts, b->d.npages, b->cfg.max_slots * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
-  KQ_TRY(hipStreamSynchronize(b->stream));
-  return 0;
-}
+int kq_pag_pull_counts(kq_pag_bank *b, uint32_t *counts) { return kq::pull_counts(b, "kq_pag_pull_counts", counts); }
 
 int kq_pag_pull_page(kq_pag_bank *b, unsigned slot, unsigned index, unsigned char *dst, size_t cap, kq_pag_page_info *info) {
+  const char *fn = "kq_pag_pull_page";
   if (!b) {
-    kq_internal_set_error("kq_pag_pull_page: null bank");
+    kq_internal_set_error("%s: null bank", fn);
     return -1;
   }
   if (!dst) {
-    kq_internal_set_error("kq_pag_pull_page: null dst");
+    kq_internal_set_error("%s: null dst", fn);
     return -1;
   }
   std::lock_guard<std::mutex> lk(b->mu);
-  if (slot >= b->cfg.max_slots) {
-    kq_internal_set_error("kq_pag_pull_page: slot %u >= max_slots %u", slot, b->cfg.max_slots);
-    return -1;
-  }
-  unsigned n = 0;
-  kq::DeviceScope dev_scope_(b->cfg.device);
-  if (b->dev_ready) {
-    KQ_TRY(hipMemcpyAsync(&n, b->d.npages + slot, sizeof n, hipMemcpyDeviceToHost, b->stream));
-    KQ_TRY(hipStreamSynchronize(b->stream));
-  }
-  if (index >= n) {
-    kq_internal_set_error("kq_pag_pull_page: slot %u has %u pages", slot, n);
-    return -1;
-  }
-  size_t const at = (size_t)slot * b->max_pages + index;
+  std::optional<kq::DeviceScope> scope;
   kq_pag_page_info r;
-  KQ_TRY(hipMemcpyAsync(&r, b->d.info + at, sizeof r, hipMemcpyDeviceToHost, b->stream));
-  KQ_TRY(hipStreamSynchronize(b->stream));
+  size_t at;
+  if (kq::pull_record(b, fn, slot, index, "pages", &r, &at, scope)) return -1;
   size_t const take = std::min(cap, (size_t)3 * r.nwords);
   if (take) {
     KQ_TRY(hipMemcpyAsync(dst, b->d.pages + at * 3 * b->mpw, take, hipMemcpyDeviceToHost, b->stream));
@@ -485,17 +423,7 @@ int kq_pag_pull_page(kq_pag_bank *b, unsigned slot, unsigned index, unsigned cha
   return (int)(3 * r.nwords);
 }
 
-int kq_pag_clear_pages(kq_pag_bank *b) {
-  if (!b) {
-    kq_internal_set_error("kq_pag_clear_pages: null bank");
-    return -1;
-  }
-  std::lock_guard<std::mutex> lk(b->mu);
-  if (!b->dev_ready) return 0;
-  kq::DeviceScope dev_scope_(b->cfg.device);
-  KQ_TRY(hipMemsetAsync(b->d.npages, 0, b->cfg.max_slots * sizeof(unsigned), b->stream));
-  return 0;
-}
+int kq_pag_clear_pages(kq_pag_bank *b) { return kq::clear_arena(b, "kq_pag_clear_pages"); }
 
 int kq_pag_get_taps(const kq_pag_bank *b, int16_t *dst, size_t cap) {
   if (!b) {
@@ -514,19 +442,7 @@ int kq_pag_get_taps(const kq_pag_bank *b, int16_t *dst, size_t cap) {
 int kq_pag_sync(kq_pag_bank *b) { return kq::sync_bank(b, "kq_pag_sync"); }
 
 int kq_pag_reset(kq_pag_bank *b) {
-  if (!b) {
-    kq_internal_set_error("kq_pag_reset: null bank");
-    return -1;
-  }
-  std::lock_guard<std::mutex> lk(b->mu);
-  b->n_cur = 0;
-  if (!b->dev_ready) return 0;
-  kq::DeviceScope dev_scope_(b->cfg.device);
-  KQ_TRY(hipStreamSynchronize(b->stream));
-  for (int s : b->d.slots.all)
-    if (cold_start(b, (unsigned)s)) return -1;
-  KQ_TRY(hipStreamSynchronize(b->stream));
-  return 0;
+  return kq::reset_slots(b, "kq_pag_reset", [b](unsigned s) { return cold_start(b, s); });
 }
 
 }  // extern "C"

@@ -30,11 +30,12 @@
 #include "kq_device.hpp"
 #include "kq_host.hpp"
 #include "kq_slots.hpp"
+#include "kq_tonecorr.hpp"
 
 namespace {
 
+using kq::tonecorr::kTable;
 constexpr unsigned kMaxSlots = 16384;
-constexpr int kTable = 1024;
 constexpr int kThreads = 256, kWaves = kThreads / 64;
 constexpr int kTile = 3200;                     // samples a wave keeps in LDS: 64 frames of B = 48 at stride 50; with the rest
                                                 // the workgroup stays under 40 KiB, four workgroups to a CU
@@ -43,12 +44,10 @@ constexpr int kRow = kHist + 64 + 1;            // a wave's reduced sums of one 
 constexpr unsigned kWait = 0, kIdle = 1, kChar = 2;
 
 struct RttyGeom {
-  int B, Bs;                     // Bs: a frame's stride in LDS, >= B, Bs / 2 odd
-  unsigned magic;                // ceil(2^32 / B): x / B = umulhi(x, magic) for x < 2^16
+  kq::tonecorr::FrameGrid grid;
   unsigned warm, snr;
   unsigned long long min_p;
   int max_events;
-  float scale;
 };
 
 struct RttyPar {  // per slot, written by the host when a call finds the slot set anew
@@ -66,7 +65,7 @@ struct CallArgs {
   RttyGeom g;
   const RttyPar *par;
   const int *list;               // active slots, ascending
-  const int *rowmap;             // per list entry: the row of `src` (host input, staged) or null (par.source)
+  const int *rowmap;             // per list entry: the row of in.src (host input, staged) or null (par.source)
   const short *table;            // [1024]
   kq_rtty_status *state;         // [S]
   RttyHist *hist;                // [S]
@@ -75,29 +74,11 @@ struct CallArgs {
   int nlist;
   int L;                         // lanes to a frame, a power of two <= 64
   int64_t n0, n1;                // the call's samples
-  // input
-  const void *src;
-  int format;
-  size_t src_stride, row_stride;
-  unsigned block_len;
+  kq::PcmIn in;
   // output
   kq_rtty_status *st;
   size_t sstride;
 };
-
-// q of the call's i-th sample (i < 2^28)
-__device__ __forceinline__ int load_q(CallArgs const &a, size_t row, unsigned i) {
-  unsigned const k = i / a.block_len, j = i - k * a.block_len;
-  size_t const idx = row * a.src_stride + (size_t)k * a.row_stride + j;
-  if (a.format == KQ_PCM_S16BE) {
-    const unsigned char *p = reinterpret_cast<const unsigned char *>(a.src) + 2 * idx;
-    int const w = (int)(short)(unsigned short)(((unsigned)p[0] << 8) | p[1]);
-    return w < -32767 ? -32767 : w;
-  }
-  float const v = rintf(reinterpret_cast<const float *>(a.src)[idx] * a.g.scale);
-  if (!(v == v)) return 0;
-  return (int)fminf(fmaxf(v, -32767.f), 32767.f);
-}
 
 __device__ __forceinline__ unsigned sat_inc(unsigned v) { return v == 0xFFFFFFFFu ? v : v + 1; }
 
@@ -110,7 +91,7 @@ __device__ __forceinline__ void file_event(RttyGeom const &g, kq_rtty_status &s,
   kq_rtty_event r;
   r.code = s.code;
   r.flags = flags;
-  r.start_sample = s.start * (unsigned long long)g.B;
+  r.start_sample = s.start * (unsigned long long)g.grid.B;
   r.sig = s.sig;
   r.nse = s.nse;
   ev[nev++] = r;
@@ -182,13 +163,12 @@ __global__ __launch_bounds__(kThreads) void k_rtty(CallArgs c) {
   int const tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = (int)blockIdx.x * kWaves + wave;
   bool const live = li < c.nlist;
   int const slot = live ? c.list[li] : 0;
-  for (int i = tid; i < kTable; i += kThreads)
-    CS[i] = ((int)c.table[i] & 0xFFFF) | ((int)c.table[(i - 256) & (kTable - 1)] << 16);
+  kq::tonecorr::load_packed_table(CS, c.table, tid, kThreads);
   RttyPar const par = c.par[slot];
   size_t const row = live && c.rowmap ? (size_t)c.rowmap[li] : (size_t)par.source;
-  int const B = g.B, L = c.L, F = 64 / L, f = lane / L, p = lane & (L - 1);
+  int const B = g.grid.B, L = c.L, F = 64 / L, f = lane / L, p = lane & (L - 1);
   int const W = live ? min(max(par.W, 1), kHist + 1) : 1;  // (the host keeps it in 8..32)
-  unsigned const inc_m = par.inc_m, inc_s = par.inc_s, step_m = (unsigned)L * inc_m, step_s = (unsigned)L * inc_s;
+  unsigned const inc[2] = {par.inc_m, par.inc_s};
   // carried: lane 0 holds the record, the open frame's sums in it; the history goes to the front of A
   kq_rtty_status s{};
   unsigned nev = 0;
@@ -200,41 +180,13 @@ __global__ __launch_bounds__(kThreads) void k_rtty(CallArgs c) {
   if (lane < kHist)
     for (int t = 0; t < 4; t++) A[wave][t][lane] = live ? c.hist[slot].v[t][lane] : 0;
   long long cy[4] = {s.acc_im, s.acc_qm, s.acc_is, s.acc_qs};
-  short *q = qs[wave];
   int64_t n = c.n0, k0 = c.n0 / B;
   while (n < c.n1) {  // one piece: the frames k0 .. k0 + F - 1, from n to their end or the call's; x counts from k0 B
     int64_t const pe = (k0 + F) * (int64_t)B, e = pe < c.n1 ? pe : c.n1;
     int const x0 = (int)(n - k0 * B), x1 = x0 + (int)(e - n);  // x1 <= F B
-    __syncthreads();  // the piece before is done with q, A, Pb, carry and lastsum (and the first finds CS and A loaded)
-    if (live) {
-      for (int x = x0 + lane; x < x1; x += 64) {
-        unsigned const fr = __umulhi((unsigned)x, g.magic);
-        q[fr * g.Bs + ((unsigned)x - fr * (unsigned)B)] = (short)load_q(c, row, (unsigned)(n - c.n0) + (unsigned)(x - x0));
-      }
-    }
-    __syncthreads();
-    long long sm[4] = {0, 0, 0, 0};
-    int const xa = x0 > f * B ? x0 : f * B, xb = x1 < (f + 1) * B ? x1 : (f + 1) * B;
-    if (live) {
-      unsigned const at = (unsigned)(k0 * B) + (unsigned)(xa + p);  // (n inc) mod 2^32 needs n mod 2^32 only
-      unsigned pm = at * inc_m, ps = at * inc_s;
-      const short *qf = q + f * (g.Bs - B);
-      for (int x = xa + p; x < xb; x += L, pm += step_m, ps += step_s) {
-        int const v = qf[x], cm = CS[pm >> 22], cs = CS[ps >> 22];
-        sm[0] += (long long)v * (short)cm;
-        sm[1] += (long long)v * (cm >> 16);
-        sm[2] += (long long)v * (short)cs;
-        sm[3] += (long long)v * (cs >> 16);
-      }
-    }
-    for (int off = L >> 1; off; off >>= 1)
-      for (int t = 0; t < 4; t++) sm[t] += __shfl_xor(sm[t], off);
-    if (lane == 0)  // frame 0 of the call's first piece goes on from the carried sums
-      for (int t = 0; t < 4; t++) {
-        sm[t] += cy[t];
-        cy[t] = 0;
-      }
-    int const done = (int)__umulhi((unsigned)x1, g.magic);  // frames of the piece that are complete
+    long long sm[4];  // (its first barrier: the piece before is done with q, A, Pb, carry and lastsum, and A is loaded)
+    kq::tonecorr::correlate_piece<2>(g.grid, c.in, row, live, lane, L, c.n0, n, k0, x0, x1, qs[wave], CS, inc, sm, cy);
+    int const done = (int)__umulhi((unsigned)x1, g.grid.magic);  // frames of the piece that are complete
     if (p == 0 && f * B < x1) {
       if (f < done) {
         for (int t = 0; t < 4; t++) A[wave][t][kHist + f] = (int)(sm[t] >> 12);
@@ -286,49 +238,27 @@ __global__ __launch_bounds__(kThreads) void k_rtty(CallArgs c) {
   }
 }
 
-// C[j] = rint(32767 cos(2 pi j / 1024)), made once
-std::vector<short> const &cos_table() {
-  static std::vector<short> const table = [] {
-    std::vector<short> t((size_t)kTable);
-    for (int j = 0; j < kTable; j++) t[j] = (short)std::lrint(32767.0 * std::cos(2.0 * M_PI * j / kTable));
-    return t;
-  }();
-  return table;
-}
-
 }  // namespace
 
 struct kq_rtty_bank : kq::HostSide {
+  static constexpr bool kDeferred = true;
   kq_rtty_config cfg;
   std::mutex mu;
   bool dev_ready = false;
   RttyGeom g{};
   int Lmin = 1;                  // the least lanes to a frame whose piece fits kTile
   uint64_t n_cur = 0;
-  // kq_rtty_set and kq_rtty_remove touch no device: they change `want`, and the next call that needs the device brings
-  // the slots in `dirty` there (a cold start for each that is set)
-  std::vector<RttyPar> want;
-  std::vector<unsigned> dirty;
-  std::vector<char> is_dirty;
-  size_t nwant = 0;              // active entries of `want`
+  kq::DeferredSlots<RttyPar> def;
   struct Dev {  // kq::lazy_device
     kq::SlotTable<RttyPar> slots;
     short *table = nullptr;
     kq_rtty_status *state = nullptr;
     RttyHist *hist = nullptr;
-    kq_rtty_event *ev = nullptr;
-    unsigned *nev = nullptr;
+    kq::EventArena<kq_rtty_event> arena;
     kq_rtty_status *st = nullptr;        // host-memory calls
   } d;
 
-  // no device yet and no slot that wants one: the entry points then ask for none
-  bool deviceless() const { return !dev_ready && nwant == 0; }
-
-  void touch(unsigned slot) {
-    if (is_dirty[slot]) return;
-    is_dirty[slot] = 1;
-    dirty.push_back(slot);
-  }
+  int to_device();
 };
 
 namespace {
@@ -337,56 +267,24 @@ int make_device(kq_rtty_bank *b) {
   auto &d = b->d;
   if (b->open_stream(b->cfg.stream)) return -1;
   size_t const S = b->cfg.max_slots;
-  if (d.slots.alloc(*b, S) || b->alloc(&d.table, (size_t)kTable) || b->alloc(&d.state, S, true) || b->alloc(&d.hist, S, true) ||
-      b->alloc(&d.ev, S * (size_t)b->g.max_events) || b->alloc(&d.nev, S, true))
+  if (d.slots.alloc(*b, S) || kq::tonecorr::alloc_table(*b, &d.table) || b->alloc(&d.state, S, true) ||
+      b->alloc(&d.hist, S, true) || d.arena.alloc(*b, S, b->cfg.max_events))
     return -1;
-  KQ_TRY(hipMemcpyAsync(d.table, cos_table().data(), kTable * sizeof(short), hipMemcpyHostToDevice, b->stream));
   KQ_TRY(hipStreamSynchronize(b->stream));
   return 0;
 }
-
-// The slots that were set or removed since the last call, to the device: the record and the history of a slot that is set
-// start cold (all zero: the header's state at the set) and its arena empty.  Consecutive slots go together: a run of them
-// costs one copy of its parameters and, where they are set, three memsets, however long it is (4096 slots set before the
-// first call are four runtime calls, not sixteen thousand).  Waits for the stream first and last.  Without a device and
-// without a slot that wants one nothing happens.
-int flush(kq_rtty_bank *b) {
-  if (b->dirty.empty()) return 0;
-  auto forget = [b] {
-    for (unsigned s : b->dirty) b->is_dirty[s] = 0;
-    b->dirty.clear();
-  };
-  if (b->deviceless()) {
-    forget();
-    return 0;
-  }
-  if (kq::lazy_device(b, make_device)) return -1;
-  KQ_TRY(hipStreamSynchronize(b->stream));
-  auto &t = b->d.slots;
-  std::sort(b->dirty.begin(), b->dirty.end());
-  for (unsigned s : b->dirty) t.par[s] = b->want[s];
-  for (size_t i = 0; i < b->dirty.size();) {  // a run: consecutive slots, all set or all removed
-    unsigned const s0 = b->dirty[i];
-    int const set = t.par[s0].active;
-    size_t j = i + 1;
-    while (j < b->dirty.size() && b->dirty[j] == b->dirty[j - 1] + 1 && t.par[b->dirty[j]].active == set) j++;
-    size_t const n = j - i;
-    if (set) {
-      KQ_TRY(hipMemsetAsync(b->d.state + s0, 0, n * sizeof(kq_rtty_status), b->stream));
-      KQ_TRY(hipMemsetAsync(b->d.hist + s0, 0, n * sizeof(RttyHist), b->stream));
-      KQ_TRY(hipMemsetAsync(b->d.nev + s0, 0, n * sizeof(unsigned), b->stream));
-    }
-    KQ_TRY(hipMemcpyAsync(t.d_par + s0, &t.par[s0], n * sizeof(RttyPar), hipMemcpyHostToDevice, b->stream));  // (t.par stays)
-    i = j;
-  }
-  if (t.upload(*b, b->dirty.back())) return -1;  // the active list and the wait (and that one record once more)
-  forget();
-  return 0;
-}
-
-bool in_range(unsigned v, unsigned lo, unsigned hi) { return v >= lo && v <= hi; }
 
 }  // namespace
+
+// kq::DeferredSlots::flush; the record and the history of a slot that is set start cold (all zero: the header's state at
+// the set) and its arena empty
+int kq_rtty_bank::to_device() {
+  return def.flush(this, make_device, [this](size_t s0, size_t n) {
+    KQ_TRY(hipMemsetAsync(d.state + s0, 0, n * sizeof(kq_rtty_status), stream));
+    KQ_TRY(hipMemsetAsync(d.hist + s0, 0, n * sizeof(RttyHist), stream));
+    return d.arena.clear(*this, s0, n);
+  });
+}
 
 extern "C" {
 
@@ -396,59 +294,23 @@ kq_rtty_bank *kq_rtty_create(const kq_rtty_config *cfg) {
     kq_internal_set_error("%s: null config", fn);
     return nullptr;
   }
-  double const Fs = cfg->samprate;
-  if (!(Fs > 0) || !std::isfinite(Fs)) {
-    kq_internal_set_error("%s: samprate %.10g must be positive and finite", fn, Fs);
+  if (!kq::samprate_ok(fn, cfg->samprate) || !kq::field_in_range(fn, "block_len", cfg->block_len, 8, 256) ||
+      !kq::field_in_range(fn, "warm", cfg->warm, 0, 65535) || !kq::field_in_range(fn, "snr", cfg->snr, 16, 4095) ||
+      !kq::min_p_ok(fn, cfg->min_p) || !kq::input_scale_ok(fn, cfg->input_scale) ||
+      !kq::field_in_range(fn, "max_slots", cfg->max_slots, 1, kMaxSlots) ||
+      !kq::field_in_range(fn, "max_events", cfg->max_events, 1, 4096) || !kq::max_samples_ok(fn, cfg->max_samples))
     return nullptr;
-  }
-  if (!in_range(cfg->block_len, 8, 256)) {
-    kq_internal_set_error("%s: block_len %u must be 8..256", fn, cfg->block_len);
-    return nullptr;
-  }
-  if (cfg->warm > 65535) {
-    kq_internal_set_error("%s: warm %u must be 0..65535", fn, cfg->warm);
-    return nullptr;
-  }
-  if (!in_range(cfg->snr, 16, 4095)) {
-    kq_internal_set_error("%s: snr %u must be 16..4095", fn, cfg->snr);
-    return nullptr;
-  }
-  if (cfg->min_p > (1ull << 55)) {
-    kq_internal_set_error("%s: min_p %llu must be 0..2^55", fn, (unsigned long long)cfg->min_p);
-    return nullptr;
-  }
-  if (!std::isfinite(cfg->input_scale) || !(cfg->input_scale > 0)) {
-    kq_internal_set_error("%s: input_scale must be finite and positive", fn);
-    return nullptr;
-  }
-  if (!in_range(cfg->max_slots, 1, kMaxSlots)) {
-    kq_internal_set_error("%s: max_slots %u must be 1..%u", fn, cfg->max_slots, kMaxSlots);
-    return nullptr;
-  }
-  if (!in_range(cfg->max_events, 1, 4096)) {
-    kq_internal_set_error("%s: max_events %u must be 1..4096", fn, cfg->max_events);
-    return nullptr;
-  }
-  if (cfg->max_samples == 0 || cfg->max_samples > ((size_t)1 << 28)) {
-    kq_internal_set_error("%s: max_samples %zu must be 1..2^28", fn, cfg->max_samples);
-    return nullptr;
-  }
-  (void)cos_table();  // the table exists from here on
+  (void)kq::tonecorr::cos_table();  // the table exists from here on
   kq_rtty_bank *b = new kq_rtty_bank;
   b->cfg = *cfg;
-  b->want.assign(cfg->max_slots, RttyPar{});
-  b->is_dirty.assign(cfg->max_slots, 0);
+  b->def.init(cfg->max_slots);
   RttyGeom &g = b->g;
-  g.B = (int)cfg->block_len;
-  g.Bs = g.B + ((g.B & 1) ? 1 : 0);  // even
-  if ((g.Bs & 3) == 0) g.Bs += 2;    // and Bs / 2 odd
-  g.magic = (unsigned)((0x100000000ull + cfg->block_len - 1) / cfg->block_len);
+  g.grid = kq::tonecorr::frame_grid(cfg->block_len);
   g.warm = cfg->warm;
   g.snr = cfg->snr;
   g.min_p = cfg->min_p;
   g.max_events = (int)cfg->max_events;
-  g.scale = cfg->input_scale;
-  while ((64 / b->Lmin) * g.Bs > kTile) b->Lmin *= 2;  // ends at 8: Bs <= 258
+  b->Lmin = kq::tonecorr::least_lanes(g.grid, kTile);  // 8 at the most: Bs <= 258
   return b;
 }
 
@@ -476,10 +338,7 @@ int kq_rtty_set(kq_rtty_bank *b, unsigned slot, const kq_rtty_params *p) {
     kq_internal_set_error("%s: mark and space are both %g", fn, fm);
     return -1;
   }
-  if (!in_range(p->nbits, 5, 8)) {
-    kq_internal_set_error("%s: nbits %u must be 5..8", fn, p->nbits);
-    return -1;
-  }
+  if (!kq::field_in_range(fn, "nbits", p->nbits, 5, 8)) return -1;
   if (!(baud > 0) || !std::isfinite(baud)) {
     kq_internal_set_error("%s: baud %g must be positive and finite", fn, baud);
     return -1;
@@ -498,65 +357,27 @@ int kq_rtty_set(kq_rtty_bank *b, unsigned slot, const kq_rtty_params *p) {
   np.tb = (int)tb;
   np.W = (np.tb + 128) >> 8;
   np.nbits = (int)p->nbits;
-  b->nwant += !b->want[slot].active;
-  b->want[slot] = np;
-  b->touch(slot);
+  b->def.set(slot, np);
   return 0;
 }
 
-int kq_rtty_remove(kq_rtty_bank *b, unsigned slot) {
-  if (!b) {
-    kq_internal_set_error("kq_rtty_remove: null bank");
-    return -1;
-  }
-  std::lock_guard<std::mutex> lk(b->mu);
-  if (slot >= b->cfg.max_slots || !b->want[slot].active) {
-    kq_internal_set_error("kq_rtty_remove: slot %u holds no decoder", slot);
-    return -1;
-  }
-  b->want[slot] = RttyPar{};
-  b->nwant--;
-  b->touch(slot);
-  return 0;
-}
+int kq_rtty_remove(kq_rtty_bank *b, unsigned slot) { return kq::deferred_remove(b, slot, "kq_rtty_remove"); }
 
 int kq_rtty_process(kq_rtty_bank *b, const void *src, int format, size_t src_stride, size_t row_stride, unsigned block_len,
                     unsigned nblocks, int on_device, kq_rtty_status *status, size_t status_stride) {
+  const char *fn = "kq_rtty_process";
   if (!b) {
-    kq_internal_set_error("kq_rtty_process: null bank");
-    return -1;
-  }
-  if (format != KQ_PCM_F32 && format != KQ_PCM_S16BE) {
-    kq_internal_set_error("kq_rtty_process: unknown sample format %d", format);
+    kq_internal_set_error("%s: null bank", fn);
     return -1;
   }
   std::lock_guard<std::mutex> lk(b->mu);
-  if (!kq::blocks_ok("kq_rtty_process", b->cfg.max_samples, row_stride, block_len, nblocks)) return -1;
+  if (!kq::call_args_ok(fn, format, b->cfg.max_samples, row_stride, block_len, nblocks, status, status_stride)) return -1;
   size_t const ncall = (size_t)block_len * nblocks;
-  if (status && status_stride < 1) {
-    kq_internal_set_error("kq_rtty_process: status_stride %zu < 1", status_stride);
-    return -1;
-  }
-  if (ncall == 0) return 0;
-  if (!src) {
-    kq_internal_set_error("kq_rtty_process: null src");
-    return -1;
-  }
-  if (b->deviceless()) {
-    (void)flush(b);
-    b->n_cur += ncall;
-    return 0;
-  }
-  kq::DeviceScope dev_scope_(b->cfg.device);
-  if (flush(b)) return -1;
-  kq::CallWork const work = kq::call_work(b, "kq_rtty_process", ncall, src, "src");
-  if (work == kq::CALL_IDLE) {
-    b->n_cur += ncall;
-    return 0;
-  }
-  if (work != kq::CALL_RUN) return work;
+  std::optional<kq::DeviceScope> scope;
+  kq::CallWork const work = kq::begin_call(b, fn, ncall, src, scope);
+  if (work != kq::CALL_RUN) return work == kq::CALL_FAILED ? -1 : 0;
   auto &d = b->d;
-  size_t const S = b->cfg.max_slots, nlist = d.slots.all.size();
+  size_t const nlist = d.slots.all.size();
   CallArgs a{};
   a.g = b->g;
   a.par = d.slots.d_par;
@@ -564,130 +385,32 @@ int kq_rtty_process(kq_rtty_bank *b, const void *src, int format, size_t src_str
   a.table = d.table;
   a.state = d.state;
   a.hist = d.hist;
-  a.ev = d.ev;
-  a.nev = d.nev;
+  a.ev = d.arena.ev;
+  a.nev = d.arena.n;
   a.nlist = (int)nlist;
   a.n0 = (int64_t)b->n_cur;
   a.n1 = a.n0 + (int64_t)ncall;
-  // lanes to a frame: what the piece needs, and more where the call's frames (at most nf) do not fill a wave
-  size_t const nf = (ncall + (size_t)b->g.B - 2) / (size_t)b->g.B + 1;
-  a.L = b->Lmin;
-  while (a.L < 64 && (size_t)(2 * a.L) * nf <= 64) a.L *= 2;
-  a.format = format;
-  a.block_len = block_len;
-  if (on_device) {
-    a.src = src;
-    a.src_stride = src_stride;
-    a.row_stride = row_stride;
-    a.rowmap = nullptr;
-    a.st = status;
-    a.sstride = status_stride;
-  } else {
-    kq::Staged in;
-    if (d.slots.stage_rows(*b, src, format == KQ_PCM_S16BE ? 2 : 4, src_stride, row_stride, block_len, nblocks,
-                           b->cfg.max_samples * 4, &in))
-      return -1;
-    a.src = in.src;
-    a.src_stride = in.src_stride;
-    a.row_stride = in.row_stride;
-    a.rowmap = in.rowmap;
-    if (status && !d.st && b->alloc(&d.st, S)) return -1;
-    a.st = status ? d.st : nullptr;
-    a.sstride = 1;
-  }
+  a.L = kq::tonecorr::lanes_for_call(b->g.grid, b->Lmin, ncall);
+  if (kq::bind_pcm(&a.in, &a.rowmap, *b, d.slots, b->cfg.max_samples, b->cfg.input_scale, src, format, src_stride, row_stride, block_len,
+                   nblocks, on_device) ||
+      kq::bind_status(b, on_device, status, status_stride, &a.st, &a.sstride))
+    return -1;
   hipLaunchKernelGGL(k_rtty, dim3((unsigned)((nlist + kWaves - 1) / kWaves)), dim3(kThreads), 0, b->stream, a);
   KQ_TRY(hipGetLastError());
   b->n_cur += ncall;
-  if (!on_device) {
-    auto back = [&](size_t s0, size_t n) {  // the records of the active slots
-      return kq::copy_rows_back(*b, status, status_stride, d.st, 1, 1, sizeof(kq_rtty_status), s0, n);
-    };
-    if (status && d.slots.for_runs(back)) return -1;
-    KQ_TRY(hipStreamSynchronize(b->stream));
-  }
-  return 0;
+  return on_device ? 0 : kq::end_host_call(b, status, status_stride, nullptr);
 }
 
-int kq_rtty_pull_counts(kq_rtty_bank *b, uint32_t *counts) {
-  if (!b) {
-    kq_internal_set_error("kq_rtty_pull_counts: null bank");
-    return -1;
-  }
-  if (!counts) {
-    kq_internal_set_error("kq_rtty_pull_counts: null counts");
-    return -1;
-  }
-  std::lock_guard<std::mutex> lk(b->mu);
-  if (b->deviceless()) {
-    (void)flush(b);
-    std::memset(counts, 0, b->cfg.max_slots * sizeof(uint32_t));
-    return 0;
-  }
-  kq::DeviceScope dev_scope_(b->cfg.device);
-  if (flush(b)) return -1;  // a slot set since the last call shows its empty arena
-  KQ_TRY(hipMemcpyAsync(counts, b->d.nev, b->cfg.max_slots * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
-  KQ_TRY(hipStreamSynchronize(b->stream));
-  return 0;
-}
+int kq_rtty_pull_counts(kq_rtty_bank *b, uint32_t *counts) { return kq::pull_counts(b, "kq_rtty_pull_counts", counts); }
 
 int kq_rtty_pull_event(kq_rtty_bank *b, unsigned slot, unsigned index, kq_rtty_event *event) {
-  if (!b) {
-    kq_internal_set_error("kq_rtty_pull_event: null bank");
-    return -1;
-  }
-  if (!event) {
-    kq_internal_set_error("kq_rtty_pull_event: null event");
-    return -1;
-  }
-  std::lock_guard<std::mutex> lk(b->mu);
-  if (slot >= b->cfg.max_slots) {
-    kq_internal_set_error("kq_rtty_pull_event: slot %u >= max_slots %u", slot, b->cfg.max_slots);
-    return -1;
-  }
-  unsigned n = 0;
-  if (b->deviceless()) {
-    (void)flush(b);
-    kq_internal_set_error("kq_rtty_pull_event: slot %u has %u events", slot, n);
-    return -1;
-  }
-  kq::DeviceScope dev_scope_(b->cfg.device);
-  if (flush(b)) return -1;
-  KQ_TRY(hipMemcpyAsync(&n, b->d.nev + slot, sizeof n, hipMemcpyDeviceToHost, b->stream));
-  KQ_TRY(hipStreamSynchronize(b->stream));
-  if (index >= n) {
-    kq_internal_set_error("kq_rtty_pull_event: slot %u has %u events", slot, n);
-    return -1;
-  }
-  size_t const at = (size_t)slot * b->cfg.max_events + index;
-  KQ_TRY(hipMemcpyAsync(event, b->d.ev + at, sizeof *event, hipMemcpyDeviceToHost, b->stream));
-  KQ_TRY(hipStreamSynchronize(b->stream));
-  return 0;
+  return kq::pull_event(b, "kq_rtty_pull_event", slot, index, event);
 }
 
-int kq_rtty_clear_events(kq_rtty_bank *b) {
-  if (!b) {
-    kq_internal_set_error("kq_rtty_clear_events: null bank");
-    return -1;
-  }
-  std::lock_guard<std::mutex> lk(b->mu);
-  if (!b->dev_ready) return 0;
-  kq::DeviceScope dev_scope_(b->cfg.device);
-  KQ_TRY(hipMemsetAsync(b->d.nev, 0, b->cfg.max_slots * sizeof(unsigned), b->stream));
-  return 0;
-}
+int kq_rtty_clear_events(kq_rtty_bank *b) { return kq::clear_arena(b, "kq_rtty_clear_events"); }
 
 int kq_rtty_get_table(const kq_rtty_bank *b, int16_t *dst, size_t cap) {
-  if (!b) {
-    kq_internal_set_error("kq_rtty_get_table: null bank");
-    return -1;
-  }
-  if (!dst && cap) {
-    kq_internal_set_error("kq_rtty_get_table: null dst");
-    return -1;
-  }
-  size_t const n = std::min(cap, (size_t)kTable);
-  if (n) std::memcpy(dst, cos_table().data(), n * sizeof(int16_t));
-  return kTable;
+  return kq::tonecorr::get_table(b, "kq_rtty_get_table", dst, cap);
 }
 
 int kq_rtty_get_slot(kq_rtty_bank *b, unsigned slot, kq_rtty_slot *out) {
@@ -700,11 +423,11 @@ int kq_rtty_get_slot(kq_rtty_bank *b, unsigned slot, kq_rtty_slot *out) {
     return -1;
   }
   std::lock_guard<std::mutex> lk(b->mu);
-  if (slot >= b->cfg.max_slots || !b->want[slot].active) {
+  if (!b->def.is_set(slot)) {
     kq_internal_set_error("kq_rtty_get_slot: slot %u holds no decoder", slot);
     return -1;
   }
-  RttyPar const &w = b->want[slot];
+  RttyPar const &w = b->def.want[slot];
   out->inc_m = w.inc_m;
   out->inc_s = w.inc_s;
   out->tb = (uint32_t)w.tb;
@@ -714,16 +437,6 @@ int kq_rtty_get_slot(kq_rtty_bank *b, unsigned slot, kq_rtty_slot *out) {
 
 int kq_rtty_sync(kq_rtty_bank *b) { return kq::sync_bank(b, "kq_rtty_sync"); }
 
-int kq_rtty_reset(kq_rtty_bank *b) {
-  if (!b) {
-    kq_internal_set_error("kq_rtty_reset: null bank");
-    return -1;
-  }
-  std::lock_guard<std::mutex> lk(b->mu);
-  b->n_cur = 0;
-  for (unsigned s = 0; s < b->cfg.max_slots; s++)  // every slot that is set starts cold at the next call
-    if (b->want[s].active) b->touch(s);
-  return 0;
-}
+int kq_rtty_reset(kq_rtty_bank *b) { return kq::deferred_reset(b, "kq_rtty_reset"); }
 
 }  // extern "C"

@@ -26,12 +26,13 @@
 #include "kq_device.hpp"
 #include "kq_host.hpp"
 #include "kq_slots.hpp"
+#include "kq_tonecorr.hpp"
 
 namespace {
 
 constexpr unsigned kMaxSlots = 4096;
 constexpr int kMaxTones = 32;
-constexpr int kTable = 1024;
+using kq::tonecorr::kTable;
 constexpr int kThreads = 256, kWaves = kThreads / 64;
 constexpr int kTile = 2048;                     // samples in LDS at a time
 
@@ -41,7 +42,6 @@ struct ToneGeom {
   unsigned long long min_e;      // min_ms B
   unsigned frac, ratio, twist, min_blocks;
   int max_events;
-  float scale;
 };
 
 struct TonePar {  // per slot, written by the host at kq_tone_set
@@ -60,7 +60,7 @@ struct CallArgs {
   ToneGeom g;
   const TonePar *par;
   const int *list;               // active slots, ascending
-  const int *rowmap;             // per list entry: the row of `src` (host input, staged) or null (par.source)
+  const int *rowmap;             // per list entry: the row of in.src (host input, staged) or null (par.source)
   const short *table;            // [1024]
   const unsigned *incs;          // [T]
   ToneState *state;              // [S]
@@ -69,31 +69,13 @@ struct CallArgs {
   kq_tone_event *ev;             // [S][max_events]
   unsigned *nev;                 // [S]
   int64_t n0, n1;                // the call's samples
-  // input
-  const void *src;
-  int format;
-  size_t src_stride, row_stride;
-  unsigned block_len;
+  kq::PcmIn in;
   // output
   kq_tone_status *st;
   size_t sstride;
   unsigned long long *pw;
   size_t pstride;
 };
-
-// q of the call's i-th sample (i < 2^28)
-__device__ __forceinline__ int load_q(CallArgs const &a, size_t row, unsigned i) {
-  unsigned const k = i / a.block_len, j = i - k * a.block_len;
-  size_t const idx = row * a.src_stride + (size_t)k * a.row_stride + j;
-  if (a.format == KQ_PCM_S16BE) {
-    const unsigned char *p = reinterpret_cast<const unsigned char *>(a.src) + 2 * idx;
-    int const w = (int)(short)(unsigned short)(((unsigned)p[0] << 8) | p[1]);
-    return w < -32767 ? -32767 : w;
-  }
-  float const v = rintf(reinterpret_cast<const float *>(a.src)[idx] * a.g.scale);
-  if (!(v == v)) return 0;
-  return (int)fminf(fmaxf(v, -32767.f), 32767.f);
-}
 
 // of P[lo .. hi - 1]: the lowest index that attains the maximum, its P, and the largest of the others (0 if none)
 __device__ __forceinline__ void group_best(const unsigned long long *P, int lo, int hi, int *best, unsigned long long *pb,
@@ -191,7 +173,7 @@ __global__ __launch_bounds__(kThreads) void k_tone(CallArgs c) {
     if (e > n + kTile) e = n + kTile;
     int const len = (int)(e - n);
     __syncthreads();  // the piece before is done with q (and the first finds C loaded)
-    for (int i = tid; i < len; i += kThreads) q[i] = (short)load_q(c, row, (unsigned)(n - c.n0) + (unsigned)i);
+    for (int i = tid; i < len; i += kThreads) q[i] = (short)kq::load_q(c.in, row, (unsigned)(n - c.n0) + (unsigned)i);
     __syncthreads();
     if (live) {
       unsigned ph = ((unsigned)n + (unsigned)p) * inc;  // (n inc) mod 2^32 needs n mod 2^32 only
@@ -266,19 +248,10 @@ __global__ __launch_bounds__(kThreads) void k_tone(CallArgs c) {
   }
 }
 
-// C[j] = rint(32767 cos(2 pi j / 1024)), made once
-std::vector<short> const &cos_table() {
-  static std::vector<short> const table = [] {
-    std::vector<short> t((size_t)kTable);
-    for (int j = 0; j < kTable; j++) t[j] = (short)std::lrint(32767.0 * std::cos(2.0 * M_PI * j / kTable));
-    return t;
-  }();
-  return table;
-}
-
 }  // namespace
 
 struct kq_tone_bank : kq::HostSide {
+  static constexpr bool kDeferred = false;
   kq_tone_config cfg;
   std::mutex mu;
   bool dev_ready = false;
@@ -293,8 +266,7 @@ struct kq_tone_bank : kq::HostSide {
     ToneState *state = nullptr;
     long long *acc = nullptr;
     unsigned long long *last = nullptr;
-    kq_tone_event *ev = nullptr;
-    unsigned *nev = nullptr;
+    kq::EventArena<kq_tone_event> arena;
     kq_tone_status *st = nullptr;        // host-memory calls
     unsigned long long *pw = nullptr;    // host-memory calls: [S][T + 1]
   } d;
@@ -306,11 +278,10 @@ int make_device(kq_tone_bank *b) {
   auto &d = b->d;
   if (b->open_stream(b->cfg.stream)) return -1;
   size_t const S = b->cfg.max_slots, T = (size_t)b->g.T;
-  if (d.slots.alloc(*b, S) || b->alloc(&d.table, (size_t)kTable) || b->alloc(&d.incs, T) || b->alloc(&d.state, S, true) ||
+  if (d.slots.alloc(*b, S) || kq::tonecorr::alloc_table(*b, &d.table) || b->alloc(&d.incs, T) || b->alloc(&d.state, S, true) ||
       b->alloc(&d.acc, S * (2 * T + 1), true) || b->alloc(&d.last, S * T, true) ||
-      b->alloc(&d.ev, S * (size_t)b->g.max_events) || b->alloc(&d.nev, S, true))
+      d.arena.alloc(*b, S, b->cfg.max_events))
     return -1;
-  KQ_TRY(hipMemcpyAsync(d.table, cos_table().data(), kTable * sizeof(short), hipMemcpyHostToDevice, b->stream));
   KQ_TRY(hipMemcpyAsync(d.incs, b->incs.data(), T * sizeof(unsigned), hipMemcpyHostToDevice, b->stream));
   KQ_TRY(hipStreamSynchronize(b->stream));
   return 0;
@@ -327,11 +298,8 @@ int cold_start(kq_tone_bank *b, unsigned s) {
   KQ_TRY(hipMemcpyAsync(b->d.state + s, &init, sizeof init, hipMemcpyHostToDevice, b->stream));
   KQ_TRY(hipMemsetAsync(b->d.acc + s * (2 * T + 1), 0, (2 * T + 1) * sizeof(long long), b->stream));
   KQ_TRY(hipMemsetAsync(b->d.last + s * T, 0, T * sizeof(unsigned long long), b->stream));
-  KQ_TRY(hipMemsetAsync(b->d.nev + s, 0, sizeof(unsigned), b->stream));
-  return 0;
+  return b->d.arena.clear(*b, s, 1);
 }
-
-bool in_range(unsigned v, unsigned lo, unsigned hi) { return v >= lo && v <= hi; }
 
 }  // namespace
 
@@ -344,18 +312,9 @@ kq_tone_bank *kq_tone_create(const kq_tone_config *cfg) {
     return nullptr;
   }
   double const Fs = cfg->samprate;
-  if (!(Fs > 0) || !std::isfinite(Fs)) {
-    kq_internal_set_error("%s: samprate %.10g must be positive and finite", fn, Fs);
+  if (!kq::samprate_ok(fn, Fs) || !kq::field_in_range(fn, "block_len", cfg->block_len, 8, 4096) ||
+      !kq::field_in_range(fn, "ntones", cfg->ntones, 1, kMaxTones))
     return nullptr;
-  }
-  if (!in_range(cfg->block_len, 8, 4096)) {
-    kq_internal_set_error("%s: block_len %u must be 8..4096", fn, cfg->block_len);
-    return nullptr;
-  }
-  if (!in_range(cfg->ntones, 1, kMaxTones)) {
-    kq_internal_set_error("%s: ntones %u must be 1..%d", fn, cfg->ntones, kMaxTones);
-    return nullptr;
-  }
   if (cfg->group0 == 0 || (uint64_t)cfg->group0 + cfg->group1 != cfg->ntones) {
     kq_internal_set_error("%s: groups of %u and %u tones must be one or two that are not empty and cover ntones %u", fn,
                           cfg->group0, cfg->group1, cfg->ntones);
@@ -372,39 +331,12 @@ kq_tone_bank *kq_tone_create(const kq_tone_config *cfg) {
       return nullptr;
     }
   }
-  if (!in_range(cfg->frac, 1, 128)) {
-    kq_internal_set_error("%s: frac %u must be 1..128", fn, cfg->frac);
+  if (!kq::field_in_range(fn, "frac", cfg->frac, 1, 128) || !kq::field_in_range(fn, "ratio", cfg->ratio, 16, 4095) ||
+      !kq::field_in_range(fn, "twist", cfg->twist, 16, 4095) || !kq::field_in_range(fn, "min_blocks", cfg->min_blocks, 1, 65535) ||
+      !kq::input_scale_ok(fn, cfg->input_scale) || !kq::field_in_range(fn, "max_slots", cfg->max_slots, 1, kMaxSlots) ||
+      !kq::field_in_range(fn, "max_events", cfg->max_events, 1, 4096) || !kq::max_samples_ok(fn, cfg->max_samples))
     return nullptr;
-  }
-  if (!in_range(cfg->ratio, 16, 4095)) {
-    kq_internal_set_error("%s: ratio %u must be 16..4095", fn, cfg->ratio);
-    return nullptr;
-  }
-  if (!in_range(cfg->twist, 16, 4095)) {
-    kq_internal_set_error("%s: twist %u must be 16..4095", fn, cfg->twist);
-    return nullptr;
-  }
-  if (!in_range(cfg->min_blocks, 1, 65535)) {
-    kq_internal_set_error("%s: min_blocks %u must be 1..65535", fn, cfg->min_blocks);
-    return nullptr;
-  }
-  if (!std::isfinite(cfg->input_scale) || !(cfg->input_scale > 0)) {
-    kq_internal_set_error("%s: input_scale must be finite and positive", fn);
-    return nullptr;
-  }
-  if (!in_range(cfg->max_slots, 1, kMaxSlots)) {
-    kq_internal_set_error("%s: max_slots %u must be 1..%u", fn, cfg->max_slots, kMaxSlots);
-    return nullptr;
-  }
-  if (!in_range(cfg->max_events, 1, 4096)) {
-    kq_internal_set_error("%s: max_events %u must be 1..4096", fn, cfg->max_events);
-    return nullptr;
-  }
-  if (cfg->max_samples == 0 || cfg->max_samples > ((size_t)1 << 28)) {
-    kq_internal_set_error("%s: max_samples %zu must be 1..2^28", fn, cfg->max_samples);
-    return nullptr;
-  }
-  (void)cos_table();  // the table exists from here on
+  (void)kq::tonecorr::cos_table();  // the table exists from here on
   kq_tone_bank *b = new kq_tone_bank;
   b->cfg = *cfg;
   b->freqs.assign(cfg->freqs, cfg->freqs + cfg->ntones);
@@ -423,7 +355,6 @@ kq_tone_bank *kq_tone_create(const kq_tone_config *cfg) {
   g.twist = cfg->twist;
   g.min_blocks = cfg->min_blocks;
   g.max_events = (int)cfg->max_events;
-  g.scale = cfg->input_scale;
   return b;
 }
 
@@ -453,32 +384,21 @@ int kq_tone_remove(kq_tone_bank *b, unsigned slot) { return kq::remove_slot(b, s
 int kq_tone_process(kq_tone_bank *b, const void *src, int format, size_t src_stride, size_t row_stride, unsigned block_len,
                     unsigned nblocks, int on_device, kq_tone_status *status, size_t status_stride, uint64_t *powers,
                     size_t powers_stride) {
+  const char *fn = "kq_tone_process";
   if (!b) {
-    kq_internal_set_error("kq_tone_process: null bank");
-    return -1;
-  }
-  if (format != KQ_PCM_F32 && format != KQ_PCM_S16BE) {
-    kq_internal_set_error("kq_tone_process: unknown sample format %d", format);
+    kq_internal_set_error("%s: null bank", fn);
     return -1;
   }
   std::lock_guard<std::mutex> lk(b->mu);
-  if (!kq::blocks_ok("kq_tone_process", b->cfg.max_samples, row_stride, block_len, nblocks)) return -1;
+  if (!kq::call_args_ok(fn, format, b->cfg.max_samples, row_stride, block_len, nblocks, status, status_stride)) return -1;
   size_t const ncall = (size_t)block_len * nblocks, T = (size_t)b->g.T;
-  if (status && status_stride < 1) {
-    kq_internal_set_error("kq_tone_process: status_stride %zu < 1", status_stride);
-    return -1;
-  }
   if (powers && powers_stride < T + 1) {
-    kq_internal_set_error("kq_tone_process: powers_stride %zu < ntones + 1 = %zu", powers_stride, T + 1);
+    kq_internal_set_error("%s: powers_stride %zu < ntones + 1 = %zu", fn, powers_stride, T + 1);
     return -1;
   }
-  kq::CallWork const work = kq::call_work(b, "kq_tone_process", ncall, src, "src");
-  if (work == kq::CALL_IDLE) {
-    b->n_cur += ncall;
-    return 0;
-  }
-  if (work != kq::CALL_RUN) return work;
-  kq::DeviceScope dev_scope_(b->cfg.device);
+  std::optional<kq::DeviceScope> scope;
+  kq::CallWork const work = kq::begin_call(b, fn, ncall, src, scope);
+  if (work != kq::CALL_RUN) return work == kq::CALL_FAILED ? -1 : 0;
   auto &d = b->d;
   size_t const S = b->cfg.max_slots, nlist = d.slots.all.size();
   CallArgs a{};
@@ -490,126 +410,36 @@ int kq_tone_process(kq_tone_bank *b, const void *src, int format, size_t src_str
   a.state = d.state;
   a.acc = d.acc;
   a.last = d.last;
-  a.ev = d.ev;
-  a.nev = d.nev;
+  a.ev = d.arena.ev;
+  a.nev = d.arena.n;
   a.n0 = (int64_t)b->n_cur;
   a.n1 = a.n0 + (int64_t)ncall;
-  a.format = format;
-  a.block_len = block_len;
-  if (on_device) {
-    a.src = src;
-    a.src_stride = src_stride;
-    a.row_stride = row_stride;
-    a.rowmap = nullptr;
-    a.st = status;
-    a.sstride = status_stride;
-    a.pw = reinterpret_cast<unsigned long long *>(powers);
-    a.pstride = powers_stride;
-  } else {
-    kq::Staged in;
-    if (d.slots.stage_rows(*b, src, format == KQ_PCM_S16BE ? 2 : 4, src_stride, row_stride, block_len, nblocks,
-                           b->cfg.max_samples * 4, &in))
-      return -1;
-    a.src = in.src;
-    a.src_stride = in.src_stride;
-    a.row_stride = in.row_stride;
-    a.rowmap = in.rowmap;
-    if (status && !d.st && b->alloc(&d.st, S)) return -1;
-    if (powers && !d.pw && b->alloc(&d.pw, S * (T + 1))) return -1;
-    a.st = status ? d.st : nullptr;
-    a.sstride = 1;
-    a.pw = powers ? d.pw : nullptr;
-    a.pstride = T + 1;
-  }
+  if (kq::bind_pcm(&a.in, &a.rowmap, *b, d.slots, b->cfg.max_samples, b->cfg.input_scale, src, format, src_stride, row_stride, block_len,
+                   nblocks, on_device) ||
+      kq::bind_status(b, on_device, status, status_stride, &a.st, &a.sstride))
+    return -1;
+  if (!on_device && powers && !d.pw && b->alloc(&d.pw, S * (T + 1))) return -1;
+  a.pw = on_device || !powers ? reinterpret_cast<unsigned long long *>(powers) : d.pw;
+  a.pstride = on_device ? powers_stride : T + 1;
   hipLaunchKernelGGL(k_tone, dim3((unsigned)nlist), dim3(kThreads), 0, b->stream, a);
   KQ_TRY(hipGetLastError());
   b->n_cur += ncall;
-  if (!on_device) {
-    auto back = [&](size_t s0, size_t n) {  // the records of the active slots
-      if (status && kq::copy_rows_back(*b, status, status_stride, d.st, 1, 1, sizeof(kq_tone_status), s0, n)) return -1;
-      if (powers && kq::copy_rows_back(*b, powers, powers_stride, d.pw, T + 1, T + 1, sizeof(uint64_t), s0, n)) return -1;
-      return 0;
-    };
-    if ((status || powers) && d.slots.for_runs(back)) return -1;
-    KQ_TRY(hipStreamSynchronize(b->stream));
-  }
-  return 0;
+  if (on_device) return 0;
+  return kq::end_host_call(b, status, status_stride, [&](size_t s0, size_t n) {  // the powers ride with the records
+    return powers ? kq::copy_rows_back(*b, powers, powers_stride, d.pw, T + 1, T + 1, sizeof(uint64_t), s0, n) : 0;
+  });
 }
 
-int kq_tone_pull_counts(kq_tone_bank *b, uint32_t *counts) {
-  if (!b) {
-    kq_internal_set_error("kq_tone_pull_counts: null bank");
-    return -1;
-  }
-  if (!counts) {
-    kq_internal_set_error("kq_tone_pull_counts: null counts");
-    return -1;
-  }
-  std::lock_guard<std::mutex> lk(b->mu);
-  if (!b->dev_ready) {
-    std::memset(counts, 0, b->cfg.max_slots * sizeof(uint32_t));
-    return 0;
-  }
-  kq::DeviceScope dev_scope_(b->cfg.device);
-  KQ_TRY(hipMemcpyAsync(counts, b->d.nev, b->cfg.max_slots * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
-  KQ_TRY(hipStreamSynchronize(b->stream));
-  return 0;
-}
+int kq_tone_pull_counts(kq_tone_bank *b, uint32_t *counts) { return kq::pull_counts(b, "kq_tone_pull_counts", counts); }
 
 int kq_tone_pull_event(kq_tone_bank *b, unsigned slot, unsigned index, kq_tone_event *event) {
-  if (!b) {
-    kq_internal_set_error("kq_tone_pull_event: null bank");
-    return -1;
-  }
-  if (!event) {
-    kq_internal_set_error("kq_tone_pull_event: null event");
-    return -1;
-  }
-  std::lock_guard<std::mutex> lk(b->mu);
-  if (slot >= b->cfg.max_slots) {
-    kq_internal_set_error("kq_tone_pull_event: slot %u >= max_slots %u", slot, b->cfg.max_slots);
-    return -1;
-  }
-  unsigned n = 0;
-  kq::DeviceScope dev_scope_(b->cfg.device);
-  if (b->dev_ready) {
-    KQ_TRY(hipMemcpyAsync(&n, b->d.nev + slot, sizeof n, hipMemcpyDeviceToHost, b->stream));
-    KQ_TRY(hipStreamSynchronize(b->stream));
-  }
-  if (index >= n) {
-    kq_internal_set_error("kq_tone_pull_event: slot %u has %u events", slot, n);
-    return -1;
-  }
-  size_t const at = (size_t)slot * b->cfg.max_events + index;
-  KQ_TRY(hipMemcpyAsync(event, b->d.ev + at, sizeof *event, hipMemcpyDeviceToHost, b->stream));
-  KQ_TRY(hipStreamSynchronize(b->stream));
-  return 0;
+  return kq::pull_event(b, "kq_tone_pull_event", slot, index, event);
 }
 
-int kq_tone_clear_events(kq_tone_bank *b) {
-  if (!b) {
-    kq_internal_set_error("kq_tone_clear_events: null bank");
-    return -1;
-  }
-  std::lock_guard<std::mutex> lk(b->mu);
-  if (!b->dev_ready) return 0;
-  kq::DeviceScope dev_scope_(b->cfg.device);
-  KQ_TRY(hipMemsetAsync(b->d.nev, 0, b->cfg.max_slots * sizeof(unsigned), b->stream));
-  return 0;
-}
+int kq_tone_clear_events(kq_tone_bank *b) { return kq::clear_arena(b, "kq_tone_clear_events"); }
 
 int kq_tone_get_table(const kq_tone_bank *b, int16_t *dst, size_t cap) {
-  if (!b) {
-    kq_internal_set_error("kq_tone_get_table: null bank");
-    return -1;
-  }
-  if (!dst && cap) {
-    kq_internal_set_error("kq_tone_get_table: null dst");
-    return -1;
-  }
-  size_t const n = std::min(cap, (size_t)kTable);
-  if (n) std::memcpy(dst, cos_table().data(), n * sizeof(int16_t));
-  return kTable;
+  return kq::tonecorr::get_table(b, "kq_tone_get_table", dst, cap);
 }
 
 int kq_tone_get_incs(const kq_tone_bank *b, uint32_t *dst, size_t cap) {
@@ -629,19 +459,7 @@ int kq_tone_get_incs(const kq_tone_bank *b, uint32_t *dst, size_t cap) {
 int kq_tone_sync(kq_tone_bank *b) { return kq::sync_bank(b, "kq_tone_sync"); }
 
 int kq_tone_reset(kq_tone_bank *b) {
-  if (!b) {
-    kq_internal_set_error("kq_tone_reset: null bank");
-    return -1;
-  }
-  std::lock_guard<std::mutex> lk(b->mu);
-  b->n_cur = 0;
-  if (!b->dev_ready) return 0;
-  kq::DeviceScope dev_scope_(b->cfg.device);
-  KQ_TRY(hipStreamSynchronize(b->stream));
-  for (int s : b->d.slots.all)
-    if (cold_start(b, (unsigned)s)) return -1;
-  KQ_TRY(hipStreamSynchronize(b->stream));
-  return 0;
+  return kq::reset_slots(b, "kq_tone_reset", [b](unsigned s) { return cold_start(b, s); });
 }
 
 }  // extern "C"

@@ -7,7 +7,7 @@ import ctypes as C
 
 import numpy as np
 
-from .bank import Handle, KqError, _err, load_library
+from ._slotbank import EventBank
 from .packet import KQ_PCM_F32, KQ_PCM_S16BE
 
 MAX_SLOTS = 16384
@@ -39,157 +39,39 @@ def cw_params(source=0, pitch=700.0, wpm=20.0):
     return CwParams(source, pitch, wpm)
 
 
-def _bind(L):
-    if getattr(L, "_kq_cw_bound", False):
-        return L
-    L.kq_cw_create.restype = C.c_void_p
-    L.kq_cw_create.argtypes = [C.POINTER(CwConfig)]
-    L.kq_cw_destroy.argtypes = [C.c_void_p]
-    L.kq_cw_set.argtypes = [C.c_void_p, C.c_uint, C.POINTER(CwParams)]
-    L.kq_cw_remove.argtypes = [C.c_void_p, C.c_uint]
-    L.kq_cw_process.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_uint, C.c_uint, C.c_int,
-                                C.c_void_p, C.c_size_t]
-    L.kq_cw_pull_counts.argtypes = [C.c_void_p, C.c_void_p]
-    L.kq_cw_pull_event.argtypes = [C.c_void_p, C.c_uint, C.c_uint, C.c_void_p]
-    L.kq_cw_clear_events.argtypes = [C.c_void_p]
-    L.kq_cw_get_table.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-    L.kq_cw_get_inc.argtypes = [C.c_void_p, C.c_uint, C.c_void_p]
-    L.kq_cw_sync.argtypes = [C.c_void_p]
-    L.kq_cw_reset.argtypes = [C.c_void_p]
-    L.kq_bank_stream.restype = C.c_void_p
-    L.kq_bank_stream.argtypes = [C.c_void_p]
-    L._kq_cw_bound = True
-    return L
-
-
-class CwBank(Handle):
+class CwBank(EventBank):
     """Up to max_slots Morse decoders on frames of block_len samples at samprate, following speeds of min_wpm to max_wpm.
     morse.cw_config(fs, max_wpm) gives the keywords for a top speed: CwBank(fs, max_slots=..., max_samples=...,
-    **cw_config(fs, 60)).  For process_bank, create it on the receiver bank's stream: CwBank.beside(bank, ...)."""
+    **cw_config(fs, 60)).  For process_bank, create it on the receiver bank's stream: CwBank.beside(bank, ...).  set()
+    touches no device: the next call does."""
     _destroy = "kq_cw_destroy"
+    _prefix, _config, _params, _make_params, _status = "kq_cw", CwConfig, CwParams, staticmethod(cw_params), STATUS_DTYPE
+    _event_dtype, _event = EVENT_DTYPE, Event
+    _entry = dict(EventBank._entry, get_inc=[C.c_uint, C.c_void_p])
 
     def __init__(self, samprate, block_len, max_slots, max_samples, min_wpm=5.0, max_wpm=60.0, deb=2, warm=64, snr=256,
                  min_p=1 << 16, input_scale=32767.0, max_events=256, device=0, stream=None):
-        self.lib = _bind(load_library())
-        cfg = CwConfig(device, samprate, block_len, min_wpm, max_wpm, deb, warm, snr, min_p, input_scale, max_slots,
-                       max_events, max_samples, stream)
-        self.h = self.lib.kq_cw_create(C.byref(cfg))
-        if not self.h:
-            raise KqError("kq_cw_create: " + _err(self.lib))
+        self._create(device, samprate, block_len, min_wpm, max_wpm, deb, warm, snr, min_p, input_scale, max_slots, max_events,
+                     max_samples, stream)
         self.samprate, self.block_len, self.min_wpm, self.max_wpm = samprate, block_len, min_wpm, max_wpm
         self.deb, self.warm, self.snr, self.min_p = deb, warm, snr, min_p
         self.input_scale, self.max_slots, self.max_events, self.max_samples = input_scale, max_slots, max_events, max_samples
         self.device, self.stream = device, stream
-        self.n = 0   # samples taken so far
-
-    @classmethod
-    def beside(cls, bank, block_len, max_slots, **kw):
-        """a decoder bank on a receiver Bank's stream, sized for its calls, decoding its output rate (samprate / D)"""
-        lib = _bind(load_library())
-        return cls(bank.samprate / bank.D, block_len, max_slots, bank.max_blocks * bank.olen,
-                   stream=lib.kq_bank_stream(bank.h), **kw)
-
-    def set(self, slot, params=None, **kw):
-        """put a decoder in `slot` (a CwParams, or cw_params() keywords); it starts cold at the next call.  Touches no
-        device: the next call does"""
-        p = params if params is not None else cw_params(**kw)
-        self._chk(self.lib.kq_cw_set(self.h, slot, C.byref(p)), "kq_cw_set")
-
-    def remove(self, slot):
-        self._chk(self.lib.kq_cw_remove(self.h, slot), "kq_cw_remove")
-
-    def get_table(self):
-        """C: the cosine table, int16 [1024]"""
-        c = np.zeros(TABLE, np.int16)
-        assert self._chk(self.lib.kq_cw_get_table(self.h, c.ctypes.data, TABLE), "kq_cw_get_table") == TABLE
-        return c
 
     def get_inc(self, slot):
         """the slot's phase increment"""
         v = np.zeros(1, np.uint32)
-        self._chk(self.lib.kq_cw_get_inc(self.h, slot, v.ctypes.data), "kq_cw_get_inc")
+        self._call("get_inc", slot, v.ctypes.data)
         return int(v[0])
 
-    def process(self, x, nblocks=1, fmt=KQ_PCM_F32):
-        """x: host [rows][n] (row = source), float32, or for KQ_PCM_S16BE int16 values that go out in network byte order; n
-        split into nblocks equal blocks.  Synchronous.  Returns status: STATUS_DTYPE [max_slots] (empty slots 0)."""
-        x = np.asarray(x)
-        if x.ndim == 1:
-            x = x[None, :]
-        x = np.ascontiguousarray(x, ">i2" if fmt == KQ_PCM_S16BE else np.float32)
-        n = x.shape[1]
-        if n % nblocks:
-            raise ValueError("%d samples do not split into %d blocks" % (n, nblocks))
-        st = np.zeros(self.max_slots, STATUS_DTYPE)
-        self._chk(self.lib.kq_cw_process(self.h, x.ctypes.data, fmt, n, n // nblocks, n // nblocks, nblocks, 0, st.ctypes.data,
-                                         1), "kq_cw_process")
-        self.n += n
-        return st
 
-    def process_device(self, src_ptr, src_stride, row_stride, block_len, nblocks, status_ptr=None, status_stride=1,
-                       fmt=KQ_PCM_F32):
-        """asynchronous on the handle's stream; every pointer is device memory"""
-        self._chk(self.lib.kq_cw_process(self.h, src_ptr, fmt, src_stride, row_stride, block_len, nblocks, 1, status_ptr,
-                                         status_stride), "kq_cw_process")
-        self.n += block_len * nblocks
-
-    def process_bank(self, bank, status=None):
-        """Decode a receiver Bank's last call straight from its device audio plane on the bank's stream, with no host round
-        trip and no host wait: kq_bank_join first orders the decode behind the bank's demodulators.  status: a contiguous
-        torch device tensor int32 [max_slots][STATUS_WORDS] to write, or None for a new zeroed one (status_array() views
-        it as STATUS_DTYPE).  Returns status.  The decode waits for what torch's current stream has queued, and that
-        stream waits for the decode."""
-        import torch
-        if self.stream is None or self.stream != self.lib.kq_bank_stream(bank.h):
-            raise ValueError("process_bank needs a CwBank on the bank's stream (CwBank.beside(bank, ...))")
-        nb = bank.lib.kq_bank_last_blocks(bank.h)
-        olen = bank.olen
-        dev = torch.device("cuda", self.device)
-        if status is None:
-            status = torch.zeros((self.max_slots, STATUS_WORDS), dtype=torch.int32, device=dev)
-        if not status.is_contiguous() or status.shape != (self.max_slots, STATUS_WORDS):
-            raise ValueError("status must be a contiguous int32 [max_slots][%d]" % STATUS_WORDS)
-        ext = torch.cuda.ExternalStream(self.stream, device=dev)
-        cur = torch.cuda.current_stream(dev)
-        ext.wait_stream(cur)   # the buffers, made or last used on torch's stream, before the decoder writes them
-        bank.join()            # the demodulators that write the plane, before the decoder reads it
-        self.process_device(bank.audio_device_ptr(), bank.max_blocks * 2 * olen, 2 * olen, olen, nb, status.data_ptr(), 1)
-        cur.wait_stream(ext)
-        return status
-
-    def counts(self):
-        """events in every slot's arena, uint32 [max_slots]; synchronous"""
-        c = np.zeros(self.max_slots, np.uint32)
-        self._chk(self.lib.kq_cw_pull_counts(self.h, c.ctypes.data), "kq_cw_pull_counts")
-        return c
-
-    def event(self, slot, index):
-        """one event of a slot's arena, an Event (code, nelem, unit, start_sample, end_sample, peak); synchronous"""
-        r = np.zeros(1, EVENT_DTYPE)
-        self._chk(self.lib.kq_cw_pull_event(self.h, slot, index, r.ctypes.data), "kq_cw_pull_event")
-        return Event(*(int(r[0][k]) for k in Event._fields))
-
-    def events(self, slot, count=None):
-        """every event of a slot's arena, in order"""
-        if count is None:
-            count = int(self.counts()[slot])
-        return [self.event(slot, k) for k in range(count)]
-
-    def clear_events(self):
-        self._chk(self.lib.kq_cw_clear_events(self.h), "kq_cw_clear_events")
-
-    def sync(self):
-        self._chk(self.lib.kq_cw_sync(self.h), "kq_cw_sync")
-
-    def reset(self):
-        self._chk(self.lib.kq_cw_reset(self.h), "kq_cw_reset")
-        self.n = 0
+def _bind(L):
+    return CwBank._bind(L)
 
 
 def status_array(st):
     """a status tensor / int32 array [..][STATUS_WORDS] from process_bank as a STATUS_DTYPE array"""
-    a = st.cpu().numpy() if hasattr(st, "cpu") else np.asarray(st)
-    return np.ascontiguousarray(a, np.int32).view(STATUS_DTYPE)[..., 0]
+    return CwBank.status_array(st)
 
 
 __all__ = ["CwBank", "CwConfig", "CwParams", "cw_params", "status_array", "Event", "STATUS_DTYPE", "STATUS_WORDS",

@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from .bank import Handle, KqError, _err, load_library
+from ._slotbank import SlotBank
 from .packet import KQ_PCM_F32, KQ_PCM_S16BE
 
 MAX_SLOTS = 4096
@@ -32,152 +32,55 @@ def fsk_params(source=0, scrambled=1, min_bytes=8):
     return FskParams(source, int(scrambled), min_bytes)
 
 
-def _bind(L):
-    if getattr(L, "_kq_fsk_bound", False):
-        return L
-    L.kq_fsk_create.restype = C.c_void_p
-    L.kq_fsk_create.argtypes = [C.POINTER(FskConfig)]
-    L.kq_fsk_destroy.argtypes = [C.c_void_p]
-    L.kq_fsk_set.argtypes = [C.c_void_p, C.c_uint, C.POINTER(FskParams)]
-    L.kq_fsk_remove.argtypes = [C.c_void_p, C.c_uint]
-    L.kq_fsk_process.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_uint, C.c_uint, C.c_int,
-                                 C.c_void_p, C.c_size_t]
-    L.kq_fsk_pull_counts.argtypes = [C.c_void_p, C.c_void_p]
-    L.kq_fsk_pull_frame.argtypes = [C.c_void_p, C.c_uint, C.c_uint, C.c_void_p, C.c_size_t, C.c_void_p]
-    L.kq_fsk_clear_frames.argtypes = [C.c_void_p]
-    L.kq_fsk_get_taps.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-    L.kq_fsk_sync.argtypes = [C.c_void_p]
-    L.kq_fsk_reset.argtypes = [C.c_void_p]
-    L.kq_bank_stream.restype = C.c_void_p
-    L.kq_bank_stream.argtypes = [C.c_void_p]
-    L._kq_fsk_bound = True
-    return L
-
-
-class FskBank(Handle):
+class FskBank(SlotBank):
     """Up to max_slots decoders on one geometry (Fs = samprate, baud, a low-pass of `taps`, a threshold window of
-    window_bits bits).  For process_bank, create it on the receiver bank's stream: FskBank.beside(bank, ...)."""
+    window_bits bits), on the discriminator output of flat FM channels.  For process_bank, create it on the receiver
+    bank's stream: FskBank.beside(bank, ...)."""
     _destroy = "kq_fsk_destroy"
+    _prefix, _config, _params, _make_params, _status = "kq_fsk", FskConfig, FskParams, staticmethod(fsk_params), STATUS_DTYPE
+    _article, _int_rate = "an", True
+    _entry = {"pull_frame": [C.c_uint, C.c_uint, C.c_void_p, C.c_size_t, C.c_void_p], "clear_frames": [],
+              "get_taps": [C.c_void_p, C.c_size_t]}
 
     def __init__(self, samprate, baud, taps, max_slots, max_samples, cutoff_hz=None, kaiser_beta=2.0, window_bits=16.0,
                  input_scale=4096.0, pll_shift=3, max_frames=16, max_frame_bytes=512, device=0, stream=None):
-        self.lib = _bind(load_library())
         if cutoff_hz is None:
             cutoff_hz = 0.6 * baud
-        cfg = FskConfig(device, samprate, baud, taps, cutoff_hz, kaiser_beta, window_bits, input_scale, pll_shift, max_slots,
-                        max_frames, max_frame_bytes, max_samples, stream)
-        self.h = self.lib.kq_fsk_create(C.byref(cfg))
-        if not self.h:
-            raise KqError("kq_fsk_create: " + _err(self.lib))
+        self._create(device, samprate, baud, taps, cutoff_hz, kaiser_beta, window_bits, input_scale, pll_shift, max_slots,
+                     max_frames, max_frame_bytes, max_samples, stream)
         self.samprate, self.baud, self.taps = samprate, baud, taps
         self.max_slots, self.max_samples, self.max_frame_bytes = max_slots, max_samples, max_frame_bytes
         self.device, self.stream = device, stream
-        self.n = 0   # samples taken so far
-
-    @classmethod
-    def beside(cls, bank, baud, taps, max_slots, **kw):
-        """a decoder bank on a receiver Bank's stream, sized for its calls, decoding its output rate (samprate / D)"""
-        lib = _bind(load_library())
-        return cls(bank.samprate // bank.D, baud, taps, max_slots, bank.max_blocks * bank.olen,
-                   stream=lib.kq_bank_stream(bank.h), **kw)
-
-    def set(self, slot, params=None, **kw):
-        """put a decoder in `slot` (an FskParams, or fsk_params() keywords); it starts cold at the next call"""
-        p = params if params is not None else fsk_params(**kw)
-        self._chk(self.lib.kq_fsk_set(self.h, slot, C.byref(p)), "kq_fsk_set")
-
-    def remove(self, slot):
-        self._chk(self.lib.kq_fsk_remove(self.h, slot), "kq_fsk_remove")
 
     def get_taps(self):
         """hq: the quantised low-pass, int16 [taps]"""
         hq = np.zeros(self.taps, np.int16)
-        assert self._chk(self.lib.kq_fsk_get_taps(self.h, hq.ctypes.data, self.taps), "kq_fsk_get_taps") == self.taps
+        assert self._call("get_taps", hq.ctypes.data, self.taps) == self.taps
         return hq
-
-    def process(self, x, nblocks=1, fmt=KQ_PCM_F32):
-        """x: host [rows][n] (row = source), float32, or for KQ_PCM_S16BE int16 values that go out in network byte order; n
-        split into nblocks equal blocks.  Synchronous.  Returns status, STATUS_DTYPE [max_slots] (rows of empty slots 0)."""
-        x = np.asarray(x)
-        if x.ndim == 1:
-            x = x[None, :]
-        x = np.ascontiguousarray(x, ">i2" if fmt == KQ_PCM_S16BE else np.float32)
-        n = x.shape[1]
-        if n % nblocks:
-            raise ValueError("%d samples do not split into %d blocks" % (n, nblocks))
-        st = np.zeros(self.max_slots, STATUS_DTYPE)
-        self._chk(self.lib.kq_fsk_process(self.h, x.ctypes.data, fmt, n, n // nblocks, n // nblocks, nblocks, 0, st.ctypes.data,
-                                          1), "kq_fsk_process")
-        self.n += n
-        return st
-
-    def process_device(self, src_ptr, src_stride, row_stride, block_len, nblocks, status_ptr=None, status_stride=1,
-                       fmt=KQ_PCM_F32):
-        """asynchronous on the handle's stream; every pointer is device memory"""
-        self._chk(self.lib.kq_fsk_process(self.h, src_ptr, fmt, src_stride, row_stride, block_len, nblocks, 1, status_ptr,
-                                          status_stride), "kq_fsk_process")
-        self.n += block_len * nblocks
-
-    def process_bank(self, bank, status=None):
-        """Decode a receiver Bank's last call straight from its device audio plane (flat FM channels) on the bank's stream,
-        with no host round trip and no host wait: kq_bank_join first orders the decode behind the bank's demodulators.
-        status: a contiguous torch device tensor int32 [max_slots][8] to write, or None for a new zeroed one (status_array()
-        views it as STATUS_DTYPE).  Returns it.  The decode waits for what torch's current stream has queued, and that
-        stream waits for the decode."""
-        import torch
-        if self.stream is None or self.stream != self.lib.kq_bank_stream(bank.h):
-            raise ValueError("process_bank needs an FskBank on the bank's stream (FskBank.beside(bank, ...))")
-        nb = bank.lib.kq_bank_last_blocks(bank.h)
-        olen = bank.olen
-        dev = torch.device("cuda", self.device)
-        if status is None:
-            status = torch.zeros((self.max_slots, 8), dtype=torch.int32, device=dev)
-        if not status.is_contiguous() or status.shape != (self.max_slots, 8):
-            raise ValueError("status must be a contiguous int32 [max_slots][8]")
-        ext = torch.cuda.ExternalStream(self.stream, device=dev)
-        cur = torch.cuda.current_stream(dev)
-        ext.wait_stream(cur)   # the buffer, made or last used on torch's stream, before the decoder writes it
-        bank.join()            # the demodulators that write the plane, before the decoder reads it
-        self.process_device(bank.audio_device_ptr(), bank.max_blocks * 2 * olen, 2 * olen, olen, nb, status.data_ptr(), 1)
-        cur.wait_stream(ext)
-        return status
-
-    def counts(self):
-        """frames in every slot's arena, uint32 [max_slots]; synchronous"""
-        c = np.zeros(self.max_slots, np.uint32)
-        self._chk(self.lib.kq_fsk_pull_counts(self.h, c.ctypes.data), "kq_fsk_pull_counts")
-        return c
 
     def frame(self, slot, index):
         """(bytes, end_sample, end_bit) of one frame of a slot's arena; synchronous"""
         buf = np.zeros(self.max_frame_bytes, np.uint8)
         info = np.zeros(1, INFO_DTYPE)
-        n = self._chk(self.lib.kq_fsk_pull_frame(self.h, slot, index, buf.ctypes.data, buf.size, info.ctypes.data),
-                      "kq_fsk_pull_frame")
+        n = self._call("pull_frame", slot, index, buf.ctypes.data, buf.size, info.ctypes.data)
         assert n == int(info[0]["length"])
         return bytes(buf[:n]), int(info[0]["end_sample"]), int(info[0]["end_bit"])
 
     def frames(self, slot, count=None):
         """every frame of a slot's arena, in order, as (bytes, end_sample, end_bit)"""
-        if count is None:
-            count = int(self.counts()[slot])
-        return [self.frame(slot, k) for k in range(count)]
+        return self._records(self.frame, slot, count)
 
     def clear_frames(self):
-        self._chk(self.lib.kq_fsk_clear_frames(self.h), "kq_fsk_clear_frames")
+        self._call("clear_frames")
 
-    def sync(self):
-        self._chk(self.lib.kq_fsk_sync(self.h), "kq_fsk_sync")
 
-    def reset(self):
-        self._chk(self.lib.kq_fsk_reset(self.h), "kq_fsk_reset")
-        self.n = 0
+def _bind(L):
+    return FskBank._bind(L)
 
 
 def status_array(st):
     """a status tensor / int32 array [..][8] from process_bank as a STATUS_DTYPE array"""
-    a = st.cpu().numpy() if hasattr(st, "cpu") else np.asarray(st)
-    return np.ascontiguousarray(a, np.int32).view(STATUS_DTYPE)[..., 0]
+    return FskBank.status_array(st)
 
 
 __all__ = ["FskBank", "FskConfig", "FskParams", "fsk_params", "status_array", "STATUS_DTYPE", "INFO_DTYPE", "MAX_SLOTS", "TILE"]

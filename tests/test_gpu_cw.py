@@ -244,6 +244,38 @@ def test_slot_lifecycle(gpu):
     bank.close()
 
 
+def test_cold_start_of_slots_set_before_the_first_call(gpu):
+    """Slots set before the first call reach the device in runs (0 to 2 together, 4 alone; 3 was set and removed again):
+    each starts from its own dot length u0, an empty character with both gaps reported, and an empty arena, and the slots
+    never set stay all zero.  After reset() the same holds for a slot set anew at another speed."""
+    Fs, B, S = 12000.0, 48, 8
+    u_min, u_max = cm.unit_limits(Fs, B, 5.0, 60.0)
+    u0 = lambda wpm: min(max(cm.unit_start(Fs, B, wpm), u_min), u_max)
+    wpm = {0: 12.0, 1: 20.0, 2: 25.0, 4: 32.0}
+    bank = CwBank(Fs, B, S, 2 * B)
+    for s, w in wpm.items():
+        bank.set(s, source=0, pitch=700.0, wpm=w)
+    bank.set(3, source=0, pitch=700.0, wpm=40.0)
+    bank.remove(3)
+    assert len({u0(w) for w in wpm.values()}) == 4
+    zeros = np.zeros((1, 2 * B), np.float32)
+
+    def check(st):
+        for s in range(S):
+            if s in wpm:
+                assert (int(st[s]["unit"]), int(st[s]["code"]), int(st[s]["flags"]), int(st[s]["frames"])) == (u0(wpm[s]), 1, 3, 2), s
+            else:
+                assert not st[s].tobytes().strip(b"\0"), s
+        assert not bank.counts().any()
+
+    check(bank.process(zeros))
+    bank.reset()
+    wpm[2] = 16.0
+    bank.set(2, source=0, pitch=700.0, wpm=wpm[2])
+    check(bank.process(zeros))
+    bank.close()
+
+
 # ---- loopback: a keyed USB station through a receiver bank's CW channel, decoded in place ----
 FS, INTERP, LB, MB, DRX = 12288000, 256, 8192, 8193, 256     # 48 kHz audio into the modulator and out of the receiver
 

@@ -3,6 +3,8 @@ kq::lazy_device of kq_host.hpp) on the CPU: a toy slot bank compiled against the
 (tests/tsan/slots_harness.cpp).  A set-up that fails at each of its runtime objects in turn must leave the handle holding
 nothing, start over at the next set and leave nothing for the leak checker at destroy; the staging of a host-memory call,
 the runs of active slots, the copy-back and the table's upload are checked against what kq_wfm / kq_rds / kq_fsk rely on.
+A second toy bank with deferred slots and an event arena does the same for what kq_cw / kq_rtty rely on: set, remove and
+reset without a device, the flush of mixed runs, a flush whose set-up fails at each object, the arena's entry points.
 The GPU pool runs no sanitizers, so this is where the host layer's memory handling is checked."""
 import os
 import shutil

@@ -1,8 +1,10 @@
 // AddressSanitizer / UndefinedBehaviorSanitizer run of kq_slots.hpp and kq::lazy_device (kq_host.hpp) on the CPU, against the
 // device-less stand-in for the HIP runtime (mock/hip/hip_runtime.h): a toy slot bank with the shape of kq_wfm / kq_rds /
 // kq_fsk's host halves.  A set-up that fails at every one of its runtime objects in turn, the staging of a host-memory
-// call, the runs of active slots and the copy-back, and the table's upload.  LeakSanitizer has the last word: whatever a
-// failed set-up or a destroy leaves behind fails the run.
+// call, the runs of active slots and the copy-back, and the table's upload.  A second toy bank has the shape of kq_cw /
+// kq_rtty's: deferred slots (kq::DeferredSlots and its flush) and an arena of events (kq::EventArena) -- set, remove and
+// reset with no device, a flush of mixed runs, a flush whose set-up fails at every object in turn, the arena's entry points
+// with and without a device.  LeakSanitizer has the last word: whatever a failed set-up or a destroy leaves behind fails the run.
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -225,11 +227,228 @@ void table_staging_runs() {
   CHECK(kq::destroy_bank(b, "toy_destroy") == 0);
 }
 
+// ---- a second toy bank, with the shape of kq_cw / kq_rtty's host halves: deferred slots and an arena of events --------------
+constexpr int kDefObjects = 8;  // what def_make_device makes: a stream and seven allocations
+
+struct DefPar {
+  int active;
+  unsigned source;
+  int value;
+};
+
+struct DefEvent {
+  unsigned code, slot;
+};
+
+struct def_bank : kq::HostSide {
+  static constexpr bool kDeferred = true;
+  toy_config cfg;
+  std::mutex mu;
+  bool dev_ready = false;
+  uint64_t n_cur = 0;
+  kq::DeferredSlots<DefPar> def;
+  std::vector<std::pair<size_t, size_t>> colds;  // the runs flush() asked a cold start for
+  struct Dev {
+    kq::SlotTable<DefPar> slots;
+    int *state = nullptr;  // [S]: the slot's value at its cold start
+    kq::EventArena<DefEvent> arena;
+    int *st = nullptr;
+  } d;
+
+  int to_device();
+};
+
+int def_make_device(def_bank *b) {
+  size_t const S = b->cfg.max_slots;
+  if (b->open_stream(b->cfg.stream) || b->d.slots.alloc(*b, S) || b->alloc(&b->d.state, S, true) || b->d.arena.alloc(*b, S, 4) ||
+      b->alloc(&b->d.st, S))
+    return -1;
+  KQ_TRY(hipStreamSynchronize(b->stream));
+  return 0;
+}
+
+int def_bank::to_device() {
+  std::vector<int> cold(def.dirty.size());  // as kq_cw's records: host memory that a run is copied from
+  size_t used = 0;
+  return def.flush(this, def_make_device, [&](size_t s0, size_t n) {
+    colds.emplace_back(s0, n);
+    int *r = cold.data() + used;
+    used += n;
+    for (size_t i = 0; i < n; i++) r[i] = d.slots.par[s0 + i].value;
+    KQ_TRY(hipMemcpyAsync(d.state + s0, r, n * sizeof(int), hipMemcpyHostToDevice, stream));
+    return d.arena.clear(*this, s0, n);
+  });
+}
+
+def_bank *def_create(unsigned max_slots) {
+  def_bank *b = new def_bank;
+  b->cfg = toy_config{0, max_slots, 64, nullptr};
+  b->def.init(max_slots);
+  return b;
+}
+
+void def_set(def_bank *b, unsigned slot, int value) {
+  std::lock_guard<std::mutex> lk(b->mu);
+  b->def.set(slot, DefPar{1, slot, value});
+}
+
+bool def_holds_nothing(const def_bank *b) {
+  auto const &d = b->d;
+  return !b->dev_ready && b->held.empty() && b->streams.empty() && !b->stream && d.slots.par.empty() && d.slots.all.empty() &&
+         !d.slots.d_par && !d.slots.d_list && !d.slots.d_rowmap && !d.state && !d.arena.ev && !d.arena.n && d.arena.cap == 0 && !d.st;
+}
+
+// what a kernel would have filed: n events in the slot's arena
+void def_file(def_bank *b, unsigned slot, unsigned n) {
+  for (unsigned i = 0; i < n; i++) b->d.arena.ev[slot * b->d.arena.cap + i] = DefEvent{100 * slot + i, slot};
+  b->d.arena.n[slot] = n;
+}
+
+void deferred_without_a_device() {
+  unsigned const S = 8;
+  def_bank *b = def_create(S);
+  int const mallocs = mock_hip().mallocs, copies = mock_hip().copies;
+  std::optional<kq::DeviceScope> scope;
+  // set, remove and reset touch no device; with no slot left that wants one, neither do the entry points that read it
+  def_set(b, 1, 10);
+  def_set(b, 2, 20);
+  def_set(b, 2, 21);
+  CHECK(b->def.nwant == 2 && (b->def.dirty == std::vector<unsigned>{1, 2}) && b->def.is_set(2) && !b->def.is_set(3) && !b->def.is_set(S));
+  CHECK(kq::deferred_remove(b, 3, "toy_remove") == -1 && last_error == "toy_remove: slot 3 holds no decoder");
+  CHECK(kq::deferred_remove(b, S, "toy_remove") == -1 && last_error == "toy_remove: slot 8 holds no decoder");
+  CHECK(kq::deferred_remove((def_bank *)nullptr, 1, "toy_remove") == -1 && last_error == "toy_remove: null bank");
+  CHECK(kq::deferred_remove(b, 1, "toy_remove") == 0 && kq::deferred_remove(b, 2, "toy_remove") == 0 && b->def.nwant == 0);
+  b->n_cur = 99;
+  CHECK(kq::deferred_reset(b, "toy_reset") == 0 && b->n_cur == 0 && b->def.dirty.size() == 2);
+  CHECK(kq::deferred_reset((def_bank *)nullptr, "toy_reset") == -1 && last_error == "toy_reset: null bank");
+  std::vector<uint32_t> counts(S, 0xFFFFFFFFu);
+  CHECK(kq::pull_counts(b, "toy_pull_counts", counts.data()) == 0 && counts == std::vector<uint32_t>(S, 0u));
+  CHECK(b->def.dirty.empty() && !b->def.is_dirty[1] && !b->def.is_dirty[2]);  // forgotten: there was nowhere to bring them
+  DefEvent e{7, 7};
+  CHECK(kq::pull_event(b, "toy_pull_event", 1, 0, &e) == -1 && last_error == "toy_pull_event: slot 1 has 0 events" && e.code == 7);
+  CHECK(kq::pull_event(b, "toy_pull_event", S, 0, &e) == -1 && last_error == "toy_pull_event: slot 8 >= max_slots 8");
+  CHECK(kq::pull_event(b, "toy_pull_event", 1, 0, (DefEvent *)nullptr) == -1 && last_error == "toy_pull_event: null event");
+  CHECK(kq::pull_counts(b, "toy_pull_counts", nullptr) == -1 && last_error == "toy_pull_counts: null counts");
+  CHECK(kq::pull_counts((def_bank *)nullptr, "toy_pull_counts", counts.data()) == -1 && last_error == "toy_pull_counts: null bank");
+  CHECK(kq::clear_arena(b, "toy_clear") == 0);
+  CHECK(kq::clear_arena((def_bank *)nullptr, "toy_clear") == -1 && last_error == "toy_clear: null bank");
+  CHECK(kq::begin_call(b, "toy_process", 0, b, scope) == kq::CALL_EMPTY && b->n_cur == 0);
+  CHECK(kq::begin_call(b, "toy_process", 15, nullptr, scope) == kq::CALL_FAILED && last_error == "toy_process: null src");
+  CHECK(kq::begin_call(b, "toy_process", 15, b, scope) == kq::CALL_IDLE && b->n_cur == 15 && !scope);
+  CHECK(def_holds_nothing(b) && mock_hip().mallocs == mallocs && mock_hip().copies == copies && b->colds.empty());
+  CHECK(kq::destroy_bank(b, "toy_destroy") == 0);
+}
+
+void deferred_flush_and_arena() {
+  using Runs = std::vector<std::pair<size_t, size_t>>;
+  unsigned const S = 8;
+  def_bank *b = def_create(S);
+  auto &t = b->d.slots;
+  // before the first call: 0, 1, 2 together, 4 alone, 3 set and removed again in the middle
+  def_set(b, 4, 40);
+  def_set(b, 0, 5);
+  def_set(b, 3, 30);
+  def_set(b, 1, 10);
+  def_set(b, 2, 20);
+  CHECK(kq::deferred_remove(b, 3, "toy_remove") == 0 && b->def.nwant == 4 && def_holds_nothing(b));
+  std::vector<uint32_t> counts(S, 0xFFFFFFFFu);
+  int copies = mock_hip().copies;
+  CHECK(kq::pull_counts(b, "toy_pull_counts", counts.data()) == 0 && counts == std::vector<uint32_t>(S, 0u));
+  CHECK(b->dev_ready && b->held.size() == 7 && b->streams.size() == 1 && b->def.dirty.empty());
+  CHECK((b->colds == Runs{{0, 3}, {4, 1}}));
+  // three runs of parameters, two cold starts, upload's record and list, the counts
+  CHECK(mock_hip().copies == copies + 3 + 2 + 2 + 1);
+  CHECK((t.all == std::vector<int>{0, 1, 2, 4}));
+  for (size_t i = 0; i < t.all.size(); i++) CHECK(t.d_list[i] == t.all[i]);
+  for (unsigned s = 0; s < S; s++) {
+    bool const set = s < 3 || s == 4;
+    CHECK(t.d_par[s].active == (set ? 1 : 0) && t.d_par[s].value == b->def.want[s].value && t.d_par[s].source == (set ? s : 0));
+    CHECK(b->d.state[s] == b->def.want[s].value);
+  }
+  CHECK(b->d.state[0] == 5 && b->d.state[4] == 40 && b->d.state[3] == 0);
+  // events, and the index past them
+  def_file(b, 0, 2);
+  def_file(b, 2, 4);
+  DefEvent e{7, 7};
+  CHECK(kq::pull_event(b, "toy_pull_event", 0, 2, &e) == -1 && last_error == "toy_pull_event: slot 0 has 2 events" && e.code == 7);
+  CHECK(kq::pull_event(b, "toy_pull_event", 0, 1, &e) == 0 && e.code == 1 && e.slot == 0);
+  CHECK(kq::pull_event(b, "toy_pull_event", 2, 3, &e) == 0 && e.code == 203 && e.slot == 2);
+  CHECK(kq::pull_event(b, "toy_pull_event", 3, 0, &e) == -1 && last_error == "toy_pull_event: slot 3 has 0 events");
+  // a slot set again starts cold with an empty arena, a removed one keeps its arena; the others are left alone
+  def_set(b, 2, 22);
+  CHECK(kq::deferred_remove(b, 0, "toy_remove") == 0);
+  b->colds.clear();
+  CHECK(kq::pull_counts(b, "toy_pull_counts", counts.data()) == 0 && (counts == std::vector<uint32_t>{2, 0, 0, 0, 0, 0, 0, 0}));
+  CHECK((b->colds == Runs{{2, 1}}) && b->d.state[2] == 22 && b->d.state[1] == 10 && (t.all == std::vector<int>{1, 2, 4}));
+  CHECK(t.d_par[0].active == 0 && t.d_par[2].value == 22);
+  // reset: every slot that is set starts cold again, in runs
+  def_file(b, 1, 1);
+  b->colds.clear();
+  b->n_cur = 5;
+  CHECK(kq::deferred_reset(b, "toy_reset") == 0 && b->n_cur == 0);
+  std::optional<kq::DeviceScope> scope;
+  CHECK(kq::begin_call(b, "toy_process", 15, b, scope) == kq::CALL_RUN && b->n_cur == 0 && scope);
+  CHECK((b->colds == Runs{{1, 2}, {4, 1}}) && b->d.arena.n[1] == 0 && b->d.arena.n[0] == 2);
+  // the status records of a host-memory call: the bank's own plane at stride 1, the active slots' rows back
+  {
+    std::vector<int> host(S * 2, -1);
+    int *st = nullptr;
+    size_t stride = 0;
+    CHECK(kq::bind_status(b, 1, host.data(), (size_t)2, &st, &stride) == 0 && st == host.data() && stride == 2);
+    CHECK(kq::bind_status(b, 0, (int *)nullptr, (size_t)2, &st, &stride) == 0 && st == nullptr && stride == 1);
+    CHECK(kq::bind_status(b, 0, host.data(), (size_t)2, &st, &stride) == 0 && st == b->d.st && stride == 1);
+    for (unsigned s = 0; s < S; s++) b->d.st[s] = 1000 + (int)s;
+    CHECK(kq::end_host_call(b, host.data(), (size_t)2, nullptr) == 0);
+    for (unsigned s = 0; s < S; s++) CHECK(host[2 * s] == (t.active(s) ? 1000 + (int)s : -1) && host[2 * s + 1] == -1);
+    int more = 0;
+    CHECK(kq::end_host_call(b, (int *)nullptr, (size_t)2, [&](size_t, size_t n) { return more += (int)n, 0; }) == 0 && more == 3);
+  }
+  // clear: every arena empty, the slots as they were
+  CHECK(kq::clear_arena(b, "toy_clear") == 0);
+  CHECK(kq::pull_counts(b, "toy_pull_counts", counts.data()) == 0 && counts == std::vector<uint32_t>(S, 0u));
+  CHECK((t.all == std::vector<int>{1, 2, 4}));
+  CHECK(kq::destroy_bank(b, "toy_destroy") == 0);
+}
+
+void deferred_failed_setup() {
+  unsigned const S = 8;
+  for (int k = 1; k <= kDefObjects; k++) {
+    def_bank *b = def_create(S);
+    def_set(b, 2, 7);
+    def_set(b, 3, 8);
+    std::vector<uint32_t> counts(S, 0xFFFFFFFFu);
+    mock_hip().fail_in = k;
+    CHECK(kq::pull_counts(b, "toy_pull_counts", counts.data()) == -1);
+    CHECK(mock_hip().fail_in == 0);  // the k-th object was reached
+    CHECK(def_holds_nothing(b) && b->def.dirty.size() == 2 && b->def.nwant == 2 && b->colds.empty());
+    CHECK(counts[0] == 0xFFFFFFFFu);
+    DefEvent e{7, 7};
+    if (k & 1) {  // the next entry point starts over
+      CHECK(kq::pull_event(b, "toy_pull_event", 2, 0, &e) == -1 && last_error == "toy_pull_event: slot 2 has 0 events");
+    } else {
+      CHECK(kq::pull_counts(b, "toy_pull_counts", counts.data()) == 0 && counts == std::vector<uint32_t>(S, 0u));
+    }
+    CHECK(b->dev_ready && b->held.size() == 7 && b->def.dirty.empty() && (b->d.slots.all == std::vector<int>{2, 3}));
+    CHECK(b->d.state[2] == 7 && b->d.state[3] == 8 && b->colds.size() == 1);
+    CHECK(kq::destroy_bank(b, "toy_destroy") == 0);
+  }
+  // one whose device never came, destroyed with its slots still waiting
+  def_bank *b = def_create(S);
+  def_set(b, 0, 1);
+  std::optional<kq::DeviceScope> scope;
+  mock_hip().fail_in = 4;
+  CHECK(kq::begin_call(b, "toy_process", 15, b, scope) == kq::CALL_FAILED && def_holds_nothing(b) && b->n_cur == 0);
+  CHECK(kq::destroy_bank(b, "toy_destroy") == 0);
+}
+
 }  // namespace
 
 int main() {
   failed_setup();
   table_staging_runs();
+  deferred_without_a_device();
+  deferred_flush_and_arena();
+  deferred_failed_setup();
   if (failures) {
     fprintf(stderr, "slot banks' host layer: %d checks failed\n", failures);
     return 1;
