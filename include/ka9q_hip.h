@@ -1624,6 +1624,158 @@ int kq_rtty_sync(kq_rtty_bank *bank);
 /* Stream index back to 0; every slot restarts cold with its settings at the next call, as if set again */
 int kq_rtty_reset(kq_rtty_bank *bank);
 
+/* --- PSK31 / PSK63 / PSK125 decoder bank ------------------------------------------------------------------------------------
+ * Up to 16384 decoder slots, each reading differential BPSK with Varicode framing (PSK31 at 31.25 baud and its faster
+ * siblings at 62.5 and 125) at one audio pitch from one audio row, as characters.  A receiver bank's USB / LSB channels can
+ * be decoded in place on its stream after kq_bank_join, and several slots may read one row at different pitches, so that a
+ * 3 kHz passband is skimmed with a slot every 50 Hz or so.  The reference has no PSK decoder: the algorithm is defined
+ * here.  Everything after the quantiser is exact integer arithmetic, so no result depends on how sums are ordered or how
+ * the stream is cut into calls.
+ * Per slot, x[n] is its input row; n counts samples since create or kq_psk_reset on a grid shared by every slot, and
+ * x[n] = 0 before the slot was set.  Fs = samprate, B = block_len (8..256); frame k is the samples [k B, (k + 1) B).
+ *   quantise   kq_cw_*'s: q[n] = clamp(rint(x[n] input_scale), -32767, 32767), one float multiply, round to nearest even,
+ *              NaN reads as 0; a KQ_PCM_S16BE word is taken as q itself, -32768 as -32767.
+ *   table      kq_cw_*'s: C[j] = rint(32767 cos(2 pi j / 1024)) as int16 (kq_psk_get_table).
+ *   correlate  inc = rint(pitch 2^32 / Fs) in double, pitch the float of the params (kq_psk_get_slot); ph(n) = (n inc) mod
+ *              2^32 -- no oscillator state is carried -- and j = ph(n) >> 22.  Per frame I = sum q[n] C[j], Q = sum q[n]
+ *              C[(j - 256) & 1023]: exact integers in 64 bits, |I|, |Q| <= 256 * 32767^2 < 2^38.  They are reduced as a =
+ *              I >> 13, b = Q >> 13 (arithmetic shifts): |a|, |b| < 2^25.  A signal above the pitch turns (I, Q) clockwise.
+ *   symbol     tb = rint(256 Fs / (B baud)) in double, baud the float of the params: the symbol in 1/256 frame, 2048 <= tb
+ *              <= 8192 (8 to 32 frames in a symbol).  W = (tb + 128) >> 8 frames, 8..32.  q = tb >> 2, a quarter symbol.
+ *   window     SI[k], SQ[k]: the sums of a and b over the frames k - W + 1 .. k, zeros before the set; 32 terms at the
+ *              most, so below 2^30 in magnitude.  P = SI^2 + SQ^2 as uint64, below 2^61.  The window is a rectangle one
+ *              symbol long, coherent because the reference phase depends on n alone.  It is not the matched filter of
+ *              PSK31's cosine-shaped symbols.
+ *   state      frames, ph (0 early, 1 centre, 2 late: the point taken next), t (signed, in 1/256 frame, to that point),
+ *              pe, ee, el (early and late power, the last and the smoothed two), c and p (the window sums at this
+ *              symbol's centre and at the one before), pc, R = (rot_r, rot_i) (the smoothed product of neighbouring
+ *              symbols: the turn per symbol that a frequency offset makes), sig, qre, qim, shreg, over, the counters.  At
+ *              the set all of it is zero.
+ *   step       one per completed frame k: frames += 1, saturating; t -= 256.  If t >= 128 nothing more happens in this
+ *              frame.  Otherwise the frame is a point, taken in turn by ph:
+ *                early   pe = P, t += q, ph = 1.
+ *                centre  c = (SI, SQ), pc = P, t += q, ph = 2.
+ *                late    ph = 0, and with pl = P the symbol is read, in this order:
+ *     1 timing    ee += (pe - ee) >> 3, el += (pl - el) >> 3 (arithmetic shifts of signed differences, here and below; every
+ *                 term is below 2^61).  m = max(ee, el).  adj = -(tb >> 5) if ee > el and ee - el > (m >> 3), +(tb >> 5) if
+ *                 el > ee and el - ee > (m >> 3), else 0.  t += tb - 2 q + adj.  The powers are smoothed over symbols so
+ *                 that a reversal on one side of a symbol only does not pull the clock.
+ *     2 product   D = c conj(p): Dr = cr pr + ci pi, Di = ci pr - cr pi, each two products below 2^60, so below 2^61 in
+ *                 magnitude.  Then p = c.
+ *     3 normalise norm(x, y): s = max(bitlength(max(|x|, |y|)) - 24, 0), giving (x >> s, y >> s), both 2^24 at the most in
+ *                 magnitude (arithmetic shifts: only -2^24 itself comes out that large).  d = norm(D); r = norm(R), or
+ *                 (1, 0) while R is (0, 0).
+ *     4 decision  Re = dr rr + di ri, Im = di rr - dr ri: 2^49 at the most.  bit = Re >= 0.  No reversal is a 1.
+ *     5 rotation  D' = bit ? D : -D.  R += (D' - R) >> 4 per component: |D' - R| < 2^62, and |R| stays below 2^61 as D does.
+ *                 Then, if 2 rot_r < |rot_i|: rot_r = |rot_i| >> 1.  The estimate stays within atan 2 = 63.4 degrees per
+ *                 symbol, which is +-5.5 Hz at 31.25 baud; without the clamp it can settle half a turn off after a stretch
+ *                 of noise and invert every bit from there on.
+ *     6 levels    qre += (|Re| - qre) >> 4, qim += (|Im| - qim) >> 4, sig += (pc - sig) >> 4.
+ *     7 validity  valid = frames >= warm and sig >= min_p and 16 qre >= snr qim (16 qre <= 2^53, snr qim < 2^61: one word).
+ *                 If not valid: shreg = 0, over = 0, and the step ends.
+ *     8 Varicode  over = 1 if bit 13 of shreg is set; shreg = (shreg << 1 | bit) & 0x3FFF.  If (shreg & 3) == 0 (a gap of
+ *                 two reversals): code = shreg >> 2, and when code != 0 an event is filed with flags = over, or flags = 1
+ *                 if code > 1023 (more than ten bits between gaps: no character); then shreg = 0, over = 0.
+ *   event      code: the character's bits behind their own leading 1, as sent, the first in the highest place (e is 0b11,
+ *              a space 0b1: ka9q_sdr_amd/varicode.py holds the table); flags; end_sample = (k + 1) B, the end of the frame
+ *              that read the second reversal of the gap; sig; rot_r, rot_i = r of step 3 as int32: the turn per symbol
+ *              the decision was made against, -atan2(rot_i, rot_r) / (2 pi) baud Hz above the pitch.  events += 1 for
+ *              each; it goes to the slot's arena, or dropped += 1 when that holds max_events.  events and dropped saturate
+ *              at 2^32 - 1, as frames does.
+ * kq_psk_remove and kq_psk_reset discard the open character.  Carried between calls: the open frame's I and Q, the reduced
+ * sums of the last 31 frames (W - 1 at the most), the two window sums and all of the state above; so the same stream split
+ * differently into calls or blocks gives the same events and status.  kq_psk_status holds all of it but the past frames.
+ * The code is differential, so the carrier's phase and the signal's polarity change nothing.
+ * Limits (refused by kq_psk_create / kq_psk_set with the reason in kq_last_error, before any HIP call): samprate positive
+ * and finite; 8 <= B <= 256; warm 0..65535; snr 16..4095; min_p <= 2^55; input_scale > 0; max_slots 1..16384; max_events
+ * 1..4096; max_samples 1..2^28; per slot 0 < pitch < Fs / 2, baud positive and finite with 2048 <= tb <= 8192.
+ * Device memory per slot: 32 max_events of arena, 416 of state, history and parameters; 2 KiB of table per bank.
+ * Absent: QPSK31 (its convolutional code needs a Viterbi decoder: a later bank) and a matched filter.  The rectangular
+ * window keeps the eye open -- at the centre it reads an amplitude of 0.64 where both neighbours are reversals, 0.82
+ * with one, 1.0 with none -- at a cost in noise margin.  The rotation estimate follows +-5.5 Hz at 31.25 baud and no
+ * more; the clock tolerates the 100 ppm of a sound card.  There is no squelch beyond step 7: when a signal stops, the
+ * gate takes a few symbols to shut, and a slot 50 Hz beside a strong signal reads its splatter as a few characters (of
+ * neighbouring slots the largest qre / qim is on the signal).  Copy off the air has not been measured.  In the model
+ * (tests/test_psk_model.py), at (12000, 24, 31.25) with snr = 32 and white noise, five runs of 171 characters each are
+ * whole at an Es/N0 (the carrier's power times the symbol over N0) of 20 and 14 dB; 0.7 % of the characters are lost at
+ * 12 dB, 19 % at 10 dB and 77 % at 8 dB, where the validity gate is shut most of the time.
+ * Calls: as kq_rtty_*.  kq_psk_create, kq_psk_set and kq_psk_remove touch no device. */
+typedef struct kq_psk_bank kq_psk_bank;
+typedef struct kq_psk_config {
+  int device;
+  double samprate;           /* Fs: input samples per second; a double, so that 39 062.5 is exact */
+  unsigned block_len;        /* B: samples per frame, 8..256 */
+  unsigned warm;             /* frames after the set in which nothing is read while the levels train (64) */
+  unsigned snr;              /* least qre / qim, in sixteenths (32: a ratio of 2; noise alone gives about 1) */
+  uint64_t min_p;            /* least sig (65536) */
+  float input_scale;         /* 32767 suits audio of full scale 1 */
+  unsigned max_slots;        /* slots 0 .. max_slots - 1 (limit 16384) */
+  unsigned max_events;       /* arena places per slot between kq_psk_clear_events calls */
+  size_t max_samples;        /* largest nblocks * block_len of one kq_psk_process call */
+  void *stream;              /* hipStream_t, NULL = own stream; kq_bank_stream(bank) puts it beside a receiver bank */
+} kq_psk_config;
+typedef struct kq_psk_params {
+  unsigned source;           /* input row this slot decodes (a receiver bank's channel index) */
+  float pitch;               /* Hz */
+  float baud;
+} kq_psk_params;
+typedef struct kq_psk_status {
+  uint32_t frames;           /* completed since the slot was set */
+  uint32_t ph;               /* the point taken next: 0 early, 1 centre, 2 late */
+  int32_t t;                 /* 1/256 frame to that point */
+  uint32_t shreg;            /* the open character's bits */
+  uint32_t over;             /* 1: a set bit has left shreg */
+  uint32_t events;           /* filed since the set, those dropped included */
+  uint32_t dropped;
+  uint32_t reserved;         /* 0 */
+  uint64_t sig;              /* the power at the symbols' centres */
+  uint64_t qre, qim;         /* the decision's |Re| and |Im|: of slots on one row the largest qre / qim is on the signal */
+  uint64_t ee, el;           /* the smoothed early and late power */
+  uint64_t pe, pc;           /* the power at the last early point and the last centre */
+  int64_t rot_r, rot_i;      /* R */
+  int32_t cr, ci, pr, pi;    /* c and p */
+  int32_t sum_i, sum_q;      /* the window sums at the last completed frame */
+  int64_t acc_i, acc_q;      /* I and Q of the open frame */
+} kq_psk_status;
+typedef struct kq_psk_event {
+  uint32_t code;
+  uint32_t flags;            /* bit 0: more than ten bits between gaps, code holds the last of them */
+  uint64_t end_sample;       /* the end of the frame that read the gap */
+  uint64_t sig;              /* at that symbol */
+  int32_t rot_r, rot_i;      /* r at that symbol */
+} kq_psk_event;
+typedef struct kq_psk_slot {
+  uint32_t inc;              /* the phase increment of the pitch */
+  uint32_t tb;               /* the symbol in 1/256 frame */
+  uint32_t W;                /* the window in frames */
+  uint32_t reserved;         /* 0 */
+} kq_psk_slot;
+
+kq_psk_bank *kq_psk_create(const kq_psk_config *cfg);
+int kq_psk_destroy(kq_psk_bank *bank);
+/* Put a decoder in `slot` (or replace the one there): a cold start at the next call's first sample, its arena empty.
+ * Touches no device: the next kq_psk_process, kq_psk_pull_counts or kq_psk_pull_event brings every slot set or removed
+ * since the last one there, and waits for the handle's stream to do so (once, however many slots changed). */
+int kq_psk_set(kq_psk_bank *bank, unsigned slot, const kq_psk_params *params);
+/* The slot stops from the next call; its arena stays readable.  Touches no device either */
+int kq_psk_remove(kq_psk_bank *bank, unsigned slot);
+/* Input, status and on_device as in kq_rtty_process (status may be NULL; nothing is written for an empty slot). */
+int kq_psk_process(kq_psk_bank *bank, const void *src, int format, size_t src_stride, size_t row_stride, unsigned block_len,
+                   unsigned nblocks, int on_device, kq_psk_status *status, size_t status_stride);
+/* Events in every slot's arena, counts[max_slots], in one copy; synchronous */
+int kq_psk_pull_counts(kq_psk_bank *bank, uint32_t *counts);
+/* Copies event `index` of `slot`; returns 0, or -1 */
+int kq_psk_pull_event(kq_psk_bank *bank, unsigned slot, unsigned index, kq_psk_event *event);
+/* Empties every arena (on the handle's stream); the status counters and the open characters go on */
+int kq_psk_clear_events(kq_psk_bank *bank);
+/* C (at most cap words); returns 1024 */
+int kq_psk_get_table(const kq_psk_bank *bank, int16_t *dst, size_t cap);
+/* inc, tb and W of `slot`, without a device; -1 when the slot holds no decoder */
+int kq_psk_get_slot(kq_psk_bank *bank, unsigned slot, kq_psk_slot *out);
+int kq_psk_sync(kq_psk_bank *bank);
+/* Stream index back to 0; every slot restarts cold with its settings at the next call, as if set again */
+int kq_psk_reset(kq_psk_bank *bank);
+
 /* --- rational resampler bank ----------------------------------------------------------------------------------------------
  * Up to 65536 slots, each one row of PCM (mono or stereo) resampled from Fi = in_rate_num / in_rate_den Hz (a receiver
  * bank's samprate and decimate, so 39 062.5 Hz is exact) to Fo = out_rate Hz: kq_afsk_*, RTP PCM and the players are 48 kHz,

@@ -46,5 +46,7 @@ from .cw import CwBank, CwParams, cw_params  # noqa: F401,E402  (cw.STATUS_DTYPE
 from . import morse  # noqa: F401,E402
 from .rtty import RttyBank, RttyParams, rtty_params  # noqa: F401,E402  (rtty.STATUS_DTYPE: the RTTY decoder's)
 from . import baudot  # noqa: F401,E402
+from .psk import PskBank, PskParams, psk_params  # noqa: F401,E402  (psk.STATUS_DTYPE: the PSK decoder's)
+from . import varicode  # noqa: F401,E402
 from .monitor import KQ_MON_F32, KQ_MON_S16BE, MonBank, MonParams, mon_params  # noqa: F401,E402  (monitor.STATUS_DTYPE: the mixer's)
 from .resample import RsmpBank, RsmpParams, rsmp_params  # noqa: F401,E402
