@@ -1776,6 +1776,159 @@ int kq_psk_sync(kq_psk_bank *bank);
 /* Stream index back to 0; every slot restarts cold with its settings at the next call, as if set again */
 int kq_psk_reset(kq_psk_bank *bank);
 
+/* --- ACARS decoder bank -------------------------------------------------------------------------------------------------------
+ * Up to 4096 decoder slots, each reading ACARS blocks from the audio of one AM channel (demod_am's output; a receiver
+ * bank's audio plane can be decoded in place on its stream after kq_bank_join), so that an airband bank of 760 channels
+ * hands out blocks instead of 760 audio streams.  ACARS is 2400 bit/s MSK: a bit equal to the one before is 2400 Hz, one
+ * that differs 1200 Hz, the phase continuous -- MSK around 1800 Hz, precoded so that a coherent detector's decisions are
+ * the data bits.  A block: a pre-key of 2400 Hz; + * SYN SYN SOH (0x2b 0x2a 0x16 0x16 0x01); mode, address (7), ack,
+ * label (2), block id; STX and up to 220 characters of text, or neither; ETX (0x03) or ETB (0x17); the block check, 2 bytes,
+ * low first; DEL.  Characters are 7 bits, least significant first, bit 7 making the parity odd.  The check is
+ * CRC-16/KERMIT (0x8408 reflected, initial value 0, no final xor) over the bytes as sent, parity bits included, from mode
+ * through ETX / ETB; run on over the two check bytes it leaves 0.  This is ARINC 618's block as the open decoders read it,
+ * written down from memory: nothing here has been checked against a signal off the air.  The reference has no ACARS
+ * decoder: the algorithm is defined here.  Everything after the quantiser is exact integer arithmetic, so no result depends
+ * on how sums are ordered or how the stream is cut into calls.
+ * Per slot, x[n] is its input row; n counts samples since create or kq_acars_reset on a grid shared by every slot, and
+ * x[n] = 0 before the slot was set.  Fs = samprate.  Integers made from Fs in double, rint to nearest even: FL = rint(2 Fs /
+ * 2400) taps (8..80), w = ceil(Fs / 2400) (4..40), e = max(1, rint(Fs / 9600)) (1..10, e <= w), tb = rint(256 Fs / 2400),
+ * o_k = rint((k - 39) Fs / 2400) for k = 0..39 (o_39 = 0, H39 = -o_0 <= 1560), inc = rint(1800 2^32 / Fs).
+ *   quantise   as kq_fsk_*: q[n] = clamp(rint(x[n] input_scale), -32767, 32767), one float multiply, round to nearest even,
+ *              NaN reads as 0; a KQ_PCM_S16BE word is taken as q itself, -32768 as -32767.  |q| < 2^15.
+ *   mix        kq_cw_*'s table C[j] = rint(32767 cos(2 pi j / 1024)); j = ((n inc) mod 2^32) >> 22 -- no oscillator state
+ *              is carried and nothing feeds back -- and z[n] = q[n] (C[j] - i C[(j - 256) & 1023]).  |Re z|, |Im z| <= 32767^2
+ *              < 2^30.
+ *   filter     hq[i] = rint(32767 cos(pi (i - (FL - 1) / 2) / FL)) as int16 (kq_acars_get_taps): the half cosine two bits
+ *              long, MSK's matched filter.  v[n] = sum_i hq[i] z[n - i], exact in 64 bits: each component is at most
+ *              80 * 32767^3 < 2^51.33.  a[n] = v[n] >> 30 per component (arithmetic shift): below 2^21.33, an int32.
+ *   sync       d_k = +-1: the 40 bits of + * SYN SYN SOH, parity bits included, in the order sent.  c[n] = sum_k d_k
+ *              (-i)^k a[n + o_k] (the correlation against d_k i^k, one bit apart): a component is 40 terms, below 2^26.66.
+ *              e[n] = sum_k |a[n + o_k]|^2 < 40 * 2 * 2^42.66 < 2^49.  |c|^2 as uint64 < 2^54.4.  The metric |c|^2 / (40 e)
+ *              is 1 at the most.  n passes when |c|^2 > 0 and |c|^2 sync_den >= 40 sync_num e (both sides below 2^62.4:
+ *              sync_den <= 255).  p is a sync when it passes, |c[p]|^2 > |c[m]|^2 for p - w <= m < p and |c[p]|^2 >=
+ *              |c[m]|^2 for p < m <= p + w (of equals the first), p >= search_from, and no block is open.  It is decided
+ *              when sample p + w has arrived, however the stream is cut.
+ *              At a sync: syncs += 1; R = (Re c >> 5, Im c >> 5) (below 2^21.66: the sign of the audio is inside, so no
+ *              polarity is left to resolve); t = 256 p (in 1/256 sample); k = 39; sync_sample = p, sync_c2 = |c|^2, sync_e =
+ *              e; nbits, cur, length, parity_errors, crc, ending, cnt, acc = 0.  p lies (FL - 1) / 2 samples -- the
+ *              filter's delay -- behind the end of SOH's last bit.
+ *   bit        while a block is open, in order, each when sample n + w has arrived: n = (t + tb + 128) >> 8; t += tb;
+ *              k += 1 (mod 2^32); u = a[n] (-i)^(k mod 4), ue and ul the same of a[n - e] and a[n + e].  With <x, R> = Re x
+ *              Re R + Im x Im R (below 2^44.1): bit = <u, R> >= 0.  acc += |<ue, R>| - |<ul, R>|.  Then R += (u - R) >> 4 per
+ *              component if bit else (-u - R) >> 4 (arithmetic; R stays below 2^22).  cnt += 1; at cnt == 8, with r2 =
+ *              |R|^2 of the new R (< 2^44.4): t -= tb >> 5 if 4 acc > r2, t += tb >> 5 if 4 acc < -r2 (|acc| < 2^48); acc =
+ *              cnt = 0.  The early / late difference over 8 bits moves the clock when it exceeds a quarter of |R|.
+ *   frame      the bit goes into cur at place nbits and into crc (crc = (crc >> 1) ^ (0x8408 if (crc ^ bit) & 1)); at the
+ *              8th, the byte is stored behind the others (from the mode character on: length += 1).  If ending != 0 (bytes
+ *              of the check left, + 4 behind an ETB): ending -= 1 and at (ending & 3) == 0 the block closes, good when crc
+ *              == 0.  Else: parity_errors += 1 for a byte of even parity; a byte with (byte & 0x7f) ETX or ETB and length
+ *              <= max_block_bytes - 2 sets ending = 2 (ETB: 6); else, when length >= max_block_bytes - 2, the block closes
+ *              as an overrun.
+ *   close      at the bit's sample n: blocks_good, overruns or blocks_bad += 1.  A good block, or any other with
+ *              parity_errors <= max_parity_errors (so that the host can repair it), goes to the slot's arena, or dropped
+ *              += 1 when that holds max_blocks; the rest: discarded += 1.  Then in_block = 0, ending = 0, search_from =
+ *              n + 1: the search goes on behind the block's last bit (DEL is not read).  Counters saturate at 2^32 - 1.
+ *   record     the bytes from mode through the check, parity bits kept; length; flags (KQ_ACARS_GOOD, KQ_ACARS_ETB,
+ *              KQ_ACARS_OVERRUN); parity_errors; sync_sample; end_sample = n of the last bit; sync_c2 and sync_e (the metric is
+ *              sync_c2 / (40 sync_e)); r2 = |R|^2 at the close.
+ * A call's results look back on the H = H39 + 2 w + FL - 1 samples before it (1719 at the most; 214 at 12 kHz).  Carried
+ * between calls, in the form the next call needs them: the last FL - 1 values of q, the last HA = H39 + 2 w values of a, the
+ * last 2 w of |c|^2 with the threshold's verdict -- each a function of the samples alone -- kq_acars_status, which is all
+ * of the state above, and the open block's bytes.  So the same stream cut differently into calls or blocks gives the same
+ * records and status.
+ * Limits (refused by kq_acars_create / kq_acars_set with the reason in kq_last_error, before any HIP call): samprate finite,
+ * 9600 <= Fs <= 96000 (4 to 40 samples per bit); input_scale > 0; sync_den 1..255, sync_num 1..sync_den; max_parity_errors
+ * 0..255; max_block_bytes 16..256; max_slots 1..4096; max_blocks 1..4096; max_samples 1..2^28.
+ * Device memory per slot: 8 HA + 16 w + 4 (FL - 1) bytes of the past (13.9 KiB at 96 kHz, 1.7 KiB at 12 kHz), 256 of open
+ * block, max_blocks (max_block_bytes + 56) of arena, 128 of state and parameters; 2.5 KiB of tables per bank.
+ * Absent: a squelch other than the metric; soft decisions; the reading of DEL; anything above the block (multi-block
+ * messages are the host's: ka9q_sdr_amd/arinc618.py parses and repairs).  In the model (tests/test_acars_model.py), at 12
+ * kHz with white noise, five runs of ten blocks each are whole at an Eb/N0 of 14 and 10 dB; at 8 dB 39 are good and 11
+ * repairable, at 6 dB 5 good, 27 repairable and 18 lost.  120 s of noise alone and of a steady 2400 Hz tone file nothing and
+ * never pass the threshold (metric 0.27 and 0.18 at the most against 0.5).
+ * Calls: as kq_psk_*.  kq_acars_create, kq_acars_set and kq_acars_remove touch no device. */
+#define KQ_ACARS_GOOD 1u     /* the check closed */
+#define KQ_ACARS_ETB 2u      /* ended by ETB: another block of the message follows */
+#define KQ_ACARS_OVERRUN 4u  /* max_block_bytes passed without ETX / ETB */
+typedef struct kq_acars_bank kq_acars_bank;
+typedef struct kq_acars_config {
+  int device;
+  double samprate;           /* Fs: input samples per second; a double, so that 39 062.5 is exact */
+  float input_scale;         /* 32767 suits audio of full scale 1 */
+  unsigned sync_num, sync_den; /* the sync threshold on |c|^2 / (40 e): 1 / 2 */
+  unsigned max_parity_errors; /* a block whose check fails is filed with this many at the most (3) */
+  unsigned max_block_bytes;  /* longest block, check included (256) */
+  unsigned max_slots;        /* slots 0 .. max_slots - 1 (limit 4096) */
+  unsigned max_blocks;       /* arena places per slot between kq_acars_clear_blocks calls */
+  size_t max_samples;        /* largest nblocks * block_len of one kq_acars_process call */
+  void *stream;              /* hipStream_t, NULL = own stream; kq_bank_stream(bank) puts it beside a receiver bank */
+} kq_acars_config;
+typedef struct kq_acars_params {
+  unsigned source;           /* input row this slot decodes (a receiver bank's channel index) */
+} kq_acars_params;
+typedef struct kq_acars_status {
+  uint32_t syncs;            /* since the slot was set, as the counters below */
+  uint32_t blocks_good, blocks_bad, overruns;   /* closed: check good, check bad, no ETX / ETB */
+  uint32_t dropped;          /* refused by a full arena */
+  uint32_t discarded;        /* bad or overrun with more than max_parity_errors: counted only */
+  uint32_t in_block;         /* 1: a block is open */
+  uint32_t k;                /* bits since the sync's first, mod 2^32 */
+  uint32_t nbits, cur;       /* the open character */
+  uint32_t length;           /* bytes of the open block */
+  uint32_t parity_errors;
+  uint32_t crc;
+  uint32_t ending;           /* bytes of the check left, + 4 behind an ETB */
+  uint32_t cnt;              /* bits gathered in acc */
+  uint32_t reserved;         /* 0 */
+  int64_t t;                 /* the last bit's time, 1/256 sample */
+  int64_t search_from;       /* no sync before this sample */
+  int64_t acc;               /* early minus late */
+  uint64_t sync_sample, sync_c2, sync_e;   /* of the last sync */
+  int32_t rr, ri;            /* R */
+} kq_acars_status;
+typedef struct kq_acars_block_info {
+  uint32_t length;
+  uint32_t flags;            /* KQ_ACARS_* */
+  uint32_t parity_errors;
+  uint32_t reserved;         /* 0 */
+  uint64_t sync_sample, end_sample;
+  uint64_t sync_c2, sync_e;
+  uint64_t r2;
+} kq_acars_block_info;
+typedef struct kq_acars_slot {
+  uint32_t source;
+  uint32_t inc;              /* the mixer's phase increment */
+  uint32_t taps;             /* FL */
+  uint32_t w, e, tb;
+  uint32_t history;          /* H: the samples before a call that its results look back on */
+  uint32_t piece;            /* samples the kernel takes through LDS at a time (a seam for call splits) */
+} kq_acars_slot;
+
+kq_acars_bank *kq_acars_create(const kq_acars_config *cfg);
+int kq_acars_destroy(kq_acars_bank *bank);
+/* Put a decoder in `slot` (or replace the one there): a cold start at the next call's first sample, its arena empty.
+ * Touches no device, as kq_psk_set */
+int kq_acars_set(kq_acars_bank *bank, unsigned slot, const kq_acars_params *params);
+/* The slot stops from the next call and its open block is discarded; its arena stays readable.  Touches no device either */
+int kq_acars_remove(kq_acars_bank *bank, unsigned slot);
+/* Input, status and on_device as in kq_fsk_process (status may be NULL; nothing is written for an empty slot). */
+int kq_acars_process(kq_acars_bank *bank, const void *src, int format, size_t src_stride, size_t row_stride, unsigned block_len,
+                     unsigned nblocks, int on_device, kq_acars_status *status, size_t status_stride);
+/* Blocks in every slot's arena, counts[max_slots], in one copy; synchronous */
+int kq_acars_pull_counts(kq_acars_bank *bank, uint32_t *counts);
+/* Copies block `index` of `slot` (at most cap bytes) and its record (info may be NULL); returns its length, or -1 */
+int kq_acars_pull_block(kq_acars_bank *bank, unsigned slot, unsigned index, unsigned char *dst, size_t cap,
+                        kq_acars_block_info *info);
+/* Empties every arena (on the handle's stream); the status counters and the open blocks go on */
+int kq_acars_clear_blocks(kq_acars_bank *bank);
+/* hq (at most cap words); returns FL */
+int kq_acars_get_taps(const kq_acars_bank *bank, int16_t *dst, size_t cap);
+/* the slot's source and the bank's integers, without a device; -1 when the slot holds no decoder */
+int kq_acars_get_slot(kq_acars_bank *bank, unsigned slot, kq_acars_slot *out);
+int kq_acars_sync(kq_acars_bank *bank);
+/* Stream index back to 0; every slot restarts cold with its settings at the next call, as if set again */
+int kq_acars_reset(kq_acars_bank *bank);
+
 /* --- rational resampler bank ----------------------------------------------------------------------------------------------
  * Up to 65536 slots, each one row of PCM (mono or stereo) resampled from Fi = in_rate_num / in_rate_den Hz (a receiver
  * bank's samprate and decimate, so 39 062.5 Hz is exact) to Fo = out_rate Hz: kq_afsk_*, RTP PCM and the players are 48 kHz,

@@ -48,5 +48,7 @@ from .rtty import RttyBank, RttyParams, rtty_params  # noqa: F401,E402  (rtty.ST
 from . import baudot  # noqa: F401,E402
 from .psk import PskBank, PskParams, psk_params  # noqa: F401,E402  (psk.STATUS_DTYPE: the PSK decoder's)
 from . import varicode  # noqa: F401,E402
+from .acars import AcarsBank, AcarsParams, acars_params  # noqa: F401,E402  (acars.STATUS_DTYPE: the ACARS decoder's)
+from . import arinc618  # noqa: F401,E402
 from .monitor import KQ_MON_F32, KQ_MON_S16BE, MonBank, MonParams, mon_params  # noqa: F401,E402  (monitor.STATUS_DTYPE: the mixer's)
 from .resample import RsmpBank, RsmpParams, rsmp_params  # noqa: F401,E402
