@@ -1929,6 +1929,180 @@ int kq_acars_sync(kq_acars_bank *bank);
 /* Stream index back to 0; every slot restarts cold with its settings at the next call, as if set again */
 int kq_acars_reset(kq_acars_bank *bank);
 
+/* --- HF ALE (MIL-STD-188-141 Appendix A, 8-FSK) decoder bank ------------------------------------------------------------------
+ * Up to 16384 decoder slots, each reading second-generation Automatic Link Establishment words from one audio row: a
+ * receiver bank with a USB channel parked on every ALE frequency, and a slot on each, hears every sounding and call.  A
+ * bank's USB channels can be decoded in place on its stream after kq_bank_join.  The reference has no ALE decoder: the
+ * algorithm is defined here.  Everything after the quantiser is exact integer arithmetic, so no result depends on how sums
+ * are ordered or how the stream is cut into calls.
+ * The signal, WRITTEN DOWN FROM MEMORY (no copy of the standard was at hand; ka9q_sdr_amd/ale2g.py says the same): eight
+ * tones at 750 + 250 t Hz, t = 0..7, phase-continuous, 125 symbols a second, three bits a symbol with the highest sent
+ * first; the tones 0..7 carry 000 001 011 010 110 111 101 100.  A word is 24 bits, highest first: a 3-bit preamble (DATA 0,
+ * THRU 1, TO 2, TWAS 3, FROM 4, TIS 5, CMD 6, REP 7) and three 7-bit ASCII characters, in addresses from the 38 of 0-9 A-Z
+ * @ ?.  Its halves A (bits 23..12) and B (bits 11..0) are each encoded with the extended Golay (24,12,8) code, 12 data bits
+ * then 12 check bits, B's check bits inverted; A23 B23 A22 B22 .. A0 B0 and one stuff bit 0 make 49 bits, which are sent
+ * three times in a row: 147 bits, 49 symbols, 392 ms.  The check bits here are the remainder of data x^11 by g(x) = x^11 +
+ * x^10 + x^6 + x^5 + x^4 + x^2 + 1 (0xC75) followed by the overall parity bit.  That this is a (24,12,8) code whose 2325
+ * error patterns of weight <= 3 have distinct syndromes is tested; that it equals the standard's generator matrix bit for
+ * bit is NOT verified.  The 4096-entry parity table (ale2g.PARITY, golay_parity() in kq_ale.hip) is the single statement of
+ * the code, so a correction is a table swap.
+ * Per slot, x[n] is its input row; n counts samples since create or kq_ale_reset on a grid shared by every slot, and x[n] = 0
+ * before the slot was set.  Fs = samprate, B = block_len (8..256); frame k is the samples [k B, (k + 1) B).
+ *   quantise   kq_cw_*'s: q[n] = clamp(rint(x[n] input_scale), -32767, 32767), one float multiply, round to nearest even,
+ *              NaN reads as 0; a KQ_PCM_S16BE word is taken as q itself, -32768 as -32767.
+ *   table      kq_cw_*'s: C[j] = rint(32767 cos(2 pi j / 1024)) as int16 (kq_ale_get_table).
+ *   correlate  tone t is at f0 + t df in double, f0 and df the floats of the params; inc[t] = rint((f0 + t df) 2^32 / Fs)
+ *              (kq_ale_get_slot); ph_t(n) = (n inc[t]) mod 2^32 -- no oscillator state is carried -- and j = ph_t(n) >> 22.
+ *              Per frame and tone I = sum q[n] C[j], Q = sum q[n] C[(j - 256) & 1023]: exact integers in 64 bits.  The
+ *              vector (I, Q) is at most 256 * 32767 * 32768 < 2^38 long (a table entry's pair is at most 32767.8 long).
+ *              Reduced as kq_rtty_* does: a = I >> 12, b = Q >> 12 (arithmetic shifts), (a, b) at most 2^26 + 2 long.
+ *   symbol     tb = rint(256 Fs / (B baud)) in double, baud the float of the params: the symbol in 1/256 frame, 2048 <= tb
+ *              <= 8192 (8 to 32 frames in a symbol).  W = (tb + 128) >> 8 frames, 8..32.  q = tb >> 2, a quarter symbol.
+ *   window     per tone SI_t[k], SQ_t[k]: the sums of a and b over the frames k - W + 1 .. k, zeros before the set; 32 terms
+ *              at the most, so each fits int32 and the vector is at most 2^31 + 64 long.  P_t = SI_t^2 + SQ_t^2 as uint64,
+ *              below 2^63.  The tones are orthogonal over a symbol, so this is the matched filter.  best = max P_t, sym =
+ *              the lowest t that has it, oth = the sum over the other seven t of (P_t >> 3), below 2^63: seven eighths of
+ *              the mean of the other seven, taken so that no sum passes 64 bits and no division is needed.
+ *   state      frames, ph (0 early, 1 centre, 2 late: the point taken next), t (signed, in 1/256 frame, to that point), pe,
+ *              ee, el (early and late power, the last and the smoothed two), sym, pc and oth (of the last centre), sig, nse,
+ *              the register r0, r1, r2 (49 bits each), nsym, sync_at, wpos, synced, bad, the counters.  At the set all zero.
+ *   step       one per completed frame k: frames += 1, saturating; t -= 256.  If t >= 128 nothing more happens in this
+ *              frame.  Otherwise the frame is a point, taken in turn by ph:
+ *                early   pe = best, t += q, ph = 1.
+ *                centre  sym, pc = best and oth are taken, t += q, ph = 2.
+ *                late    ph = 0, and with pl = best the symbol is read, in this order:
+ *     1 timing    kq_psk_*'s: ee += (pe - ee) >> 3, el += (pl - el) >> 3 (arithmetic shifts of signed differences, here and
+ *                 below; every term is below 2^63).  m = max(ee, el).  adj = -(tb >> 5) if ee > el and ee - el > (m >> 3),
+ *                 +(tb >> 5) if el > ee and el - ee > (m >> 3), else 0.  t += tb - 2 q + adj.  Where neighbouring symbols
+ *                 carry the same tone both sides read alike and the clock holds.
+ *     2 levels    sig += (pc - sig) >> 4, nse += (oth - nse) >> 4.  valid = frames >= warm and sig >= min_p and 16 sig >= snr
+ *                 nse, the two products taken exactly (they pass 64 bits: 128-bit compare).
+ *     3 register  g = the three bits of tone sym.  r0 = (r0 << 3 | r1 >> 46) mod 2^49, r1 = (r1 << 3 | r2 >> 46) mod 2^49,
+ *                 r2 = (r2 << 3 | g) mod 2^49, each from the values before.  nsym += 1 (mod 2^32); if synced, wpos += 1.
+ *     4 gate      if not valid: synced = 0, bad = 0, wpos = 0, and the step ends: the register has shifted all the same.
+ *     5 word      if synced and wpos < 49 the step ends.  Otherwise the attempt: maj = (r0 & r1) | (r0 & r2) | (r1 & r2);
+ *                 split = popcount((r0 ^ r1) | (r0 ^ r2)), the places where the copies differ; A = bits 48, 46 .. 2 of maj
+ *                 and B = bits 47, 45 .. 1, the first named in bit 23; B ^= 0xFFF; per half the syndrome = parity[half >> 12]
+ *                 ^ (half & 0xFFF), and by a second 4096-entry table the one error pattern of weight <= 3 with that
+ *                 syndrome, or weight 4 where there is none (1771 of 4096 syndromes).  err_a, err_b = the weights; word =
+ *                 A's and B's data bits, corrected where the weight is below 4, as received where it is 4.
+ *                   not synced  The word is filed (flags 0) only if err_a <= acq_err and err_b <= acq_err, bit 0 of maj
+ *                               (the stuff bit) is 0, and -- for every preamble but CMD -- all three characters are among
+ *                               the 38.  Then synced = 1, sync_at = nsym, wpos = 0, bad = 0.
+ *                   synced      wpos = 0.  If both weights are below 4 the word is filed (flags 0) with no further test and
+ *                               bad = 0.  Otherwise it is filed with flags bit 0 set, so that the client sees the hole;
+ *                               bad += 1, and at bad == lose: synced = 0, bad = 0.
+ *                 2325 / 4096 of all 24-bit words lie within three bits of a codeword, so a search at every symbol must
+ *                 not use the code's full reach: with acq_err = 1 a random half passes with probability 25 / 4096, a random
+ *                 147 bits with (25 / 4096)^2 / 2 and, outside CMD, (38 / 128)^3 of that.
+ *   event      word (24 bits); flags; err_a, err_b; split; end_sample = (k + 1) B, the end of the frame of the late point
+ *              that read the word's last symbol; sig, nse at that symbol.  events += 1 for each; it goes to the slot's
+ *              arena, or dropped += 1 when that holds max_events.  events and dropped saturate at 2^32 - 1, as frames.
+ * A departure from word sync by counting: (nsym - sync_at) mod 49 == 0 is kept as wpos, which counts 0..49 and does not
+ * mind nsym wrapping.  kq_ale_remove and kq_ale_reset discard the register.  Carried between calls: the open frame's I and Q
+ * per tone, the reduced sums of the last 31 frames (W - 1 at the most), the sixteen window sums and all of the state above;
+ * so the same stream split differently into calls or blocks gives the same events and status.  kq_ale_status holds all of
+ * it but the past frames.
+ * Limits (refused by kq_ale_create / kq_ale_set with the reason in kq_last_error, before any HIP call): samprate positive
+ * and finite; 8 <= B <= 256; warm 0..65535; snr 16..4095; min_p <= 2^55; input_scale > 0; acq_err 0..3; lose 1..15;
+ * max_slots 1..16384; max_events 1..4096; max_samples 1..2^28; per slot f0 and df finite, df not 0 (it may be negative: an
+ * LSB channel), every tone above 0 and below Fs / 2, baud positive and finite with 2048 <= tb <= 8192.
+ * Device memory per slot: 48 max_events of arena, about 2.4 KiB of state, history and parameters; 18 KiB of tables per bank.
+ * The default snr of 80 (sig / nse = 5): in the model 60 s of noise alone hold 16 sig / nse between 56 and 82, mean 66 (the
+ * largest of eight noise powers is about 3.6 times the mean of the other seven, and nse is 7 / 8 of that mean), a signal
+ * at an Es/N0 of 6 dB between 79 and 122, at 8 dB between 112 and 158.  The gate is a squelch only: noise and a steady tone
+ * file nothing with the gate held open either, by the code and the character test alone (tests/test_ale_model.py).  So a
+ * gate that opens on noise costs nothing but the attempts, while one that shuts on a weak signal costs words: 80 is the
+ * top of what noise reaches (it is valid at 101 of 7497 symbols of noise), not the middle between noise and signal.  When
+ * a signal ends in silence sig and nse fall together and the gate stays open until sig < min_p; in noise it shuts.
+ * Absent: soft decisions, a per-tone fading correction, any AFC beyond what f0 is set to, the AMD / DTM / DBM message
+ * protocols above the word, 3G ALE.  It has not met a signal off the air, and until it has, the Golay table above stands
+ * unverified against the standard.  In the model, at (8000, 8) and (39062.5, 32) with white noise, four runs of 16 random
+ * words behind four lead-in words are whole at an Es/N0 (a tone's power times the symbol over N0) of 20, 14, 12, 10 and 8
+ * dB (64 of 64 at both geometries); at 6 dB 27 and 32 of 64 are read, and one word at each is read wrong (in word sync a
+ * half is taken with up to three corrections).  Measured on the integer model on a CPU; the kernel equals it bit for bit.
+ * Calls: as kq_psk_*.  kq_ale_create, kq_ale_set and kq_ale_remove touch no device. */
+typedef struct kq_ale_bank kq_ale_bank;
+typedef struct kq_ale_config {
+  int device;
+  double samprate;           /* Fs: input samples per second; a double, so that 39 062.5 is exact */
+  unsigned block_len;        /* B: samples per frame, 8..256 */
+  unsigned warm;             /* frames after the set in which nothing is read while the levels train (64) */
+  unsigned snr;              /* least sig / nse, in sixteenths (80; noise alone gives about 66) */
+  uint64_t min_p;            /* least sig (65536) */
+  float input_scale;         /* 32767 suits audio of full scale 1 */
+  unsigned max_slots;        /* slots 0 .. max_slots - 1 (limit 16384) */
+  unsigned max_events;       /* arena places per slot between kq_ale_clear_events calls */
+  size_t max_samples;        /* largest nblocks * block_len of one kq_ale_process call */
+  void *stream;              /* hipStream_t, NULL = own stream; kq_bank_stream(bank) puts it beside a receiver bank */
+  unsigned acq_err;          /* most bits corrected per Golay half to accept a word while not in word sync, 0..3 (1) */
+  unsigned lose;             /* failed words in a row that end word sync, 1..15 (2) */
+} kq_ale_config;
+typedef struct kq_ale_params {
+  unsigned source;           /* input row this slot decodes (a receiver bank's channel index) */
+  float f0;                  /* Hz, tone 0 (750) */
+  float df;                  /* Hz between tones (250; negative on an LSB channel) */
+  float baud;                /* 125 */
+} kq_ale_params;
+typedef struct kq_ale_status {
+  uint32_t frames;           /* completed since the slot was set */
+  uint32_t ph;               /* the point taken next: 0 early, 1 centre, 2 late */
+  int32_t t;                 /* 1/256 frame to that point */
+  uint32_t sym;              /* the tone at the last centre */
+  uint32_t nsym;             /* symbols read since the set */
+  uint32_t sync_at;          /* nsym at the word that made word sync */
+  uint32_t wpos;             /* symbols since the last word, while synced */
+  uint32_t synced;
+  uint32_t bad;              /* failed words in a row */
+  uint32_t events;           /* filed since the set, those dropped included */
+  uint32_t dropped;
+  uint32_t reserved;         /* 0 */
+  uint64_t sig, nse;         /* the largest power at the symbols' centres, and 7 / 8 of the mean of the other seven */
+  uint64_t ee, el;           /* the smoothed early and late power */
+  uint64_t pe, pc, oth;      /* best at the last early point, best and oth at the last centre */
+  uint64_t r0, r1, r2;       /* the last 147 bits, the oldest 49 in r0, the first of each in bit 48 */
+  int32_t sum[8][2];         /* SI_t, SQ_t at the last completed frame */
+  int64_t acc[8][2];         /* I and Q of the open frame, per tone */
+} kq_ale_status;
+typedef struct kq_ale_event {
+  uint32_t word;             /* preamble << 21 | three characters of 7 bits */
+  uint32_t flags;            /* bit 0: a half could not be decoded; word holds the data bits as received */
+  uint32_t err_a, err_b;     /* bits corrected per half, 4: more than three wrong */
+  uint32_t split;            /* places of 49 where the three copies differ */
+  uint32_t reserved;         /* 0 */
+  uint64_t end_sample;       /* the end of the frame that read the word's last symbol */
+  uint64_t sig, nse;         /* at that symbol */
+} kq_ale_event;
+typedef struct kq_ale_slot {
+  uint32_t inc[8];           /* the phase increments of the tones */
+  uint32_t tb;               /* the symbol in 1/256 frame */
+  uint32_t W;                /* the window in frames */
+} kq_ale_slot;
+
+kq_ale_bank *kq_ale_create(const kq_ale_config *cfg);
+int kq_ale_destroy(kq_ale_bank *bank);
+/* Put a decoder in `slot` (or replace the one there): a cold start at the next call's first sample, its arena empty.
+ * Touches no device, as kq_psk_set */
+int kq_ale_set(kq_ale_bank *bank, unsigned slot, const kq_ale_params *params);
+/* The slot stops from the next call; its arena stays readable.  Touches no device either */
+int kq_ale_remove(kq_ale_bank *bank, unsigned slot);
+/* Input, status and on_device as in kq_rtty_process (status may be NULL; nothing is written for an empty slot). */
+int kq_ale_process(kq_ale_bank *bank, const void *src, int format, size_t src_stride, size_t row_stride, unsigned block_len,
+                   unsigned nblocks, int on_device, kq_ale_status *status, size_t status_stride);
+/* Events in every slot's arena, counts[max_slots], in one copy; synchronous */
+int kq_ale_pull_counts(kq_ale_bank *bank, uint32_t *counts);
+/* Copies event `index` of `slot`; returns 0, or -1 */
+int kq_ale_pull_event(kq_ale_bank *bank, unsigned slot, unsigned index, kq_ale_event *event);
+/* Empties every arena (on the handle's stream); the status counters, the register and word sync go on */
+int kq_ale_clear_events(kq_ale_bank *bank);
+/* C (at most cap words); returns 1024 */
+int kq_ale_get_table(const kq_ale_bank *bank, int16_t *dst, size_t cap);
+/* inc[8], tb and W of `slot`, without a device; -1 when the slot holds no decoder */
+int kq_ale_get_slot(kq_ale_bank *bank, unsigned slot, kq_ale_slot *out);
+int kq_ale_sync(kq_ale_bank *bank);
+/* Stream index back to 0; every slot restarts cold with its settings at the next call, as if set again */
+int kq_ale_reset(kq_ale_bank *bank);
+
 /* --- rational resampler bank ----------------------------------------------------------------------------------------------
  * Up to 65536 slots, each one row of PCM (mono or stereo) resampled from Fi = in_rate_num / in_rate_den Hz (a receiver
  * bank's samprate and decimate, so 39 062.5 Hz is exact) to Fo = out_rate Hz: kq_afsk_*, RTP PCM and the players are 48 kHz,

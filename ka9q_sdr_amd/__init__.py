@@ -50,5 +50,7 @@ from .psk import PskBank, PskParams, psk_params  # noqa: F401,E402  (psk.STATUS_
 from . import varicode  # noqa: F401,E402
 from .acars import AcarsBank, AcarsParams, acars_params  # noqa: F401,E402  (acars.STATUS_DTYPE: the ACARS decoder's)
 from . import arinc618  # noqa: F401,E402
+from .ale import AleBank, AleParams, ale_params  # noqa: F401,E402  (ale.STATUS_DTYPE: the ALE decoder's)
+from . import ale2g  # noqa: F401,E402
 from .monitor import KQ_MON_F32, KQ_MON_S16BE, MonBank, MonParams, mon_params  # noqa: F401,E402  (monitor.STATUS_DTYPE: the mixer's)
 from .resample import RsmpBank, RsmpParams, rsmp_params  # noqa: F401,E402

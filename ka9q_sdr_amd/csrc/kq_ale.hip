@@ -1,0 +1,556 @@
+// kq_ale.hip -- HF ALE (MIL-STD-188-141 Appendix A, 8-FSK) decoder bank: the audio of USB channels -> 24-bit ALE words, as
+// events (word, flags, err_a, err_b, split, end, sig, nse) on gfx950.
+//
+// Per slot (include/ka9q_hip.h, kq_ale_*): quantise as kq_cw_*, correlate every frame of B samples against eight tones from
+// the 1024-entry cosine table with phases that are functions of the sample index alone, slide a window one symbol long (W
+// frames) over the frames' reduced sums, take the largest of the eight powers, and step the symbol clock once per
+// completed frame; at every third point of the clock a symbol is read: the levels, the gate, the 147-bit register, and --
+// at every symbol while there is no word sync, at every 49th while there is -- the word attempt: majority vote over the
+// three copies, de-interleave, Golay (24,12) by two 4096-entry tables.  All exact integers after the quantiser.  State on
+// the device, per slot: one kq_ale_status record, the reduced sums of the last 31 frames, and the arena of events; per bank
+// the cosine table and the two Golay tables.  The signal format is written down from memory (the header says what is and
+// what is not verified); golay_parity() below is the single statement of the code, as PARITY is in ka9q_sdr_amd/ale2g.py.
+//
+// k_ale   k_psk's mapping: one wave per slot, four slots to a workgroup.  The call's samples go through LDS once, a piece
+//         of 64 / L frames at a time (kq::tonecorr::correlate_piece<8>).  The frame leaders write the sixteen reduced sums
+//         to LDS behind the 31 carried frames of history (W <= 32); the window sums are spread over the wave, a (frame,
+//         tone, I / Q) to a lane at a time -- rows of kRow words with kRow = 2 mod 32, so that the sixteen series of two
+//         neighbouring frames fall into 32 banks -- and lane f then squares frame f's eight pairs and keeps the largest
+//         power, its tone and the others' sum.  Lane 0 walks the piece's frames in order through the clock: most frames
+//         cost it a subtraction and a compare, and it reads LDS at the points only.  Both Golay tables sit in LDS (16 KiB),
+//         because a slot without word sync looks into them at every symbol and the walk is serial.  B and the frame grid
+//         are the bank's, so every wave of a workgroup has the same pieces and the barriers are uniform.  The carried
+//         record and the history are read once and written once per call.  No atomics, no scratch.
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <mutex>
+#include <vector>
+
+#include "ka9q_hip.h"
+#include "kq_device.hpp"
+#include "kq_host.hpp"
+#include "kq_slots.hpp"
+#include "kq_tonecorr.hpp"
+
+namespace {
+
+using kq::tonecorr::kTable;
+constexpr unsigned kMaxSlots = 16384;
+constexpr int kThreads = 256, kWaves = kThreads / 64;
+constexpr int kTile = 3200;                     // samples a wave keeps in LDS: 64 frames of B = 48 at stride 50
+constexpr int kHist = 31;                       // frames of history a slot carries: W - 1 at the most
+constexpr int kRow = 98;                        // a wave's reduced sums of one kind: the history, a piece's 64 frames and pad
+constexpr int kWin = 66;                        // a wave's window sums of one kind over a piece
+constexpr int NT = 8, NS = 2 * NT;              // tones; series (I and Q of each)
+constexpr int kGolay = 4096;
+constexpr unsigned long long kM49 = (1ull << 49) - 1;
+
+// the code: the 12 check bits of 12 data bits -- the remainder of data x^11 by g(x) = 0xC75, then the overall parity bit
+unsigned golay_parity(unsigned d) {
+  unsigned r = d << 11;
+  for (int i = 22; i >= 11; i--)
+    if (r >> i & 1) r ^= 0xC75u << (i - 11);
+  return r << 1 | ((unsigned)(__builtin_popcount(d) + __builtin_popcount(r)) & 1u);
+}
+
+// [0, 4096) the parity table; [4096, 8192) by syndrome: weight << 12 | the data bits of the one error pattern of weight <= 3
+// with that syndrome, 4 << 12 where there is none.  Made once, at the first kq_ale_create.
+std::vector<unsigned short> const &golay_tables() {
+  static std::vector<unsigned short> const tables = [] {
+    std::vector<unsigned short> t((size_t)2 * kGolay, (unsigned short)(4u << 12));
+    for (unsigned d = 0; d < kGolay; d++) t[d] = (unsigned short)golay_parity(d);
+    t[kGolay] = 0;
+    for (int i = 0; i < 24; i++)
+      for (int j = i; j < 24; j++)
+        for (int k = j; k < 24; k++) {  // i == j or j == k give the lighter patterns
+          unsigned const e = 1u << i | 1u << j | 1u << k;
+          t[kGolay + (t[e >> 12] ^ (e & 0xFFFu))] = (unsigned short)((unsigned)__builtin_popcount(e) << 12 | e >> 12);
+        }
+    return t;
+  }();
+  return tables;
+}
+
+struct AleGeom {
+  kq::tonecorr::FrameGrid grid;
+  unsigned warm, snr, acq_err, lose;
+  unsigned long long min_p;
+  int max_events;
+};
+
+struct AlePar {  // per slot, written by the host when a call finds the slot set anew
+  int active;
+  unsigned source;
+  unsigned inc[NT];
+  int tb, W;
+};
+
+struct AleHist {
+  int v[NS][kHist];              // a, b of tone t at [2 t], [2 t + 1]; [kHist - 1] is the last completed frame
+};
+
+struct CallArgs {
+  AleGeom g;
+  const AlePar *par;
+  const int *list;               // active slots, ascending
+  const int *rowmap;             // per list entry: the row of in.src (host input, staged) or null (par.source)
+  const short *table;            // [1024]
+  const unsigned short *golay;   // [2][4096]
+  kq_ale_status *state;          // [S]
+  AleHist *hist;                 // [S]
+  kq_ale_event *ev;              // [S][max_events]
+  unsigned *nev;                 // [S]
+  int nlist;
+  int L;                         // lanes to a frame, a power of two <= 64
+  int64_t n0, n1;                // the call's samples
+  kq::PcmIn in;
+  // output
+  kq_ale_status *st;
+  size_t sstride;
+};
+
+__device__ __forceinline__ unsigned sat_inc(unsigned v) { return v == 0xFFFFFFFFu ? v : v + 1; }
+
+// v += (x - v) >> 4 and the like: both below 2^63, so the difference fits
+__device__ __forceinline__ void smooth(uint64_t &v, uint64_t x, int sh) {
+  v = (uint64_t)((long long)v + (((long long)x - (long long)v) >> sh));
+}
+
+// bits 0, 2, .. 46 of x, packed
+__device__ __forceinline__ unsigned even_bits(unsigned long long x) {
+  x &= 0x5555555555555555ull;
+  x = (x | x >> 1) & 0x3333333333333333ull;
+  x = (x | x >> 2) & 0x0F0F0F0F0F0F0F0Full;
+  x = (x | x >> 4) & 0x00FF00FF00FF00FFull;
+  x = (x | x >> 8) & 0x0000FFFF0000FFFFull;
+  x = (x | x >> 16) & 0x00000000FFFFFFFFull;
+  return (unsigned)x;
+}
+
+__device__ __forceinline__ bool in_set(unsigned c) {
+  return (c >= '0' && c <= '9') || (c >= '@' && c <= 'Z') || c == '?';
+}
+
+__device__ __forceinline__ void file(AleGeom const &g, kq_ale_status &s, unsigned word, unsigned flags, unsigned ea, unsigned eb,
+                                     unsigned split, unsigned long long k, kq_ale_event *ev, unsigned &nev) {
+  s.events = sat_inc(s.events);
+  if (nev >= (unsigned)g.max_events) {
+    s.dropped = sat_inc(s.dropped);
+    return;
+  }
+  kq_ale_event r;
+  r.word = word;
+  r.flags = flags;
+  r.err_a = ea;
+  r.err_b = eb;
+  r.split = split;
+  r.reserved = 0;
+  r.end_sample = (k + 1) * (unsigned long long)g.grid.B;
+  r.sig = s.sig;
+  r.nse = s.nse;
+  ev[nev++] = r;
+}
+
+// the header's steps 1 to 5: the late point of a symbol at frame k, with the late power pl
+__device__ __forceinline__ void symbol(AleGeom const &g, AlePar const &par, kq_ale_status &s, unsigned long long pl,
+                                       unsigned long long k, const unsigned short *gol, kq_ale_event *ev, unsigned &nev) {
+  // 1 timing
+  smooth(s.ee, s.pe, 3);
+  smooth(s.el, pl, 3);
+  unsigned long long const m = s.ee > s.el ? s.ee : s.el;
+  int adj = 0;
+  if (s.ee > s.el && s.ee - s.el > (m >> 3)) adj = -(par.tb >> 5);
+  else if (s.el > s.ee && s.el - s.ee > (m >> 3)) adj = par.tb >> 5;
+  s.t += par.tb - 2 * (par.tb >> 2) + adj;
+  // 2 levels and gate: 16 sig >= snr nse in 128 bits
+  smooth(s.sig, s.pc, 4);
+  smooth(s.nse, s.oth, 4);
+  unsigned long long const lh = s.sig >> 60, ll = s.sig << 4, rh = __umul64hi(s.nse, (unsigned long long)g.snr),
+                           rl = s.nse * (unsigned long long)g.snr;
+  bool const valid = s.frames >= g.warm && s.sig >= g.min_p && (lh > rh || (lh == rh && ll >= rl));
+  // 3 register (the Gray map 0 1 3 2 6 7 5 4, a nibble to a tone)
+  s.r0 = (s.r0 << 3 | s.r1 >> 46) & kM49;
+  s.r1 = (s.r1 << 3 | s.r2 >> 46) & kM49;
+  s.r2 = (s.r2 << 3 | (unsigned long long)((0x45762310u >> (4 * s.sym)) & 7u)) & kM49;
+  s.nsym += 1;
+  if (s.synced) s.wpos += 1;
+  // 4 gate
+  if (!valid) {
+    s.synced = s.bad = s.wpos = 0;
+    return;
+  }
+  // 5 word attempt
+  if (s.synced && s.wpos < 49) return;
+  unsigned long long const maj = (s.r0 & s.r1) | (s.r0 & s.r2) | (s.r1 & s.r2);
+  if (!s.synced && (maj & 1)) return;  // (the stuff bit: nothing else of the attempt is kept)
+  unsigned const split = (unsigned)__popcll((s.r0 ^ s.r1) | (s.r0 ^ s.r2));
+  unsigned const A = even_bits(maj >> 2), Bh = even_bits(maj >> 1) ^ 0xFFFu;
+  unsigned const xa = gol[kGolay + (gol[A >> 12] ^ (A & 0xFFFu))], xb = gol[kGolay + (gol[Bh >> 12] ^ (Bh & 0xFFFu))];
+  unsigned const ea = xa >> 12, eb = xb >> 12;
+  unsigned const word = ((A >> 12) ^ (xa & 0xFFFu)) << 12 | ((Bh >> 12) ^ (xb & 0xFFFu));
+  if (!s.synced) {
+    bool const chars = word >> 21 == 6u || (in_set(word >> 14 & 0x7Fu) && in_set(word >> 7 & 0x7Fu) && in_set(word & 0x7Fu));
+    if (ea <= g.acq_err && eb <= g.acq_err && chars) {
+      s.synced = 1;
+      s.sync_at = s.nsym;
+      s.wpos = s.bad = 0;
+      file(g, s, word, 0, ea, eb, split, k, ev, nev);
+    }
+    return;
+  }
+  s.wpos = 0;
+  if (ea < 4 && eb < 4) {
+    s.bad = 0;
+    file(g, s, word, 0, ea, eb, split, k, ev, nev);
+  } else {
+    file(g, s, word, 1, ea, eb, split, k, ev, nev);
+    s.bad += 1;
+    if (s.bad >= g.lose) s.synced = s.bad = 0;
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void k_ale(CallArgs c) {
+  __shared__ int CS[kTable];                       // C[j] in the low half, C[(j - 256) & 1023] in the high
+  __shared__ unsigned short GL[2 * kGolay];        // the parity table, then the error patterns by syndrome
+  __shared__ __align__(16) unsigned char raw[kWaves][2 * kTile];  // a wave's samples; once they are correlated, its window sums
+  __shared__ int A[kWaves][NS][kRow];              // reduced sums: [0, kHist) the frames before the piece, then the piece's
+  __shared__ unsigned long long Pb[kWaves][64];    // the largest of the eight powers at every frame of the piece,
+  __shared__ unsigned long long Ob[kWaves][64];    // the other seven, each >> 3, summed,
+  __shared__ int Yb[kWaves][64];                   // and the tone
+  __shared__ long long carry[kWaves][NS];
+  __shared__ int lastsum[kWaves][NS];
+  AleGeom const &g = c.g;
+  int const tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = (int)blockIdx.x * kWaves + wave;
+  bool const live = li < c.nlist;
+  int const slot = live ? c.list[li] : 0;
+  kq::tonecorr::load_packed_table(CS, c.table, tid, kThreads);
+  for (int i = tid; i < kGolay; i += kThreads)     // two entries to a word
+    reinterpret_cast<unsigned *>(GL)[i] = reinterpret_cast<const unsigned *>(c.golay)[i];
+  AlePar const par = c.par[slot];
+  size_t const row = live && c.rowmap ? (size_t)c.rowmap[li] : (size_t)par.source;
+  int const B = g.grid.B, L = c.L, F = 64 / L, f = lane / L, p = lane & (L - 1);
+  int const W = live ? min(max(par.W, 1), kHist + 1) : 1;  // (the host keeps it in 8..32)
+  int const q = par.tb >> 2;
+  short *const qs = reinterpret_cast<short *>(raw[wave]);
+  int(*const Wd)[kWin] = reinterpret_cast<int(*)[kWin]>(raw[wave]);  // [NS][kWin]: the window sums at every frame of the piece
+  static_assert(NS * kWin * sizeof(int) <= 2 * kTile, "the window sums fit where the samples were");
+  // carried: lane 0 holds the record, the open frame's sums in it; the history goes to the front of A
+  kq_ale_status s{};
+  unsigned nev = 0;
+  kq_ale_event *ev = c.ev + (size_t)slot * g.max_events;
+  long long cy[NS];
+#pragma unroll
+  for (int t = 0; t < NS; t++) cy[t] = 0;
+  if (live && lane == 0) {
+    s = c.state[slot];
+    nev = c.nev[slot];
+#pragma unroll
+    for (int t = 0; t < NS; t++) {
+      cy[t] = s.acc[t >> 1][t & 1];
+      lastsum[wave][t] = s.sum[t >> 1][t & 1];
+    }
+  }
+  if (lane < kHist)
+    for (int t = 0; t < NS; t++) A[wave][t][lane] = live ? c.hist[slot].v[t][lane] : 0;
+  int64_t n = c.n0, k0 = c.n0 / B;
+  while (n < c.n1) {  // one piece: the frames k0 .. k0 + F - 1, from n to their end or the call's; x counts from k0 B
+    int64_t const pe = (k0 + F) * (int64_t)B, e = pe < c.n1 ? pe : c.n1;
+    int const x0 = (int)(n - k0 * B), x1 = x0 + (int)(e - n);  // x1 <= F B
+    long long sm[NS];  // (its first barrier: the piece before is done with raw, A, Pb, Ob, Yb and carry, and A is loaded)
+    kq::tonecorr::correlate_piece<NT>(g.grid, c.in, row, live, lane, L, c.n0, n, k0, x0, x1, qs, CS, par.inc, sm, cy);
+    int const done = (int)__umulhi((unsigned)x1, g.grid.magic);  // frames of the piece that are complete
+    if (p == 0 && f * B < x1) {
+      if (f < done) {
+#pragma unroll
+        for (int t = 0; t < NS; t++) A[wave][t][kHist + f] = (int)(sm[t] >> 12);
+      } else {  // the call ends inside frame f
+#pragma unroll
+        for (int t = 0; t < NS; t++) carry[wave][t] = sm[t];
+      }
+    }
+    __syncthreads();
+    for (int it = lane; it < done * NS; it += 64) {  // the window of series t that ends at frame fr: W entries, the last at kHist + fr
+      int const fr = it >> 4, t = it & (NS - 1);
+      int w = 0;
+      for (int i = 0; i < W; i++) w += A[wave][t][kHist + fr - i];
+      Wd[t][fr] = w;
+    }
+    __syncthreads();
+    int keep[NS];
+    if (lane < kHist)  // what the next piece finds in front: the last kHist frames
+#pragma unroll
+      for (int t = 0; t < NS; t++) keep[t] = A[wave][t][done + lane];
+    if (lane < done) {
+      unsigned long long best = 0, tot = 0;
+      int sym = 0;
+#pragma unroll
+      for (int t = 0; t < NT; t++) {
+        long long const wi = Wd[2 * t][lane], wq = Wd[2 * t + 1][lane];
+        unsigned long long const P = (unsigned long long)(wi * wi) + (unsigned long long)(wq * wq);
+        tot += P >> 3;
+        if (P > best) {  // ties to the lowest tone
+          best = P;
+          sym = t;
+        }
+      }
+      Pb[wave][lane] = best;
+      Ob[wave][lane] = tot - (best >> 3);
+      Yb[wave][lane] = sym;
+      if (lane == done - 1)
+#pragma unroll
+        for (int t = 0; t < NS; t++) lastsum[wave][t] = Wd[t][lane];
+    }
+    __syncthreads();
+    if (lane < kHist)
+#pragma unroll
+      for (int t = 0; t < NS; t++) A[wave][t][lane] = keep[t];
+    if (live && lane == 0) {
+      for (int i = 0; i < done; i++) {  // the header's step, frame k0 + i
+        s.frames = sat_inc(s.frames);
+        s.t -= 256;
+        if (s.t >= 128) continue;
+        unsigned long long const P = Pb[wave][i];
+        if (s.ph == 0) {
+          s.pe = P;
+          s.t += q;
+          s.ph = 1;
+        } else if (s.ph == 1) {
+          s.sym = (unsigned)Yb[wave][i];
+          s.pc = P;
+          s.oth = Ob[wave][i];
+          s.t += q;
+          s.ph = 2;
+        } else {
+          s.ph = 0;
+          symbol(g, par, s, P, (unsigned long long)(k0 + i), GL, ev, nev);
+        }
+      }
+      if (done * B < x1)
+#pragma unroll
+        for (int t = 0; t < NS; t++) cy[t] = carry[wave][t];
+    }
+    n = e;
+    k0 += F;
+  }
+  __syncthreads();
+  if (live && lane < kHist)
+    for (int t = 0; t < NS; t++) c.hist[slot].v[t][lane] = A[wave][t][lane];
+  if (live && lane == 0) {
+#pragma unroll
+    for (int t = 0; t < NS; t++) {
+      s.acc[t >> 1][t & 1] = cy[t];
+      s.sum[t >> 1][t & 1] = lastsum[wave][t];
+    }
+    c.state[slot] = s;
+    c.nev[slot] = nev;
+    if (c.st) c.st[(size_t)slot * c.sstride] = s;
+  }
+}
+
+}  // namespace
+
+struct kq_ale_bank : kq::HostSide {
+  static constexpr bool kDeferred = true;
+  kq_ale_config cfg;
+  std::mutex mu;
+  bool dev_ready = false;
+  AleGeom g{};
+  int Lmin = 1;                  // the least lanes to a frame whose piece fits kTile
+  uint64_t n_cur = 0;
+  kq::DeferredSlots<AlePar> def;
+  struct Dev {  // kq::lazy_device
+    kq::SlotTable<AlePar> slots;
+    short *table = nullptr;
+    unsigned short *golay = nullptr;
+    kq_ale_status *state = nullptr;
+    AleHist *hist = nullptr;
+    kq::EventArena<kq_ale_event> arena;
+    kq_ale_status *st = nullptr;         // host-memory calls
+  } d;
+
+  int to_device();
+};
+
+namespace {
+
+int make_device(kq_ale_bank *b) {
+  auto &d = b->d;
+  if (b->open_stream(b->cfg.stream)) return -1;
+  size_t const S = b->cfg.max_slots;
+  if (d.slots.alloc(*b, S) || kq::tonecorr::alloc_table(*b, &d.table) || b->alloc(&d.golay, (size_t)2 * kGolay) ||
+      b->alloc(&d.state, S, true) || b->alloc(&d.hist, S, true) || d.arena.alloc(*b, S, b->cfg.max_events))
+    return -1;
+  KQ_TRY(hipMemcpyAsync(d.golay, golay_tables().data(), 2 * kGolay * sizeof(unsigned short), hipMemcpyHostToDevice, b->stream));
+  KQ_TRY(hipStreamSynchronize(b->stream));
+  return 0;
+}
+
+}  // namespace
+
+// kq::DeferredSlots::flush; the record and the history of a slot that is set start cold (all zero: the header's state at
+// the set) and its arena empty
+int kq_ale_bank::to_device() {
+  return def.flush(this, make_device, [this](size_t s0, size_t n) {
+    KQ_TRY(hipMemsetAsync(d.state + s0, 0, n * sizeof(kq_ale_status), stream));
+    KQ_TRY(hipMemsetAsync(d.hist + s0, 0, n * sizeof(AleHist), stream));
+    return d.arena.clear(*this, s0, n);
+  });
+}
+
+extern "C" {
+
+kq_ale_bank *kq_ale_create(const kq_ale_config *cfg) {
+  const char *fn = "kq_ale_create";
+  if (!cfg) {
+    kq_internal_set_error("%s: null config", fn);
+    return nullptr;
+  }
+  if (!kq::samprate_ok(fn, cfg->samprate) || !kq::field_in_range(fn, "block_len", cfg->block_len, 8, 256) ||
+      !kq::field_in_range(fn, "warm", cfg->warm, 0, 65535) || !kq::field_in_range(fn, "snr", cfg->snr, 16, 4095) ||
+      !kq::min_p_ok(fn, cfg->min_p) || !kq::input_scale_ok(fn, cfg->input_scale) ||
+      !kq::field_in_range(fn, "acq_err", cfg->acq_err, 0, 3) || !kq::field_in_range(fn, "lose", cfg->lose, 1, 15) ||
+      !kq::field_in_range(fn, "max_slots", cfg->max_slots, 1, kMaxSlots) ||
+      !kq::field_in_range(fn, "max_events", cfg->max_events, 1, 4096) || !kq::max_samples_ok(fn, cfg->max_samples))
+    return nullptr;
+  (void)kq::tonecorr::cos_table();  // the tables exist from here on
+  (void)golay_tables();
+  kq_ale_bank *b = new kq_ale_bank;
+  b->cfg = *cfg;
+  b->def.init(cfg->max_slots);
+  AleGeom &g = b->g;
+  g.grid = kq::tonecorr::frame_grid(cfg->block_len);
+  g.warm = cfg->warm;
+  g.snr = cfg->snr;
+  g.acq_err = cfg->acq_err;
+  g.lose = cfg->lose;
+  g.min_p = cfg->min_p;
+  g.max_events = (int)cfg->max_events;
+  b->Lmin = kq::tonecorr::least_lanes(g.grid, kTile);  // 8 at the most: Bs <= 258
+  return b;
+}
+
+int kq_ale_destroy(kq_ale_bank *b) { return kq::destroy_bank(b, "kq_ale_destroy"); }
+
+int kq_ale_set(kq_ale_bank *b, unsigned slot, const kq_ale_params *p) {
+  const char *fn = "kq_ale_set";
+  if (!kq::set_args_ok(fn, slot, p, kMaxSlots)) return -1;
+  if (!b) {
+    kq_internal_set_error("%s: null bank", fn);
+    return -1;
+  }
+  std::lock_guard<std::mutex> lk(b->mu);
+  if (!kq::slot_in_bank(fn, slot, b->cfg.max_slots)) return -1;
+  double const Fs = b->cfg.samprate, f0 = p->f0, df = p->df, baud = p->baud;
+  if (!std::isfinite(f0) || !std::isfinite(df) || df == 0) {
+    kq_internal_set_error("%s: f0 %g and df %g must be finite and df not 0", fn, f0, df);
+    return -1;
+  }
+  for (int t = 0; t < NT; t += NT - 1) {  // the outer two bound the rest
+    double const f = f0 + t * df;
+    if (!(f > 0) || !(f < 0.5 * Fs)) {
+      kq_internal_set_error("%s: tone %d at %g (f0 %g, df %g) must be above 0 and below samprate / 2", fn, t, f, f0, df);
+      return -1;
+    }
+  }
+  if (!(baud > 0) || !std::isfinite(baud)) {
+    kq_internal_set_error("%s: baud %g must be positive and finite", fn, baud);
+    return -1;
+  }
+  double const tb = std::rint(256.0 * Fs / ((double)b->cfg.block_len * baud));
+  if (!(tb >= 2048.0) || !(tb <= 8192.0)) {
+    kq_internal_set_error("%s: baud %g makes tb %.10g, a symbol of %g frames of %u samples, outside 2048..8192 (8 to 32 frames)",
+                          fn, baud, tb, tb / 256.0, b->cfg.block_len);
+    return -1;
+  }
+  AlePar np{};
+  np.active = 1;
+  np.source = p->source;
+  for (int t = 0; t < NT; t++) np.inc[t] = (unsigned)std::llrint((f0 + t * df) * 4294967296.0 / Fs);
+  np.tb = (int)tb;
+  np.W = (np.tb + 128) >> 8;
+  b->def.set(slot, np);
+  return 0;
+}
+
+int kq_ale_remove(kq_ale_bank *b, unsigned slot) { return kq::deferred_remove(b, slot, "kq_ale_remove"); }
+
+int kq_ale_process(kq_ale_bank *b, const void *src, int format, size_t src_stride, size_t row_stride, unsigned block_len,
+                   unsigned nblocks, int on_device, kq_ale_status *status, size_t status_stride) {
+  const char *fn = "kq_ale_process";
+  if (!b) {
+    kq_internal_set_error("%s: null bank", fn);
+    return -1;
+  }
+  std::lock_guard<std::mutex> lk(b->mu);
+  if (!kq::call_args_ok(fn, format, b->cfg.max_samples, row_stride, block_len, nblocks, status, status_stride)) return -1;
+  size_t const ncall = (size_t)block_len * nblocks;
+  std::optional<kq::DeviceScope> scope;
+  kq::CallWork const work = kq::begin_call(b, fn, ncall, src, scope);
+  if (work != kq::CALL_RUN) return work == kq::CALL_FAILED ? -1 : 0;
+  auto &d = b->d;
+  size_t const nlist = d.slots.all.size();
+  CallArgs a{};
+  a.g = b->g;
+  a.par = d.slots.d_par;
+  a.list = d.slots.d_list;
+  a.table = d.table;
+  a.golay = d.golay;
+  a.state = d.state;
+  a.hist = d.hist;
+  a.ev = d.arena.ev;
+  a.nev = d.arena.n;
+  a.nlist = (int)nlist;
+  a.n0 = (int64_t)b->n_cur;
+  a.n1 = a.n0 + (int64_t)ncall;
+  a.L = kq::tonecorr::lanes_for_call(b->g.grid, b->Lmin, ncall);
+  if (kq::bind_pcm(&a.in, &a.rowmap, *b, d.slots, b->cfg.max_samples, b->cfg.input_scale, src, format, src_stride, row_stride, block_len,
+                   nblocks, on_device) ||
+      kq::bind_status(b, on_device, status, status_stride, &a.st, &a.sstride))
+    return -1;
+  hipLaunchKernelGGL(k_ale, dim3((unsigned)((nlist + kWaves - 1) / kWaves)), dim3(kThreads), 0, b->stream, a);
+  KQ_TRY(hipGetLastError());
+  b->n_cur += ncall;
+  return on_device ? 0 : kq::end_host_call(b, status, status_stride, nullptr);
+}
+
+int kq_ale_pull_counts(kq_ale_bank *b, uint32_t *counts) { return kq::pull_counts(b, "kq_ale_pull_counts", counts); }
+
+int kq_ale_pull_event(kq_ale_bank *b, unsigned slot, unsigned index, kq_ale_event *event) {
+  return kq::pull_event(b, "kq_ale_pull_event", slot, index, event);
+}
+
+int kq_ale_clear_events(kq_ale_bank *b) { return kq::clear_arena(b, "kq_ale_clear_events"); }
+
+int kq_ale_get_table(const kq_ale_bank *b, int16_t *dst, size_t cap) {
+  return kq::tonecorr::get_table(b, "kq_ale_get_table", dst, cap);
+}
+
+int kq_ale_get_slot(kq_ale_bank *b, unsigned slot, kq_ale_slot *out) {
+  if (!b) {
+    kq_internal_set_error("kq_ale_get_slot: null bank");
+    return -1;
+  }
+  if (!out) {
+    kq_internal_set_error("kq_ale_get_slot: null out");
+    return -1;
+  }
+  std::lock_guard<std::mutex> lk(b->mu);
+  if (!b->def.is_set(slot)) {
+    kq_internal_set_error("kq_ale_get_slot: slot %u holds no decoder", slot);
+    return -1;
+  }
+  AlePar const &w = b->def.want[slot];
+  for (int t = 0; t < NT; t++) out->inc[t] = w.inc[t];
+  out->tb = (uint32_t)w.tb;
+  out->W = (uint32_t)w.W;
+  return 0;
+}
+
+int kq_ale_sync(kq_ale_bank *b) { return kq::sync_bank(b, "kq_ale_sync"); }
+
+int kq_ale_reset(kq_ale_bank *b) { return kq::deferred_reset(b, "kq_ale_reset"); }
+
+}  // extern "C"

@@ -10,7 +10,7 @@
 //                     host-memory call (bind_status, end_host_call), the checks the configs share (field_in_range, ...)
 //   event banks       kq::EventArena: the [S][max_events] records and [S] counts, with the bodies of pull_counts,
 //                     pull_event and clear (kq_fsk and kq_pag keep their frame and page infos in one and pull them themselves)
-//   deferred banks    (kq_cw, kq_rtty) kq::DeferredSlots: set and remove touch no device; the next entry point that needs
+//   deferred banks    (kq_cw, kq_rtty, kq_psk, kq_ale) kq::DeferredSlots: set and remove touch no device; the next entry point that needs
 //                     the device brings the changed slots there, a run at a time (flush)
 //
 // A bank here is a struct on kq::HostSide with `cfg` (device, max_slots, max_samples), `mu`, `dev_ready`, `n_cur` (PCM

@@ -1,13 +1,13 @@
 // kq_tonecorr.hpp -- what the banks that correlate PCM against tones from a cosine table share (kq_tone: DTMF and selective
-// calling; kq_cw: Morse; kq_rtty: start-stop FSK; kq_psk: PSK31), and the quantiser that the FSK front end (kq_fskfront.hpp) shares with them.
+// calling; kq_cw: Morse; kq_rtty: start-stop FSK; kq_psk: PSK31; kq_ale: ALE 8-FSK), and the quantiser that the FSK front end (kq_fskfront.hpp) shares with them.
 //
 //   load_q           the header's quantiser (include/ka9q_hip.h, kq_fsk_*): sample i of a call, f32 or s16be, over kq::PcmIn
 //   cos_table        C[j] = rint(32767 cos(2 pi j / 1024)), one instance for the library; get_table, the body of
 //                    kq_*_get_table; load_packed_table, cosine and sine of an entry in one LDS word
-//   FrameGrid        kq_cw, kq_rtty and kq_psk: frames of B samples on a grid that starts at sample 0 of the stream, each at a stride
+//   FrameGrid        kq_cw, kq_rtty, kq_psk and kq_ale: frames of B samples on a grid that starts at sample 0 of the stream, each at a stride
 //                    Bs >= B in LDS with Bs / 2 odd, so that lanes reading sample i of 32 consecutive frames hit 32 banks; the
 //                    choice of L, the lanes to a frame, per bank (least_lanes) and per call (lanes_for_call)
-//   correlate_piece  the front half of k_cw's, k_rtty's and k_psk's piece loop: 64 / L frames through LDS, NT tones each
+//   correlate_piece  the front half of k_cw's, k_rtty's, k_psk's and k_ale's piece loop: 64 / L frames through LDS, NT tones each
 //
 // What a bank does with the sums -- its tracker, its history, its events -- stays with the bank, and so does k_tone, which
 // has another shape (a workgroup per slot, many tones).
