@@ -37,6 +37,8 @@
 namespace {
 
 using kq::tonecorr::kTable;
+using kq::tonecorr::mag;
+using kq::tonecorr::sat_inc;
 constexpr unsigned kMaxSlots = 4096;
 constexpr int kThreads = 256;
 constexpr int kPat = 40;                        // preamble bits
@@ -91,10 +93,6 @@ __host__ __device__ inline int lds_fixed_words() { return kTable / 2 + kMaxTaps 
 __host__ __device__ inline int lds_wave_words(AcGeom const &g) {
   return (g.piece + g.FL - 1) + (g.HA + g.piece) + (2 * g.w + g.piece) + g.piece / 64;
 }
-
-__device__ __forceinline__ unsigned sat_inc(unsigned v) { return v == 0xFFFFFFFFu ? v : v + 1; }
-
-__device__ __forceinline__ long long mag(long long v) { return v < 0 ? -v : v; }
 
 // (r + j i) (-j)^m
 __device__ __forceinline__ void turn(int r, int i, unsigned m, int &xr, int &xi) {

@@ -11,37 +11,32 @@
 // the cosine table and the two Golay tables.  The signal format is written down from memory (the header says what is and
 // what is not verified); golay_parity() below is the single statement of the code, as PARITY is in ka9q_sdr_amd/ale2g.py.
 //
-// k_ale   k_psk's mapping: one wave per slot, four slots to a workgroup.  The call's samples go through LDS once, a piece
-//         of 64 / L frames at a time (kq::tonecorr::correlate_piece<8>).  The frame leaders write the sixteen reduced sums
-//         to LDS behind the 31 carried frames of history (W <= 32); the window sums are spread over the wave, a (frame,
-//         tone, I / Q) to a lane at a time -- rows of kRow words with kRow = 2 mod 32, so that the sixteen series of two
-//         neighbouring frames fall into 32 banks -- and lane f then squares frame f's eight pairs and keeps the largest
-//         power, its tone and the others' sum.  Lane 0 walks the piece's frames in order through the clock: most frames
-//         cost it a subtraction and a compare, and it reads LDS at the points only.  Both Golay tables sit in LDS (16 KiB),
-//         because a slot without word sync looks into them at every symbol and the walk is serial.  B and the frame grid
-//         are the bank's, so every wave of a workgroup has the same pieces and the barriers are uniform.  The carried
-//         record and the history are read once and written once per call.  No atomics, no scratch.
+// k_ale   a frame-grid kernel with a window and a symbol clock (kq_tonecorr.hpp describes the mapping): eight tones,
+//         sixteen series.  The window sums are spread over the wave, a (frame, tone, I / Q) to a lane at a time -- rows of
+//         kRow words with kRow = 2 mod 32, so that the sixteen series of two neighbouring frames fall into 32 banks -- and
+//         lane f then squares frame f's eight pairs and keeps the largest power, its tone and the others' sum.  Lane 0
+//         walks the piece's frames in order through the clock: it reads LDS at the points only.  Both Golay tables sit in
+//         LDS (16 KiB), because a slot without word sync looks into them at every symbol and the walk is serial.
 #include <hip/hip_runtime.h>
-#include <algorithm>
 #include <cmath>
 #include <cstdint>
-#include <cstring>
 #include <mutex>
 #include <vector>
 
 #include "ka9q_hip.h"
-#include "kq_device.hpp"
-#include "kq_host.hpp"
-#include "kq_slots.hpp"
 #include "kq_tonecorr.hpp"
+
+namespace tc = kq::tonecorr;
 
 namespace {
 
-using kq::tonecorr::kTable;
+using tc::kHist;
+using tc::kTable;
+using tc::sat_inc;
+using tc::smooth;
 constexpr unsigned kMaxSlots = 16384;
 constexpr int kThreads = 256, kWaves = kThreads / 64;
 constexpr int kTile = 3200;                     // samples a wave keeps in LDS: 64 frames of B = 48 at stride 50
-constexpr int kHist = 31;                       // frames of history a slot carries: W - 1 at the most
 constexpr int kRow = 98;                        // a wave's reduced sums of one kind: the history, a piece's 64 frames and pad
 constexpr int kWin = 66;                        // a wave's window sums of one kind over a piece
 constexpr int NT = 8, NS = 2 * NT;              // tones; series (I and Q of each)
@@ -88,36 +83,29 @@ struct AlePar {  // per slot, written by the host when a call finds the slot set
   int tb, W;
 };
 
-struct AleHist {
-  int v[NS][kHist];              // a, b of tone t at [2 t], [2 t + 1]; [kHist - 1] is the last completed frame
+struct AleTables {  // the bank's own, beside the cosine table
+  unsigned short *golay = nullptr;  // [2][4096]
+  int make(kq::HostSide &h) {       // (queued: the caller waits)
+    if (h.alloc(&golay, (size_t)2 * kGolay)) return -1;
+    KQ_TRY(hipMemcpyAsync(golay, golay_tables().data(), 2 * kGolay * sizeof(unsigned short), hipMemcpyHostToDevice, h.stream));
+    return 0;
+  }
 };
 
-struct CallArgs {
-  AleGeom g;
-  const AlePar *par;
-  const int *list;               // active slots, ascending
-  const int *rowmap;             // per list entry: the row of in.src (host input, staged) or null (par.source)
-  const short *table;            // [1024]
-  const unsigned short *golay;   // [2][4096]
-  kq_ale_status *state;          // [S]
-  AleHist *hist;                 // [S]
-  kq_ale_event *ev;              // [S][max_events]
-  unsigned *nev;                 // [S]
-  int nlist;
-  int L;                         // lanes to a frame, a power of two <= 64
-  int64_t n0, n1;                // the call's samples
-  kq::PcmIn in;
-  // output
-  kq_ale_status *st;
-  size_t sstride;
+struct AleKind {
+  using Config = kq_ale_config;
+  using Geom = AleGeom;
+  using Par = AlePar;
+  using Status = kq_ale_status;
+  using Event = kq_ale_event;
+  using Hist = tc::FrameHist<NS>;  // a, b of tone t at [2 t], [2 t + 1]
+  using Tables = AleTables;
+  static constexpr bool kZeroCold = true;
 };
 
-__device__ __forceinline__ unsigned sat_inc(unsigned v) { return v == 0xFFFFFFFFu ? v : v + 1; }
-
-// v += (x - v) >> 4 and the like: both below 2^63, so the difference fits
-__device__ __forceinline__ void smooth(uint64_t &v, uint64_t x, int sh) {
-  v = (uint64_t)((long long)v + (((long long)x - (long long)v) >> sh));
-}
+struct CallArgs : tc::GridBank<AleKind>::Args {
+  const unsigned short *golay;
+};
 
 // bits 0, 2, .. 46 of x, packed
 __device__ __forceinline__ unsigned even_bits(unsigned long long x) {
@@ -158,19 +146,11 @@ __device__ __forceinline__ void file(AleGeom const &g, kq_ale_status &s, unsigne
 __device__ __forceinline__ void symbol(AleGeom const &g, AlePar const &par, kq_ale_status &s, unsigned long long pl,
                                        unsigned long long k, const unsigned short *gol, kq_ale_event *ev, unsigned &nev) {
   // 1 timing
-  smooth(s.ee, s.pe, 3);
-  smooth(s.el, pl, 3);
-  unsigned long long const m = s.ee > s.el ? s.ee : s.el;
-  int adj = 0;
-  if (s.ee > s.el && s.ee - s.el > (m >> 3)) adj = -(par.tb >> 5);
-  else if (s.el > s.ee && s.el - s.ee > (m >> 3)) adj = par.tb >> 5;
-  s.t += par.tb - 2 * (par.tb >> 2) + adj;
-  // 2 levels and gate: 16 sig >= snr nse in 128 bits
+  tc::clock_adjust(s, par.tb, pl);
+  // 2 levels and gate
   smooth(s.sig, s.pc, 4);
   smooth(s.nse, s.oth, 4);
-  unsigned long long const lh = s.sig >> 60, ll = s.sig << 4, rh = __umul64hi(s.nse, (unsigned long long)g.snr),
-                           rl = s.nse * (unsigned long long)g.snr;
-  bool const valid = s.frames >= g.warm && s.sig >= g.min_p && (lh > rh || (lh == rh && ll >= rl));
+  bool const gate = tc::gate16(s.sig, s.nse, g.snr), valid = s.frames >= g.warm && s.sig >= g.min_p && gate;
   // 3 register (the Gray map 0 1 3 2 6 7 5 4, a nibble to a tone)
   s.r0 = (s.r0 << 3 | s.r1 >> 46) & kM49;
   s.r1 = (s.r1 << 3 | s.r2 >> 46) & kM49;
@@ -223,66 +203,42 @@ __global__ __launch_bounds__(kThreads) void k_ale(CallArgs c) {
   __shared__ long long carry[kWaves][NS];
   __shared__ int lastsum[kWaves][NS];
   AleGeom const &g = c.g;
-  int const tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = (int)blockIdx.x * kWaves + wave;
-  bool const live = li < c.nlist;
-  int const slot = live ? c.list[li] : 0;
-  kq::tonecorr::load_packed_table(CS, c.table, tid, kThreads);
-  for (int i = tid; i < kGolay; i += kThreads)     // two entries to a word
+  auto const w = tc::wave_place<kThreads>(c, CS);
+  int const wave = w.wave, lane = w.lane, W = tc::window_frames(w.live, w.par.W);
+  for (int i = (int)threadIdx.x; i < kGolay; i += kThreads)  // two entries to a word
     reinterpret_cast<unsigned *>(GL)[i] = reinterpret_cast<const unsigned *>(c.golay)[i];
-  AlePar const par = c.par[slot];
-  size_t const row = live && c.rowmap ? (size_t)c.rowmap[li] : (size_t)par.source;
-  int const B = g.grid.B, L = c.L, F = 64 / L, f = lane / L, p = lane & (L - 1);
-  int const W = live ? min(max(par.W, 1), kHist + 1) : 1;  // (the host keeps it in 8..32)
-  int const q = par.tb >> 2;
+  int const q = w.par.tb >> 2;
   short *const qs = reinterpret_cast<short *>(raw[wave]);
   int(*const Wd)[kWin] = reinterpret_cast<int(*)[kWin]>(raw[wave]);  // [NS][kWin]: the window sums at every frame of the piece
   static_assert(NS * kWin * sizeof(int) <= 2 * kTile, "the window sums fit where the samples were");
-  // carried: lane 0 holds the record, the open frame's sums in it; the history goes to the front of A
   kq_ale_status s{};
   unsigned nev = 0;
-  kq_ale_event *ev = c.ev + (size_t)slot * g.max_events;
+  kq_ale_event *ev = tc::load_record(c, w, s, nev);
   long long cy[NS];
 #pragma unroll
   for (int t = 0; t < NS; t++) cy[t] = 0;
-  if (live && lane == 0) {
-    s = c.state[slot];
-    nev = c.nev[slot];
+  if (w.live && lane == 0) {
 #pragma unroll
     for (int t = 0; t < NS; t++) {
       cy[t] = s.acc[t >> 1][t & 1];
       lastsum[wave][t] = s.sum[t >> 1][t & 1];
     }
   }
-  if (lane < kHist)
-    for (int t = 0; t < NS; t++) A[wave][t][lane] = live ? c.hist[slot].v[t][lane] : 0;
-  int64_t n = c.n0, k0 = c.n0 / B;
-  while (n < c.n1) {  // one piece: the frames k0 .. k0 + F - 1, from n to their end or the call's; x counts from k0 B
-    int64_t const pe = (k0 + F) * (int64_t)B, e = pe < c.n1 ? pe : c.n1;
-    int const x0 = (int)(n - k0 * B), x1 = x0 + (int)(e - n);  // x1 <= F B
+  tc::load_hist(A[wave], c.hist, w);
+  for (tc::Piece pc(c.n0, w.B); pc.n < c.n1; pc.next(w.F)) {
+    pc.span(c.n1, w.B, w.F);
     long long sm[NS];  // (its first barrier: the piece before is done with raw, A, Pb, Ob, Yb and carry, and A is loaded)
-    kq::tonecorr::correlate_piece<NT>(g.grid, c.in, row, live, lane, L, c.n0, n, k0, x0, x1, qs, CS, par.inc, sm, cy);
-    int const done = (int)__umulhi((unsigned)x1, g.grid.magic);  // frames of the piece that are complete
-    if (p == 0 && f * B < x1) {
-      if (f < done) {
-#pragma unroll
-        for (int t = 0; t < NS; t++) A[wave][t][kHist + f] = (int)(sm[t] >> 12);
-      } else {  // the call ends inside frame f
-#pragma unroll
-        for (int t = 0; t < NS; t++) carry[wave][t] = sm[t];
-      }
-    }
+    tc::correlate_piece<NT>(c, w, pc, qs, CS, w.par.inc, sm, cy);
+    int const done = pc.done(g.grid);
+    tc::file_sums(A[wave], carry[wave], w, pc, done, sm, 12);
     __syncthreads();
-    for (int it = lane; it < done * NS; it += 64) {  // the window of series t that ends at frame fr: W entries, the last at kHist + fr
+    for (int it = lane; it < done * NS; it += 64) {  // series t at frame fr
       int const fr = it >> 4, t = it & (NS - 1);
-      int w = 0;
-      for (int i = 0; i < W; i++) w += A[wave][t][kHist + fr - i];
-      Wd[t][fr] = w;
+      Wd[t][fr] = tc::window_sum(A[wave][t], fr, W);
     }
     __syncthreads();
     int keep[NS];
-    if (lane < kHist)  // what the next piece finds in front: the last kHist frames
-#pragma unroll
-      for (int t = 0; t < NS; t++) keep[t] = A[wave][t][done + lane];
+    tc::keep_hist(A[wave], lane, done, keep);
     if (lane < done) {
       unsigned long long best = 0, tot = 0;
       int sym = 0;
@@ -304,10 +260,8 @@ __global__ __launch_bounds__(kThreads) void k_ale(CallArgs c) {
         for (int t = 0; t < NS; t++) lastsum[wave][t] = Wd[t][lane];
     }
     __syncthreads();
-    if (lane < kHist)
-#pragma unroll
-      for (int t = 0; t < NS; t++) A[wave][t][lane] = keep[t];
-    if (live && lane == 0) {
+    tc::put_hist(A[wave], lane, keep);
+    if (w.live && lane == 0) {
       for (int i = 0; i < done; i++) {  // the header's step, frame k0 + i
         s.frames = sat_inc(s.frames);
         s.t -= 256;
@@ -325,80 +279,27 @@ __global__ __launch_bounds__(kThreads) void k_ale(CallArgs c) {
           s.ph = 2;
         } else {
           s.ph = 0;
-          symbol(g, par, s, P, (unsigned long long)(k0 + i), GL, ev, nev);
+          symbol(g, w.par, s, P, (unsigned long long)(pc.k0 + i), GL, ev, nev);
         }
       }
-      if (done * B < x1)
-#pragma unroll
-        for (int t = 0; t < NS; t++) cy[t] = carry[wave][t];
+      tc::take_carry(carry[wave], w, pc, done, cy);
     }
-    n = e;
-    k0 += F;
   }
   __syncthreads();
-  if (live && lane < kHist)
-    for (int t = 0; t < NS; t++) c.hist[slot].v[t][lane] = A[wave][t][lane];
-  if (live && lane == 0) {
+  tc::store_hist(A[wave], c.hist, w);
+  if (w.live && lane == 0) {
 #pragma unroll
     for (int t = 0; t < NS; t++) {
       s.acc[t >> 1][t & 1] = cy[t];
       s.sum[t >> 1][t & 1] = lastsum[wave][t];
     }
-    c.state[slot] = s;
-    c.nev[slot] = nev;
-    if (c.st) c.st[(size_t)slot * c.sstride] = s;
   }
+  tc::store_record(c, w, s, nev);
 }
 
 }  // namespace
 
-struct kq_ale_bank : kq::HostSide {
-  static constexpr bool kDeferred = true;
-  kq_ale_config cfg;
-  std::mutex mu;
-  bool dev_ready = false;
-  AleGeom g{};
-  int Lmin = 1;                  // the least lanes to a frame whose piece fits kTile
-  uint64_t n_cur = 0;
-  kq::DeferredSlots<AlePar> def;
-  struct Dev {  // kq::lazy_device
-    kq::SlotTable<AlePar> slots;
-    short *table = nullptr;
-    unsigned short *golay = nullptr;
-    kq_ale_status *state = nullptr;
-    AleHist *hist = nullptr;
-    kq::EventArena<kq_ale_event> arena;
-    kq_ale_status *st = nullptr;         // host-memory calls
-  } d;
-
-  int to_device();
-};
-
-namespace {
-
-int make_device(kq_ale_bank *b) {
-  auto &d = b->d;
-  if (b->open_stream(b->cfg.stream)) return -1;
-  size_t const S = b->cfg.max_slots;
-  if (d.slots.alloc(*b, S) || kq::tonecorr::alloc_table(*b, &d.table) || b->alloc(&d.golay, (size_t)2 * kGolay) ||
-      b->alloc(&d.state, S, true) || b->alloc(&d.hist, S, true) || d.arena.alloc(*b, S, b->cfg.max_events))
-    return -1;
-  KQ_TRY(hipMemcpyAsync(d.golay, golay_tables().data(), 2 * kGolay * sizeof(unsigned short), hipMemcpyHostToDevice, b->stream));
-  KQ_TRY(hipStreamSynchronize(b->stream));
-  return 0;
-}
-
-}  // namespace
-
-// kq::DeferredSlots::flush; the record and the history of a slot that is set start cold (all zero: the header's state at
-// the set) and its arena empty
-int kq_ale_bank::to_device() {
-  return def.flush(this, make_device, [this](size_t s0, size_t n) {
-    KQ_TRY(hipMemsetAsync(d.state + s0, 0, n * sizeof(kq_ale_status), stream));
-    KQ_TRY(hipMemsetAsync(d.hist + s0, 0, n * sizeof(AleHist), stream));
-    return d.arena.clear(*this, s0, n);
-  });
-}
+struct kq_ale_bank : tc::GridBank<AleKind> {};
 
 extern "C" {
 
@@ -415,20 +316,10 @@ kq_ale_bank *kq_ale_create(const kq_ale_config *cfg) {
       !kq::field_in_range(fn, "max_slots", cfg->max_slots, 1, kMaxSlots) ||
       !kq::field_in_range(fn, "max_events", cfg->max_events, 1, 4096) || !kq::max_samples_ok(fn, cfg->max_samples))
     return nullptr;
-  (void)kq::tonecorr::cos_table();  // the tables exist from here on
-  (void)golay_tables();
-  kq_ale_bank *b = new kq_ale_bank;
-  b->cfg = *cfg;
-  b->def.init(cfg->max_slots);
-  AleGeom &g = b->g;
-  g.grid = kq::tonecorr::frame_grid(cfg->block_len);
-  g.warm = cfg->warm;
-  g.snr = cfg->snr;
-  g.acq_err = cfg->acq_err;
-  g.lose = cfg->lose;
-  g.min_p = cfg->min_p;
-  g.max_events = (int)cfg->max_events;
-  b->Lmin = kq::tonecorr::least_lanes(g.grid, kTile);  // 8 at the most: Bs <= 258
+  (void)golay_tables();  // the tables exist from here on
+  kq_ale_bank *b = tc::finish_create<kq_ale_bank>(cfg, kTile);  // Lmin 8 at the most: Bs <= 258
+  b->g.acq_err = cfg->acq_err;
+  b->g.lose = cfg->lose;
   return b;
 }
 
@@ -436,41 +327,20 @@ int kq_ale_destroy(kq_ale_bank *b) { return kq::destroy_bank(b, "kq_ale_destroy"
 
 int kq_ale_set(kq_ale_bank *b, unsigned slot, const kq_ale_params *p) {
   const char *fn = "kq_ale_set";
-  if (!kq::set_args_ok(fn, slot, p, kMaxSlots)) return -1;
-  if (!b) {
-    kq_internal_set_error("%s: null bank", fn);
-    return -1;
-  }
-  std::lock_guard<std::mutex> lk(b->mu);
-  if (!kq::slot_in_bank(fn, slot, b->cfg.max_slots)) return -1;
-  double const Fs = b->cfg.samprate, f0 = p->f0, df = p->df, baud = p->baud;
+  std::unique_lock<std::mutex> lk;
+  if (!tc::open_set(b, fn, slot, p, kMaxSlots, lk)) return -1;
+  double const Fs = b->cfg.samprate, f0 = p->f0, df = p->df;
   if (!std::isfinite(f0) || !std::isfinite(df) || df == 0) {
     kq_internal_set_error("%s: f0 %g and df %g must be finite and df not 0", fn, f0, df);
     return -1;
   }
-  for (int t = 0; t < NT; t += NT - 1) {  // the outer two bound the rest
-    double const f = f0 + t * df;
-    if (!(f > 0) || !(f < 0.5 * Fs)) {
-      kq_internal_set_error("%s: tone %d at %g (f0 %g, df %g) must be above 0 and below samprate / 2", fn, t, f, f0, df);
-      return -1;
-    }
-  }
-  if (!(baud > 0) || !std::isfinite(baud)) {
-    kq_internal_set_error("%s: baud %g must be positive and finite", fn, baud);
-    return -1;
-  }
-  double const tb = std::rint(256.0 * Fs / ((double)b->cfg.block_len * baud));
-  if (!(tb >= 2048.0) || !(tb <= 8192.0)) {
-    kq_internal_set_error("%s: baud %g makes tb %.10g, a symbol of %g frames of %u samples, outside 2048..8192 (8 to 32 frames)",
-                          fn, baud, tb, tb / 256.0, b->cfg.block_len);
-    return -1;
-  }
+  for (int t = 0; t < NT; t += NT - 1)  // the outer two bound the rest
+    if (!tc::tone_ok(fn, Fs, f0 + t * df, "tone %d at %g (f0 %g, df %g)", t, f0 + t * df, f0, df)) return -1;
   AlePar np{};
+  if (!tc::symbol_period(fn, Fs, b->cfg.block_len, p->baud, "symbol", &np.tb, &np.W)) return -1;
   np.active = 1;
   np.source = p->source;
   for (int t = 0; t < NT; t++) np.inc[t] = (unsigned)std::llrint((f0 + t * df) * 4294967296.0 / Fs);
-  np.tb = (int)tb;
-  np.W = (np.tb + 128) >> 8;
   b->def.set(slot, np);
   return 0;
 }
@@ -479,41 +349,11 @@ int kq_ale_remove(kq_ale_bank *b, unsigned slot) { return kq::deferred_remove(b,
 
 int kq_ale_process(kq_ale_bank *b, const void *src, int format, size_t src_stride, size_t row_stride, unsigned block_len,
                    unsigned nblocks, int on_device, kq_ale_status *status, size_t status_stride) {
-  const char *fn = "kq_ale_process";
-  if (!b) {
-    kq_internal_set_error("%s: null bank", fn);
-    return -1;
-  }
-  std::lock_guard<std::mutex> lk(b->mu);
-  if (!kq::call_args_ok(fn, format, b->cfg.max_samples, row_stride, block_len, nblocks, status, status_stride)) return -1;
-  size_t const ncall = (size_t)block_len * nblocks;
-  std::optional<kq::DeviceScope> scope;
-  kq::CallWork const work = kq::begin_call(b, fn, ncall, src, scope);
-  if (work != kq::CALL_RUN) return work == kq::CALL_FAILED ? -1 : 0;
-  auto &d = b->d;
-  size_t const nlist = d.slots.all.size();
-  CallArgs a{};
-  a.g = b->g;
-  a.par = d.slots.d_par;
-  a.list = d.slots.d_list;
-  a.table = d.table;
-  a.golay = d.golay;
-  a.state = d.state;
-  a.hist = d.hist;
-  a.ev = d.arena.ev;
-  a.nev = d.arena.n;
-  a.nlist = (int)nlist;
-  a.n0 = (int64_t)b->n_cur;
-  a.n1 = a.n0 + (int64_t)ncall;
-  a.L = kq::tonecorr::lanes_for_call(b->g.grid, b->Lmin, ncall);
-  if (kq::bind_pcm(&a.in, &a.rowmap, *b, d.slots, b->cfg.max_samples, b->cfg.input_scale, src, format, src_stride, row_stride, block_len,
-                   nblocks, on_device) ||
-      kq::bind_status(b, on_device, status, status_stride, &a.st, &a.sstride))
-    return -1;
-  hipLaunchKernelGGL(k_ale, dim3((unsigned)((nlist + kWaves - 1) / kWaves)), dim3(kThreads), 0, b->stream, a);
-  KQ_TRY(hipGetLastError());
-  b->n_cur += ncall;
-  return on_device ? 0 : kq::end_host_call(b, status, status_stride, nullptr);
+  return tc::process<CallArgs>(b, "kq_ale_process", src, format, src_stride, row_stride, block_len, nblocks, on_device, status,
+                               status_stride, kWaves, [b](CallArgs &a, unsigned blocks) {
+                                 a.golay = b->d.tables.golay;
+                                 hipLaunchKernelGGL(k_ale, dim3(blocks), dim3(kThreads), 0, b->stream, a);
+                               });
 }
 
 int kq_ale_pull_counts(kq_ale_bank *b, uint32_t *counts) { return kq::pull_counts(b, "kq_ale_pull_counts", counts); }
@@ -529,23 +369,12 @@ int kq_ale_get_table(const kq_ale_bank *b, int16_t *dst, size_t cap) {
 }
 
 int kq_ale_get_slot(kq_ale_bank *b, unsigned slot, kq_ale_slot *out) {
-  if (!b) {
-    kq_internal_set_error("kq_ale_get_slot: null bank");
-    return -1;
-  }
-  if (!out) {
-    kq_internal_set_error("kq_ale_get_slot: null out");
-    return -1;
-  }
-  std::lock_guard<std::mutex> lk(b->mu);
-  if (!b->def.is_set(slot)) {
-    kq_internal_set_error("kq_ale_get_slot: slot %u holds no decoder", slot);
-    return -1;
-  }
-  AlePar const &w = b->def.want[slot];
-  for (int t = 0; t < NT; t++) out->inc[t] = w.inc[t];
-  out->tb = (uint32_t)w.tb;
-  out->W = (uint32_t)w.W;
+  std::unique_lock<std::mutex> lk;
+  const AlePar *w = tc::wanted(b, "kq_ale_get_slot", slot, out, "out", lk);
+  if (!w) return -1;
+  for (int t = 0; t < NT; t++) out->inc[t] = w->inc[t];
+  out->tb = (uint32_t)w->tb;
+  out->W = (uint32_t)w->W;
   return 0;
 }
 

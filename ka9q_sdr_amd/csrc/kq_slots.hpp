@@ -1,17 +1,22 @@
-// kq_slots.hpp -- the host half that the slot banks share (kq_wfm, kq_rds, kq_fsk, kq_pag, kq_tone, kq_cw, kq_rtty, kq_rsmp: up
-// to max_slots decoders, each on a source row of the call's input, set and removed one at a time, processed together).  On
+// kq_slots.hpp -- the host half that the slot banks share (kq_wfm, kq_rds, kq_rsmp and the PCM decoders below: up to
+// max_slots decoders, each on a source row of the call's input, set and removed one at a time, processed together).  On
 // top of kq::HostSide (kq_host.hpp); host only, so that it also compiles against the device-less stand-in for the runtime.
 // The kernels, their argument blocks and the launches stay with each bank.
 //
 //   every slot bank   the slot table and its device copy, the staging of a host-memory call's distinct source rows, the
 //                     copy-back of the active slots' rows, destroy / sync / remove, the argument checks of set and process
-//   PCM decoders      (kq_fsk, kq_pag, kq_tone, kq_cw, kq_rtty) the call's input binding (PcmIn, bind_pcm), the checks of a
-//                     call and what is left of it (call_args_ok, begin_call), where the status records go and the tail of a
-//                     host-memory call (bind_status, end_host_call), the checks the configs share (field_in_range, ...)
-//   event banks       kq::EventArena: the [S][max_events] records and [S] counts, with the bodies of pull_counts,
-//                     pull_event and clear (kq_fsk and kq_pag keep their frame and page infos in one and pull them themselves)
-//   deferred banks    (kq_cw, kq_rtty, kq_psk, kq_ale) kq::DeferredSlots: set and remove touch no device; the next entry point that needs
-//                     the device brings the changed slots there, a run at a time (flush)
+//   PCM decoders      (kq_fsk, kq_pag, kq_tone, kq_cw, kq_rtty, kq_psk, kq_acars, kq_ale) the call's input binding (PcmIn,
+//                     bind_pcm), the checks of a call and what is left of it (call_args_ok, begin_call), where the status
+//                     records go and the tail of a host-memory call (bind_status, end_host_call), the checks the configs
+//                     share (field_in_range, ...)
+//   event banks       kq::EventArena: the [S][max_events] records and [S] counts.  kq_tone, kq_cw, kq_rtty, kq_psk and
+//                     kq_ale file events in it and take the bodies of pull_counts, pull_event and clear; kq_fsk, kq_pag and
+//                     kq_acars keep their frame, page and block infos in one, take the counts and clear bodies, and pull a
+//                     record with pull_record before they fetch its bytes themselves
+//   deferred banks    (kq_cw, kq_rtty, kq_psk, kq_acars, kq_ale) kq::DeferredSlots: set and remove touch no device; the next
+//                     entry point that needs the device brings the changed slots there, a run at a time (flush)
+//   frame-grid banks  (kq_cw, kq_rtty, kq_psk, kq_ale) stand on kq_gridbank.hpp, on top of this file: one bank template and
+//                     one body for create's tail, set's shared checks, process and the getters' opening
 //
 // A bank here is a struct on kq::HostSide with `cfg` (device, max_slots, max_samples), `mu`, `dev_ready`, `n_cur` (PCM
 // decoders), `static constexpr bool kDeferred` (event banks) and the device half `d` that kq::lazy_device() makes, whose

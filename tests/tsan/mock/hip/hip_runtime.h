@@ -39,6 +39,7 @@ inline mock_hip_state &mock_hip() {
 }
 inline bool mock_object_fails() { return mock_hip().fail_in.load() > 0 && mock_hip().fail_in.fetch_sub(1) == 1; }
 inline const char *hipGetErrorString(hipError_t e) { return e == hipSuccess ? "no error" : "mock error"; }
+inline hipError_t hipGetLastError() { return hipSuccess; }
 inline hipError_t hipGetDeviceCount(int *n) {
   *n = 1;
   return hipSuccess;

@@ -1,17 +1,20 @@
 // AddressSanitizer / UndefinedBehaviorSanitizer run of kq_slots.hpp and kq::lazy_device (kq_host.hpp) on the CPU, against the
 // device-less stand-in for the HIP runtime (mock/hip/hip_runtime.h): a toy slot bank with the shape of kq_wfm / kq_rds /
 // kq_fsk's host halves.  A set-up that fails at every one of its runtime objects in turn, the staging of a host-memory
-// call, the runs of active slots and the copy-back, and the table's upload.  A second toy bank has the shape of kq_cw /
-// kq_rtty's: deferred slots (kq::DeferredSlots and its flush) and an arena of events (kq::EventArena) -- set, remove and
-// reset with no device, a flush of mixed runs, a flush whose set-up fails at every object in turn, the arena's entry points
-// with and without a device.  LeakSanitizer has the last word: whatever a failed set-up or a destroy leaves behind fails the run.
+// call, the runs of active slots and the copy-back, and the table's upload.  A second toy bank stands on the frame-grid
+// banks' host template (kq_gridbank.hpp, as kq_cw / kq_rtty / kq_psk / kq_ale do): deferred slots (kq::DeferredSlots and
+// its flush) and an arena of events (kq::EventArena) -- set, remove and reset with no device, a flush of mixed runs, a flush
+// whose set-up fails at every object in turn, the arena's entry points with and without a device.  A third has a history
+// and a table of its own, and the shared parts of set and of the getters are checked word for word, symbol_period at both
+// edges.  The template's process body launches a kernel and is not part of this run.  LeakSanitizer has the last word:
+// whatever a failed set-up or a destroy leaves behind fails the run.
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <string>
 #include <utility>
 
-#include "kq_slots.hpp"
+#include "kq_gridbank.hpp"
 
 static std::string last_error;
 void kq_internal_set_error(const char *fmt, ...) {
@@ -227,12 +230,14 @@ void table_staging_runs() {
   CHECK(kq::destroy_bank(b, "toy_destroy") == 0);
 }
 
-// ---- a second toy bank, with the shape of kq_cw / kq_rtty's host halves: deferred slots and an arena of events --------------
-constexpr int kDefObjects = 8;  // what def_make_device makes: a stream and seven allocations
+// ---- a second toy bank, on the frame-grid banks' host template (kq_gridbank.hpp: kq_cw / kq_rtty / kq_psk / kq_ale's host
+// halves): deferred slots and an arena of events, a cold start that is not all zero, no history ------------------------------
+namespace tc = kq::tonecorr;
+constexpr int kDefObjects = 8;  // what GridBank::make_device makes here: a stream and seven allocations
 
 struct DefPar {
   int active;
-  unsigned source;
+  unsigned source;  // (def_set: the slot's own number)
   int value;
 };
 
@@ -240,62 +245,64 @@ struct DefEvent {
   unsigned code, slot;
 };
 
-struct def_bank : kq::HostSide {
-  static constexpr bool kDeferred = true;
-  toy_config cfg;
-  std::mutex mu;
-  bool dev_ready = false;
-  uint64_t n_cur = 0;
-  kq::DeferredSlots<DefPar> def;
-  std::vector<std::pair<size_t, size_t>> colds;  // the runs flush() asked a cold start for
-  struct Dev {
-    kq::SlotTable<DefPar> slots;
-    int *state = nullptr;  // [S]: the slot's value at its cold start
-    kq::EventArena<DefEvent> arena;
-    int *st = nullptr;
-  } d;
-
-  int to_device();
+struct DefGeom {
+  tc::FrameGrid grid;
+  unsigned warm, snr;
+  unsigned long long min_p;
+  int max_events;
 };
 
-int def_make_device(def_bank *b) {
-  size_t const S = b->cfg.max_slots;
-  if (b->open_stream(b->cfg.stream) || b->d.slots.alloc(*b, S) || b->alloc(&b->d.state, S, true) || b->d.arena.alloc(*b, S, 4) ||
-      b->alloc(&b->d.st, S))
-    return -1;
-  KQ_TRY(hipStreamSynchronize(b->stream));
-  return 0;
-}
+struct def_config {
+  int device;
+  unsigned max_slots;
+  size_t max_samples;
+  void *stream;
+  unsigned block_len, warm, snr, max_events;
+  unsigned long long min_p;
+};
 
-int def_bank::to_device() {
-  std::vector<int> cold(def.dirty.size());  // as kq_cw's records: host memory that a run is copied from
-  size_t used = 0;
-  return def.flush(this, def_make_device, [&](size_t s0, size_t n) {
-    colds.emplace_back(s0, n);
-    int *r = cold.data() + used;
-    used += n;
-    for (size_t i = 0; i < n; i++) r[i] = d.slots.par[s0 + i].value;
-    KQ_TRY(hipMemcpyAsync(d.state + s0, r, n * sizeof(int), hipMemcpyHostToDevice, stream));
-    return d.arena.clear(*this, s0, n);
-  });
-}
+// The slots that were started cold, consecutive ones merged.  The template's cold hook sees one slot at a time, so this
+// says which slots flush() started cold, not where it split its runs (two runs of set slots never touch, so the two agree
+// wherever flush() is right); the counts of copies below are what still sees the runs.
+std::vector<std::pair<size_t, size_t>> colds;
+
+struct DefKind {
+  using Config = def_config;
+  using Geom = DefGeom;
+  using Par = DefPar;
+  using Status = int;  // [S]: the slot's value at its cold start
+  using Event = DefEvent;
+  using Hist = void;
+  using Tables = tc::NoTables;
+  static constexpr bool kZeroCold = false;
+  static void cold(DefPar const &p, int &r) {  // as kq_cw's records: host memory that a run is copied from
+    if (!colds.empty() && colds.back().first + colds.back().second == p.source) colds.back().second++;
+    else colds.emplace_back(p.source, 1);
+    r = p.value;
+  }
+};
+
+struct def_bank : tc::GridBank<DefKind> {};
 
 def_bank *def_create(unsigned max_slots) {
-  def_bank *b = new def_bank;
-  b->cfg = toy_config{0, max_slots, 64, nullptr};
-  b->def.init(max_slots);
+  def_config const cfg{0, max_slots, 64, nullptr, 24, 3, 16, 4, 5};
+  def_bank *b = tc::finish_create<def_bank>(&cfg, 3200);
+  CHECK(b->g.grid.B == 24 && b->g.grid.Bs == 26 && b->Lmin == 1 && b->g.warm == 3 && b->g.snr == 16 && b->g.min_p == 5 &&
+        b->g.max_events == 4 && b->cfg.max_slots == max_slots && b->def.want.size() == max_slots);
   return b;
 }
 
 void def_set(def_bank *b, unsigned slot, int value) {
-  std::lock_guard<std::mutex> lk(b->mu);
+  std::unique_lock<std::mutex> lk;
+  CHECK(tc::open_set(b, "toy_set", slot, &value, kMaxSlots, lk) && lk.owns_lock());
   b->def.set(slot, DefPar{1, slot, value});
 }
 
 bool def_holds_nothing(const def_bank *b) {
   auto const &d = b->d;
   return !b->dev_ready && b->held.empty() && b->streams.empty() && !b->stream && d.slots.par.empty() && d.slots.all.empty() &&
-         !d.slots.d_par && !d.slots.d_list && !d.slots.d_rowmap && !d.state && !d.arena.ev && !d.arena.n && d.arena.cap == 0 && !d.st;
+         !d.slots.d_par && !d.slots.d_list && !d.slots.d_rowmap && !d.table && !d.state && !d.hist && !d.arena.ev && !d.arena.n &&
+         d.arena.cap == 0 && !d.st;
 }
 
 // what a kernel would have filed: n events in the slot's arena
@@ -306,6 +313,7 @@ void def_file(def_bank *b, unsigned slot, unsigned n) {
 
 void deferred_without_a_device() {
   unsigned const S = 8;
+  colds.clear();
   def_bank *b = def_create(S);
   int const mallocs = mock_hip().mallocs, copies = mock_hip().copies;
   std::optional<kq::DeviceScope> scope;
@@ -335,13 +343,14 @@ void deferred_without_a_device() {
   CHECK(kq::begin_call(b, "toy_process", 0, b, scope) == kq::CALL_EMPTY && b->n_cur == 0);
   CHECK(kq::begin_call(b, "toy_process", 15, nullptr, scope) == kq::CALL_FAILED && last_error == "toy_process: null src");
   CHECK(kq::begin_call(b, "toy_process", 15, b, scope) == kq::CALL_IDLE && b->n_cur == 15 && !scope);
-  CHECK(def_holds_nothing(b) && mock_hip().mallocs == mallocs && mock_hip().copies == copies && b->colds.empty());
+  CHECK(def_holds_nothing(b) && mock_hip().mallocs == mallocs && mock_hip().copies == copies && colds.empty());
   CHECK(kq::destroy_bank(b, "toy_destroy") == 0);
 }
 
 void deferred_flush_and_arena() {
   using Runs = std::vector<std::pair<size_t, size_t>>;
   unsigned const S = 8;
+  colds.clear();
   def_bank *b = def_create(S);
   auto &t = b->d.slots;
   // before the first call: 0, 1, 2 together, 4 alone, 3 set and removed again in the middle
@@ -355,9 +364,11 @@ void deferred_flush_and_arena() {
   int copies = mock_hip().copies;
   CHECK(kq::pull_counts(b, "toy_pull_counts", counts.data()) == 0 && counts == std::vector<uint32_t>(S, 0u));
   CHECK(b->dev_ready && b->held.size() == 7 && b->streams.size() == 1 && b->def.dirty.empty());
-  CHECK((b->colds == Runs{{0, 3}, {4, 1}}));
-  // three runs of parameters, two cold starts, upload's record and list, the counts
-  CHECK(mock_hip().copies == copies + 3 + 2 + 2 + 1);
+  CHECK((colds == Runs{{0, 3}, {4, 1}}));
+  // the cosine table (the template's set-up sends it), three runs of parameters, two cold starts, upload's record and list,
+  // the counts
+  CHECK(mock_hip().copies == copies + 1 + 3 + 2 + 2 + 1);
+  CHECK(std::memcmp(b->d.table, tc::cos_table().data(), tc::kTable * sizeof(short)) == 0);
   CHECK((t.all == std::vector<int>{0, 1, 2, 4}));
   for (size_t i = 0; i < t.all.size(); i++) CHECK(t.d_list[i] == t.all[i]);
   for (unsigned s = 0; s < S; s++) {
@@ -377,18 +388,18 @@ void deferred_flush_and_arena() {
   // a slot set again starts cold with an empty arena, a removed one keeps its arena; the others are left alone
   def_set(b, 2, 22);
   CHECK(kq::deferred_remove(b, 0, "toy_remove") == 0);
-  b->colds.clear();
+  colds.clear();
   CHECK(kq::pull_counts(b, "toy_pull_counts", counts.data()) == 0 && (counts == std::vector<uint32_t>{2, 0, 0, 0, 0, 0, 0, 0}));
-  CHECK((b->colds == Runs{{2, 1}}) && b->d.state[2] == 22 && b->d.state[1] == 10 && (t.all == std::vector<int>{1, 2, 4}));
+  CHECK((colds == Runs{{2, 1}}) && b->d.state[2] == 22 && b->d.state[1] == 10 && (t.all == std::vector<int>{1, 2, 4}));
   CHECK(t.d_par[0].active == 0 && t.d_par[2].value == 22);
   // reset: every slot that is set starts cold again, in runs
   def_file(b, 1, 1);
-  b->colds.clear();
+  colds.clear();
   b->n_cur = 5;
   CHECK(kq::deferred_reset(b, "toy_reset") == 0 && b->n_cur == 0);
   std::optional<kq::DeviceScope> scope;
   CHECK(kq::begin_call(b, "toy_process", 15, b, scope) == kq::CALL_RUN && b->n_cur == 0 && scope);
-  CHECK((b->colds == Runs{{1, 2}, {4, 1}}) && b->d.arena.n[1] == 0 && b->d.arena.n[0] == 2);
+  CHECK((colds == Runs{{1, 2}, {4, 1}}) && b->d.arena.n[1] == 0 && b->d.arena.n[0] == 2);
   // the status records of a host-memory call: the bank's own plane at stride 1, the active slots' rows back
   {
     std::vector<int> host(S * 2, -1);
@@ -413,6 +424,7 @@ void deferred_flush_and_arena() {
 void deferred_failed_setup() {
   unsigned const S = 8;
   for (int k = 1; k <= kDefObjects; k++) {
+    colds.clear();
     def_bank *b = def_create(S);
     def_set(b, 2, 7);
     def_set(b, 3, 8);
@@ -420,7 +432,7 @@ void deferred_failed_setup() {
     mock_hip().fail_in = k;
     CHECK(kq::pull_counts(b, "toy_pull_counts", counts.data()) == -1);
     CHECK(mock_hip().fail_in == 0);  // the k-th object was reached
-    CHECK(def_holds_nothing(b) && b->def.dirty.size() == 2 && b->def.nwant == 2 && b->colds.empty());
+    CHECK(def_holds_nothing(b) && b->def.dirty.size() == 2 && b->def.nwant == 2 && colds.empty());
     CHECK(counts[0] == 0xFFFFFFFFu);
     DefEvent e{7, 7};
     if (k & 1) {  // the next entry point starts over
@@ -429,7 +441,7 @@ void deferred_failed_setup() {
       CHECK(kq::pull_counts(b, "toy_pull_counts", counts.data()) == 0 && counts == std::vector<uint32_t>(S, 0u));
     }
     CHECK(b->dev_ready && b->held.size() == 7 && b->def.dirty.empty() && (b->d.slots.all == std::vector<int>{2, 3}));
-    CHECK(b->d.state[2] == 7 && b->d.state[3] == 8 && b->colds.size() == 1);
+    CHECK(b->d.state[2] == 7 && b->d.state[3] == 8 && colds.size() == 1);
     CHECK(kq::destroy_bank(b, "toy_destroy") == 0);
   }
   // one whose device never came, destroyed with its slots still waiting
@@ -441,6 +453,118 @@ void deferred_failed_setup() {
   CHECK(kq::destroy_bank(b, "toy_destroy") == 0);
 }
 
+// ---- a third, as kq_ale's: a history window, a table of its own, and a cold start that is all zero --------------------------
+constexpr int kWinObjects = 10;  // a stream and nine allocations
+
+struct WinTables {
+  short *extra = nullptr;
+  int make(kq::HostSide &h) {
+    if (h.alloc(&extra, 16)) return -1;
+    short const ones[16] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
+    KQ_TRY(hipMemcpyAsync(extra, ones, sizeof ones, hipMemcpyHostToDevice, h.stream));  // (the mock copies at once)
+    return 0;
+  }
+};
+
+struct WinKind : DefKind {
+  using Hist = tc::FrameHist<2>;
+  using Tables = WinTables;
+  static constexpr bool kZeroCold = true;
+};
+
+struct win_bank : tc::GridBank<WinKind> {};
+
+void windowed_bank() {
+  unsigned const S = 8;
+  def_config const cfg{0, S, 64, nullptr, 48, 0, 16, 4, 0};
+  std::vector<uint32_t> counts(S);
+  for (int k = 0; k <= kWinObjects; k++) {  // 0: nothing fails
+    win_bank *b = tc::finish_create<win_bank>(&cfg, 3200);
+    CHECK(b->g.grid.Bs == 50 && b->Lmin == 1);
+    std::unique_lock<std::mutex> lk;
+    int v = 0;
+    CHECK(tc::open_set(b, "toy_set", 1, &v, kMaxSlots, lk));
+    b->def.set(1, DefPar{1, 1, 11});
+    b->def.set(2, DefPar{1, 2, 12});
+    lk.unlock();
+    mock_hip().fail_in = k;
+    if (k) {
+      CHECK(kq::pull_counts(b, "toy_pull_counts", counts.data()) == -1 && mock_hip().fail_in == 0);
+      CHECK(!b->dev_ready && b->held.empty() && b->streams.empty() && !b->d.table && !b->d.tables.extra && !b->d.state && !b->d.hist);
+    }
+    CHECK(kq::pull_counts(b, "toy_pull_counts", counts.data()) == 0 && b->dev_ready && b->held.size() == 9);
+    CHECK(b->d.tables.extra[15] == 1 && b->d.table[0] == 32767);
+    // what a call would leave; a slot set again starts from zeros, record and history, its neighbour keeps both
+    for (unsigned s = 1; s <= 2; s++) {
+      b->d.state[s] = 100 + (int)s;
+      for (int t = 0; t < 2; t++)
+        for (int i = 0; i < tc::kHist; i++) b->d.hist[s].v[t][i] = 7;
+    }
+    CHECK(tc::open_set(b, "toy_set", 2, &v, kMaxSlots, lk));
+    b->def.set(2, DefPar{1, 2, 13});
+    lk.unlock();
+    CHECK(kq::pull_counts(b, "toy_pull_counts", counts.data()) == 0);
+    CHECK(b->d.state[1] == 101 && b->d.state[2] == 0 && b->d.hist[1].v[1][tc::kHist - 1] == 7);
+    for (int t = 0; t < 2; t++)
+      for (int i = 0; i < tc::kHist; i++) CHECK(b->d.hist[2].v[t][i] == 0);
+    CHECK(kq::destroy_bank(b, "toy_destroy") == 0);
+  }
+}
+
+// the shared parts of kq_*_set and the getters' opening, word for word
+void set_and_get_openings() {
+  def_bank *b = def_create(8);
+  int v = 0;
+  {
+    std::unique_lock<std::mutex> lk;
+    CHECK(!tc::open_set(b, "toy_set", kMaxSlots, &v, kMaxSlots, lk) && last_error == "toy_set: slot 4096 is beyond any bank (4096 slots at most)");
+    CHECK(!tc::open_set(b, "toy_set", 0, nullptr, kMaxSlots, lk) && last_error == "toy_set: null params" && !lk.owns_lock());
+    CHECK(!tc::open_set((def_bank *)nullptr, "toy_set", 0, &v, kMaxSlots, lk) && last_error == "toy_set: null bank" && !lk.owns_lock());
+    CHECK(!tc::open_set(b, "toy_set", 8, &v, kMaxSlots, lk) && last_error == "toy_set: slot 8 >= max_slots 8" && lk.owns_lock());
+  }
+  CHECK(tc::tone_ok("toy_set", 12000.0, 1000.0, "pitch %g", 1000.0) && tc::tone_ok("toy_set", 12000.0, 5999.9, "mark %g", 5999.9));
+  CHECK(!tc::tone_ok("toy_set", 12000.0, 0.0, "mark %g", 0.0) && last_error == "toy_set: mark 0 must be above 0 and below samprate / 2");
+  CHECK(!tc::tone_ok("toy_set", 12000.0, 6000.0, "space %g", 6000.0) && last_error == "toy_set: space 6000 must be above 0 and below samprate / 2");
+  CHECK(!tc::tone_ok("toy_set", 12000.0, std::nan(""), "pitch %g", 1.5) && last_error == "toy_set: pitch 1.5 must be above 0 and below samprate / 2");
+  CHECK(!tc::tone_ok("toy_set", 12000.0, -250.0, "tone %d at %g (f0 %g, df %g)", 7, -250.0, 1500.0, -250.0) &&
+        last_error == "toy_set: tone 7 at -250 (f0 1500, df -250) must be above 0 and below samprate / 2");
+  // tb = rint(256 Fs / (B baud)) = rint(128000 / baud) at both edges of 2048..8192
+  int tb = -1, W = -1;
+  CHECK(tc::symbol_period("toy_set", 12000.0, 24, 128000.0 / 2048.0, "bit", &tb, &W) && tb == 2048 && W == 8);
+  CHECK(tc::symbol_period("toy_set", 12000.0, 24, 128000.0 / 8192.0, "symbol", &tb, &W) && tb == 8192 && W == 32);
+  CHECK(tc::symbol_period("toy_set", 12000.0, 24, 128000.0 / 2047.6, "bit", &tb, &W) && tb == 2048 && W == 8);
+  CHECK(tc::symbol_period("toy_set", 12000.0, 24, 128000.0 / 8192.4, "bit", &tb, &W) && tb == 8192 && W == 32);
+  CHECK(tc::symbol_period("toy_set", 12000.0, 24, 45.45, "bit", &tb, &W) && tb == 2816 && W == 11);
+  tb = W = -1;
+  CHECK(!tc::symbol_period("toy_set", 12000.0, 24, 128000.0 / 2047.4, "bit", &tb, &W) && tb == -1 && W == -1);
+  CHECK(last_error.find("toy_set: baud 62.5") == 0 &&
+        last_error.find(" makes tb 2047, a bit of 7.99609 frames of 24 samples, outside 2048..8192 (8 to 32 frames)") != std::string::npos);
+  CHECK(!tc::symbol_period("toy_set", 12000.0, 24, 128000.0 / 8192.6, "symbol", &tb, &W) && tb == -1 && W == -1);
+  CHECK(last_error.find(" makes tb 8193, a symbol of 32.0039 frames of 24 samples, outside 2048..8192 (8 to 32 frames)") != std::string::npos);
+  CHECK(!tc::symbol_period("toy_set", 12000.0, 24, 0.0, "bit", &tb, &W) && last_error == "toy_set: baud 0 must be positive and finite");
+  CHECK(!tc::symbol_period("toy_set", 12000.0, 24, INFINITY, "bit", &tb, &W) && last_error == "toy_set: baud inf must be positive and finite");
+  CHECK(!tc::symbol_period("toy_set", 12000.0, 24, std::nan(""), "bit", &tb, &W) && tb == -1);
+  // the getters
+  def_set(b, 3, 33);
+  {
+    std::unique_lock<std::mutex> lk;
+    CHECK(!tc::wanted((def_bank *)nullptr, "toy_get", 3, &v, "out", lk) && last_error == "toy_get: null bank");
+    CHECK(!tc::wanted(b, "toy_get", 3, nullptr, "inc", lk) && last_error == "toy_get: null inc" && !lk.owns_lock());
+    CHECK(!tc::wanted(b, "toy_get", 4, &v, "out", lk) && last_error == "toy_get: slot 4 holds no decoder");
+  }
+  {
+    std::unique_lock<std::mutex> lk;
+    CHECK(!tc::wanted(b, "toy_get", 8, &v, "out", lk) && last_error == "toy_get: slot 8 holds no decoder");
+  }
+  {
+    std::unique_lock<std::mutex> lk;
+    const DefPar *w = tc::wanted(b, "toy_get", 3, &v, "out", lk);
+    CHECK(w && w->value == 33 && w->source == 3 && lk.owns_lock());
+  }
+  CHECK(def_holds_nothing(b));  // none of it touched a device
+  CHECK(kq::destroy_bank(b, "toy_destroy") == 0);
+}
+
 }  // namespace
 
 int main() {
@@ -449,6 +573,8 @@ int main() {
   deferred_without_a_device();
   deferred_flush_and_arena();
   deferred_failed_setup();
+  windowed_bank();
+  set_and_get_openings();
   if (failures) {
     fprintf(stderr, "slot banks' host layer: %d checks failed\n", failures);
     return 1;
