@@ -27,6 +27,42 @@ __device__ __forceinline__ float rdlane(float v, int src) {
 }
 __device__ __forceinline__ int bitrev6(int i) { return (int)(__brev((unsigned)i) >> 26); }
 
+// a * b, complex, with the rounding steps spelled out.  The FM demodulator exists in a one-wave and a four-wave form that
+// promise the same bits for the same channel (tests/test_gpu_step_shed.py).  Written as `cmul(a, b)` the de-emphasis
+// filter's products did not keep that promise: the compiler contracts and packs a plain product site by site, and the two
+// forms came out a few units in the last place apart.  R, I say which of the two products of the real and of the imaginary
+// part is rounded on its own, the other one being fused into the sum:
+//   R = 1: fma(a.x, b.x, -(a.y b.y));  R = 2: both rounded
+//   I = 0: fma(a.y, b.x, a.x b.y);     I = 1: fma(a.x, b.y, a.y b.x)
+// Each site below names what the four-wave form -- the one the default workload runs -- was compiled to, so its bits stay.
+template <int R, int I>
+__device__ __forceinline__ float2 cmul_as(float2 a, float2 b) {
+#pragma clang fp contract(off)
+  float re, im;
+  if (R == 1) {
+    float const t = a.y * b.y;
+    re = __builtin_fmaf(a.x, b.x, -t);
+  } else {
+    float const t0 = a.x * b.x, t1 = a.y * b.y;
+    re = t0 - t1;
+  }
+  if (I == 0) {
+    float const t = a.x * b.y;
+    im = __builtin_fmaf(a.y, b.x, t);
+  } else {
+    float const t = a.y * b.x;
+    im = __builtin_fmaf(a.x, b.y, t);
+  }
+  return make_float2(re, im);
+}
+// the de-emphasis filter's three kinds of product: a forward (decimation in frequency) stage's twiddle, the response on the
+// two separated spectra, an inverse stage's twiddle
+__device__ __forceinline__ float2 cmul_fwd_stage(float2 d, float2 w, int s) {
+  return s == 5 ? cmul_as<2, 0>(d, w) : cmul_as<1, 1>(d, w);
+}
+__device__ __forceinline__ float2 cmul_response(float2 h, float2 z) { return cmul_as<1, 0>(h, z); }
+__device__ __forceinline__ float2 cmul_inv_stage(float2 z, float2 w) { return cmul_as<1, 0>(z, w); }
+
 __device__ __forceinline__ void put_status(kq_chan_status &st, const Geom &g, const ChanDev &ch, const Planes &pl, int c, int b,
                                            int compute_n0, double n0_rate, float &n0) {
   st.if_power = pl.if_power[b];
@@ -202,18 +238,18 @@ __device__ void fm_channel_pair(const Geom &g, const ChanDev &ch, const Planes &
 #pragma unroll
       for (int s = 5; s >= 0; s--) {  // forward, decimation in frequency: natural in, bit-reversed out
         float2 const r = lane_xor_pow2(z, s, lane);
-        z = ((lane >> s) & 1) ? cmul(csub(r, z), wf[s]) : cadd(z, r);
+        z = ((lane >> s) & 1) ? cmul_fwd_stage(csub(r, z), wf[s], s) : cadd(z, r);
       }
       float2 const zm = cconj(shfl2(z, herm_src));  // conj(Z[64 - k])
       float2 const z1 = make_float2(0.5f * (z.x + zm.x), 0.5f * (z.y + zm.y));     // spectrum of the real part
       float2 const z2 = make_float2(0.5f * (z.y - zm.y), -0.5f * (z.x - zm.x));    // spectrum of the imaginary part
-      float2 g1 = cmul(HAf, z1), g2 = cmul(HAf, z2);  // filter.c:206-208 on both
+      float2 g1 = cmul_response(HAf, z1), g2 = cmul_response(HAf, z2);  // filter.c:206-208 on both
       if (real_bin) g1.y = g2.y = 0.f;                // the c2r transform ignores these imaginary parts
       z = make_float2(g1.x - g2.y, g1.y + g2.x);      // g1 + j g2
 #pragma unroll
       for (int s = 0; s < 6; s++) {  // backward, decimation in time: bit-reversed in, natural out
         int const bit = (lane >> s) & 1;
-        float2 const v = bit ? cmul(z, wi[s]) : z;
+        float2 const v = bit ? cmul_inv_stage(z, wi[s]) : z;
         float2 const r = lane_xor_pow2(v, s, lane);
         z = bit ? csub(r, v) : cadd(v, r);
       }
@@ -450,12 +486,12 @@ __device__ void fm_channel_four_waves(const Geom &g, const ChanDev &ch, const Pl
 #pragma unroll
         for (int s = 5; s >= 0; s--) {  // forward, decimation in frequency: natural in, bit-reversed out
           float2 const r = lane_xor_pow2(z, s, lane);
-          z = ((lane >> s) & 1) ? cmul(csub(r, z), wf[s]) : cadd(z, r);
+          z = ((lane >> s) & 1) ? cmul_fwd_stage(csub(r, z), wf[s], s) : cadd(z, r);
         }
         float2 const zm = cconj(shfl2(z, herm_src));  // conj(Z[64 - k])
         float2 const z1 = make_float2(0.5f * (z.x + zm.x), 0.5f * (z.y + zm.y));     // spectrum of the real part
         float2 const z2 = make_float2(0.5f * (z.y - zm.y), -0.5f * (z.x - zm.x));    // spectrum of the imaginary part
-        float2 g1 = cmul(HAf, z1), g2 = cmul(HAf, z2);  // filter.c:206-208 on both
+        float2 g1 = cmul_response(HAf, z1), g2 = cmul_response(HAf, z2);  // filter.c:206-208 on both
         if (real_bin) g1.y = g2.y = 0.f;                // the c2r transform ignores these imaginary parts
         s_z[par][lane] = make_float2(g1.x - g2.y, g1.y + g2.x);  // g1 + j g2
         hist = have1 ? xo : out;  // lanes 0-31: the last block processed becomes the history (filter.c:168)
@@ -505,7 +541,7 @@ __device__ void fm_channel_four_waves(const Geom &g, const ChanDev &ch, const Pl
 #pragma unroll
       for (int s = 0; s < 6; s++) {  // backward, decimation in time: bit-reversed in, natural out
         int const bit = (lane >> s) & 1;
-        float2 const v = bit ? cmul(z, wi[s]) : z;
+        float2 const v = bit ? cmul_inv_stage(z, wi[s]) : z;
         float2 const r = lane_xor_pow2(v, s, lane);
         z = bit ? csub(r, v) : cadd(v, r);
       }

@@ -649,6 +649,9 @@ __global__ __launch_bounds__(kT, 4) void k_filter_full16k(Geom g, ChanDev ch, Pl
   // (the exchange buffer is free since the last barrier of transpose 2; done first so that ya / yb die before compute_n0)
   float2 *Xs = xch;
   float2 *G = Xs + Ndec;
+  // the wave's number, on the scalar unit: what only one wave does (the N/D = 64 prefetch and epilogue, the reduction slots) is
+  // a scalar branch or a scalar address from here on, not a comparison and an address per lane
+  int const wv = __builtin_amdgcn_readfirstlane(t >> 6);
   auto to_f2 = [](v2f a) { return make_float2(a.x, a.y); };
   if constexpr (BIG != 0) {
     // bins k = 4 q + r4 of this sub-transform that the slave reads, to global memory at k mod N_dec (k_epilogue64k)
@@ -674,10 +677,14 @@ __global__ __launch_bounds__(kT, 4) void k_filter_full16k(Geom g, ChanDev ch, Pl
     }
   } else if (Ndec <= 1024) {
     // the slave's bins all lie in the first and the last 1024: rows k3 = 0 and k3 = 15 only
-    if (ka <= Ndec / 2) Xs[ka] = to_f2(ya[0]);
-    if (kb <= Ndec / 2) Xs[kb] = to_f2(yb[0]);
-    if (ka + 15 * 1024 > kN - Ndec / 2) Xs[ka - 1024 + Ndec] = to_f2(ya[15]);
-    if (kb + 15 * 1024 > kN - Ndec / 2) Xs[kb - 1024 + Ndec] = to_f2(yb[15]);
+    // (kb = ka + 16: the four conditions are comparisons of ka with scalars, the four addresses two lane addresses and an
+    // immediate offset)
+    int const hd = Ndec / 2;
+    float2 *const lo = Xs + ka, *const hi = lo + (Ndec - 1024);
+    if (ka <= hd) lo[0] = to_f2(ya[0]);
+    if (ka <= hd - kFull16kHalf) lo[kFull16kHalf] = to_f2(yb[0]);
+    if (ka > 1024 - hd) hi[0] = to_f2(ya[15]);
+    if (ka > 1024 - kFull16kHalf - hd) hi[kFull16kHalf] = to_f2(yb[15]);
   } else {
 #pragma unroll
     for (int k3 = 0; k3 < 16; k3++) {
@@ -696,10 +703,26 @@ __global__ __launch_bounds__(kT, 4) void k_filter_full16k(Geom g, ChanDev ch, Pl
   }
   // N/D = 64: the wave that will run the inverse transform fetches what it needs now, under compute_n0
   const float2 *H = ch.resp + (size_t)c * Ndec;
-  bool const isb = (ch.fflags[c] & FLAG_ISB) != 0;
-  v2f epi_h = {0.f, 0.f}, epi_h2 = {0.f, 0.f}, epi_w[5] = {};
+  // (the channel's words are read through the constant address space, as the compute_n0 masks below are: the host writes them
+  // on this stream between launches, nothing writes them while a filter kernel runs -- scalar loads, no vector register)
+  typedef const int __attribute__((address_space(4))) *chan_words;
+  int const cu = __builtin_amdgcn_readfirstlane(c);
+  // (the flag word stays one scalar register and is tested where it is used: as a truth value carried from here to the
+  // epilogue it is a register pair, and the tail has none to spare)
+  int const isb_word = ((chan_words)ch.fflags)[cu] & FLAG_ISB;
+  auto isb_now = [&]() {
+    int w = isb_word;
+    asm("" : "+s"(w));
+    return w != 0;
+  };
+  bool const isb = isb_now();
+  // Only the waves that run an epilogue load these, and nothing else reads them: they start out undefined (an empty
+  // definition, no instruction), not as fourteen zeros written by every wave.
+  v2f epi_h, epi_h2, epi_w[5];
+  asm("" : "=v"(epi_h), "=v"(epi_h2));
+  asm("" : "=v"(epi_w[0]), "=v"(epi_w[1]), "=v"(epi_w[2]), "=v"(epi_w[3]), "=v"(epi_w[4]));
   bool const epi64 = BIG == 0 && (EPI == 1 || (EPI == 0 && Ndec == 64));
-  if (epi64 && t < 64) {
+  if (epi64 && wv == 0) {
     int const q = (int)(__brev((unsigned)t) >> 26);
     epi_h = ld2(H + q);
     if (isb) epi_h2 = ld2(H + ((64 - q) & 63));
@@ -731,9 +754,8 @@ __global__ __launch_bounds__(kT, 4) void k_filter_full16k(Geom g, ChanDev ch, Pl
     // (read through the constant address space: nothing writes the masks while a kernel runs, and only then may the
     // compiler fetch them with scalar loads this late in the kernel, behind global stores it cannot tell apart from them)
     typedef const unsigned long long __attribute__((address_space(4))) *lane_masks;
-    int const ns = __builtin_amdgcn_readfirstlane(ch.n0slot[c]);  // channels with the same filter edges share one mask set
-    lane_masks const lm = (lane_masks)(
-        ch.n0lane + ((size_t)(ns * (BIG ? 4 : 1) + r4) * (kT / 64) + __builtin_amdgcn_readfirstlane(t >> 6)) * 32);
+    int const ns = ((chan_words)ch.n0slot)[cu];  // channels with the same filter edges share one mask set
+    lane_masks const lm = (lane_masks)(ch.n0lane + ((size_t)(ns * (BIG ? 4 : 1) + r4) * (kT / 64) + wv) * 32);
 #pragma unroll
     for (int k3 = 0; k3 < 16; k3++) {
       // spelled out (given `x*x + y*y` on both halves the compiler pairs the additions into one v_pk_add_f32 behind three
@@ -765,11 +787,13 @@ __global__ __launch_bounds__(kT, 4) void k_filter_full16k(Geom g, ChanDev ch, Pl
       s2 = ((a0 + a1) + (a2 + a3)) + ((a4 + a5) + (a6 + a7));
     }
     float const tot = wave_sum_to63(s2.x + s2.y);
-    if ((t & 63) == 63) red_f[0][t >> 6] = tot;
+    bool const last_lane = (t & 63) == 63;
+    if (last_lane) red_f[0][wv] = tot;
     __syncthreads();
-    float total = 0;
+    // (starts from the first slot, not from 0: the slots are sums of squares, never -0, so 0 + slot is the slot)
+    float total = red_f[0][0];
 #pragma unroll
-    for (int k = 0; k < kT / 64; k++) total += red_f[0][k];
+    for (int k = 1; k < kT / 64; k++) total += red_f[0][k];
     int bins1 = outside;
     unsigned long long *const slots = BIG ? big.sync + ((size_t)c * g.max_blocks + b) * 12 : nullptr;
     if constexpr (BIG != 0) {
@@ -795,13 +819,28 @@ __global__ __launch_bounds__(kT, 4) void k_filter_full16k(Geom g, ChanDev ch, Pl
       int const e = (__float_as_int(thr) >> 23) & 0xff;  // biased exponent, 1..254 here
       float const scale = __int_as_float((127 + 40 + 127 - e) << 23);
       float const cs = thr * scale;  // exact: a power-of-two scaling inside the normal range
-      v2f const nsc = (v2f){-scale, -scale}, c2 = (v2f){cs, cs};
-      v2f acc_e = (v2f){0.f, 0.f}, acc_o = acc_e, cnt_e = acc_e, cnt_o = acc_e;
+      // scale and cs are one register each: both halves of the packed instruction read the low word (op_sel_hi), the sign of
+      // scale is a source modifier, and the upper words of the pairs are never read -- no negation, no copies into pairs
+      v2f sc2, c2;
+      sc2.x = scale;
+      c2.x = cs;
+      asm("" : "=v"(sc2.y), "=v"(c2.y));
+      v2f acc_e, acc_o, cnt_e, cnt_o;
 #pragma unroll
       for (int k3 = 0; k3 < 16; k3++) {
         v2f keep;
-        asm("v_pk_fma_f32 %0, %1, %2, %3 clamp" : "=v"(keep) : "v"(nsc), "v"(pp[k3]), "v"(c2));
-        if (k3 & 1) {
+        asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,0] neg_lo:[1,0,0] neg_hi:[1,0,0] clamp"
+            : "=v"(keep)
+            : "v"(sc2), "v"(pp[k3]), "v"(c2));
+        // the first term of each chain stands alone: keep is 0 or 1 and a bin's power is never -0, so keep * p + 0 is the
+        // product and keep + 0 is keep, bit for bit
+        if (k3 == 0) {
+          acc_e = keep * pp[k3];
+          cnt_e = keep;
+        } else if (k3 == 1) {
+          acc_o = keep * pp[k3];
+          cnt_o = keep;
+        } else if (k3 & 1) {
           acc_o = rfft::pk_fma(keep, pp[k3], acc_o);
           cnt_o += keep;
         } else {
@@ -811,9 +850,9 @@ __global__ __launch_bounds__(kT, 4) void k_filter_full16k(Geom g, ChanDev ch, Pl
       }
       v2f const acc2 = acc_e + acc_o, cnt2 = cnt_e + cnt_o;
       float const acc = wave_sum_to63(acc2.x + acc2.y), cnt = wave_sum_to63(cnt2.x + cnt2.y);
-      if ((t & 63) == 63) {
-        red_f[1][t >> 6] = acc;
-        red_c[t >> 6] = cnt;
+      if (last_lane) {
+        red_f[1][wv] = acc;
+        red_c[wv] = cnt;
       }
       // the sums meet behind the barrier that also publishes the slave's bins, below
     } else {
@@ -842,6 +881,9 @@ __global__ __launch_bounds__(kT, 4) void k_filter_full16k(Geom g, ChanDev ch, Pl
           acc += ta ? pp[k3].x : 0.f;
           acc += tb ? pp[k3].y : 0.f;
           wave_bins += __popcll(__ballot(ta)) + __popcll(__ballot(tb));
+          // counted here and now: left alone the compiler keeps all 32 comparison masks -- 64 scalar registers -- for the one
+          // lane that stores the count, and pays for them with lane spills on the fast path above
+          asm volatile("" : "+s"(wave_bins));
         }
         acc = wave_sum(acc);
         __syncthreads();  // the previous round's slots have been read
@@ -882,9 +924,9 @@ __global__ __launch_bounds__(kT, 4) void k_filter_full16k(Geom g, ChanDev ch, Pl
   // (the last wave's first lane: wave 0 has the inverse transform to run, and this division -- float, then double -- would
   // sit in front of it on the workgroup's critical path)
   if (N0 && n0_fast && t == kT - 64) {
-    float tf = 0, bins = 0;
+    float tf = red_f[1][0], bins = red_c[0];  // (neither is ever -0: no 0 + in front)
 #pragma unroll
-    for (int k = 0; k < kT / 64; k++) {
+    for (int k = 1; k < kT / 64; k++) {
       tf += red_f[1][k];
       bins += red_c[k];
     }
@@ -908,10 +950,13 @@ __global__ __launch_bounds__(kT, 4) void k_filter_full16k(Geom g, ChanDev ch, Pl
     // cfg 3 / 4: one wave multiplies and runs the 64-point inverse transform in its registers (lane exchanges, no
     // barriers); the other seven are done.  Its response bins and stage twiddles were fetched before compute_n0
     // (epi_*), so nothing here waits for memory: the workgroup's slot on the CU is held by this tail alone.
-    if (t >= 64) return;
+    // (compared afresh: kept from the prefetch's `wv == 0` the answer would occupy a scalar register pair through compute_n0)
+    int wv_now = wv;
+    asm("" : "+s"(wv_now));
+    if (wv_now != 0) return;
     int const q = (int)(__brev((unsigned)t) >> 26);  // decimation in time: bit-reversed in, natural out
     v2f z = pk_cmul(epi_h, ld2(Xs + q));
-    if (isb && q != 0 && q != 32) {  // filter.c:242-248
+    if (isb_now() && q != 0 && q != 32) {  // filter.c:242-248
       v2f const other = pk_cmul(epi_h2, ld2(Xs + 64 - q));
       v2f const oc = (v2f){other.x, -other.y};
       z = q < 32 ? z + oc : z - oc;

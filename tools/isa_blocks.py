@@ -7,6 +7,12 @@
 Prints, for every basic block of at least `min_instructions`, the number of vector-ALU instructions (packed ones
 separately), scalar, LDS and global-memory instructions.  With --ops BLOCK the opcode histogram of that block.
 The dynamic count of a path is the sum over the blocks it runs through; compare with SQ_INSTS_VALU / SQ_WAVES.
+
+  python3 tools/isa_blocks.py FILE.s KERNEL --path START DECISIONS
+
+walks one executed path instead: from START (a block label, or `barrier:N` = behind the kernel's N-th s_barrier) to
+s_endpgm, one letter of DECISIONS per conditional branch met (T taken, N falls through), and prints the branches with what
+was decided and the vector instructions of the path by opcode.  (Loops: one letter per trip.)
 """
 import collections
 import re
@@ -31,9 +37,73 @@ def kernel_lines(path, name):
     return out
 
 
+def walk(lines, start, decisions):
+    """Instructions executed from `start` (a label, or `barrier:N` = behind the N-th s_barrier of the kernel, counted from 1)
+    to s_endpgm.  Every conditional branch met consumes one letter of `decisions`: T taken, N not taken; s_branch is
+    followed.  Returns (opcode histogram, [(branch line, target, letter)])."""
+    labels = {}
+    for i, s in enumerate(lines):
+        m = re.match(r"^(\.LBB\d+_\d+):", s)
+        if m:
+            labels[m.group(1)] = i
+    if start.startswith("barrier:"):
+        want, seen = int(start.split(":")[1]), 0
+        for i, s in enumerate(lines):
+            if s.startswith("s_barrier"):
+                seen += 1
+                if seen == want:
+                    break
+        else:
+            raise SystemExit("fewer than %d barriers" % want)
+        pc = i + 1
+    else:
+        pc = labels[start]
+    ops, taken, d = collections.Counter(), [], list(decisions)
+    while pc < len(lines):
+        s = lines[pc]
+        pc += 1
+        if not s or s[0] in ";." or s.endswith(":"):
+            continue
+        f = s.replace(",", " ").split()
+        op = f[0]
+        ops[op] += 1
+        if op == "s_endpgm":
+            break
+        if op == "s_branch":
+            pc = labels[f[1]]
+        elif op.startswith("s_cbranch"):
+            if not d:
+                raise SystemExit("out of decisions at: " + s)
+            letter = d.pop(0)
+            taken.append((s, letter))
+            if letter == "T":
+                pc = labels[f[1]]
+    if d:
+        raise SystemExit("decisions left over: " + "".join(d))
+    return ops, taken
+
+
+def print_path(lines, start, decisions):
+    ops, taken = walk(lines, start, decisions)
+    for s, letter in taken:
+        print("  %-40s %s" % (s, "taken" if letter == "T" else "falls through"))
+    valu = {k: v for k, v in ops.items() if k.startswith("v_")}
+    packed = sum(v for k, v in valu.items() if k.startswith("v_pk_"))
+    print("executed path from %s [%s]: valu %d (packed %d) salu %d lds %d vmem %d" % (
+        start, decisions, sum(valu.values()), packed, sum(v for k, v in ops.items() if k.startswith("s_")),
+        sum(v for k, v in ops.items() if k.startswith("ds_")),
+        sum(v for k, v in ops.items() if k.startswith(("global_", "buffer_", "flat_", "scratch_")))))
+    for k, v in sorted(valu.items(), key=lambda kv: (-kv[1], kv[0])):
+        print("    %-28s %d" % (k, v))
+
+
 def main():
     path, name = sys.argv[1], sys.argv[2]
     args = sys.argv[3:]
+    if "--path" in args:
+        i = args.index("--path")
+        print_path(kernel_lines(path, name), args[i + 1], args[i + 2])
+        return
     ops_of = None
     if "--ops" in args:
         i = args.index("--ops")
