@@ -2103,6 +2103,215 @@ int kq_ale_sync(kq_ale_bank *bank);
 /* Stream index back to 0; every slot restarts cold with its settings at the next call, as if set again */
 int kq_ale_reset(kq_ale_bank *bank);
 
+/* --- GMDSS digital selective calling (ITU-R M.493) decoder bank -----------------------------------------------------------------
+ * Up to 16384 decoder slots, each reading DSC sequences from one audio row, whole messages as events: a receiver bank with
+ * a USB channel parked on each of 2187.5, 4207.5, 6312, 8414.5, 12577 and 16804.5 kHz, and a slot on each, keeps the HF /
+ * MF watch; VHF channel 70 is read from a flat FM channel resampled to 96 kHz (kq_rsmp_*).  A bank's channels can be decoded
+ * in place on its stream after kq_bank_join, and several slots may read one row at different tone pairs.  The reference
+ * has no DSC decoder: the algorithm is defined here.  Everything after the quantiser is exact integer arithmetic, so no
+ * result depends on how sums are ordered or how the stream is cut into calls.
+ * The signal, WRITTEN DOWN FROM MEMORY (no copy of the Recommendation was at hand; ka9q_sdr_amd/itu493.py says the same).
+ * 2-FSK, state B is 1 and state Y is 0: 100 baud at 1700 +- 85 Hz on HF / MF, 1200 baud with 1300 Hz (B) and 2100 Hz (Y) on
+ * VHF.  Which tone is B turns over with the sideband, so the params name both (mark = B, space = Y) and the sync attempt
+ * takes the complement of the register as well.  A symbol is ten bits: seven information bits, the lowest first, then the
+ * number of zeros among those seven as three bits, the highest first; 128 of 1024 words are symbols, and any single wrong
+ * bit is seen.  Symbol 125 goes out as 1011111001 (the one pattern remembered on its own; tested).  A sequence is a dot
+ * pattern (20 or 200 alternating bits) and then the symbol places 0, 1, 2, ..: even places are DX, odd places RX; places 0,
+ * 2, .. 10 carry 125; places 1, 3, .. 15 carry 111, 110, .. 104; message symbol i = 0, 1, .. goes out at DX place 12 + 2 i
+ * and again at RX place 17 + 2 i, five places (500 ms at 100 baud) later.  Symbols 0 and 1 are both the format specifier;
+ * the message ends with an end-of-sequence symbol (117, 122 or 127) and one error-check symbol, the XOR of the information
+ * bits of the symbols 1 .. end-of-sequence (one format specifier, not two).  UNVERIFIED against the Recommendation: which
+ * audio tone is B on each sideband; the bit order of the count; what the DX places carry while the last RX copies go out
+ * (itu493.py repeats the end-of-sequence symbol there; the decoder never reads them); that 117, 122 and 127 appear nowhere
+ * inside a message; the layouts of the three messages itu493.py builds; the expansion sequences of M.493-13 and later.
+ * Per slot, x[n] is its input row; n counts samples since create or kq_dsc_reset on a grid shared by every slot, and x[n] = 0
+ * before the slot was set.  Fs = samprate, B = block_len (8..256); frame k is the samples [k B, (k + 1) B).
+ *   quantise, table, correlate, window   kq_rtty_*'s, to the letter: q[n], C[j], inc_m = rint(mark 2^32 / Fs) and inc_s
+ *              likewise (kq_dsc_get_slot), ph(n) = (n inc) mod 2^32, I and Q per frame and tone below 2^38, reduced a = I >>
+ *              12, b = Q >> 12, tb = rint(256 Fs / (B baud)) with 2048 <= tb <= 8192, W = (tb + 128) >> 8 frames, the window
+ *              sums SI, SQ over the frames k - W + 1 .. k (zeros before the set), Pm = SIm^2 + SQm^2 and Ps likewise as
+ *              uint64, below 2^63.  q = tb >> 2, a quarter bit.  hi = max(Pm, Ps), lo = min(Pm, Ps).
+ *   state      frames, ph (0 early, 1 centre, 2 late: the point taken next), t (signed, 1/256 frame, to that point), pe, ee,
+ *              el, ec (hi at the last early point; the smoothed early, late and centre), bit, hi and lo (of the last
+ *              centre), sig, nse, the register r (64 bits), nbits, synced, bitpos, the counters, and the open message
+ *              (kq_dsc_message: inverted, place, nsym, nres, holes, from_rx, run, ecc, eos, hole_mask, sync_sample,
+ *              msg[64]).  At the set all zero.
+ *   step       one per completed frame k: frames += 1, saturating; t -= 256.  If t >= 128 nothing more happens in this
+ *              frame.  Otherwise the frame is a point, taken in turn by ph:
+ *                early   pe = hi, t += q, ph = 1.
+ *                centre  bit = Pm >= Ps (1 is B), hi and lo are taken, t += q, ph = 2.
+ *                late    ph = 0, and with pl = hi the bit is read, in this order:
+ *     1 timing    kq_psk_*'s and kq_ale_*'s: ee += (pe - ee) >> 3, el += (pl - el) >> 3 (arithmetic shifts of signed
+ *                 differences, here and below); m = max(ee, el); adj = -(tb >> 5) if ee > el and ee - el > (m >> 3), +(tb >> 5)
+ *                 if el > ee and el - ee > (m >> 3), else 0; t += tb - 2 q + adj.  At a change of tone the window holds half of
+ *                 each and hi dips to a quarter, so the walk settles with the dips half a bit from the centre; through a
+ *                 run of equal bits both sides read alike and the clock holds.  Half a bit out the walk has no slope: the
+ *                 dips sit on the centre, early and late read alike, and of the starting phases one in twenty or so
+ *                 stayed there through a 20-bit dot pattern and lost the message.  So the centre is watched as well: ec +=
+ *                 (hi - ec) >> 3, and if adj == 0 and ec + (m >> 3) < min(ee, el) -- the centre reads worse than both
+ *                 sides -- t += tb >> 5, one step late, which the walk then takes up.  (|Pm - Ps| in place of hi, which
+ *                 falls to nothing at a change of tone, did not cure it in a one-off run on the model.)
+ *     2 levels    sig += (hi - sig) >> 4, nse += (lo - nse) >> 4.  open = frames >= warm and sig >= min_p and 16 sig >= snr
+ *                 nse, the two products taken exactly (128-bit compare).
+ *     3 register  r = (r << 1 | bit) mod 2^64, nbits += 1 (mod 2^32): shifted whether in sync or not.  It holds the last six
+ *                 symbol places and four bits, so when the RX copy of a symbol is in bits 9..0 its DX copy, five places
+ *                 older, is in bits 59..50.  A ten-bit word w (its first bit sent in bit 9) is a symbol if 7 - popcount(w >>
+ *                 3) == (w & 7); its value is the seven bits of w >> 3 reversed.
+ *     4 sync      while not synced, and only if open: the attempt on x = r, and if that fails on x = ~r.  s0 = x & 1023, s1 =
+ *                 x >> 10 & 1023, s2 = x >> 20 & 1023, s3 = x >> 30 & 1023, the last four places, s0 the latest.  s0 must be a
+ *                 symbol of value v, 104 <= v <= 110.  matches = (s2 is the word of v + 1) + (v >= 106 and s1 is the word of
+ *                 125) + (v >= 105 and s3 is the word of 125): the places the phasing sequence fixes.  At matches >= acq:
+ *                 synced = 1, inverted = (x was ~r), place = 2 (111 - v) + 1, bitpos = 0, the open message emptied (msg all
+ *                 0, nsym = nres = holes = from_rx = run = ecc = eos = 0, hole_mask = 0), sync_sample = (k + 1) B, syncs +=
+ *                 1.  With acq = 2 there are seven values of s0 and two of three other places exact: noise passes about 7 /
+ *                 1024 * 3 / 2^20 = 2e-8 of the attempts, one in 5e7 bits (six days of an open gate at 100 baud).  The step
+ *                 ends here.
+ *     5 message   while synced (the gate no longer matters: to drop sync on a fade would throw away what the time diversity
+ *                 is for): bitpos += 1, and at bitpos == 10: bitpos = 0, place += 1, and if place is odd and >= 17 message
+ *                 symbol i = (place - 17) / 2 is resolved.  With x = ~r if inverted, else r: dx = x >> 50 & 1023, rx = x &
+ *                 1023.  If dx is a symbol its value d is taken; else if rx is one, its value, and from_rx += 1; else the
+ *                 symbol is unresolved.  msg[i] = d, or 0xFF; nsym = i + 1.
+ *                   eos == 1     this is the error-check symbol.  flags bit 0 is set if it is unresolved, or holes > 0, or d
+ *                                != ecc; an unresolved one counts holes += 1, hole_mask |= 1 << i.  The message is filed,
+ *                                rule (a), and synced = 0.
+ *                   unresolved   holes += 1, hole_mask |= 1 << i, run += 1.  At run == lose the message ends, rule (c): filed
+ *                                with flags bit 2 (and bit 0) if nres >= 8, else aborted += 1, nothing filed; synced = 0.
+ *                   resolved     run = 0, nres += 1; if i >= 1, ecc ^= d; if d is 117, 122 or 127, eos = 1.
+ *                   then, if still synced and nsym == 64: filed with flags bit 1 (and bit 0), rule (b); synced = 0.
+ *   event      sym[64] (msg: the values, 0xFF where unresolved, 0 behind nsym; the last is the error-check symbol where flags
+ *              bit 0..2 are clear), nsym, flags (bit 0 the check failed or could not be made, bit 1 truncated at 64
+ *              symbols, bit 2 lost, bit 3 the stream was inverted), holes, from_rx, hole_mask, sync_sample, end_sample = (k
+ *              + 1) B of the late point that read the last bit, sig and nse there.  events += 1 for each; it goes to the
+ *              slot's arena, or dropped += 1 when that holds max_events.  frames, events, dropped, syncs and aborted
+ *              saturate at 2^32 - 1.  A single hole can be rebuilt from the error-check symbol on the host
+ *              (itu493.repair); the device does not.
+ * kq_dsc_remove and kq_dsc_reset discard the open message.  Carried between calls: the open frame's I and Q per tone, the
+ * reduced sums of the last 31 frames (W - 1 at the most), the four window sums and all of the state above; so the same
+ * stream split differently into calls or blocks gives the same events and status.  kq_dsc_status holds all of it but the
+ * past frames.
+ * Limits (refused by kq_dsc_create / kq_dsc_set with the reason in kq_last_error, before any HIP call): kq_rtty_*'s --
+ * samprate positive and finite; 8 <= B <= 256; warm 0..65535; snr 16..4095; min_p <= 2^55; input_scale > 0; max_slots
+ * 1..16384; max_events 1..4096; max_samples 1..2^28; per slot 0 < mark, space < Fs / 2, mark != space, baud positive and
+ * finite with 2048 <= tb <= 8192 -- and acq 1..3, lose 1..15.  100 baud fits B = 8..15 at 12 kHz and B = 15..60 at 48 kHz.
+ * 1200 baud needs 8 frames of 8 samples in a bit, Fs >= 76.8 kHz: a row from kq_rsmp_* at 96 kHz with B = 8..10.
+ * Device memory per slot: 120 max_events of arena, about 800 bytes of state, history and parameters; 2 KiB of table per
+ * bank.
+ * The default snr of 64 (sig / nse = 4): in the model 240 s of noise alone hold 16 sig / nse between 34 and 74, mean 48.5
+ * (the larger of two noise powers is three times the smaller in the mean), and the gate is open at 1282 of 23947 bits; a
+ * signal at an Es/N0 of 8 dB holds it between 64 and 174, mean 102, at 10 dB between 91 and 235.  The gate is a squelch on
+ * the sync attempt only: noise and a steady tone take no sync and file nothing in 240 s with the gate held open either, by
+ * the phasing sequence and the symbol code alone (tests/test_dsc_model.py).  So a gate that opens on noise costs nothing
+ * but the attempts, while one that shuts on a weak signal costs messages.
+ * Absent: NAVTEX / SITOR-B (the same modulation and five-place diversity, but the CCIR 476 alphabet, 35 code words that
+ * were not at hand and cannot be derived: nothing is built for it); soft decisions and a bit-wise vote between the copies;
+ * AFC; a per-tone threshold under selective fading; the message semantics beyond itu493.py's three builders.  NOTHING HERE
+ * HAS MET A SIGNAL OFF THE AIR.  In the model, with white noise, eight individual calls (23 message symbols each behind a
+ * 20-bit dot pattern, each in a run of its own) are filed whole with the check good at both (12000, 12) and (39062.5, 32)
+ * at an Es/N0 (a tone's power times the bit over N0) of 20, 14 and 12 dB (8 of 8); at 10 dB 7 of 8 at both, and 8 of 8 once
+ * itu493.repair has mended the one hole; at 8 dB 2 and 1 of 8 (4 and 4 mended); at 6 dB none.  The fall is steep because a
+ * message is whole only if each of its 23 symbols has one of two ten-bit copies without a wrong bit.  At 8 and 6 dB up to
+ * three of the eight runs file a message with a symbol that was not sent -- two wrong bits can keep the count right -- and
+ * the check catches it.  Measured on the integer model on a CPU (tests/test_dsc_model.py prints the figures); the kernel
+ * equals it bit for bit.
+ * Calls: as kq_rtty_*.  kq_dsc_create, kq_dsc_set and kq_dsc_remove touch no device. */
+typedef struct kq_dsc_bank kq_dsc_bank;
+typedef struct kq_dsc_config {
+  int device;
+  double samprate;           /* Fs: input samples per second; a double, so that 39 062.5 is exact */
+  unsigned block_len;        /* B: samples per frame, 8..256 */
+  unsigned warm;             /* frames after the set in which no sync is sought while the levels train (64) */
+  unsigned snr;              /* least sig / nse for a sync attempt, in sixteenths (64; noise alone gives about 48) */
+  uint64_t min_p;            /* least sig (65536) */
+  float input_scale;         /* 32767 suits audio of full scale 1 */
+  unsigned max_slots;        /* slots 0 .. max_slots - 1 (limit 16384) */
+  unsigned max_events;       /* arena places per slot between kq_dsc_clear_events calls */
+  size_t max_samples;        /* largest nblocks * block_len of one kq_dsc_process call */
+  void *stream;              /* hipStream_t, NULL = own stream; kq_bank_stream(bank) puts it beside a receiver bank */
+  unsigned acq;              /* places of the phasing sequence, beside the latest, that must match to take sync, 1..3 (2) */
+  unsigned lose;             /* unresolved symbols in a row that end a message, 1..15 (3) */
+} kq_dsc_config;
+typedef struct kq_dsc_params {
+  unsigned source;           /* input row this slot decodes (a receiver bank's channel index) */
+  float mark, space;         /* Hz: state B (1) and state Y (0); 1785 and 1615 are a guess for a USB channel, see above */
+  float baud;                /* 100, or 1200 */
+} kq_dsc_params;
+typedef struct kq_dsc_message {  /* the open (or last) message, as kq_dsc_status carries it */
+  uint32_t inverted;         /* sync was taken on the complement of the register */
+  uint32_t place;            /* the place of the last whole symbol, while synced */
+  uint32_t nsym;             /* message symbols so far */
+  uint32_t nres;             /* of them resolved */
+  uint32_t holes;            /* and unresolved */
+  uint32_t from_rx;          /* resolved by the RX copy */
+  uint32_t run;              /* unresolved in a row */
+  uint32_t ecc;              /* the XOR so far */
+  uint32_t eos;              /* the last symbol was an end of sequence: the next is the error check */
+  uint32_t reserved;         /* 0 */
+  uint64_t hole_mask;        /* bit i: message symbol i is unresolved */
+  uint64_t sync_sample;      /* the end of the frame that took sync */
+  uint8_t msg[64];           /* the values, 0xFF where unresolved, 0 behind nsym */
+} kq_dsc_message;
+typedef struct kq_dsc_status {
+  uint32_t frames;           /* completed since the slot was set */
+  uint32_t ph;               /* the point taken next: 0 early, 1 centre, 2 late */
+  int32_t t;                 /* 1/256 frame to that point */
+  uint32_t bit;              /* at the last centre */
+  uint32_t nbits;            /* bits read since the set */
+  uint32_t synced;
+  uint32_t bitpos;           /* bits of the symbol behind the last whole one, 0..9, while synced */
+  uint32_t events;           /* filed since the set, those dropped included */
+  uint32_t dropped;
+  uint32_t syncs;            /* times sync was taken */
+  uint32_t aborted;          /* messages that ended by rule (c) with fewer than eight symbols resolved */
+  uint32_t reserved;         /* 0 */
+  uint64_t sig, nse;         /* the larger and the smaller power at the bits' centres */
+  uint64_t ee, el, ec;       /* the smoothed early, late and centre power */
+  uint64_t pe, hi, lo;       /* hi at the last early point; hi and lo at the last centre */
+  uint64_t r;                /* the last 64 bits, the latest in bit 0 */
+  int32_t sum[2][2];         /* SI, SQ of mark and of space at the last completed frame */
+  int64_t acc[2][2];         /* I and Q of the open frame, mark and space */
+  kq_dsc_message open;
+} kq_dsc_status;
+typedef struct kq_dsc_event {
+  uint8_t sym[64];           /* the message symbols, 0xFF where unresolved, 0 behind nsym */
+  uint32_t nsym;
+  uint32_t flags;            /* bit 0: check failed or not made; 1: truncated; 2: lost; 3: inverted */
+  uint32_t holes;
+  uint32_t from_rx;
+  uint64_t hole_mask;
+  uint64_t sync_sample;
+  uint64_t end_sample;       /* the end of the frame that read the message's last bit */
+  uint64_t sig, nse;         /* at that bit */
+} kq_dsc_event;
+typedef struct kq_dsc_slot {
+  uint32_t inc_m, inc_s;     /* the phase increments of mark and space */
+  uint32_t tb;               /* the bit in 1/256 frame */
+  uint32_t W;                /* the window in frames */
+} kq_dsc_slot;
+
+kq_dsc_bank *kq_dsc_create(const kq_dsc_config *cfg);
+int kq_dsc_destroy(kq_dsc_bank *bank);
+/* Put a decoder in `slot` (or replace the one there): a cold start at the next call's first sample, its arena empty.
+ * Touches no device, as kq_rtty_set */
+int kq_dsc_set(kq_dsc_bank *bank, unsigned slot, const kq_dsc_params *params);
+/* The slot stops from the next call; its arena stays readable.  Touches no device either */
+int kq_dsc_remove(kq_dsc_bank *bank, unsigned slot);
+/* Input, status and on_device as in kq_rtty_process (status may be NULL; nothing is written for an empty slot). */
+int kq_dsc_process(kq_dsc_bank *bank, const void *src, int format, size_t src_stride, size_t row_stride, unsigned block_len,
+                   unsigned nblocks, int on_device, kq_dsc_status *status, size_t status_stride);
+/* Events in every slot's arena, counts[max_slots], in one copy; synchronous */
+int kq_dsc_pull_counts(kq_dsc_bank *bank, uint32_t *counts);
+/* Copies event `index` of `slot`; returns 0, or -1 */
+int kq_dsc_pull_event(kq_dsc_bank *bank, unsigned slot, unsigned index, kq_dsc_event *event);
+/* Empties every arena (on the handle's stream); the status counters, the register and an open message go on */
+int kq_dsc_clear_events(kq_dsc_bank *bank);
+/* C (at most cap words); returns 1024 */
+int kq_dsc_get_table(const kq_dsc_bank *bank, int16_t *dst, size_t cap);
+/* inc_m, inc_s, tb and W of `slot`, without a device; -1 when the slot holds no decoder */
+int kq_dsc_get_slot(kq_dsc_bank *bank, unsigned slot, kq_dsc_slot *out);
+int kq_dsc_sync(kq_dsc_bank *bank);
+/* Stream index back to 0; every slot restarts cold with its settings at the next call, as if set again */
+int kq_dsc_reset(kq_dsc_bank *bank);
+
 /* --- rational resampler bank ----------------------------------------------------------------------------------------------
  * Up to 65536 slots, each one row of PCM (mono or stereo) resampled from Fi = in_rate_num / in_rate_den Hz (a receiver
  * bank's samprate and decimate, so 39 062.5 Hz is exact) to Fo = out_rate Hz: kq_afsk_*, RTP PCM and the players are 48 kHz,

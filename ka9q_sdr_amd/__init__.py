@@ -52,5 +52,7 @@ from .acars import AcarsBank, AcarsParams, acars_params  # noqa: F401,E402  (aca
 from . import arinc618  # noqa: F401,E402
 from .ale import AleBank, AleParams, ale_params  # noqa: F401,E402  (ale.STATUS_DTYPE: the ALE decoder's)
 from . import ale2g  # noqa: F401,E402
+from .dsc import DscBank, DscParams, dsc_params  # noqa: F401,E402  (dsc.STATUS_DTYPE: the DSC decoder's)
+from . import itu493  # noqa: F401,E402
 from .monitor import KQ_MON_F32, KQ_MON_S16BE, MonBank, MonParams, mon_params  # noqa: F401,E402  (monitor.STATUS_DTYPE: the mixer's)
 from .resample import RsmpBank, RsmpParams, rsmp_params  # noqa: F401,E402

@@ -1,0 +1,392 @@
+// kq_dsc.hip -- GMDSS digital selective calling (ITU-R M.493) decoder bank: the audio of SSB channels (or of a flat FM
+// channel at 96 kHz) -> whole DSC messages, as events (the symbols, nsym, flags, holes, from_rx, hole_mask, sync and end,
+// sig, nse) on gfx950.
+//
+// Per slot (include/ka9q_hip.h, kq_dsc_*): quantise as kq_cw_*, correlate every frame of B samples against the mark and the
+// space tone from the 1024-entry cosine table with phases that are functions of the sample index alone, slide a window one
+// bit long (W frames) over the frames' reduced sums -- kq_rtty_*'s front half to the letter -- and step the bit clock once
+// per completed frame; at every third point of the clock a bit is read: the levels, the gate, the 64-bit register, and --
+// at every bit while there is no sync -- the attempt on the phasing sequence, on the register and on its complement; in
+// sync, at every tenth bit a symbol place, and at every odd place from 17 on a message symbol resolved from its DX copy in
+// bits 59..50 or its RX copy in bits 9..0.  All exact integers after the quantiser.  State on the device, per slot: one
+// kq_dsc_status record, the reduced sums of the last 31 frames, and the arena of events; per bank the table.  The signal
+// format is written down from memory (the header says what is and what is not verified).
+//
+// k_dsc   a frame-grid kernel with a window and a symbol clock (kq_tonecorr.hpp describes the mapping): two tones, four
+//         series, as k_rtty.  Lane f sums its own W entries per series and squares, and lane 0 walks the piece's (Pm, Ps)
+//         pairs in order through the clock: it reads LDS at the points only.  The symbol code is a popcount and a bit
+//         reversal, so the tracker has no table.  The record's tail, the open message (kq_dsc_message: 64 bytes written at a
+//         running index, and the counts beside them that change once in ten bits), goes from the device's memory to LDS and
+//         back by the wave's first lanes and never through lane 0's registers: there the index would put it in scratch, and
+//         its 30 words beside the 40 of the head would cost the fourth workgroup of a CU.
+#include <hip/hip_runtime.h>
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+#include <mutex>
+
+#include "ka9q_hip.h"
+#include "kq_tonecorr.hpp"
+
+namespace tc = kq::tonecorr;
+
+namespace {
+
+using tc::kHist;
+using tc::kTable;
+using tc::sat_inc;
+using tc::smooth;
+constexpr unsigned kMaxSlots = 16384;
+constexpr int kThreads = 256, kWaves = kThreads / 64;
+constexpr int kTile = 3200;                     // samples a wave keeps in LDS: 64 frames of B = 48 at stride 50; with the rest
+                                                // the workgroup stays under 40 KiB, four workgroups to a CU
+constexpr int kRow = kHist + 64 + 1;            // a wave's reduced sums of one kind: the history and a piece's frames
+constexpr int kMsg = 64;                        // symbols to a message at the most
+constexpr unsigned kW125 = 0x2F9;               // symbol 125 as sent: 1011111001
+constexpr unsigned kCheck = 1, kTruncated = 2, kLost = 4, kInverted = 8;
+
+struct DscGeom {
+  kq::tonecorr::FrameGrid grid;
+  unsigned warm, snr, acq, lose;
+  unsigned long long min_p;
+  int max_events;
+};
+
+struct DscPar {  // per slot, written by the host when a call finds the slot set anew
+  int active;
+  unsigned source;
+  unsigned inc_m, inc_s;
+  int tb, W;
+};
+
+struct DscKind {
+  using Config = kq_dsc_config;
+  using Geom = DscGeom;
+  using Par = DscPar;
+  using Status = kq_dsc_status;
+  using Event = kq_dsc_event;
+  using Hist = tc::FrameHist<4>;  // a, b of mark, a, b of space
+  using Tables = tc::NoTables;
+  static constexpr bool kZeroCold = true;
+};
+using CallArgs = tc::GridBank<DscKind>::Args;
+
+// the symbol code: a ten-bit word, its first bit sent in bit 9
+__device__ __forceinline__ bool is_symbol(unsigned w) { return 7u - (unsigned)__popc(w >> 3) == (w & 7u); }
+__device__ __forceinline__ unsigned value_of(unsigned w) { return __brev(w >> 3) >> 25; }
+__device__ __forceinline__ unsigned word_of(unsigned v) { return (__brev(v) >> 25) << 3 | (7u - (unsigned)__popc(v)); }
+
+// step 4 on x: the place of the latest symbol, or -1
+__device__ __forceinline__ int phasing(unsigned long long x, unsigned acq) {
+  unsigned const s0 = (unsigned)x & 1023u, s1 = (unsigned)(x >> 10) & 1023u, s2 = (unsigned)(x >> 20) & 1023u,
+                 s3 = (unsigned)(x >> 30) & 1023u;
+  if (!is_symbol(s0)) return -1;
+  unsigned const v = value_of(s0);
+  if (v < 104 || v > 110) return -1;
+  unsigned const m = (unsigned)(s2 == word_of(v + 1)) + (unsigned)(v >= 106 && s1 == kW125) + (unsigned)(v >= 105 && s3 == kW125);
+  return m >= acq ? (int)(2 * (111 - v) + 1) : -1;
+}
+
+__device__ __forceinline__ void file(DscGeom const &g, kq_dsc_status &s, kq_dsc_message const &m, unsigned flags,
+                                     unsigned long long k, kq_dsc_event *ev, unsigned &nev) {
+  s.events = sat_inc(s.events);
+  if (nev >= (unsigned)g.max_events) {
+    s.dropped = sat_inc(s.dropped);
+    return;
+  }
+  kq_dsc_event &r = ev[nev++];
+  unsigned *sym = reinterpret_cast<unsigned *>(r.sym);
+  const unsigned *msg = reinterpret_cast<const unsigned *>(m.msg);
+#pragma unroll
+  for (int i = 0; i < kMsg / 4; i++) sym[i] = msg[i];
+  r.nsym = m.nsym;
+  r.flags = flags | (m.inverted ? kInverted : 0u);
+  r.holes = m.holes;
+  r.from_rx = m.from_rx;
+  r.hole_mask = m.hole_mask;
+  r.sync_sample = m.sync_sample;
+  r.end_sample = (k + 1) * (unsigned long long)g.grid.B;
+  r.sig = s.sig;
+  r.nse = s.nse;
+}
+
+// the header's steps 1 to 5: the late point of a bit at frame k, with the late power pl; m: the open message, in LDS
+__device__ __forceinline__ void bit_step(DscGeom const &g, DscPar const &par, kq_dsc_status &s, kq_dsc_message &m,
+                                         unsigned long long pl, unsigned long long k, kq_dsc_event *ev, unsigned &nev) {
+  // 1 timing
+  tc::clock_adjust(s, par.tb, pl);
+  smooth(s.ec, s.hi, 3);
+  unsigned long long const top = s.ee > s.el ? s.ee : s.el, low = s.ee > s.el ? s.el : s.ee;
+  if (top - low <= (top >> 3) && s.ec + (top >> 3) < low) s.t += par.tb >> 5;  // (adj == 0) half a bit out: no slope there
+  // 2 levels and gate
+  smooth(s.sig, s.hi, 4);
+  smooth(s.nse, s.lo, 4);
+  bool const open = s.frames >= g.warm && s.sig >= g.min_p && tc::gate16(s.sig, s.nse, g.snr);
+  // 3 register
+  s.r = s.r << 1 | (unsigned long long)s.bit;
+  s.nbits += 1;
+  // 4 sync
+  if (!s.synced) {
+    if (!open) return;
+    int place = phasing(s.r, g.acq);
+    unsigned inv = 0;
+    if (place < 0) {
+      place = phasing(~s.r, g.acq);
+      inv = 1;
+    }
+    if (place < 0) return;
+    s.synced = 1;
+    s.bitpos = 0;
+    s.syncs = sat_inc(s.syncs);
+    m.inverted = inv;
+    m.place = (unsigned)place;
+    m.nsym = m.nres = m.holes = m.from_rx = m.run = m.ecc = m.eos = 0;
+    m.hole_mask = 0;
+    m.sync_sample = (k + 1) * (unsigned long long)g.grid.B;
+    unsigned *msg = reinterpret_cast<unsigned *>(m.msg);
+#pragma unroll
+    for (int i = 0; i < kMsg / 4; i++) msg[i] = 0;
+    return;
+  }
+  // 5 message
+  s.bitpos += 1;
+  if (s.bitpos < 10) return;
+  s.bitpos = 0;
+  unsigned const place = m.place + 1;
+  m.place = place;
+  if (!(place & 1u) || place < 17) return;
+  unsigned const i = (place - 17) >> 1;  // below kMsg: rule (b) ends the message at 64
+  unsigned long long const x = m.inverted ? ~s.r : s.r;
+  unsigned const dx = (unsigned)(x >> 50) & 1023u, rx = (unsigned)x & 1023u;
+  bool const by_dx = is_symbol(dx), by_rx = is_symbol(rx), got = by_dx || by_rx;
+  unsigned const d = by_dx ? value_of(dx) : value_of(rx);
+  if (!by_dx && by_rx) m.from_rx += 1;
+  m.msg[i & (kMsg - 1)] = (unsigned char)(got ? d : 0xFFu);
+  m.nsym = i + 1;
+  if (!got) {
+    m.holes += 1;
+    m.hole_mask |= 1ull << (i & 63u);
+  }
+  if (m.eos) {  // (a) the error-check symbol
+    file(g, s, m, !got || m.holes || d != m.ecc ? kCheck : 0u, k, ev, nev);
+    s.synced = 0;
+    return;
+  }
+  if (!got) {
+    m.run += 1;
+    if (m.run >= g.lose) {  // (c)
+      if (m.nres >= 8) file(g, s, m, kLost | kCheck, k, ev, nev);
+      else s.aborted = sat_inc(s.aborted);
+      s.synced = 0;
+      return;
+    }
+  } else {
+    m.run = 0;
+    m.nres += 1;
+    if (i >= 1) m.ecc ^= d;
+    if (d == 117 || d == 122 || d == 127) m.eos = 1;
+  }
+  if (i + 1 == kMsg) {  // (b)
+    file(g, s, m, kTruncated | kCheck, k, ev, nev);
+    s.synced = 0;
+  }
+}
+
+constexpr int kHead = (int)offsetof(kq_dsc_status, open), kOpenWords = (int)sizeof(kq_dsc_message) / 4;
+static_assert(kHead % 8 == 0 && sizeof(kq_dsc_message) % 8 == 0 && kOpenWords <= 64, "the record's head and its tail");
+
+// tc::load_record and tc::store_record for a record in two parts: the head into lane 0, the tail (the open message) into
+// LDS by the wave's first lanes
+template <class Place>
+__device__ __forceinline__ kq_dsc_event *load_parts(CallArgs const &c, Place const &w, kq_dsc_status &s, kq_dsc_message &m,
+                                                    unsigned &nev) {
+  if (w.live && w.lane == 0) {
+    __builtin_memcpy(&s, &c.state[w.slot], kHead);
+    nev = c.nev[w.slot];
+  }
+  if (w.lane < kOpenWords)
+    reinterpret_cast<unsigned *>(&m)[w.lane] = w.live ? reinterpret_cast<const unsigned *>(&c.state[w.slot].open)[w.lane] : 0u;
+  return c.ev + (size_t)w.slot * c.g.max_events;
+}
+
+template <class Place>
+__device__ __forceinline__ void store_parts(CallArgs const &c, Place const &w, kq_dsc_status const &s, kq_dsc_message const &m,
+                                            unsigned nev) {
+  if (!w.live) return;
+  kq_dsc_status *const out = c.st ? c.st + (size_t)w.slot * c.sstride : nullptr;
+  if (w.lane == 0) {
+    __builtin_memcpy(&c.state[w.slot], &s, kHead);
+    c.nev[w.slot] = nev;
+    if (out) __builtin_memcpy(out, &s, kHead);
+  }
+  if (w.lane < kOpenWords) {
+    unsigned const v = reinterpret_cast<const unsigned *>(&m)[w.lane];
+    reinterpret_cast<unsigned *>(&c.state[w.slot].open)[w.lane] = v;
+    if (out) reinterpret_cast<unsigned *>(&out->open)[w.lane] = v;
+  }
+}
+
+// (four waves to a SIMD asked for: left to itself the allocator takes more VGPRs than the 128 that four workgroups to a CU
+// allow; with the bound it takes 123 and no scratch)
+__global__ __launch_bounds__(kThreads, 4) void k_dsc(CallArgs c) {
+  __shared__ int CS[kTable];                       // C[j] in the low half, C[(j - 256) & 1023] in the high
+  __shared__ short qs[kWaves][kTile];
+  __shared__ int A[kWaves][4][kRow];               // reduced sums: [0, kHist) the frames before the piece, then the piece's
+  __shared__ unsigned long long Pb[kWaves][2][64];
+  __shared__ long long carry[kWaves][4];
+  __shared__ int lastsum[kWaves][4];
+  __shared__ kq_dsc_message OPEN[kWaves];          // the record's tail: between its load and its store lane 0 alone has it
+  DscGeom const &g = c.g;
+  auto const w = tc::wave_place<kThreads>(c, CS);
+  int const wave = w.wave, lane = w.lane, W = tc::window_frames(w.live, w.par.W);
+  unsigned const inc[2] = {w.par.inc_m, w.par.inc_s};
+  int const q = w.par.tb >> 2;
+  kq_dsc_status s{};
+  unsigned nev = 0;
+  kq_dsc_event *ev = load_parts(c, w, s, OPEN[wave], nev);  // (the first barrier of correlate_piece is behind it)
+  tc::load_hist(A[wave], c.hist, w);
+  long long cy[4] = {s.acc[0][0], s.acc[0][1], s.acc[1][0], s.acc[1][1]};
+  for (tc::Piece pc(c.n0, w.B); pc.n < c.n1; pc.next(w.F)) {
+    pc.span(c.n1, w.B, w.F);
+    long long sm[4];  // (its first barrier: the piece before is done with q, A, Pb, carry and lastsum, and A is loaded)
+    tc::correlate_piece<2>(c, w, pc, qs[wave], CS, inc, sm, cy);
+    int const done = pc.done(g.grid);
+    tc::file_sums(A[wave], carry[wave], w, pc, done, sm, 12);
+    __syncthreads();
+    int keep[4] = {0, 0, 0, 0};
+    if (lane < done) {
+      int v[4] = {0, 0, 0, 0};  // the window that ends at frame `lane`: W entries, the last at kHist + lane; the four series
+      for (int i = 0; i < W; i++)  // side by side, as k_rtty has them
+        for (int t = 0; t < 4; t++) v[t] += A[wave][t][kHist + lane - i];
+      Pb[wave][0][lane] = (unsigned long long)((long long)v[0] * v[0]) + (unsigned long long)((long long)v[1] * v[1]);
+      Pb[wave][1][lane] = (unsigned long long)((long long)v[2] * v[2]) + (unsigned long long)((long long)v[3] * v[3]);
+      if (lane == done - 1)
+        for (int t = 0; t < 4; t++) lastsum[wave][t] = v[t];
+    }
+    tc::keep_hist(A[wave], lane, done, keep);
+    __syncthreads();
+    tc::put_hist(A[wave], lane, keep);
+    if (w.live && lane == 0) {
+      for (int i = 0; i < done; i++) {  // the header's step, frame k0 + i
+        s.frames = sat_inc(s.frames);
+        s.t -= 256;
+        if (s.t >= 128) continue;
+        unsigned long long const Pm = Pb[wave][0][i], Ps = Pb[wave][1][i], hi = Pm >= Ps ? Pm : Ps, lo = Pm >= Ps ? Ps : Pm;
+        if (s.ph == 0) {
+          s.pe = hi;
+          s.t += q;
+          s.ph = 1;
+        } else if (s.ph == 1) {
+          s.bit = Pm >= Ps ? 1u : 0u;
+          s.hi = hi;
+          s.lo = lo;
+          s.t += q;
+          s.ph = 2;
+        } else {
+          s.ph = 0;
+          bit_step(g, w.par, s, OPEN[wave], hi, (unsigned long long)(pc.k0 + i), ev, nev);
+        }
+      }
+      if (done) {
+        s.sum[0][0] = lastsum[wave][0];
+        s.sum[0][1] = lastsum[wave][1];
+        s.sum[1][0] = lastsum[wave][2];
+        s.sum[1][1] = lastsum[wave][3];
+      }
+      tc::take_carry(carry[wave], w, pc, done, cy);
+    }
+  }
+  __syncthreads();
+  tc::store_hist(A[wave], c.hist, w);
+  s.acc[0][0] = cy[0];
+  s.acc[0][1] = cy[1];
+  s.acc[1][0] = cy[2];
+  s.acc[1][1] = cy[3];
+  store_parts(c, w, s, OPEN[wave], nev);  // (behind the barrier above)
+}
+
+}  // namespace
+
+struct kq_dsc_bank : tc::GridBank<DscKind> {};
+
+extern "C" {
+
+kq_dsc_bank *kq_dsc_create(const kq_dsc_config *cfg) {
+  const char *fn = "kq_dsc_create";
+  if (!cfg) {
+    kq_internal_set_error("%s: null config", fn);
+    return nullptr;
+  }
+  if (!kq::samprate_ok(fn, cfg->samprate) || !kq::field_in_range(fn, "block_len", cfg->block_len, 8, 256) ||
+      !kq::field_in_range(fn, "warm", cfg->warm, 0, 65535) || !kq::field_in_range(fn, "snr", cfg->snr, 16, 4095) ||
+      !kq::min_p_ok(fn, cfg->min_p) || !kq::input_scale_ok(fn, cfg->input_scale) ||
+      !kq::field_in_range(fn, "acq", cfg->acq, 1, 3) || !kq::field_in_range(fn, "lose", cfg->lose, 1, 15) ||
+      !kq::field_in_range(fn, "max_slots", cfg->max_slots, 1, kMaxSlots) ||
+      !kq::field_in_range(fn, "max_events", cfg->max_events, 1, 4096) || !kq::max_samples_ok(fn, cfg->max_samples))
+    return nullptr;
+  kq_dsc_bank *b = tc::finish_create<kq_dsc_bank>(cfg, kTile);  // Lmin 8 at the most: Bs <= 258
+  b->g.acq = cfg->acq;
+  b->g.lose = cfg->lose;
+  return b;
+}
+
+int kq_dsc_destroy(kq_dsc_bank *b) { return kq::destroy_bank(b, "kq_dsc_destroy"); }
+
+int kq_dsc_set(kq_dsc_bank *b, unsigned slot, const kq_dsc_params *p) {
+  const char *fn = "kq_dsc_set";
+  std::unique_lock<std::mutex> lk;
+  if (!tc::open_set(b, fn, slot, p, kMaxSlots, lk)) return -1;
+  double const Fs = b->cfg.samprate, fm = p->mark, fs = p->space;
+  if (!tc::tone_ok(fn, Fs, fm, "mark %g", fm) || !tc::tone_ok(fn, Fs, fs, "space %g", fs)) return -1;
+  if (p->mark == p->space) {
+    kq_internal_set_error("%s: mark and space are both %g", fn, fm);
+    return -1;
+  }
+  DscPar np{};
+  if (!tc::symbol_period(fn, Fs, b->cfg.block_len, p->baud, "bit", &np.tb, &np.W)) return -1;
+  np.active = 1;
+  np.source = p->source;
+  np.inc_m = (unsigned)std::llrint(fm * 4294967296.0 / Fs);
+  np.inc_s = (unsigned)std::llrint(fs * 4294967296.0 / Fs);
+  b->def.set(slot, np);
+  return 0;
+}
+
+int kq_dsc_remove(kq_dsc_bank *b, unsigned slot) { return kq::deferred_remove(b, slot, "kq_dsc_remove"); }
+
+int kq_dsc_process(kq_dsc_bank *b, const void *src, int format, size_t src_stride, size_t row_stride, unsigned block_len,
+                   unsigned nblocks, int on_device, kq_dsc_status *status, size_t status_stride) {
+  return tc::process<CallArgs>(b, "kq_dsc_process", src, format, src_stride, row_stride, block_len, nblocks, on_device, status,
+                               status_stride, kWaves, [b](CallArgs &a, unsigned blocks) {
+                                 hipLaunchKernelGGL(k_dsc, dim3(blocks), dim3(kThreads), 0, b->stream, a);
+                               });
+}
+
+int kq_dsc_pull_counts(kq_dsc_bank *b, uint32_t *counts) { return kq::pull_counts(b, "kq_dsc_pull_counts", counts); }
+
+int kq_dsc_pull_event(kq_dsc_bank *b, unsigned slot, unsigned index, kq_dsc_event *event) {
+  return kq::pull_event(b, "kq_dsc_pull_event", slot, index, event);
+}
+
+int kq_dsc_clear_events(kq_dsc_bank *b) { return kq::clear_arena(b, "kq_dsc_clear_events"); }
+
+int kq_dsc_get_table(const kq_dsc_bank *b, int16_t *dst, size_t cap) {
+  return kq::tonecorr::get_table(b, "kq_dsc_get_table", dst, cap);
+}
+
+int kq_dsc_get_slot(kq_dsc_bank *b, unsigned slot, kq_dsc_slot *out) {
+  std::unique_lock<std::mutex> lk;
+  const DscPar *w = tc::wanted(b, "kq_dsc_get_slot", slot, out, "out", lk);
+  if (!w) return -1;
+  out->inc_m = w->inc_m;
+  out->inc_s = w->inc_s;
+  out->tb = (uint32_t)w->tb;
+  out->W = (uint32_t)w->W;
+  return 0;
+}
+
+int kq_dsc_sync(kq_dsc_bank *b) { return kq::sync_bank(b, "kq_dsc_sync"); }
+
+int kq_dsc_reset(kq_dsc_bank *b) { return kq::deferred_reset(b, "kq_dsc_reset"); }
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-// kq_gridbank.hpp -- the host half that the frame-grid decoders share (kq_cw, kq_rtty, kq_psk, kq_ale), on top of
+// kq_gridbank.hpp -- the host half that the frame-grid decoders share (kq_cw, kq_rtty, kq_psk, kq_ale, kq_dsc), on top of
 // kq_slots.hpp: deferred event banks of PCM decoders whose kernels correlate frames of B samples on a grid that starts at
 // sample 0 of the stream (the device half: kq_tonecorr.hpp, which includes this file).  Host only, so that it compiles
 // against the device-less stand-in for the runtime; the launch stays with each bank.

@@ -5,18 +5,18 @@
 //
 //   every slot bank   the slot table and its device copy, the staging of a host-memory call's distinct source rows, the
 //                     copy-back of the active slots' rows, destroy / sync / remove, the argument checks of set and process
-//   PCM decoders      (kq_fsk, kq_pag, kq_tone, kq_cw, kq_rtty, kq_psk, kq_acars, kq_ale) the call's input binding (PcmIn,
-//                     bind_pcm), the checks of a call and what is left of it (call_args_ok, begin_call), where the status
-//                     records go and the tail of a host-memory call (bind_status, end_host_call), the checks the configs
-//                     share (field_in_range, ...)
-//   event banks       kq::EventArena: the [S][max_events] records and [S] counts.  kq_tone, kq_cw, kq_rtty, kq_psk and
-//                     kq_ale file events in it and take the bodies of pull_counts, pull_event and clear; kq_fsk, kq_pag and
-//                     kq_acars keep their frame, page and block infos in one, take the counts and clear bodies, and pull a
-//                     record with pull_record before they fetch its bytes themselves
-//   deferred banks    (kq_cw, kq_rtty, kq_psk, kq_acars, kq_ale) kq::DeferredSlots: set and remove touch no device; the next
-//                     entry point that needs the device brings the changed slots there, a run at a time (flush)
-//   frame-grid banks  (kq_cw, kq_rtty, kq_psk, kq_ale) stand on kq_gridbank.hpp, on top of this file: one bank template and
-//                     one body for create's tail, set's shared checks, process and the getters' opening
+//   PCM decoders      (kq_fsk, kq_pag, kq_tone, kq_cw, kq_rtty, kq_psk, kq_acars, kq_ale, kq_dsc) the call's input binding
+//                     (PcmIn, bind_pcm), the checks of a call and what is left of it (call_args_ok, begin_call), where the
+//                     status records go and the tail of a host-memory call (bind_status, end_host_call), the checks the
+//                     configs share (field_in_range, ...)
+//   event banks       kq::EventArena: the [S][max_events] records and [S] counts.  kq_tone, kq_cw, kq_rtty, kq_psk, kq_ale
+//                     and kq_dsc file events in it and take the bodies of pull_counts, pull_event and clear; kq_fsk, kq_pag
+//                     and kq_acars keep their frame, page and block infos in one, take the counts and clear bodies, and
+//                     pull a record with pull_record before they fetch its bytes themselves
+//   deferred banks    (kq_cw, kq_rtty, kq_psk, kq_acars, kq_ale, kq_dsc) kq::DeferredSlots: set and remove touch no device;
+//                     the next entry point that needs the device brings the changed slots there, a run at a time (flush)
+//   frame-grid banks  (kq_cw, kq_rtty, kq_psk, kq_ale, kq_dsc) stand on kq_gridbank.hpp, on top of this file: one bank
+//                     template and one body for create's tail, set's shared checks, process and the getters' opening
 //
 // A bank here is a struct on kq::HostSide with `cfg` (device, max_slots, max_samples), `mu`, `dev_ready`, `n_cur` (PCM
 // decoders), `static constexpr bool kDeferred` (event banks) and the device half `d` that kq::lazy_device() makes, whose

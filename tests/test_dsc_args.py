@@ -1,0 +1,257 @@
+"""Argument checks of the DSC decoder bank (kq_dsc_*): every limit is refused with -1 / NULL and a reason that names the
+function and the field before any HIP call, so they hold without a GPU (kq_dsc_create, kq_dsc_set and kq_dsc_remove touch
+no device: the next call does); the cosine table, the phase increments, the bit length and the window the bank hands out
+against the model's; and the record layouts against the dtypes."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import dsc_model as dm
+import ka9q_sdr_amd as kq
+from ka9q_sdr_amd import itu493
+from ka9q_sdr_amd.dsc import EVENT_DTYPE, STATUS_DTYPE, STATUS_WORDS, DscConfig, DscParams, DscSlot, _bind, dsc_params
+
+
+@pytest.fixture(scope="module")
+def lib():
+    kq.build_library()
+    return _bind(kq.load_library())
+
+
+def _cfg(**kw):
+    c = dict(device=0, samprate=12000.0, block_len=12, warm=64, snr=64, min_p=1 << 16, input_scale=32767.0, max_slots=8,
+             max_events=4, max_samples=1 << 14, stream=None, acq=2, lose=3)
+    c.update(kw)
+    return DscConfig(*c.values())
+
+
+@pytest.fixture
+def bank(lib):
+    h = lib.kq_dsc_create(C.byref(_cfg()))
+    assert h, lib.kq_last_error()
+    yield h
+    assert lib.kq_dsc_destroy(h) == 0
+
+
+NAMES = {"kq_dsc_create", "kq_dsc_destroy", "kq_dsc_set", "kq_dsc_remove", "kq_dsc_process", "kq_dsc_pull_counts",
+         "kq_dsc_pull_event", "kq_dsc_clear_events", "kq_dsc_get_table", "kq_dsc_get_slot", "kq_dsc_sync", "kq_dsc_reset"}
+
+
+def test_symbols_exported_and_declared(lib):
+    import test_abi
+    decl = test_abi._declared("ka9q_hip.h")
+    assert NAMES <= decl and {n for n in decl if n.startswith("kq_dsc_")} == NAMES
+    for n in sorted(NAMES):
+        assert hasattr(lib, n), n
+    assert kq.DscBank and kq.DscParams and kq.dsc_params and kq.itu493.modulate and kq.itu493.read and kq.itu493.repair
+    assert kq.itu493.dsc_config and kq.dsc.status_array and kq.dsc.EVENT_DTYPE
+
+
+def test_record_layouts():
+    """kq_dsc_status is a head of 168 bytes and kq_dsc_message behind it; kq_dsc_event a multiple of eight bytes"""
+    assert STATUS_DTYPE.itemsize == 288 and STATUS_WORDS == 72 and EVENT_DTYPE.itemsize == 120 and EVENT_DTYPE.itemsize % 8 == 0
+    f = STATUS_DTYPE.fields
+    assert f["t"][1] == 8 and f["bitpos"][1] == 24 and f["aborted"][1] == 40 and f["sig"][1] == 48 and f["r"][1] == 112
+    assert f["sum"][1] == 120 and f["acc"][1] == 136 and f["inverted"][1] == 168 and f["eos"][1] == 200
+    assert f["hole_mask"][1] == 208 and f["sync_sample"][1] == 216 and f["msg"][1] == 224
+    e = EVENT_DTYPE.fields
+    assert e["sym"][1] == 0 and e["nsym"][1] == 64 and e["from_rx"][1] == 76 and e["hole_mask"][1] == 80 and e["nse"][1] == 112
+    assert C.sizeof(DscParams) == 16 and C.sizeof(DscConfig) == 80 and C.sizeof(DscSlot) == 16
+    assert DscConfig.samprate.offset == 8 and DscConfig.block_len.offset == 16 and DscConfig.min_p.offset == 32
+    assert DscConfig.input_scale.offset == 40 and DscConfig.max_samples.offset == 56 and DscConfig.stream.offset == 64
+    assert DscConfig.acq.offset == 72 and DscConfig.lose.offset == 76 and DscParams.baud.offset == 12
+    assert tuple(STATUS_DTYPE.names) == dm.STATUS and kq.dsc.Event._fields == dm.Event._fields == EVENT_DTYPE.names
+
+
+def test_null_config_refused(lib):
+    assert lib.kq_dsc_create(None) is None
+    assert lib.kq_last_error() == b"kq_dsc_create: null config"
+
+
+def test_good_configs_accepted(lib):
+    """the limits themselves, and the geometries of the GPU tests; none of them asks for a device"""
+    for kw in (dict(), dict(block_len=8), dict(block_len=256, samprate=48000.0 * 8), dict(samprate=39062.5, block_len=32),
+               dict(samprate=48000.0, block_len=56), dict(samprate=96000.0, block_len=8), dict(warm=0), dict(warm=65535),
+               dict(snr=16), dict(snr=4095), dict(min_p=0), dict(min_p=1 << 55), dict(max_slots=16384, max_events=1),
+               dict(max_events=4096), dict(max_samples=1), dict(max_samples=1 << 28), dict(acq=1), dict(acq=3), dict(lose=1),
+               dict(lose=15)):
+        h = lib.kq_dsc_create(C.byref(_cfg(**kw)))
+        assert h, (kw, lib.kq_last_error())
+        assert lib.kq_dsc_destroy(h) == 0
+    for fs, baud in ((12000.0, 100.0), (39062.5, 100.0), (48000.0, 100.0), (96000.0, 1200.0)):
+        b = kq.DscBank(fs, max_slots=4, max_samples=4096, **itu493.dsc_config(fs, baud))
+        b.set(0, baud=baud)
+        assert b.get_slot(0).W == 10
+        b.close()
+
+
+@pytest.mark.parametrize("kw,why", [
+    (dict(samprate=0.0), b"samprate 0 must be positive and finite"),
+    (dict(samprate=-8000.0), b"samprate -8000"),
+    (dict(samprate=float("nan")), b"samprate nan"),
+    (dict(samprate=float("inf")), b"samprate inf"),
+    (dict(block_len=7), b"block_len 7 must be 8..256"),
+    (dict(block_len=257), b"block_len 257 must be 8..256"),
+    (dict(warm=65536), b"warm 65536 must be 0..65535"),
+    (dict(snr=15), b"snr 15 must be 16..4095"),
+    (dict(snr=4096), b"snr 4096 must be 16..4095"),
+    (dict(min_p=(1 << 55) + 1), b"min_p 36028797018963969 must be 0..2^55"),
+    (dict(input_scale=0.0), b"input_scale"),
+    (dict(input_scale=-1.0), b"input_scale"),
+    (dict(input_scale=float("nan")), b"input_scale"),
+    (dict(input_scale=float("inf")), b"input_scale"),
+    (dict(acq=0), b"acq 0 must be 1..3"),
+    (dict(acq=4), b"acq 4 must be 1..3"),
+    (dict(lose=0), b"lose 0 must be 1..15"),
+    (dict(lose=16), b"lose 16 must be 1..15"),
+    (dict(max_slots=0), b"max_slots 0 must be 1..16384"),
+    (dict(max_slots=16385), b"max_slots 16385"),
+    (dict(max_events=0), b"max_events 0 must be 1..4096"),
+    (dict(max_events=4097), b"max_events 4097"),
+    (dict(max_samples=0), b"max_samples 0"),
+    (dict(max_samples=(1 << 28) + 1), b"max_samples 268435457"),
+])
+def test_bad_config_refused(lib, kw, why):
+    assert lib.kq_dsc_create(C.byref(_cfg(**kw))) is None
+    msg = lib.kq_last_error()
+    assert msg.startswith(b"kq_dsc_create: ") and why in msg, msg
+
+
+def test_bad_slot_and_params_refused(lib, bank):
+    p = dsc_params()
+    assert lib.kq_dsc_set(None, 16384, C.byref(p)) == -1
+    assert b"slot 16384" in lib.kq_last_error()
+    assert lib.kq_dsc_set(bank, 8, C.byref(p)) == -1     # max_slots = 8
+    assert b"slot 8 >= max_slots 8" in lib.kq_last_error()
+    assert lib.kq_dsc_set(bank, 0, None) == -1
+    assert lib.kq_last_error() == b"kq_dsc_set: null params"
+    assert lib.kq_dsc_set(None, 0, C.byref(p)) == -1
+    assert lib.kq_last_error() == b"kq_dsc_set: null bank"
+    bad = [(dict(mark=0.0), b"mark 0 must be above 0 and below samprate / 2"), (dict(mark=6000.0), b"mark 6000"),
+           (dict(mark=-1.0), b"mark -1"), (dict(mark=float("nan")), b"mark nan"),
+           (dict(space=0.0), b"space 0 must be above 0 and below samprate / 2"), (dict(space=6000.0), b"space 6000"),
+           (dict(space=float("nan")), b"space nan"), (dict(mark=1700.0, space=1700.0), b"mark and space are both 1700"),
+           (dict(baud=0.0), b"baud 0 must be positive and finite"), (dict(baud=float("nan")), b"baud nan"),
+           (dict(baud=float("inf")), b"baud inf"),
+           # B = 12 at 12 kHz: 1200 baud is 0.83 frames a bit, 150 baud 6.67, 30 baud 33.3; 125 and 31.25 are the limits
+           (dict(baud=1200.0), b"baud 1200 makes tb 213"), (dict(baud=150.0), b"baud 150 makes tb 1707"),
+           (dict(baud=125.2), b"outside 2048..8192"), (dict(baud=30.0), b"baud 30 makes tb 8533"),
+           (dict(baud=31.2), b"outside 2048..8192")]
+    for kw, why in bad:
+        assert lib.kq_dsc_set(bank, 0, C.byref(dsc_params(**kw))) == -1, kw
+        assert lib.kq_last_error().startswith(b"kq_dsc_set: ") and why in lib.kq_last_error(), (kw, lib.kq_last_error())
+    out = DscSlot()
+    assert lib.kq_dsc_get_slot(bank, 0, C.byref(out)) == -1          # none of those set the slot
+    assert b"slot 0 holds no decoder" in lib.kq_last_error()
+    for baud, tb in ((125.0, 2048), (31.25, 8192), (100.0, 2560)):
+        assert lib.kq_dsc_set(bank, 1, C.byref(dsc_params(baud=baud))) == 0, lib.kq_last_error()
+        assert lib.kq_dsc_get_slot(bank, 1, C.byref(out)) == 0 and out.tb == tb and out.W == tb // 256
+    assert lib.kq_dsc_get_slot(bank, 8, C.byref(out)) == -1 and lib.kq_dsc_get_slot(bank, 1, None) == -1
+    assert lib.kq_last_error() == b"kq_dsc_get_slot: null out"
+    assert lib.kq_dsc_remove(bank, 3) == -1
+    assert b"slot 3 holds no decoder" in lib.kq_last_error()
+    assert lib.kq_dsc_remove(bank, 8) == -1
+    ev = np.zeros(1, EVENT_DTYPE)
+    assert lib.kq_dsc_pull_event(bank, 9, 0, ev.ctypes.data) == -1
+    assert b"slot 9 >= max_slots 8" in lib.kq_last_error()
+    assert lib.kq_dsc_pull_event(bank, 0, 0, None) == -1
+    assert lib.kq_last_error() == b"kq_dsc_pull_event: null event"
+    assert lib.kq_dsc_pull_counts(bank, None) == -1
+    assert lib.kq_last_error() == b"kq_dsc_pull_counts: null counts"
+    assert lib.kq_dsc_remove(bank, 1) == 0
+
+
+def test_the_frames_that_fit_a_baud_rate(lib):
+    """the header's Limits: 100 baud fits B = 8..15 at 12 kHz and B = 15..60 at 48 kHz; 1200 baud needs 76.8 kHz"""
+    out = DscSlot()
+    for fs, baud, fits in ((12000.0, 100.0, range(8, 16)), (48000.0, 100.0, range(15, 61)), (96000.0, 1200.0, range(8, 11)),
+                           (76800.0, 1200.0, range(8, 9)), (48000.0, 1200.0, range(0))):
+        for B in range(8, 70):
+            h = lib.kq_dsc_create(C.byref(_cfg(samprate=fs, block_len=B)))
+            assert h, lib.kq_last_error()
+            took = lib.kq_dsc_set(h, 0, C.byref(dsc_params(mark=1300.0, space=2100.0, baud=baud))) == 0
+            assert took == (B in fits), (fs, baud, B, lib.kq_last_error())
+            assert lib.kq_dsc_destroy(h) == 0
+
+
+def test_bad_process_refused(lib, bank):
+    buf = np.zeros(1 << 15, np.float32)
+    st = np.zeros(8, STATUS_DTYPE)
+    assert lib.kq_dsc_process(bank, buf.ctypes.data, 0, 0, 4096, 4096, 5, 0, None, 0) == -1   # 20480 > 16384
+    assert b"max_samples" in lib.kq_last_error()
+    assert lib.kq_dsc_process(bank, buf.ctypes.data, 0, 0, 100, 200, 2, 0, None, 0) == -1
+    assert b"row_stride 100 < block_len 200" in lib.kq_last_error()
+    assert lib.kq_dsc_process(bank, buf.ctypes.data, 2, 0, 16, 16, 1, 0, None, 0) == -1       # KQ_PCM_S16: the modulator's
+    assert b"unknown sample format 2" in lib.kq_last_error()
+    assert lib.kq_dsc_process(bank, buf.ctypes.data, 0, 0, 16, 16, 1, 0, st.ctypes.data, 0) == -1
+    assert b"status_stride 0 < 1" in lib.kq_last_error()
+    assert lib.kq_dsc_process(bank, None, 0, 0, 16, 16, 1, 0, None, 0) == -1
+    assert b"null src" in lib.kq_last_error()
+    assert lib.kq_dsc_process(bank, None, 0, 0, 0, 0, 0, 0, None, 0) == 0        # nothing to do
+    assert lib.kq_dsc_process(None, buf.ctypes.data, 0, 0, 16, 16, 1, 0, None, 0) == -1
+    assert lib.kq_last_error() == b"kq_dsc_process: null bank"
+
+
+def test_without_a_slot_nothing_touches_a_device(lib, bank):
+    """with no slot set -- or one set and removed again -- process, counts, clear, sync and reset succeed and touch no
+    device"""
+    buf = np.zeros(1 << 14, np.float32)
+    assert lib.kq_dsc_set(bank, 5, C.byref(dsc_params())) == 0 and lib.kq_dsc_remove(bank, 5) == 0
+    for n in (1, 1000, 16384):
+        assert lib.kq_dsc_process(bank, buf.ctypes.data, 0, 0, n, n, 1, 0, None, 0) == 0
+    counts = np.full(8, 7, np.uint32)
+    assert lib.kq_dsc_pull_counts(bank, counts.ctypes.data) == 0 and not counts.any()
+    assert lib.kq_dsc_clear_events(bank) == 0 and lib.kq_dsc_sync(bank) == 0 and lib.kq_dsc_reset(bank) == 0
+    ev = np.zeros(1, EVENT_DTYPE)
+    assert lib.kq_dsc_pull_event(bank, 0, 0, ev.ctypes.data) == -1
+    assert b"slot 0 has 0 events" in lib.kq_last_error()
+
+
+def test_set_needs_no_device_and_the_first_call_says_where_there_is_none(lib):
+    b = kq.DscBank(12000.0, 12, max_slots=4, max_samples=4096)
+    b.set(0, source=0, mark=1785.0, space=1615.0, baud=100.0)          # no device asked for yet
+    assert b.get_slot(0) == (dm.dsc_inc(1785.0, 12000.0), dm.dsc_inc(1615.0, 12000.0), 2560, 10)
+    try:
+        b.process(np.zeros((1, 480), np.float32))
+        assert lib.kq_device_count() > 0
+    except kq.KqError as e:
+        assert lib.kq_device_count() <= 0, str(e)
+    b.close()
+    with pytest.raises(kq.KqError, match="block_len 512 must be 8..256"):
+        kq.DscBank(12000.0, 512, max_slots=4, max_samples=4096)
+    with pytest.raises(kq.KqError, match="acq 0 must be 1..3"):
+        kq.DscBank(12000.0, 12, max_slots=4, max_samples=4096, acq=0)
+
+
+def test_null_handles_refused(lib):
+    for fn, args in ((lib.kq_dsc_destroy, ()), (lib.kq_dsc_sync, ()), (lib.kq_dsc_reset, ()), (lib.kq_dsc_remove, (0,)),
+                     (lib.kq_dsc_clear_events, ()), (lib.kq_dsc_pull_counts, (None,)), (lib.kq_dsc_get_table, (None, 0)),
+                     (lib.kq_dsc_get_slot, (0, None)), (lib.kq_dsc_pull_event, (0, 0, None))):
+        assert fn(None, *args) == -1
+        assert b"null bank" in lib.kq_last_error()
+
+
+@pytest.mark.parametrize("Fs,B", [(12000.0, 12), (12000.0, 8), (39062.5, 32), (48000.0, 56), (96000.0, 8)])
+def test_table_and_slot_match_the_model(lib, Fs, B):
+    """C, inc_m, inc_s, tb and W are the model's, to the last bit: one cosine and one division in double each"""
+    h = lib.kq_dsc_create(C.byref(_cfg(samprate=Fs, block_len=B)))
+    assert h, lib.kq_last_error()
+    tab = np.zeros(dm.TABLE + 2, np.int16)
+    assert lib.kq_dsc_get_table(h, tab.ctypes.data, 2) == 1024 and not tab[2:].any()        # cap is kept
+    assert lib.kq_dsc_get_table(h, tab.ctypes.data, dm.TABLE + 2) == 1024 and not tab[dm.TABLE:].any()
+    assert np.array_equal(tab[:dm.TABLE], dm.cos_table())
+    out = DscSlot()
+    lo, hi = Fs / (B * 32.0), Fs / (B * 8.0)                          # the baud rates the geometry takes
+    bauds = [b for b in (45.45, 50.0, 75.0, 100.0, 110.0, 150.0, 200.0, 300.0, 600.0, 1200.0, lo * 1.001, hi * 0.999)
+             if lo * 1.001 <= b <= hi * 0.999]
+    assert len(bauds) >= 3
+    for slot, baud in enumerate(bauds[:8]):
+        mark, space = (1785.0, 0.001, 1234.567, Fs / 2 - 1.0)[slot % 4], (1615.0, 399.99, 3141.59 % (Fs / 2), 50.0)[slot % 4]
+        assert lib.kq_dsc_set(h, slot, C.byref(dsc_params(slot, mark, space, baud))) == 0, lib.kq_last_error()
+        assert lib.kq_dsc_get_slot(h, slot, C.byref(out)) == 0
+        tb = dm.bit_length(Fs, B, baud)
+        assert (out.inc_m, out.inc_s, out.tb, out.W) == (dm.dsc_inc(mark, Fs), dm.dsc_inc(space, Fs), tb, dm.window(tb)), baud
+        assert abs(out.inc_m * Fs / 2.0 ** 32 - float(np.float32(mark))) < Fs / 2.0 ** 32 and 8 <= out.W <= 32
+    assert lib.kq_dsc_remove(h, 2) == 0 and lib.kq_dsc_get_slot(h, 2, C.byref(out)) == -1
+    assert lib.kq_dsc_destroy(h) == 0
