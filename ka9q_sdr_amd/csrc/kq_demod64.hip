@@ -12,6 +12,7 @@
 // to HBM at the end of the launch.
 #include "kq_device.hpp"
 #include <cstdlib>
+#include "kq_fmstage.hpp"
 #include "kq_ldsfft.hpp"
 
 namespace kq {
@@ -23,7 +24,7 @@ __device__ __forceinline__ float2 shfl2(float2 v, int src) {
 }
 // value of a wave-uniform lane
 __device__ __forceinline__ float rdlane(float v, int src) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
+  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), src));
 }
 __device__ __forceinline__ int bitrev6(int i) { return (int)(__brev((unsigned)i) >> 26); }
 
@@ -72,11 +73,7 @@ __device__ __forceinline__ void put_status(kq_chan_status &st, const Geom &g, co
   st.pll_lock = 0;
   st.lock_count = 0;  // N/D = 64: the PL slave would have 2 points (fm.c:203), measurement off
   if (compute_n0) {
-    float const fresh = pl.n0raw[(size_t)c * g.max_blocks + b];
-    if (isnan(n0))
-      n0 = fresh;
-    else
-      n0 = (float)((double)n0 + n0_rate * (double)(fresh - n0));  // the reference's rate is a double literal
+    n0 = n0_step(n0, pl.n0raw[(size_t)c * g.max_blocks + b], n0_rate);
     st.n0 = n0;
   } else {
     st.n0 = NAN;
@@ -98,7 +95,8 @@ __device__ __forceinline__ float hsum(float v) {
   return hreduce(v, [](float a, float b) { return a + b; });
 }
 
-// Two consecutive blocks per iteration: block b in lanes 0-31, block b+1 in lanes 32-63.
+// ---------------------------------------------------------------- FM: the stages of a pair of blocks
+// Two consecutive blocks per iteration: block b in lanes 0-31, block b+1 in lanes 32-63 (have1: the call has a block b+1).
 //  * Discriminator (fm.c:91-160): the "previous valid sample" search of fm.c:128-144 runs over the 64-bit ballot, so a
 //    sample of block b+1 finds its predecessor in block b exactly as the carried state of the reference would hand
 //    it over; per-block quantities (amplitude statistics, threshold, squelch, deviation) are reductions over a half.
@@ -108,23 +106,18 @@ __device__ __forceinline__ float hsum(float v) {
 //    multiplied by the response and come back through ONE inverse transform whose real part is the audio of block
 //    b and whose imaginary part is the audio of block b+1.
 // Half the instructions per block of the one-block-per-iteration version, which is what matters with one wave per SIMD.
-template <bool FLAT>
-__device__ void fm_channel_pair(const Geom &g, const ChanDev &ch, const Planes &pl, int c, int nblocks, int compute_n0) {
-  int const lane = threadIdx.x & 63;
-  int const h = lane >> 5, n = lane & 31;
-  float const gain = ch.fm_gain[c];
-  float const noise_gain = ch.noise_gain[c];
-  int const kbin = bitrev6(lane);
-  int const herm_src = bitrev6((64 - kbin) & 63);
-  // response on every bin: HA[k] up to Nyquist, conj(HA[64-k]) above (the Hermitian extension of the c2r transform)
-  float2 HAf = make_float2(0.f, 0.f);
-  if (!FLAT) {
-    float2 const t = ch.aresp[(size_t)c * 33 + (kbin <= 32 ? kbin : 64 - kbin)];
-    HAf = kbin <= 32 ? t : cconj(t);
-  }
-  bool const real_bin = kbin == 0 || kbin == 32;
+// The stages are cut where the four-wave pipeline hands over; what a stage takes and returns is what crosses that seam.
+// fm_channel_pair runs them back to back on one wave, fm_channel_four_waves one per wave: both forms are these expressions.
 
-  float2 wf[6], wi[6];
+// the pair's samples; zeros for a block past the call's last
+__device__ __forceinline__ float2 pair_load(const float2 *in, int b, int nblocks) {
+  int const lane = threadIdx.x & 63;
+  return (b + (lane >> 5) < nblocks) ? in[(size_t)b * 32 + lane] : make_float2(0.f, 0.f);
+}
+
+// the twiddles of the 64-point transform pair's six lane-exchange stages, forward and inverse
+__device__ __forceinline__ void deemph_twiddles(float2 (&wf)[6], float2 (&wi)[6]) {
+  int const lane = threadIdx.x & 63;
 #pragma unroll
   for (int s = 0; s < 6; s++) {
     int const half = 1 << s;
@@ -133,6 +126,201 @@ __device__ void fm_channel_pair(const Geom &g, const ChanDev &ch, const Planes &
     wf[s] = make_float2(cs, -sn);
     wi[s] = make_float2(cs, sn);
   }
+}
+// response on every bin: HA[k] up to Nyquist, conj(HA[64-k]) above (the Hermitian extension of the c2r transform)
+__device__ __forceinline__ float2 deemph_response(const ChanDev &ch, int c, int kbin) {
+  float2 const t = ch.aresp[(size_t)c * 33 + (kbin <= 32 ? kbin : 64 - kbin)];
+  return kbin <= 32 ? t : cconj(t);
+}
+
+// ---- amplitude statistics and squelch (fm.c:91-114), per half
+struct PairStats {
+  float bbp, amp, snr;  // of the lane's half
+  int sq0, sq1;         // the squelch counter after block b, after block b+1
+};
+__device__ __forceinline__ PairStats pair_stats(float2 S, int sq, bool have1) {
+  PairStats r;
+  float const t = cnrm(S);
+  float const sum_t = hsum(t), sum_a = hsum(sqrtf(t));
+  r.bbp = sum_t / 64.f;                                  // / (2*olen), fm.c:99
+  r.amp = (float)((double)sum_a / (M_SQRT2 * 32));       // fm.c:100
+  float const variance = r.bbp - r.amp * r.amp;
+  float snr = r.amp * r.amp / (2 * variance) - 1;
+  r.snr = (0.0f > snr) ? 0.0f : snr;
+  float const snr0 = rdlane(r.snr, 0), snr1 = rdlane(r.snr, 32);
+  int nsq = sq + 1;
+  nsq = nsq > 1000 ? 1000 : nsq;
+  r.sq0 = (snr0 > 2) ? 0 : nsq;
+  nsq = r.sq0 + 1;
+  nsq = nsq > 1000 ? 1000 : nsq;
+  r.sq1 = have1 ? ((snr1 > 2) ? 0 : nsq) : r.sq0;
+  return r;
+}
+
+// ---- discriminator with hold (fm.c:117-144); state, lastaudio: carried in, and out as the pair leaves them
+struct PairDisc {
+  float out, y;     // the discriminator's output after / before the hold (fm.c:128-144)
+  unsigned mask_h;  // this half's mask of valid samples
+  int blanked;      // this half's count of held samples
+};
+__device__ __forceinline__ PairDisc pair_discriminate(float2 S, float amp, int sq0, int sq1, bool have1, float2 &state,
+                                                      float &lastaudio) {
+  int const lane = threadIdx.x & 63, h = lane >> 5;
+  bool const open0 = sq0 < 2, open1 = have1 && sq1 < 2;
+  bool const my_open = h ? open1 : open0;
+  float const t = cnrm(S);
+  float const thr = (float)(0.55 * 0.55 * amp * amp);
+  unsigned long long const raw = __ballot(t > thr);
+  unsigned long long const m_lo = open0 ? (raw & 0xffffffffull) : 0ull;
+  unsigned long long const m_hi = open1 ? (raw >> 32) : 0ull;
+  unsigned long long const mask = m_lo | (m_hi << 32);
+  bool const valid = (mask >> lane) & 1ull;
+  unsigned long long const below = mask & ((1ull << lane) - 1ull);
+  unsigned long long const upto = mask & ((2ull << lane) - 1ull);
+  int const pv = below ? 63 - __clzll((long long)below) : -1;
+  int const lv = upto ? 63 - __clzll((long long)upto) : -1;
+  // with no predecessor in the mask: block b falls back on the carried state, block b+1 on what block b leaves
+  // behind when it has no valid sample either -- the carried state if b is open, zero if it is squelched
+  float2 const state_fb = (h && !open0) ? make_float2(0.f, 0.f) : state;
+  float const la_fb = (h && !open0) ? 0.f : lastaudio;
+  float2 const sp = shfl2(S, pv >= 0 ? pv : 0);
+  float2 const stc = pv >= 0 ? cconj(sp) : state_fb;
+  float2 const pr = cmul(S, stc);
+  PairDisc r;
+  r.y = valid ? atan2f(pr.y, pr.x) : 0.f;
+  float const yl = __shfl(r.y, lv >= 0 ? lv : 0, 64);
+  r.out = my_open ? (lv >= 0 ? yl : la_fb) : 0.f;
+  // carried state after the pair (fm.c:133-144, 156-160)
+  {
+    int const last0 = m_lo ? 63 - __clzll((long long)m_lo) : 0;
+    int const last1 = m_hi ? 95 - __clzll((long long)m_hi) : 0;
+    float2 const sl0 = cconj(make_float2(rdlane(S.x, last0), rdlane(S.y, last0)));
+    float2 const sl1 = cconj(make_float2(rdlane(S.x, last1), rdlane(S.y, last1)));
+    float const yl0 = rdlane(r.y, last0), yl1 = rdlane(r.y, last1);
+    float2 st0 = open0 ? (m_lo ? sl0 : state) : make_float2(0.f, 0.f);
+    float la0 = open0 ? (m_lo ? yl0 : lastaudio) : 0.f;
+    if (have1) {
+      st0 = open1 ? (m_hi ? sl1 : st0) : make_float2(0.f, 0.f);
+      la0 = open1 ? (m_hi ? yl1 : la0) : 0.f;
+    }
+    state = st0;
+    lastaudio = la0;
+  }
+  r.mask_h = (unsigned)(mask >> (32 * h));
+  r.blanked = my_open ? 32 - __popcll((mask >> (32 * h)) & 0xffffffffull) : 0;
+  return r;
+}
+
+// ---- frequency offset and peak deviation (fm.c:125-154), per half; foffset, pdev: carried in, and out as the pair leaves them
+struct PairDev {
+  float fo0, pd0, fo1, pd1;  // the readings after block b, after block b+1
+};
+__device__ __forceinline__ PairDev pair_deviation(const Geom &g, float out, float y, unsigned mask_h, int sq0, int sq1, bool have1,
+                                                  float &foffset, float &pdev) {
+  int const lane = threadIdx.x & 63, h = lane >> 5, n = lane & 31;
+  bool const valid = (mask_h >> n) & 1u;
+  float const sum_y = hsum(out);
+  float const vmax = hreduce((valid && n > 0) ? y : -INFINITY, [](float a, float b2) { return fmaxf(a, b2); });
+  float const vmin = hreduce((valid && n > 0) ? y : INFINITY, [](float a, float b2) { return fminf(a, b2); });
+  float const y_first = h ? rdlane(y, 32) : rdlane(y, 0);
+  float const seed = (mask_h & 1u) ? y_first : 0.f;
+  float pdev_pos = fmaxf(seed, vmax), pdev_neg = fminf(seed, vmin);
+  float const avg_f = sum_y / 32.f;
+  pdev_pos -= avg_f;
+  pdev_neg -= avg_f;
+  float const mx = (pdev_pos > -pdev_neg) ? pdev_pos : -pdev_neg;
+  float const fo_new = (float)(g.dsamprate * avg_f * (0.5 * M_1_PI));
+  float const pd_new = (float)(g.dsamprate * mx * (0.5 * M_1_PI));
+  PairDev r;
+  r.fo0 = (sq0 < 1) ? rdlane(fo_new, 0) : foffset, r.pd0 = (sq0 < 1) ? rdlane(pd_new, 0) : pdev;
+  r.fo1 = (have1 && sq1 < 1) ? rdlane(fo_new, 32) : r.fo0, r.pd1 = (have1 && sq1 < 1) ? rdlane(pd_new, 32) : r.pd0;
+  foffset = r.fo1;
+  pdev = r.pd1;
+  return r;
+}
+
+// ---- de-emphasis (fm.c:162-171), forward half: both windows through one complex transform -> their filtered spectra,
+// g1 + j g2.  hist, lanes 0-31: the block before b in, the last block processed out
+__device__ __forceinline__ float2 pair_deemph_forward(float out, bool have1, float &hist, const float2 (&wf)[6], float2 HAf,
+                                                      int herm_src, bool real_bin) {
+  int const lane = threadIdx.x & 63, h = lane >> 5;
+  float const xo = lane_xor<32>(out, lane);    // lanes 0-31: block b+1, lanes 32-63: block b
+  float2 z = make_float2(h ? xo : hist, out);  // real: [hist | b], imaginary: [b | b+1]
+#pragma unroll
+  for (int s = 5; s >= 0; s--) {  // forward, decimation in frequency: natural in, bit-reversed out
+    float2 const r = lane_xor_pow2(z, s, lane);
+    z = ((lane >> s) & 1) ? cmul_fwd_stage(csub(r, z), wf[s], s) : cadd(z, r);
+  }
+  float2 const zm = cconj(shfl2(z, herm_src));  // conj(Z[64 - k])
+  float2 const z1 = make_float2(0.5f * (z.x + zm.x), 0.5f * (z.y + zm.y));     // spectrum of the real part
+  float2 const z2 = make_float2(0.5f * (z.y - zm.y), -0.5f * (z.x - zm.x));    // spectrum of the imaginary part
+  float2 g1 = cmul_response(HAf, z1), g2 = cmul_response(HAf, z2);  // filter.c:206-208 on both
+  if (real_bin) g1.y = g2.y = 0.f;                // the c2r transform ignores these imaginary parts
+  hist = have1 ? xo : out;  // lanes 0-31: the last block processed becomes the history (filter.c:168)
+  return make_float2(g1.x - g2.y, g1.y + g2.x);   // g1 + j g2
+}
+
+// ---- de-emphasis, inverse half, and the audio of both blocks
+__device__ __forceinline__ void pair_inverse_audio(const Geom &g, const Planes &pl, int c, int b, bool have1, const float2 &zin,
+                                                   const float2 (&wi)[6], float gain) {
+  int const lane = threadIdx.x & 63, h = lane >> 5, n = lane & 31;
+  float2 z = zin;
+#pragma unroll
+  for (int s = 0; s < 6; s++) {  // backward, decimation in time: bit-reversed in, natural out
+    int const bit = (lane >> s) & 1;
+    float2 const v = bit ? cmul_inv_stage(z, wi[s]) : z;
+    float2 const r = lane_xor_pow2(v, s, lane);
+    z = bit ? csub(r, v) : cadd(v, r);
+  }
+  // lanes 32-63 hold the kept halves: real part block b, imaginary part block b+1 (fm.c:169-170)
+  float const a0 = z.x * gain, a1 = z.y * gain;
+  if (h) {
+    pl.audio[((size_t)c * g.max_blocks + b) * 64 + n] = a0;
+    if (have1) pl.audio[((size_t)c * g.max_blocks + b + 1) * 64 + n] = a1;
+  }
+}
+
+// ---- status records: lane 0 writes block b, lane 32 block b+1
+// per-block status inputs, every 64 blocks: lane i holds block b + i
+__device__ __forceinline__ void pair_status_inputs(const Geom &g, const Planes &pl, int c, int b, int nblocks, int compute_n0,
+                                                   float &ifp_v, float &n0raw_v) {
+  if ((b & 63) == 0) {
+    int const bb = b + (threadIdx.x & 63);
+    ifp_v = bb < nblocks ? pl.if_power[bb] : 0.f;
+    n0raw_v = (compute_n0 && bb < nblocks) ? pl.n0raw[(size_t)c * g.max_blocks + bb] : 0.f;
+  }
+}
+// st: the half's bb_power, snr, foffset, pdeviation, squelch_count, blanked (the integers as bits)
+__device__ __forceinline__ void pair_status(const Geom &g, const Planes &pl, int c, int b, bool have1, int compute_n0, float ifp_v,
+                                            float n0raw_v, float noise_gain, float &n0, const float (&st)[6]) {
+  int const lane = threadIdx.x & 63, h = lane >> 5, n = lane & 31;
+  float const ifp = h ? rdlane(ifp_v, (b + 1) & 63) : rdlane(ifp_v, b & 63);
+  float const fresh0 = rdlane(n0raw_v, b & 63), fresh1 = rdlane(n0raw_v, (b + 1) & 63);
+  float n0a = n0, n0b = n0;
+  if (compute_n0) {  // fm.c:79-82, block after block
+    n0a = n0_step(n0, fresh0, .01);
+    n0b = have1 ? n0_step(n0a, fresh1, .01) : n0a;
+    n0 = n0b;
+  }
+  if (n == 0 && (h == 0 || have1))
+    pl.status[(size_t)c * g.max_blocks + b + h] =
+        fm_status_record(ifp, noise_gain, compute_n0 ? (h ? n0b : n0a) : NAN, st[0], st[1], st[2], st[3], __float_as_int(st[4]),
+                         __float_as_int(st[5]), 32);
+}
+
+// One wave per channel: the stages back to back, every value in registers.  No LDS, no barriers.
+template <bool FLAT>
+__device__ void fm_channel_pair(const Geom &g, const ChanDev &ch, const Planes &pl, int c, int nblocks, int compute_n0) {
+  int const lane = threadIdx.x & 63;
+  int const h = lane >> 5, n = lane & 31;
+  float const gain = ch.fm_gain[c];
+  float const noise_gain = ch.noise_gain[c];
+  int const kbin = bitrev6(lane);
+  int const herm_src = bitrev6((64 - kbin) & 63);
+  float2 const HAf = FLAT ? make_float2(0.f, 0.f) : deemph_response(ch, c, kbin);
+  bool const real_bin = kbin == 0 || kbin == 32;
+  float2 wf[6], wi[6];
+  deemph_twiddles(wf, wi);
 
   float2 state = ch.fm_state[c];
   float lastaudio = ch.lastaudio[c];
@@ -143,160 +331,30 @@ __device__ void fm_channel_pair(const Geom &g, const ChanDev &ch, const Planes &
   float ifp_v = 0.f, n0raw_v = 0.f;
   const float2 *in = pl.filt + (size_t)c * g.max_blocks * 32;
 
-  float2 s_next = (h < nblocks) ? in[lane] : make_float2(0.f, 0.f);
+  float2 s_next = pair_load(in, 0, nblocks);
   for (int b = 0; b < nblocks; b += 2) {
     bool const have1 = b + 1 < nblocks;
     float2 const S = s_next;
-    if (b + 2 < nblocks) s_next = (b + 2 + h < nblocks) ? in[(size_t)(b + 2) * 32 + lane] : make_float2(0.f, 0.f);
-    if ((b & 63) == 0) {  // per-block status inputs, lane i holds block b + i
-      int const bb = b + lane;
-      ifp_v = bb < nblocks ? pl.if_power[bb] : 0.f;
-      n0raw_v = (compute_n0 && bb < nblocks) ? pl.n0raw[(size_t)c * g.max_blocks + bb] : 0.f;
-    }
-
-    // ---- amplitude statistics and squelch (fm.c:91-114), per half
-    float const t = cnrm(S);
-    float const sum_t = hsum(t), sum_a = hsum(sqrtf(t));
-    float const bbp = sum_t / 64.f;                                  // / (2*olen), fm.c:99
-    float const amp = (float)((double)sum_a / (M_SQRT2 * 32));       // fm.c:100
-    float const variance = bbp - amp * amp;
-    float snr = amp * amp / (2 * variance) - 1;
-    snr = (0.0f > snr) ? 0.0f : snr;
-    float const snr0 = rdlane(snr, 0), snr1 = rdlane(snr, 32);
-    int nsq = sq + 1;
-    nsq = nsq > 1000 ? 1000 : nsq;
-    int const sq0 = (snr0 > 2) ? 0 : nsq;
-    nsq = sq0 + 1;
-    nsq = nsq > 1000 ? 1000 : nsq;
-    int const sq1 = have1 ? ((snr1 > 2) ? 0 : nsq) : sq0;
-    bool const open0 = sq0 < 2, open1 = have1 && sq1 < 2;
-    bool const my_open = h ? open1 : open0;
-
-    // ---- discriminator with hold (fm.c:117-144)
-    float const thr = (float)(0.55 * 0.55 * amp * amp);
-    unsigned long long const raw = __ballot(t > thr);
-    unsigned long long const m_lo = open0 ? (raw & 0xffffffffull) : 0ull;
-    unsigned long long const m_hi = open1 ? (raw >> 32) : 0ull;
-    unsigned long long const mask = m_lo | (m_hi << 32);
-    bool const valid = (mask >> lane) & 1ull;
-    unsigned long long const below = mask & ((1ull << lane) - 1ull);
-    unsigned long long const upto = mask & ((2ull << lane) - 1ull);
-    int const pv = below ? 63 - __clzll((long long)below) : -1;
-    int const lv = upto ? 63 - __clzll((long long)upto) : -1;
-    // with no predecessor in the mask: block b falls back on the carried state, block b+1 on what block b leaves
-    // behind when it has no valid sample either -- the carried state if b is open, zero if it is squelched
-    float2 const state_fb = (h && !open0) ? make_float2(0.f, 0.f) : state;
-    float const la_fb = (h && !open0) ? 0.f : lastaudio;
-    float2 const sp = shfl2(S, pv >= 0 ? pv : 0);
-    float2 const stc = pv >= 0 ? cconj(sp) : state_fb;
-    float2 const pr = cmul(S, stc);
-    float const y = valid ? atan2f(pr.y, pr.x) : 0.f;
-    float const yl = __shfl(y, lv >= 0 ? lv : 0, 64);
-    float const out = my_open ? (lv >= 0 ? yl : la_fb) : 0.f;
-
-    // ---- frequency offset and peak deviation (fm.c:125-154), per half
-    float const sum_y = hsum(out);
-    float const vmax = hreduce((valid && n > 0) ? y : -INFINITY, [](float a, float b2) { return fmaxf(a, b2); });
-    float const vmin = hreduce((valid && n > 0) ? y : INFINITY, [](float a, float b2) { return fminf(a, b2); });
-    float const y_first = h ? rdlane(y, 32) : rdlane(y, 0);
-    float const seed = ((mask >> (32 * h)) & 1ull) ? y_first : 0.f;
-    float pdev_pos = fmaxf(seed, vmax), pdev_neg = fminf(seed, vmin);
-    float const avg_f = sum_y / 32.f;
-    pdev_pos -= avg_f;
-    pdev_neg -= avg_f;
-    float const mx = (pdev_pos > -pdev_neg) ? pdev_pos : -pdev_neg;
-    float const fo_new = (float)(g.dsamprate * avg_f * (0.5 * M_1_PI));
-    float const pd_new = (float)(g.dsamprate * mx * (0.5 * M_1_PI));
-    float const fo0 = (sq0 < 1) ? rdlane(fo_new, 0) : foffset, pd0 = (sq0 < 1) ? rdlane(pd_new, 0) : pdev;
-    float const fo1 = (have1 && sq1 < 1) ? rdlane(fo_new, 32) : fo0, pd1 = (have1 && sq1 < 1) ? rdlane(pd_new, 32) : pd0;
-
-    // ---- carried state after the pair (fm.c:133-144, 156-160)
-    {
-      int const last0 = m_lo ? 63 - __clzll((long long)m_lo) : 0;
-      int const last1 = m_hi ? 95 - __clzll((long long)m_hi) : 0;
-      float2 const sl0 = cconj(make_float2(rdlane(S.x, last0), rdlane(S.y, last0)));
-      float2 const sl1 = cconj(make_float2(rdlane(S.x, last1), rdlane(S.y, last1)));
-      float const yl0 = rdlane(y, last0), yl1 = rdlane(y, last1);
-      float2 st0 = open0 ? (m_lo ? sl0 : state) : make_float2(0.f, 0.f);
-      float la0 = open0 ? (m_lo ? yl0 : lastaudio) : 0.f;
-      if (have1) {
-        st0 = open1 ? (m_hi ? sl1 : st0) : make_float2(0.f, 0.f);
-        la0 = open1 ? (m_hi ? yl1 : la0) : 0.f;
-      }
-      state = st0;
-      lastaudio = la0;
-    }
-    sq = sq1;
-    foffset = fo1;
-    pdev = pd1;
-
-    // ---- de-emphasis (fm.c:162-171): both windows through one complex transform
-    float const xo = lane_xor<32>(out, lane);  // lanes 0-31: block b+1, lanes 32-63: block b
-    float a0 = out, a1 = xo;                   // flat: lanes 0-31 hold block b, and (after the exchange) block b+1
+    if (b + 2 < nblocks) s_next = pair_load(in, b + 2, nblocks);
+    pair_status_inputs(g, pl, c, b, nblocks, compute_n0, ifp_v, n0raw_v);
+    PairStats const a = pair_stats(S, sq, have1);
+    sq = a.sq1;
+    PairDisc const d = pair_discriminate(S, a.amp, a.sq0, a.sq1, have1, state, lastaudio);
+    PairDev const v = pair_deviation(g, d.out, d.y, d.mask_h, a.sq0, a.sq1, have1, foffset, pdev);
     if (!FLAT) {
-      float2 z = make_float2(h ? xo : hist, out);  // real: [hist | b], imaginary: [b | b+1]
-#pragma unroll
-      for (int s = 5; s >= 0; s--) {  // forward, decimation in frequency: natural in, bit-reversed out
-        float2 const r = lane_xor_pow2(z, s, lane);
-        z = ((lane >> s) & 1) ? cmul_fwd_stage(csub(r, z), wf[s], s) : cadd(z, r);
-      }
-      float2 const zm = cconj(shfl2(z, herm_src));  // conj(Z[64 - k])
-      float2 const z1 = make_float2(0.5f * (z.x + zm.x), 0.5f * (z.y + zm.y));     // spectrum of the real part
-      float2 const z2 = make_float2(0.5f * (z.y - zm.y), -0.5f * (z.x - zm.x));    // spectrum of the imaginary part
-      float2 g1 = cmul_response(HAf, z1), g2 = cmul_response(HAf, z2);  // filter.c:206-208 on both
-      if (real_bin) g1.y = g2.y = 0.f;                // the c2r transform ignores these imaginary parts
-      z = make_float2(g1.x - g2.y, g1.y + g2.x);      // g1 + j g2
-#pragma unroll
-      for (int s = 0; s < 6; s++) {  // backward, decimation in time: bit-reversed in, natural out
-        int const bit = (lane >> s) & 1;
-        float2 const v = bit ? cmul_inv_stage(z, wi[s]) : z;
-        float2 const r = lane_xor_pow2(v, s, lane);
-        z = bit ? csub(r, v) : cadd(v, r);
-      }
-      // lanes 32-63 hold the kept halves: real part block b, imaginary part block b+1 (fm.c:169-170)
-      a0 = z.x * gain;
-      a1 = z.y * gain;
-      if (h) {
-        pl.audio[((size_t)c * g.max_blocks + b) * 64 + n] = a0;
-        if (have1) pl.audio[((size_t)c * g.max_blocks + b + 1) * 64 + n] = a1;
-      }
-    } else {
+      float2 const z = pair_deemph_forward(d.out, have1, hist, wf, HAf, herm_src, real_bin);
+      pair_inverse_audio(g, pl, c, b, have1, z, wi, gain);
+    } else {  // no filter, no gain: lanes 0-31 hold block b, and (after the exchange) block b+1
+      float const xo = lane_xor<32>(d.out, lane);
       if (!h) {
-        pl.audio[((size_t)c * g.max_blocks + b) * 64 + n] = a0;
-        if (have1) pl.audio[((size_t)c * g.max_blocks + b + 1) * 64 + n] = a1;
+        pl.audio[((size_t)c * g.max_blocks + b) * 64 + n] = d.out;
+        if (have1) pl.audio[((size_t)c * g.max_blocks + b + 1) * 64 + n] = xo;
       }
+      hist = have1 ? xo : d.out;
     }
-    hist = have1 ? xo : out;  // lanes 0-31: the last block processed becomes the history (filter.c:168)
-
-    // ---- status records: lane 0 writes block b, lane 32 block b+1
-    float const ifp = h ? rdlane(ifp_v, (b + 1) & 63) : rdlane(ifp_v, b & 63);
-    float const fresh0 = rdlane(n0raw_v, b & 63), fresh1 = rdlane(n0raw_v, (b + 1) & 63);
-    float n0a = n0, n0b = n0;
-    if (compute_n0) {  // fm.c:79-82, block after block
-      n0a = isnan(n0) ? fresh0 : (float)((double)n0 + .01 * (double)(fresh0 - n0));
-      n0b = have1 ? (isnan(n0a) ? fresh1 : (float)((double)n0a + .01 * (double)(fresh1 - n0a))) : n0a;
-      n0 = n0b;
-    }
-    if (n == 0 && (h == 0 || have1)) {
-      kq_chan_status rec;
-      rec.if_power = ifp;
-      rec.noise_gain = noise_gain;
-      rec.plfreq = NAN;  // N/D = 64: the PL slave would have 2 points (fm.c:203), measurement off
-      rec.cphase = 0;
-      rec.pll_lock = 0;
-      rec.lock_count = 0;
-      rec.n0 = compute_n0 ? (h ? n0b : n0a) : NAN;
-      rec.bb_power = bbp;
-      rec.snr = snr;
-      rec.foffset = h ? fo1 : fo0;
-      rec.pdeviation = h ? pd1 : pd0;
-      rec.agc_gain = 0;
-      rec.squelch_count = h ? sq1 : sq0;
-      rec.hangcount = 0;
-      rec.blanked = my_open ? 32 - __popcll((mask >> (32 * h)) & 0xffffffffull) : 0;
-      rec.nout = 32;
-      pl.status[(size_t)c * g.max_blocks + b + h] = rec;
-    }
+    float const st[6] = {a.bbp, a.snr, h ? v.fo1 : v.fo0, h ? v.pd1 : v.pd0, __int_as_float(h ? a.sq1 : a.sq0),
+                         __int_as_float(d.blanked)};
+    pair_status(g, pl, c, b, have1, compute_n0, ifp_v, n0raw_v, noise_gain, n0, st);
   }
   if (!h) ch.ahist[(size_t)c * 32 + lane] = hist;
   if (lane == 0) {
@@ -314,10 +372,10 @@ __device__ void fm_channel_pair(const Geom &g, const ChanDev &ch, const Planes &
 // the forward half of the de-emphasis filter of pair i - 2, wave 3 its inverse half, the audio store and the status
 // records of pair i - 3; each hand-over goes through LDS behind the iteration's one barrier.  A wave issues at most one
 // vector instruction per 8 cycles (tools/valu_rate.hip), and with one channel per SIMD that rate is all this kernel gets:
-// splitting the ~800 dependent instructions of a pair four ways is worth what the longest quarter takes.  Every value
-// is computed by the same expressions as in fm_channel_pair.
+// splitting the ~800 dependent instructions of a pair four ways is worth what the longest quarter takes.  What it does not
+// hand over it derives again inside the stage that needs it (|S|^2 in the discriminator, `valid` from the half's mask).
 __device__ void fm_channel_four_waves(const Geom &g, const ChanDev &ch, const Planes &pl, int c, int nblocks, int compute_n0) {
-  // [parity][...]; scalars per half: see the stages
+  // [parity][...]; scalars per half
   __shared__ float2 s_S[2][64];                 // 0 -> 1: the pair's samples
   __shared__ float s_a[2][2][4];                // 0 -> 1: amplitude, bb_power, snr, squelch_count
   __shared__ float s_out[2][64], s_y[2][64];    // 1 -> 2: the discriminator's output after / before the hold (fm.c:128-144)
@@ -328,38 +386,25 @@ __device__ void fm_channel_four_waves(const Geom &g, const ChanDev &ch, const Pl
   int const h = lane >> 5, n = lane & 31;
   int const npairs = (nblocks + 1) / 2, niter = npairs + 3;
 
-  if (role == 0) {  // ---------------- statistics and squelch (fm.c:91-114), per half
+  if (role == 0) {  // ---------------- statistics and squelch
     int sq = ch.sq_count[c];
     const float2 *in = pl.filt + (size_t)c * g.max_blocks * 32;
-    float2 s_next = (h < nblocks) ? in[lane] : make_float2(0.f, 0.f);
+    float2 s_next = pair_load(in, 0, nblocks);
     for (int it = 0; it < niter; it++) {
       if (it < npairs) {
         int const b = 2 * it, par = it & 1;
         bool const have1 = b + 1 < nblocks;
         float2 const S = s_next;
-        if (b + 2 < nblocks) s_next = (b + 2 + h < nblocks) ? in[(size_t)(b + 2) * 32 + lane] : make_float2(0.f, 0.f);
-        float const t = cnrm(S);
-        float const sum_t = hsum(t), sum_a = hsum(sqrtf(t));
-        float const bbp = sum_t / 64.f;                                  // / (2*olen), fm.c:99
-        float const amp = (float)((double)sum_a / (M_SQRT2 * 32));       // fm.c:100
-        float const variance = bbp - amp * amp;
-        float snr = amp * amp / (2 * variance) - 1;
-        snr = (0.0f > snr) ? 0.0f : snr;
-        float const snr0 = rdlane(snr, 0), snr1 = rdlane(snr, 32);
-        int nsq = sq + 1;
-        nsq = nsq > 1000 ? 1000 : nsq;
-        int const sq0 = (snr0 > 2) ? 0 : nsq;
-        nsq = sq0 + 1;
-        nsq = nsq > 1000 ? 1000 : nsq;
-        int const sq1 = have1 ? ((snr1 > 2) ? 0 : nsq) : sq0;
-        sq = sq1;
+        if (b + 2 < nblocks) s_next = pair_load(in, b + 2, nblocks);
+        PairStats const a = pair_stats(S, sq, have1);
+        sq = a.sq1;
         s_S[par][lane] = S;
         if (n == 0) {
           float *st = s_a[par][h];
-          st[0] = amp;
-          st[1] = bbp;
-          st[2] = snr;
-          st[3] = __int_as_float(h ? sq1 : sq0);
+          st[0] = a.amp;
+          st[1] = a.bbp;
+          st[2] = a.snr;
+          st[3] = __int_as_float(h ? a.sq1 : a.sq0);
         }
       }
       __syncthreads();
@@ -368,64 +413,24 @@ __device__ void fm_channel_four_waves(const Geom &g, const ChanDev &ch, const Pl
     return;
   }
 
-  if (role == 1) {  // ---------------- discriminator with hold (fm.c:117-144)
+  if (role == 1) {  // ---------------- discriminator with hold
     float2 state = ch.fm_state[c];
     float lastaudio = ch.lastaudio[c];
     for (int it = 0; it < niter; it++) {
       if (it >= 1 && it - 1 < npairs) {
         int const b = 2 * (it - 1), par = (it - 1) & 1;
         bool const have1 = b + 1 < nblocks;
-        float2 const S = s_S[par][lane];
-        float const amp = s_a[par][h][0];
         int const sq0 = __float_as_int(s_a[par][0][3]), sq1 = __float_as_int(s_a[par][1][3]);
-        bool const open0 = sq0 < 2, open1 = have1 && sq1 < 2;
-        bool const my_open = h ? open1 : open0;
-        float const t = cnrm(S);
-        float const thr = (float)(0.55 * 0.55 * amp * amp);
-        unsigned long long const raw = __ballot(t > thr);
-        unsigned long long const m_lo = open0 ? (raw & 0xffffffffull) : 0ull;
-        unsigned long long const m_hi = open1 ? (raw >> 32) : 0ull;
-        unsigned long long const mask = m_lo | (m_hi << 32);
-        bool const valid = (mask >> lane) & 1ull;
-        unsigned long long const below = mask & ((1ull << lane) - 1ull);
-        unsigned long long const upto = mask & ((2ull << lane) - 1ull);
-        int const pv = below ? 63 - __clzll((long long)below) : -1;
-        int const lv = upto ? 63 - __clzll((long long)upto) : -1;
-        // with no predecessor in the mask: block b falls back on the carried state, block b+1 on what block b leaves
-        // behind when it has no valid sample either -- the carried state if b is open, zero if it is squelched
-        float2 const state_fb = (h && !open0) ? make_float2(0.f, 0.f) : state;
-        float const la_fb = (h && !open0) ? 0.f : lastaudio;
-        float2 const sp = shfl2(S, pv >= 0 ? pv : 0);
-        float2 const stc = pv >= 0 ? cconj(sp) : state_fb;
-        float2 const pr = cmul(S, stc);
-        float const y = valid ? atan2f(pr.y, pr.x) : 0.f;
-        float const yl = __shfl(y, lv >= 0 ? lv : 0, 64);
-        float const out = my_open ? (lv >= 0 ? yl : la_fb) : 0.f;
-        // carried state after the pair (fm.c:133-144, 156-160)
-        {
-          int const last0 = m_lo ? 63 - __clzll((long long)m_lo) : 0;
-          int const last1 = m_hi ? 95 - __clzll((long long)m_hi) : 0;
-          float2 const sl0 = cconj(make_float2(rdlane(S.x, last0), rdlane(S.y, last0)));
-          float2 const sl1 = cconj(make_float2(rdlane(S.x, last1), rdlane(S.y, last1)));
-          float const yl0 = rdlane(y, last0), yl1 = rdlane(y, last1);
-          float2 st0 = open0 ? (m_lo ? sl0 : state) : make_float2(0.f, 0.f);
-          float la0 = open0 ? (m_lo ? yl0 : lastaudio) : 0.f;
-          if (have1) {
-            st0 = open1 ? (m_hi ? sl1 : st0) : make_float2(0.f, 0.f);
-            la0 = open1 ? (m_hi ? yl1 : la0) : 0.f;
-          }
-          state = st0;
-          lastaudio = la0;
-        }
-        s_out[par][lane] = out;
-        s_y[par][lane] = y;
+        PairDisc const d = pair_discriminate(s_S[par][lane], s_a[par][h][0], sq0, sq1, have1, state, lastaudio);
+        s_out[par][lane] = d.out;
+        s_y[par][lane] = d.y;
         if (n == 0) {
           float *st = s_b[par][h];
           st[0] = s_a[par][h][1];
           st[1] = s_a[par][h][2];
-          st[2] = __int_as_float((int)(unsigned)(mask >> (32 * h)));   // this half's mask of valid samples
+          st[2] = __int_as_float((int)d.mask_h);
           st[3] = __int_as_float(h ? sq1 : sq0);
-          st[4] = __int_as_float(my_open ? 32 - __popcll((mask >> (32 * h)) & 0xffffffffull) : 0);
+          st[4] = __int_as_float(d.blanked);
         }
       }
       __syncthreads();
@@ -437,23 +442,13 @@ __device__ void fm_channel_four_waves(const Geom &g, const ChanDev &ch, const Pl
     return;
   }
 
-  int const kbin = bitrev6(lane);
-  if (role == 2) {  // ---------------- frequency offset and deviation (fm.c:125-154); de-emphasis, forward half (fm.c:162-171)
+  float2 wf[6], wi[6];  // (each of the two waves left uses one of them, and forms no other)
+  if (role == 2) {  // ---------------- frequency offset and deviation; de-emphasis, forward half
+    deemph_twiddles(wf, wi);
+    int const kbin = bitrev6(lane);
     int const herm_src = bitrev6((64 - kbin) & 63);
-    float2 HAf;
-    {
-      float2 const t = ch.aresp[(size_t)c * 33 + (kbin <= 32 ? kbin : 64 - kbin)];
-      HAf = kbin <= 32 ? t : cconj(t);
-    }
+    float2 const HAf = deemph_response(ch, c, kbin);
     bool const real_bin = kbin == 0 || kbin == 32;
-    float2 wf[6];
-#pragma unroll
-    for (int s = 0; s < 6; s++) {
-      int const half = 1 << s;
-      float sn, cs;
-      sincospif((float)(lane & (half - 1)) / (float)half, &sn, &cs);
-      wf[s] = make_float2(cs, -sn);
-    }
     float foffset = ch.foffset[c], pdev = ch.pdev[c];
     float hist = h ? 0.f : ch.ahist[(size_t)c * 32 + lane];  // lanes 0-31: the block before b
     for (int it = 0; it < niter; it++) {
@@ -463,44 +458,14 @@ __device__ void fm_channel_four_waves(const Geom &g, const ChanDev &ch, const Pl
         float const out = s_out[par][lane], y = s_y[par][lane];
         unsigned const mask_h = (unsigned)__float_as_int(s_b[par][h][2]);
         int const sq0 = __float_as_int(s_b[par][0][3]), sq1 = __float_as_int(s_b[par][1][3]);
-        bool const valid = (mask_h >> n) & 1u;
-        float const sum_y = hsum(out);
-        float const vmax = hreduce((valid && n > 0) ? y : -INFINITY, [](float a, float b2) { return fmaxf(a, b2); });
-        float const vmin = hreduce((valid && n > 0) ? y : INFINITY, [](float a, float b2) { return fminf(a, b2); });
-        float const y_first = h ? rdlane(y, 32) : rdlane(y, 0);
-        float const seed = (mask_h & 1u) ? y_first : 0.f;
-        float pdev_pos = fmaxf(seed, vmax), pdev_neg = fminf(seed, vmin);
-        float const avg_f = sum_y / 32.f;
-        pdev_pos -= avg_f;
-        pdev_neg -= avg_f;
-        float const mx = (pdev_pos > -pdev_neg) ? pdev_pos : -pdev_neg;
-        float const fo_new = (float)(g.dsamprate * avg_f * (0.5 * M_1_PI));
-        float const pd_new = (float)(g.dsamprate * mx * (0.5 * M_1_PI));
-        float const fo0 = (sq0 < 1) ? rdlane(fo_new, 0) : foffset, pd0 = (sq0 < 1) ? rdlane(pd_new, 0) : pdev;
-        float const fo1 = (have1 && sq1 < 1) ? rdlane(fo_new, 32) : fo0, pd1 = (have1 && sq1 < 1) ? rdlane(pd_new, 32) : pd0;
-        foffset = fo1;
-        pdev = pd1;
-
-        float const xo = lane_xor<32>(out, lane);    // lanes 0-31: block b+1, lanes 32-63: block b
-        float2 z = make_float2(h ? xo : hist, out);  // real: [hist | b], imaginary: [b | b+1]
-#pragma unroll
-        for (int s = 5; s >= 0; s--) {  // forward, decimation in frequency: natural in, bit-reversed out
-          float2 const r = lane_xor_pow2(z, s, lane);
-          z = ((lane >> s) & 1) ? cmul_fwd_stage(csub(r, z), wf[s], s) : cadd(z, r);
-        }
-        float2 const zm = cconj(shfl2(z, herm_src));  // conj(Z[64 - k])
-        float2 const z1 = make_float2(0.5f * (z.x + zm.x), 0.5f * (z.y + zm.y));     // spectrum of the real part
-        float2 const z2 = make_float2(0.5f * (z.y - zm.y), -0.5f * (z.x - zm.x));    // spectrum of the imaginary part
-        float2 g1 = cmul_response(HAf, z1), g2 = cmul_response(HAf, z2);  // filter.c:206-208 on both
-        if (real_bin) g1.y = g2.y = 0.f;                // the c2r transform ignores these imaginary parts
-        s_z[par][lane] = make_float2(g1.x - g2.y, g1.y + g2.x);  // g1 + j g2
-        hist = have1 ? xo : out;  // lanes 0-31: the last block processed becomes the history (filter.c:168)
+        PairDev const v = pair_deviation(g, out, y, mask_h, sq0, sq1, have1, foffset, pdev);
+        s_z[par][lane] = pair_deemph_forward(out, have1, hist, wf, HAf, herm_src, real_bin);
         if (n == 0) {
           float *st = s_c[par][h];
           st[0] = s_b[par][h][0];
           st[1] = s_b[par][h][1];
-          st[2] = h ? fo1 : fo0;
-          st[3] = h ? pd1 : pd0;
+          st[2] = h ? v.fo1 : v.fo0;
+          st[3] = h ? v.pd1 : v.pd0;
           st[4] = s_b[par][h][3];
           st[5] = s_b[par][h][4];
         }
@@ -516,71 +481,18 @@ __device__ void fm_channel_four_waves(const Geom &g, const ChanDev &ch, const Pl
   }
 
   // ---------------- wave 3: de-emphasis, inverse half; audio; status records
+  deemph_twiddles(wf, wi);
   float const gain = ch.fm_gain[c];
   float const noise_gain = ch.noise_gain[c];
-  float2 wi[6];
-#pragma unroll
-  for (int s = 0; s < 6; s++) {
-    int const half = 1 << s;
-    float sn, cs;
-    sincospif((float)(lane & (half - 1)) / (float)half, &sn, &cs);
-    wi[s] = make_float2(cs, sn);
-  }
   float n0 = ch.n0[c];
   float ifp_v = 0.f, n0raw_v = 0.f;
   for (int it = 0; it < niter; it++) {
     if (it >= 3) {
       int const b = 2 * (it - 3), par = (it - 3) & 1;
       bool const have1 = b + 1 < nblocks;
-      if ((b & 63) == 0) {  // per-block status inputs, lane i holds block b + i
-        int const bb = b + lane;
-        ifp_v = bb < nblocks ? pl.if_power[bb] : 0.f;
-        n0raw_v = (compute_n0 && bb < nblocks) ? pl.n0raw[(size_t)c * g.max_blocks + bb] : 0.f;
-      }
-      float2 z = s_z[par][lane];
-#pragma unroll
-      for (int s = 0; s < 6; s++) {  // backward, decimation in time: bit-reversed in, natural out
-        int const bit = (lane >> s) & 1;
-        float2 const v = bit ? cmul_inv_stage(z, wi[s]) : z;
-        float2 const r = lane_xor_pow2(v, s, lane);
-        z = bit ? csub(r, v) : cadd(v, r);
-      }
-      // lanes 32-63 hold the kept halves: real part block b, imaginary part block b+1 (fm.c:169-170)
-      float const a0 = z.x * gain, a1 = z.y * gain;
-      if (h) {
-        pl.audio[((size_t)c * g.max_blocks + b) * 64 + n] = a0;
-        if (have1) pl.audio[((size_t)c * g.max_blocks + b + 1) * 64 + n] = a1;
-      }
-      // status records: lane 0 writes block b, lane 32 block b+1
-      float const ifp = h ? rdlane(ifp_v, (b + 1) & 63) : rdlane(ifp_v, b & 63);
-      float const fresh0 = rdlane(n0raw_v, b & 63), fresh1 = rdlane(n0raw_v, (b + 1) & 63);
-      float n0a = n0, n0b = n0;
-      if (compute_n0) {  // fm.c:79-82, block after block
-        n0a = isnan(n0) ? fresh0 : (float)((double)n0 + .01 * (double)(fresh0 - n0));
-        n0b = have1 ? (isnan(n0a) ? fresh1 : (float)((double)n0a + .01 * (double)(fresh1 - n0a))) : n0a;
-        n0 = n0b;
-      }
-      if (n == 0 && (h == 0 || have1)) {
-        const float *st = s_c[par][h];
-        kq_chan_status rec;
-        rec.if_power = ifp;
-        rec.noise_gain = noise_gain;
-        rec.plfreq = NAN;  // N/D = 64: the PL slave would have 2 points (fm.c:203), measurement off
-        rec.cphase = 0;
-        rec.pll_lock = 0;
-        rec.lock_count = 0;
-        rec.n0 = compute_n0 ? (h ? n0b : n0a) : NAN;
-        rec.bb_power = st[0];
-        rec.snr = st[1];
-        rec.foffset = st[2];
-        rec.pdeviation = st[3];
-        rec.agc_gain = 0;
-        rec.squelch_count = __float_as_int(st[4]);
-        rec.hangcount = 0;
-        rec.blanked = __float_as_int(st[5]);
-        rec.nout = 32;
-        pl.status[(size_t)c * g.max_blocks + b + h] = rec;
-      }
+      pair_status_inputs(g, pl, c, b, nblocks, compute_n0, ifp_v, n0raw_v);
+      pair_inverse_audio(g, pl, c, b, have1, s_z[par][lane], wi, gain);
+      pair_status(g, pl, c, b, have1, compute_n0, ifp_v, n0raw_v, noise_gain, n0, s_c[par][h]);
     }
     __syncthreads();
   }
@@ -646,7 +558,7 @@ __device__ void agc_channel(const Geom &g, const ChanDev &ch, const Planes &pl, 
         float dc_mine = dc;
 #pragma unroll 32
         for (int i = 0; i < nsamp; i++) {
-          float const e = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, env), i));
+          float const e = rdlane(env, i);
           dc += 0.0001f * (e - dc);
           dc_mine = (lane == i) ? dc : dc_mine;
         }
@@ -711,7 +623,7 @@ __device__ void agc_channel(const Geom &g, const ChanDev &ch, const Planes &pl, 
       coast = __ballot(lane < nsamp && (LINEAR ? level * before > headroom : before * level > headroom)) == 0ull;
       if (coast) {
         g_mine = after;
-        gain_end[0] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, after), OLEN - 1));
+        gain_end[0] = rdlane(after, OLEN - 1);
         hang_end[0] = hang > OLEN ? hang - OLEN : 0;
         gain = g;
         hang = 0;
@@ -724,8 +636,7 @@ __device__ void agc_channel(const Geom &g, const ChanDev &ch, const Planes &pl, 
     if (plain) {
 #pragma unroll 32
       for (int i = 0; i < nsamp; i++) {
-        float const lv = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, level), i));
-        float const iv = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, inv), i));
+        float const lv = rdlane(level, i), iv = rdlane(inv, i);
         bool const attack = LINEAR ? lv * gain > headroom : gain * lv > headroom;
         gain = attack ? iv : gain * recovery;
         g_mine = (lane == i) ? gain : g_mine;
@@ -734,8 +645,7 @@ __device__ void agc_channel(const Geom &g, const ChanDev &ch, const Planes &pl, 
     }
 #pragma unroll 32
     for (int i = 0; i < ((held || plain || coast) ? 0 : nsamp); i++) {
-      float const lv = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, level), i));
-      float const iv = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, inv), i));
+      float const lv = rdlane(level, i), iv = rdlane(inv, i);
       bool const nan_gain = isnan(gain);
       bool const attack = nan_gain || (LINEAR ? lv * gain > headroom : gain * lv > headroom);
       float const rec = (hang != 0) ? gain : gain * recovery;
@@ -827,6 +737,8 @@ __device__ __forceinline__ float carrier_group(float env, int nsamp, int lane, f
 
 // the AGC recurrence over one group in agc_channel's four forms (held / coasting / plain / general); returns the gain
 // each lane's sample is scaled by
+// (not shared with agc_channel: that one records gain and hang counter at sample OLEN - 1 inside loops of a run-time 64-or-OLEN
+// trip count; merging the two changes the AM path's compiled loops and wants a measurement of its own)
 template <bool LINEAR, bool FULL>
 __device__ __forceinline__ float agc_group(float level, float inv, int nsamp, int lane, float headroom, float recovery,
                                            int hangmax, float &gain, int &hang) {

@@ -11,6 +11,7 @@
 #include <algorithm>
 
 #include "kq_device.hpp"
+#include "kq_fmstage.hpp"
 #include "kq_ldsfft.hpp"
 
 namespace kq {
@@ -37,27 +38,221 @@ namespace {
 __device__ __forceinline__ int top_bit(unsigned long long m) { return 63 - __clzll((long long)m); }
 __device__ __forceinline__ unsigned long long bits_upto(int k) { return (2ull << k) - 1ull; }   // bits 0..k
 __device__ __forceinline__ unsigned long long bits_below(int k) { return (1ull << k) - 1ull; }  // bits 0..k-1
+
+// ---- what k_demod_fm and k_demod_fm256 (below: the same four phases with the call's blocks held in LDS) share
+// per-block records of the current 64-block chunk; each kernel has one in LDS
+struct FmChunk {
+  float r_bb[64], r_snr[64], r_amp[64], r_la_out[64], r_la_in[64], r_foff[64], r_pdev[64];
+  int r_carry[64], r_pvc[64], r_sq[64], r_blanked[64];
+  float2 r_sc[64], r_sp[64], r_st_out[64], r_st_in[64];
+};
+// carried from block to block (fm.c:26,68-69 and struct demod); only wave 0 uses them
+struct FmCarried {
+  float2 c_state;
+  float c_la;
+  int c_sq;
+  float c_foff, c_pdev, c_n0;
+  __device__ __forceinline__ void load(const ChanDev &ch, int c) {
+    c_state = ch.fm_state[c];
+    c_la = ch.lastaudio[c];
+    c_sq = ch.sq_count[c];
+    c_foff = ch.foffset[c], c_pdev = ch.pdev[c];
+    c_n0 = ch.n0[c];
+  }
+  __device__ __forceinline__ void store(const ChanDev &ch, int c) const {
+    ch.n0[c] = c_n0;
+    ch.fm_state[c] = c_state;
+    ch.lastaudio[c] = c_la;
+    ch.sq_count[c] = c_sq;
+    ch.foffset[c] = c_foff;
+    ch.pdev[c] = c_pdev;
+  }
+};
+
+// phase A's tail: a block's statistics from its two sums (fm.c:99-103) and the blanking threshold (fm.c:121)
+__device__ __forceinline__ float fm_threshold(float amp) { return (float)(0.55 * 0.55 * amp * amp); }
+struct FmBlockStats {
+  float bb, amp, snr, thr;
+};
+__device__ __forceinline__ FmBlockStats fm_block_stats(float sum_t, float sum_a, int olen) {
+  FmBlockStats r;
+  r.bb = sum_t / (2 * olen);
+  r.amp = (float)((double)sum_a / (M_SQRT2 * olen));
+  float const variance = r.bb - r.amp * r.amp;
+  float snr = r.amp * r.amp / (2 * variance) - 1;
+  r.snr = (0.0f > snr) ? 0.0f : snr;  // misc.h max(): NaN propagates
+  r.thr = fm_threshold(r.amp);
+  return r;
+}
+// ... and its record, by lane 0; carry, pvc: the block's last strong sample and the one before it (-1: none), S: its samples
+__device__ __forceinline__ void fm_record_stats(FmChunk &rec, int k, const FmBlockStats &st, int carry, int pvc, const float2 *S) {
+  rec.r_bb[k] = st.bb;
+  rec.r_snr[k] = st.snr;
+  rec.r_amp[k] = st.amp;
+  rec.r_carry[k] = carry;
+  rec.r_pvc[k] = pvc;
+  rec.r_sc[k] = carry >= 0 ? S[carry] : make_float2(0.f, 0.f);
+  rec.r_sp[k] = pvc >= 0 ? S[pvc] : make_float2(0.f, 0.f);
+}
+
+// phase B (wave 0, lanes = blocks): squelch counters and what every block starts from
+__device__ __forceinline__ void fm_phase_b(FmChunk &rec, FmCarried &cr, int nb) {
+  int const lane = threadIdx.x & 63;
+  bool const act = lane < nb;
+  bool const reset = act && rec.r_snr[lane] > 2;  // fm.c:108-114
+  unsigned long long const rm = __ballot(reset), rl = rm & bits_upto(lane);
+  int const sq = rl ? lane - top_bit(rl) : min(cr.c_sq + lane + 1, 1000);
+  bool const open = sq < 2;
+  int const carry = act ? rec.r_carry[lane] : -1;
+  // a squelched block leaves zeros behind (fm.c:156-160), an open one with a strong sample leaves that sample
+  bool const def = act && (!open || carry >= 0);
+  float2 const sc = rec.r_sc[lane];
+  rec.r_st_out[lane] = open ? cconj(sc) : make_float2(0.f, 0.f);
+  unsigned long long const dm = __ballot(def), dl = dm & bits_below(lane);
+  int const j = dl ? top_bit(dl) : -1;
+  wave_sync();
+  float2 const st_in = j >= 0 ? rec.r_st_out[j] : cr.c_state;
+  float ylast = 0;
+  if (open && carry >= 0) {  // the discriminator output at the block's last strong sample (fm.c:130-132)
+    float2 const st = rec.r_pvc[lane] >= 0 ? cconj(rec.r_sp[lane]) : st_in;
+    float2 const pr = cmul(sc, st);
+    ylast = atan2f(pr.y, pr.x);
+  }
+  rec.r_la_out[lane] = ylast;
+  wave_sync();
+  rec.r_la_in[lane] = j >= 0 ? rec.r_la_out[j] : cr.c_la;
+  rec.r_st_in[lane] = st_in;
+  rec.r_sq[lane] = sq;
+  if (dm) {
+    int const jl = top_bit(dm);
+    cr.c_state = rec.r_st_out[jl];
+    cr.c_la = rec.r_la_out[jl];
+  }
+  cr.c_sq = __shfl(sq, nb - 1, 64);
+}
+
+// phase C, one block by one wave: discriminator and hold rule (fm.c:116-160).  S: the block's samples, Y: the wave's
+// discriminator outputs before the hold, fo: where the detected samples go.  OLEN = 0: any block length, olen samples;
+// otherwise the length itself, a multiple of 64 (no lane is ever past the block's end).  The wave's lane 0 records the result.
+struct FmBlockReadings {
+  int blanked;
+  float foff, pdev;
+};
+template <int OLEN>
+__device__ __forceinline__ FmBlockReadings fm_block_discriminate(const Geom &g, const float2 *S, float *Y, float *fo, int olen_any,
+                                                                 float thr, float2 st_in, float la_in, int sq) {
+  static_assert(OLEN % 64 == 0, "whole groups of 64 samples");
+  int const lane = threadIdx.x & 63;
+  int const olen = OLEN ? OLEN : olen_any;
+  auto const inside = [&](int n) { return OLEN != 0 || n < olen; };
+  FmBlockReadings r = {0, 0.f, 0.f};
+  if (sq >= 2) {
+    for (int n = lane; n < olen; n += 64) fo[n] = 0;  // fm.c:156-160
+    return r;
+  }
+  int carry = -1;
+  for (int cb = 0; cb < olen; cb += 64) {
+    int const n = cb + lane;
+    float2 const v = S[inside(n) ? n : 0];
+    bool const valid = inside(n) && cnrm(v) > thr;
+    unsigned long long const m = __ballot(valid), ml = m & bits_below(lane);
+    if (valid) {  // arg(s_n * conj(previous strong sample)), fm.c:130-132
+      int const pv = ml ? cb + top_bit(ml) : carry;
+      float2 const st = pv >= 0 ? cconj(S[pv]) : st_in;
+      float2 const pr = cmul(v, st);
+      Y[n] = atan2f(pr.y, pr.x);
+    }
+    if (m) carry = cb + top_bit(m);
+  }
+  wave_sync();
+  // weak samples repeat the last good audio value (fm.c:141)
+  float sum_y = 0, vmax = -INFINITY, vmin = INFINITY;
+  bool first_valid = false;
+  carry = -1;
+  for (int cb = 0; cb < olen; cb += 64) {
+    int const n = cb + lane;
+    bool const valid = inside(n) && cnrm(S[inside(n) ? n : 0]) > thr;
+    unsigned long long const m = __ballot(valid), mu = m & bits_upto(lane);
+    if (cb == 0) first_valid = (m & 1ull) != 0;
+    if (inside(n)) {
+      int const lv = mu ? cb + top_bit(mu) : carry;
+      float const y = lv >= 0 ? Y[lv] : la_in;
+      fo[n] = y;
+      sum_y += y;
+      if (valid) {
+        if (n > 0) {
+          vmax = fmaxf(vmax, y);
+          vmin = fminf(vmin, y);
+        }
+      } else {
+        r.blanked++;
+      }
+    }
+    if (m) carry = cb + top_bit(m);
+  }
+  sum_y = wave_sum(sum_y);
+  vmax = wave_max(vmax);
+  vmin = wave_min(vmin);
+  r.blanked = wave_sum_i(r.blanked);
+  // peak-deviation seeds: sample 0 seeds both only when it is strong (fm.c:125-139)
+  float const seed = first_valid ? Y[0] : 0.0f;
+  float pdev_pos = fmaxf(seed, vmax), pdev_neg = fminf(seed, vmin);
+  float const avg_f = sum_y / olen;
+  if (sq < 1) {  // fm.c:146-154
+    r.foff = (float)(g.dsamprate * avg_f * (0.5 * M_1_PI));
+    pdev_pos -= avg_f;
+    pdev_neg -= avg_f;
+    float const mx = (pdev_pos > -pdev_neg) ? pdev_pos : -pdev_neg;
+    r.pdev = (float)(g.dsamprate * mx * (0.5 * M_1_PI));
+  }
+  wave_sync();  // Y (and S, where it is the wave's own) is reused by this wave's next block
+  return r;
+}
+
+// phase D (wave 0, lanes = blocks): carried readings, the n0 smoother and the status records of blocks b0 .. b0 + nb - 1
+__device__ __forceinline__ void fm_phase_d(const FmChunk &rec, FmCarried &cr, const Geom &g, const Planes &pl, int c, int b0, int nb,
+                                           float noise_gain, int compute_n0, int olen) {
+  int const lane = threadIdx.x & 63;
+  bool const act = lane < nb;
+  int const sq = rec.r_sq[lane];
+  bool const own = act && sq < 1;
+  unsigned long long const om = __ballot(own), ol = om & bits_upto(lane);
+  int const jo = ol ? top_bit(ol) : -1;
+  float const foffset = jo >= 0 ? rec.r_foff[jo] : cr.c_foff;
+  float const pdev = jo >= 0 ? rec.r_pdev[jo] : cr.c_pdev;
+  if (om) {
+    int const jl = top_bit(om);
+    cr.c_foff = rec.r_foff[jl];
+    cr.c_pdev = rec.r_pdev[jl];
+  }
+  float n0_mine = NAN;
+  if (compute_n0) {  // fm.c:79-82: a chain in double through the blocks
+    float const fresh_v = act ? pl.n0raw[(size_t)c * g.max_blocks + b0 + lane] : 0.f;
+    for (int k = 0; k < nb; k++) {
+      float const fresh = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(fresh_v), k));
+      cr.c_n0 = n0_step(cr.c_n0, fresh, .01);
+      if (lane == k) n0_mine = cr.c_n0;
+    }
+  }
+  if (act)
+    pl.status[(size_t)c * g.max_blocks + b0 + lane] =
+        fm_status_record(pl.if_power[b0 + lane], noise_gain, n0_mine, rec.r_bb[lane], rec.r_snr[lane], foffset, pdev, sq,
+                         rec.r_blanked[lane], olen);
+}
 }  // namespace
 
 __global__ void __launch_bounds__(1024) k_demod_fm(Geom g, ChanDev ch, Planes pl, float *__restrict__ fmout,
                                                    const int *__restrict__ list, int nblocks, int compute_n0) {
   extern __shared__ __attribute__((aligned(16))) float2 lds[];
-  // per-block records of the current 64-block chunk
-  __shared__ float r_bb[64], r_snr[64], r_amp[64], r_la_out[64], r_la_in[64], r_foff[64], r_pdev[64];
-  __shared__ int r_carry[64], r_pvc[64], r_sq[64], r_blanked[64];
-  __shared__ float2 r_sc[64], r_sp[64], r_st_out[64], r_st_in[64];
+  __shared__ FmChunk rec;
   int const c = list[blockIdx.x];
   int const lane = threadIdx.x & 63;
   int const wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), W = blockDim.x >> 6;
   int const olen = g.olen;
   float2 *S = lds + (size_t)wave * olen;
   float *Y = reinterpret_cast<float *>(lds + (size_t)W * olen) + (size_t)wave * olen;
-  // carried from block to block (fm.c:26,68-69 and struct demod); only wave 0 uses them
-  float2 c_state = ch.fm_state[c];
-  float c_la = ch.lastaudio[c];
-  int c_sq = ch.sq_count[c];
-  float c_foff = ch.foffset[c], c_pdev = ch.pdev[c];
-  float c_n0 = ch.n0[c];
+  FmCarried cr;
+  cr.load(ch, c);
   float const noise_gain = ch.noise_gain[c];
 
   for (int b0 = 0; b0 < nblocks; b0 += 64) {
@@ -75,16 +270,11 @@ __global__ void __launch_bounds__(1024) k_demod_fm(Geom g, ChanDev ch, Planes pl
       }
       sum_t = wave_sum(sum_t);
       sum_a = wave_sum(sum_a);
-      float const bb = sum_t / (2 * olen);
-      float const amp = (float)((double)sum_a / (M_SQRT2 * olen));
-      float const variance = bb - amp * amp;
-      float snr = amp * amp / (2 * variance) - 1;
-      snr = (0.0f > snr) ? 0.0f : snr;  // misc.h max(): NaN propagates
-      float const thr = (float)(0.55 * 0.55 * amp * amp);  // fm.c:121
+      FmBlockStats const st = fm_block_stats(sum_t, sum_a, olen);
       int carry = -1, pvc = -1;  // last strong sample and the one before it
       for (int cb = 0; cb < olen; cb += 64) {
         int const n = cb + lane;
-        bool const valid = n < olen && cnrm(S[n < olen ? n : 0]) > thr;
+        bool const valid = n < olen && cnrm(S[n < olen ? n : 0]) > st.thr;
         unsigned long long const m = __ballot(valid);
         if (m) {
           int const top = top_bit(m);
@@ -94,187 +284,35 @@ __global__ void __launch_bounds__(1024) k_demod_fm(Geom g, ChanDev ch, Planes pl
         }
       }
       wave_sync();
-      if (lane == 0) {
-        r_bb[k] = bb;
-        r_snr[k] = snr;
-        r_amp[k] = amp;
-        r_carry[k] = carry;
-        r_pvc[k] = pvc;
-        r_sc[k] = carry >= 0 ? S[carry] : make_float2(0.f, 0.f);
-        r_sp[k] = pvc >= 0 ? S[pvc] : make_float2(0.f, 0.f);
-      }
+      if (lane == 0) fm_record_stats(rec, k, st, carry, pvc, S);
       wave_sync();
     }
     __syncthreads();
     // ---- B: squelch counters and what every block starts from
-    if (wave == 0) {
-      bool const act = lane < nb;
-      bool const reset = act && r_snr[lane] > 2;  // fm.c:108-114
-      unsigned long long const rm = __ballot(reset), rl = rm & bits_upto(lane);
-      int const sq = rl ? lane - top_bit(rl) : min(c_sq + lane + 1, 1000);
-      bool const open = sq < 2;
-      int const carry = act ? r_carry[lane] : -1;
-      // a squelched block leaves zeros behind (fm.c:156-160), an open one with a strong sample leaves that sample
-      bool const def = act && (!open || carry >= 0);
-      float2 const sc = r_sc[lane];
-      r_st_out[lane] = open ? cconj(sc) : make_float2(0.f, 0.f);
-      unsigned long long const dm = __ballot(def), dl = dm & bits_below(lane);
-      int const j = dl ? top_bit(dl) : -1;
-      wave_sync();
-      float2 const st_in = j >= 0 ? r_st_out[j] : c_state;
-      float ylast = 0;
-      if (open && carry >= 0) {  // the discriminator output at the block's last strong sample (fm.c:130-132)
-        float2 const st = r_pvc[lane] >= 0 ? cconj(r_sp[lane]) : st_in;
-        float2 const pr = cmul(sc, st);
-        ylast = atan2f(pr.y, pr.x);
-      }
-      r_la_out[lane] = ylast;
-      wave_sync();
-      r_la_in[lane] = j >= 0 ? r_la_out[j] : c_la;
-      r_st_in[lane] = st_in;
-      r_sq[lane] = sq;
-      if (dm) {
-        int const jl = top_bit(dm);
-        c_state = r_st_out[jl];
-        c_la = r_la_out[jl];
-      }
-      c_sq = __shfl(sq, nb - 1, 64);
-    }
+    if (wave == 0) fm_phase_b(rec, cr, nb);
     __syncthreads();
     // ---- C: discriminator and hold rule (fm.c:116-160)
     for (int k = wave; k < nb; k += W) {
       const float2 *in = pl.filt + ((size_t)c * g.max_blocks + b0 + k) * olen;
       float *fo = fmout + ((size_t)c * g.max_blocks + b0 + k) * olen;
-      int const sq = r_sq[k];
-      int blanked = 0;
-      float foff = 0, pdev = 0;
+      int const sq = rec.r_sq[k];
       if (sq < 2) {
-        float const amp = r_amp[k];
-        float const thr = (float)(0.55 * 0.55 * amp * amp);
-        float2 const st_in = r_st_in[k];
-        float const la_in = r_la_in[k];
         for (int n = lane; n < olen; n += 64) S[n] = in[n];
         wave_sync();
-        int carry = -1;
-        for (int cb = 0; cb < olen; cb += 64) {
-          int const n = cb + lane;
-          float2 const v = S[n < olen ? n : 0];
-          bool const valid = n < olen && cnrm(v) > thr;
-          unsigned long long const m = __ballot(valid), ml = m & bits_below(lane);
-          if (valid) {  // arg(s_n * conj(previous strong sample)), fm.c:130-132
-            int const pv = ml ? cb + top_bit(ml) : carry;
-            float2 const st = pv >= 0 ? cconj(S[pv]) : st_in;
-            float2 const pr = cmul(v, st);
-            Y[n] = atan2f(pr.y, pr.x);
-          }
-          if (m) carry = cb + top_bit(m);
-        }
-        wave_sync();
-        // weak samples repeat the last good audio value (fm.c:141)
-        float sum_y = 0, vmax = -INFINITY, vmin = INFINITY;
-        bool first_valid = false;
-        carry = -1;
-        for (int cb = 0; cb < olen; cb += 64) {
-          int const n = cb + lane;
-          bool const valid = n < olen && cnrm(S[n < olen ? n : 0]) > thr;
-          unsigned long long const m = __ballot(valid), mu = m & bits_upto(lane);
-          if (cb == 0) first_valid = (m & 1ull) != 0;
-          if (n < olen) {
-            int const lv = mu ? cb + top_bit(mu) : carry;
-            float const y = lv >= 0 ? Y[lv] : la_in;
-            fo[n] = y;
-            sum_y += y;
-            if (valid) {
-              if (n > 0) {
-                vmax = fmaxf(vmax, y);
-                vmin = fminf(vmin, y);
-              }
-            } else {
-              blanked++;
-            }
-          }
-          if (m) carry = cb + top_bit(m);
-        }
-        sum_y = wave_sum(sum_y);
-        vmax = wave_max(vmax);
-        vmin = wave_min(vmin);
-        blanked = wave_sum_i(blanked);
-        // peak-deviation seeds: sample 0 seeds both only when it is strong (fm.c:125-139)
-        float const seed = first_valid ? Y[0] : 0.0f;
-        float pdev_pos = fmaxf(seed, vmax), pdev_neg = fminf(seed, vmin);
-        float const avg_f = sum_y / olen;
-        if (sq < 1) {  // fm.c:146-154
-          foff = (float)(g.dsamprate * avg_f * (0.5 * M_1_PI));
-          pdev_pos -= avg_f;
-          pdev_neg -= avg_f;
-          float const mx = (pdev_pos > -pdev_neg) ? pdev_pos : -pdev_neg;
-          pdev = (float)(g.dsamprate * mx * (0.5 * M_1_PI));
-        }
-        wave_sync();  // S and Y are reused by this wave's next block
-      } else {
-        for (int n = lane; n < olen; n += 64) fo[n] = 0;  // fm.c:156-160
       }
+      FmBlockReadings const r = fm_block_discriminate<0>(g, S, Y, fo, olen, fm_threshold(rec.r_amp[k]), rec.r_st_in[k], rec.r_la_in[k], sq);
       if (lane == 0) {
-        r_blanked[k] = blanked;
-        r_foff[k] = foff;
-        r_pdev[k] = pdev;
+        rec.r_blanked[k] = r.blanked;
+        rec.r_foff[k] = r.foff;
+        rec.r_pdev[k] = r.pdev;
       }
     }
     __syncthreads();
     // ---- D: carried readings and the status records
-    if (wave == 0) {
-      bool const act = lane < nb;
-      int const sq = r_sq[lane];
-      bool const own = act && sq < 1;
-      unsigned long long const om = __ballot(own), ol = om & bits_upto(lane);
-      int const jo = ol ? top_bit(ol) : -1;
-      float const foffset = jo >= 0 ? r_foff[jo] : c_foff;
-      float const pdev = jo >= 0 ? r_pdev[jo] : c_pdev;
-      if (om) {
-        int const jl = top_bit(om);
-        c_foff = r_foff[jl];
-        c_pdev = r_pdev[jl];
-      }
-      float n0_mine = NAN;
-      if (compute_n0) {  // fm.c:79-82: a chain in double through the blocks
-        float const fresh_v = act ? pl.n0raw[(size_t)c * g.max_blocks + b0 + lane] : 0.f;
-        for (int k = 0; k < nb; k++) {
-          float const fresh = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(fresh_v), k));
-          c_n0 = isnan(c_n0) ? fresh : (float)((double)c_n0 + .01 * (double)(fresh - c_n0));
-          if (lane == k) n0_mine = c_n0;
-        }
-      }
-      if (act) {
-        kq_chan_status st;
-        st.if_power = pl.if_power[b0 + lane];
-        st.noise_gain = noise_gain;
-        st.plfreq = NAN;
-        st.cphase = 0;
-        st.pll_lock = 0;
-        st.lock_count = 0;
-        st.n0 = n0_mine;
-        st.bb_power = r_bb[lane];
-        st.snr = r_snr[lane];
-        st.foffset = foffset;
-        st.pdeviation = pdev;
-        st.agc_gain = 0;
-        st.squelch_count = sq;
-        st.hangcount = 0;
-        st.blanked = r_blanked[lane];
-        st.nout = olen;
-        pl.status[(size_t)c * g.max_blocks + b0 + lane] = st;
-      }
-    }
+    if (wave == 0) fm_phase_d(rec, cr, g, pl, c, b0, nb, noise_gain, compute_n0, olen);
     __syncthreads();
   }
-  if (threadIdx.x == 0) {
-    ch.n0[c] = c_n0;
-    ch.fm_state[c] = c_state;
-    ch.lastaudio[c] = c_la;
-    ch.sq_count[c] = c_sq;
-    ch.foffset[c] = c_foff;
-    ch.pdev[c] = c_pdev;
-  }
+  if (threadIdx.x == 0) cr.store(ch, c);
 }
 
 // De-emphasis overlap-save and PL slave of one (channel, block): REAL -> REAL (fm.c:162-171, 219-234;
@@ -629,18 +667,13 @@ __global__ void __launch_bounds__(512) k_demod_fm256(Geom g, ChanDev ch, Planes 
   __shared__ __attribute__((aligned(16))) float2 S[64 * olen];
   __shared__ __attribute__((aligned(16))) float FO[65 * olen];
   __shared__ float Yall[W * olen];
-  __shared__ float r_bb[64], r_snr[64], r_amp[64], r_la_out[64], r_la_in[64], r_foff[64], r_pdev[64];
-  __shared__ int r_carry[64], r_pvc[64], r_sq[64], r_blanked[64];
-  __shared__ float2 r_sc[64], r_sp[64], r_st_out[64], r_st_in[64];
+  __shared__ FmChunk rec;
   int const c = list[blockIdx.x];
   int const lane = threadIdx.x & 63;
   int const wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   float *Y = Yall + wave * olen;
-  float2 c_state = ch.fm_state[c];
-  float c_la = ch.lastaudio[c];
-  int c_sq = ch.sq_count[c];
-  float c_foff = ch.foffset[c], c_pdev = ch.pdev[c];
-  float c_n0 = ch.n0[c];
+  FmCarried cr;
+  cr.load(ch, c);
   float const noise_gain = ch.noise_gain[c];
   bool const flat = (ch.flags[c] & FLAG_FLAT) != 0;
   float const gain = ch.fm_gain[c];
@@ -678,16 +711,11 @@ __global__ void __launch_bounds__(512) k_demod_fm256(Geom g, ChanDev ch, Planes 
       }
       sum_t = wave_sum(sum_t);
       sum_a = wave_sum(sum_a);
-      float const bb = sum_t / (2 * olen);
-      float const amp = (float)((double)sum_a / (M_SQRT2 * olen));
-      float const variance = bb - amp * amp;
-      float snr = amp * amp / (2 * variance) - 1;
-      snr = (0.0f > snr) ? 0.0f : snr;  // misc.h max(): NaN propagates
-      float const thr = (float)(0.55 * 0.55 * amp * amp);  // fm.c:121
+      FmBlockStats const st = fm_block_stats(sum_t, sum_a, olen);
       int carry = -1, pvc = -1;  // last strong sample and the one before it
 #pragma unroll
       for (int h = 0; h < 2; h++) {
-        bool const valid = cnrm(h ? vb[i] : va[i]) > thr;
+        bool const valid = cnrm(h ? vb[i] : va[i]) > st.thr;
         unsigned long long const m = __ballot(valid);
         if (m) {
           int const top = top_bit(m);
@@ -697,170 +725,25 @@ __global__ void __launch_bounds__(512) k_demod_fm256(Geom g, ChanDev ch, Planes 
         }
       }
       wave_sync();
-      if (lane == 0) {
-        r_bb[k] = bb;
-        r_snr[k] = snr;
-        r_amp[k] = amp;
-        r_carry[k] = carry;
-        r_pvc[k] = pvc;
-        r_sc[k] = carry >= 0 ? Sk[carry] : make_float2(0.f, 0.f);
-        r_sp[k] = pvc >= 0 ? Sk[pvc] : make_float2(0.f, 0.f);
-      }
+      if (lane == 0) fm_record_stats(rec, k, st, carry, pvc, Sk);
     }
     __syncthreads();
-    // ---- B: squelch counters and what every block starts from (k_demod_fm's phase B)
-    if (wave == 0) {
-      bool const act = lane < nb;
-      bool const reset = act && r_snr[lane] > 2;  // fm.c:108-114
-      unsigned long long const rm = __ballot(reset), rl = rm & bits_upto(lane);
-      int const sq = rl ? lane - top_bit(rl) : min(c_sq + lane + 1, 1000);
-      bool const open = sq < 2;
-      int const carry = act ? r_carry[lane] : -1;
-      bool const def = act && (!open || carry >= 0);
-      float2 const sc = r_sc[lane];
-      r_st_out[lane] = open ? cconj(sc) : make_float2(0.f, 0.f);
-      unsigned long long const dm = __ballot(def), dl = dm & bits_below(lane);
-      int const j = dl ? top_bit(dl) : -1;
-      wave_sync();
-      float2 const st_in = j >= 0 ? r_st_out[j] : c_state;
-      float ylast = 0;
-      if (open && carry >= 0) {  // the discriminator output at the block's last strong sample (fm.c:130-132)
-        float2 const st = r_pvc[lane] >= 0 ? cconj(r_sp[lane]) : st_in;
-        float2 const pr = cmul(sc, st);
-        ylast = atan2f(pr.y, pr.x);
-      }
-      r_la_out[lane] = ylast;
-      wave_sync();
-      r_la_in[lane] = j >= 0 ? r_la_out[j] : c_la;
-      r_st_in[lane] = st_in;
-      r_sq[lane] = sq;
-      if (dm) {
-        int const jl = top_bit(dm);
-        c_state = r_st_out[jl];
-        c_la = r_la_out[jl];
-      }
-      c_sq = __shfl(sq, nb - 1, 64);
-    }
+    // ---- B: squelch counters and what every block starts from
+    if (wave == 0) fm_phase_b(rec, cr, nb);
     __syncthreads();
     // ---- C: discriminator and hold rule (fm.c:116-160), samples from LDS, detected samples into FO[k + 1]
     for (int k = wave; k < nb; k += W) {
-      const float2 *Sk = S + k * olen;
-      float *fo = FO + (k + 1) * olen;
-      int const sq = r_sq[k];
-      int blanked = 0;
-      float foff = 0, pdev = 0;
-      if (sq < 2) {
-        float const amp = r_amp[k];
-        float const thr = (float)(0.55 * 0.55 * amp * amp);
-        float2 const st_in = r_st_in[k];
-        float const la_in = r_la_in[k];
-        int carry = -1;
-        for (int cb = 0; cb < olen; cb += 64) {
-          int const n = cb + lane;
-          float2 const v = Sk[n];
-          bool const valid = cnrm(v) > thr;
-          unsigned long long const m = __ballot(valid), ml = m & bits_below(lane);
-          if (valid) {  // arg(s_n * conj(previous strong sample)), fm.c:130-132
-            int const pv = ml ? cb + top_bit(ml) : carry;
-            float2 const st = pv >= 0 ? cconj(Sk[pv]) : st_in;
-            float2 const pr = cmul(v, st);
-            Y[n] = atan2f(pr.y, pr.x);
-          }
-          if (m) carry = cb + top_bit(m);
-        }
-        wave_sync();
-        float sum_y = 0, vmax = -INFINITY, vmin = INFINITY;
-        bool first_valid = false;
-        carry = -1;
-        for (int cb = 0; cb < olen; cb += 64) {
-          int const n = cb + lane;
-          bool const valid = cnrm(Sk[n]) > thr;
-          unsigned long long const m = __ballot(valid), mu = m & bits_upto(lane);
-          if (cb == 0) first_valid = (m & 1ull) != 0;
-          int const lv = mu ? cb + top_bit(mu) : carry;
-          float const y = lv >= 0 ? Y[lv] : la_in;  // weak samples repeat the last good audio value (fm.c:141)
-          fo[n] = y;
-          sum_y += y;
-          if (valid) {
-            if (n > 0) {
-              vmax = fmaxf(vmax, y);
-              vmin = fminf(vmin, y);
-            }
-          } else {
-            blanked++;
-          }
-          if (m) carry = cb + top_bit(m);
-        }
-        sum_y = wave_sum(sum_y);
-        vmax = wave_max(vmax);
-        vmin = wave_min(vmin);
-        blanked = wave_sum_i(blanked);
-        float const seed = first_valid ? Y[0] : 0.0f;  // fm.c:125-139
-        float pdev_pos = fmaxf(seed, vmax), pdev_neg = fminf(seed, vmin);
-        float const avg_f = sum_y / olen;
-        if (sq < 1) {  // fm.c:146-154
-          foff = (float)(g.dsamprate * avg_f * (0.5 * M_1_PI));
-          pdev_pos -= avg_f;
-          pdev_neg -= avg_f;
-          float const mx = (pdev_pos > -pdev_neg) ? pdev_pos : -pdev_neg;
-          pdev = (float)(g.dsamprate * mx * (0.5 * M_1_PI));
-        }
-        wave_sync();  // Y is reused by this wave's next block
-      } else {
-        fo[lane] = 0;  // fm.c:156-160
-        fo[lane + 64] = 0;
-      }
+      FmBlockReadings const r = fm_block_discriminate<olen>(g, S + k * olen, Y, FO + (k + 1) * olen, olen, fm_threshold(rec.r_amp[k]),
+                                                            rec.r_st_in[k], rec.r_la_in[k], rec.r_sq[k]);
       if (lane == 0) {
-        r_blanked[k] = blanked;
-        r_foff[k] = foff;
-        r_pdev[k] = pdev;
+        rec.r_blanked[k] = r.blanked;
+        rec.r_foff[k] = r.foff;
+        rec.r_pdev[k] = r.pdev;
       }
     }
     __syncthreads();
     // ---- D (wave 0): carried readings and the status records; the other waves start on the audio filter meanwhile
-    if (wave == 0) {
-      bool const act = lane < nb;
-      int const sq = r_sq[lane];
-      bool const own = act && sq < 1;
-      unsigned long long const om = __ballot(own), ol = om & bits_upto(lane);
-      int const jo = ol ? top_bit(ol) : -1;
-      float const foffset = jo >= 0 ? r_foff[jo] : c_foff;
-      float const pdev = jo >= 0 ? r_pdev[jo] : c_pdev;
-      if (om) {
-        int const jl = top_bit(om);
-        c_foff = r_foff[jl];
-        c_pdev = r_pdev[jl];
-      }
-      float n0_mine = NAN;
-      if (compute_n0) {  // fm.c:79-82: a chain in double through the blocks
-        float const fresh_v = act ? pl.n0raw[(size_t)c * g.max_blocks + b0 + lane] : 0.f;
-        for (int k = 0; k < nb; k++) {
-          float const fresh = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(fresh_v), k));
-          c_n0 = isnan(c_n0) ? fresh : (float)((double)c_n0 + .01 * (double)(fresh - c_n0));
-          if (lane == k) n0_mine = c_n0;
-        }
-      }
-      if (act) {
-        kq_chan_status st;
-        st.if_power = pl.if_power[b0 + lane];
-        st.noise_gain = noise_gain;
-        st.plfreq = NAN;
-        st.cphase = 0;
-        st.pll_lock = 0;
-        st.lock_count = 0;
-        st.n0 = n0_mine;
-        st.bb_power = r_bb[lane];
-        st.snr = r_snr[lane];
-        st.foffset = foffset;
-        st.pdeviation = pdev;
-        st.agc_gain = 0;
-        st.squelch_count = sq;
-        st.hangcount = 0;
-        st.blanked = r_blanked[lane];
-        st.nout = olen;
-        pl.status[(size_t)c * g.max_blocks + b0 + lane] = st;
-      }
-    }
+    if (wave == 0) fm_phase_d(rec, cr, g, pl, c, b0, nb, noise_gain, compute_n0, olen);
     // ---- audio: REAL -> REAL de-emphasis overlap-save on pairs of blocks (fm.c:162-171), FO row k + 1 = block b0 + k
     // (the transform's constants are formed here and not at the top: held across phases A - C they spill)
     Audio256 af;
@@ -900,14 +783,7 @@ __global__ void __launch_bounds__(512) k_demod_fm256(Geom g, ChanDev ch, Planes 
     }
     __syncthreads();
   }
-  if (threadIdx.x == 0) {
-    ch.n0[c] = c_n0;
-    ch.fm_state[c] = c_state;
-    ch.lastaudio[c] = c_la;
-    ch.sq_count[c] = c_sq;
-    ch.foffset[c] = c_foff;
-    ch.pdev[c] = c_pdev;
-  }
+  if (threadIdx.x == 0) cr.store(ch, c);
 }
 
 // PL tone tracker (fm.c:236-277): per FM channel, blocks in sequence: append the PL filter output to the

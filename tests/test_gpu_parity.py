@@ -757,6 +757,60 @@ def test_cfg2_geometry_without_the_pl_measurement(gpu, seed, per_call):
             assert all(np.isnan(st["plfreq"]) for st in got[c]["status"])
 
 
+# the float fields of an FM block's record (and the flat channel's audio) that k_demod_fm and k_demod_fm256 produce bit for
+# bit alike, as measured on the commit before the two kernels shared their phases (profiles/r10/fm_forms.txt).  bb_power and
+# snr are not among them: the two kernels' phase A (a loop over the block there, two register loads here) came out 7.5e-09 and
+# 1.7e-05 apart at the most, before that commit and after it alike; the oracle tests hold both.
+FM_FORMS_BIT_EQUAL = ("foffset", "pdeviation", "n0", "audio")
+
+
+def fm_forms_runs():
+    """cfg 2's geometry, three FM channels (de-emphasised, flat, noise only) on a signal that comes and goes, fades under the
+    blanking threshold and has a stretch of exact zeros (tests/test_gpu_edge_cases.py's, on a shorter schedule); 73 blocks in
+    calls of 70 and 3: one chunk border and a ragged tail.  -> the run with the PL measurement on (k_demod_fm runs phases
+    A - D) and the one with it off (k_demod_fm256 does)."""
+    g = dict(samprate=192000, L=512, M=513, D=4)
+    fs, L, nb = g["samprate"], g["L"], 73
+    n = nb * L
+    t = np.arange(n) / fs
+    rng = np.random.default_rng(91)
+    blk = np.arange(n) // L
+    on = ((blk < 15) | ((blk >= 30) & (blk < 45)) | (blk >= 50)).astype(np.float64)
+    fade = 1.0 + 0.93 * np.cos(2 * np.pi * 211.0 * t)      # dips under 0.55 of the block average
+    sig = 0.2 * on * fade * np.exp(1j * (2 * np.pi * 30000.0 * t + 2.5 * np.sin(2 * np.pi * 900.0 * t)))
+    iq = sig + 1e-3 * (rng.standard_normal(n) + 1j * rng.standard_normal(n))
+    iq[(blk >= 45) & (blk < 50)] = 0                        # digital silence
+    iq = iq.astype(np.complex64)
+    plan = [dict(demod="fm", low=-8000.0, high=8000.0, second_lo=-30000.0 - 13.0),
+            dict(demod="fm", low=-6000.0, high=8000.0, second_lo=-30000.0 + 7.0, flat=1),
+            dict(demod="fm", low=-8000.0, high=8000.0, second_lo=30000.0)]            # nothing but noise there
+    return [_run_bank(plan, g, iq, nb, kq.KQ_FWD_FULL, compute_n0=True, per_call=70, pl_tone=pl_tone)[0] for pl_tone in (True, False)]
+
+
+def test_cfg2_geometry_both_forms_of_the_fm_phases_agree(gpu):
+    """k_demod_fm (with k_fm_audio256 behind it) and the fused k_demod_fm256 run the same four phases from one set of
+    functions (kq_demod_fm.hip: fm_block_stats, fm_phase_b, fm_block_discriminate, fm_phase_d): block by block the records
+    they write must agree -- the integer fields always, the float fields of FM_FORMS_BIT_EQUAL to the bit -- and so must the
+    flat channel's audio, which is the detected samples themselves."""
+    with_pl, without_pl = fm_forms_runs()
+    closed = blanked = 0
+    for c in range(3):
+        for b, (s1, s2) in enumerate(zip(with_pl[c]["status"], without_pl[c]["status"])):
+            for k in ("squelch_count", "blanked", "nout"):
+                assert s1[k] == s2[k], (k, c, b, s1[k], s2[k])
+            for k in FM_FORMS_BIT_EQUAL:
+                if k != "audio":
+                    assert np.array_equal(np.float32(s1[k]), np.float32(s2[k]), equal_nan=True), (k, c, b, s1[k], s2[k])
+            closed += s1["squelch_count"] >= 2
+            blanked += s1["blanked"] > 0 and s1["squelch_count"] < 2
+            assert np.isnan(s2["plfreq"])
+        assert not np.any(np.isnan([s["n0"] for s in with_pl[c]["status"][:45]]))
+    if "audio" in FM_FORMS_BIT_EQUAL:
+        for b, (a1, a2) in enumerate(zip(with_pl[1]["audio"], without_pl[1]["audio"])):
+            assert len(a1) == 128 and np.array_equal(a1, a2), ("flat audio", b)
+    assert closed > 40 and blanked > 10           # the case exercises what it is meant to
+
+
 @pytest.mark.parametrize("name,pl_tone", [("cfg2", False), ("cfg2", True), ("cfg3", True), ("cfg1", True)])
 def test_more_than_64_blocks_in_one_call(gpu, name, pl_tone):
     """A call of 150 blocks (max_blocks is the host's choice; a file replayed faster than real time uses long calls): the FM

@@ -15,8 +15,8 @@ holds a twin to.
 
 Demodulator (k_demod64, N/D = 64).  The four-wave pipeline and the one-wave form compute "every value by the same
 expressions"; the launch takes the one-wave form above 2048 workgroups.  Channels 0-2 of a 3-channel and of a
-2052-channel bank, configured alike and fed alike, must agree in every audio sample and every status field, over two calls
-of five blocks (an odd count: the last pair of a call is half empty).
+2052-channel bank, configured alike and fed alike, must agree in every audio sample and every status field (compute_n0 on: the n0
+chain included), over ten blocks in calls of one, two and five (an odd count: the last pair of a call is half empty).
 """
 import functools
 
@@ -153,7 +153,7 @@ def test_filter_tail_on_zeros_takes_the_slow_path_of_compute_n0(gpu):
 # ---------------------------------------------------------------- demodulator: four waves against one
 
 DGEOM = dict(samprate=768000, L=512, M=513, D=16)     # N = 1024, N/D = 64, 32 samples per block at 48 kHz
-DBLOCKS, DCALLS = 5, 2
+DTOTAL = 10                                           # blocks in all, whatever the call length
 
 
 def _demod_plan(nchan):
@@ -167,35 +167,42 @@ def _demod_plan(nchan):
     return plan
 
 
-def _demod_run(nchan):
+def _demod_run(nchan, dblocks):
+    """-> per channel 0-2: [(audio, status)] of the DTOTAL blocks, taken `dblocks` per call; compute_n0 on, so that the n0
+    chain through the blocks is part of every record"""
     fs, L = DGEOM["samprate"], DGEOM["L"]
-    iq = wl.make_iq(fs, DBLOCKS * DCALLS * L, seed=47, emitters=[24])
-    bank = kq.Bank(fs, L, DGEOM["M"], DGEOM["D"], nchan, DBLOCKS)
+    iq = wl.make_iq(fs, DTOTAL * L, seed=47, emitters=[24])
+    bank = kq.Bank(fs, L, DGEOM["M"], DGEOM["D"], nchan, dblocks, compute_n0=True)
     got = bank.add_channels([bank_cfg(p) for p in _demod_plan(nchan)])
     assert list(got) == list(range(nchan))
-    out = []
-    for call in range(DCALLS):
-        bank.push_iq(iq[call * DBLOCKS * L:(call + 1) * DBLOCKS * L])
-        assert bank.process() == DBLOCKS
-        out.append([[(bank.audio(c, k), bank.status(c, k)) for k in range(DBLOCKS)] for c in range(3)])
+    out = [[] for _ in range(3)]
+    for call in range(DTOTAL // dblocks):
+        bank.push_iq(iq[call * dblocks * L:(call + 1) * dblocks * L])
+        assert bank.process() == dblocks
+        for c in range(3):
+            out[c] += [(bank.audio(c, k), bank.status(c, k)) for k in range(dblocks)]
     bank.close()
     return out
 
 
-def test_demod64_four_waves_and_one_wave_agree_bit_for_bit(gpu):
+@pytest.mark.parametrize("dblocks", [1, 2, 5])
+def test_demod64_four_waves_and_one_wave_agree_bit_for_bit(gpu, dblocks):
     """Before the de-emphasis filter's complex products had their rounding steps spelled out (cmul_as in kq_demod64.hip) the
     two forms were one set of expressions in the source and two sets of rounding steps as compiled: 152 and 142 of the 320
-    audio samples of channels 0 and 1 differed, by up to 2.98e-08 (profiles/r09/demod_forms.txt)."""
-    small, big = _demod_run(3), _demod_run(2052)      # 3 workgroups: four waves per de-emphasised channel; 2052: one wave
+    audio samples of channels 0 and 1 differed, by up to 2.98e-08 (profiles/r09/demod_forms.txt).  Since then both forms call
+    one set of stage functions.  Blocks per call: 1, a lone half pair (the pipeline fills and drains without a block b+1);
+    2, one full pair; 5, two pairs and a half one.  Ten blocks in all either way."""
+    small, big = _demod_run(3, dblocks), _demod_run(2052, dblocks)      # 3 workgroups: four waves per de-emphasised channel; 2052: one wave
     closed = False
-    for call in range(DCALLS):
-        for c in range(3):
-            for k in range(DBLOCKS):
-                (a4, s4), (a1, s1) = small[call][c][k], big[call][c][k]
-                assert len(a4) == 32
-                assert np.array_equal(a4, a1), ("audio", call, c, k)
-                assert _same_status(s4, s1), ("status", call, c, k, s4, s1)
-                closed |= c == 1 and s4["squelch_count"] >= 2
-    assert small[0][0][DBLOCKS - 1][1]["squelch_count"] == 0, "the carrier's channel stays open"
+    for c in range(3):
+        for k in range(DTOTAL):
+            (a4, s4), (a1, s1) = small[c][k], big[c][k]
+            assert len(a4) == 32
+            assert np.array_equal(a4, a1), ("audio", c, k)
+            assert _same_status(s4, s1), ("status", c, k, s4, s1)
+            assert not np.isnan(s4["n0"]), ("n0", c, k)
+            closed |= c == 1 and s4["squelch_count"] >= 2
+    for k in range(4, DTOTAL):      # (from the block on at which the five-blocks-per-call form of this test looked)
+        assert small[0][k][1]["squelch_count"] == 0, "the carrier's channel stays open"
     assert closed, "the noise-only channel's squelch closes"
-    assert np.any(small[0][0][DBLOCKS - 1][0]) and np.any(small[0][2][DBLOCKS - 1][0])
+    assert np.any(small[0][4][0]) and np.any(small[2][4][0])
