@@ -309,12 +309,8 @@ kq_ale_bank *kq_ale_create(const kq_ale_config *cfg) {
     kq_internal_set_error("%s: null config", fn);
     return nullptr;
   }
-  if (!kq::samprate_ok(fn, cfg->samprate) || !kq::field_in_range(fn, "block_len", cfg->block_len, 8, 256) ||
-      !kq::field_in_range(fn, "warm", cfg->warm, 0, 65535) || !kq::field_in_range(fn, "snr", cfg->snr, 16, 4095) ||
-      !kq::min_p_ok(fn, cfg->min_p) || !kq::input_scale_ok(fn, cfg->input_scale) ||
-      !kq::field_in_range(fn, "acq_err", cfg->acq_err, 0, 3) || !kq::field_in_range(fn, "lose", cfg->lose, 1, 15) ||
-      !kq::field_in_range(fn, "max_slots", cfg->max_slots, 1, kMaxSlots) ||
-      !kq::field_in_range(fn, "max_events", cfg->max_events, 1, 4096) || !kq::max_samples_ok(fn, cfg->max_samples))
+  if (!tc::config_head_ok(fn, cfg) || !kq::field_in_range(fn, "acq_err", cfg->acq_err, 0, 3) ||
+      !kq::field_in_range(fn, "lose", cfg->lose, 1, 15) || !tc::config_tail_ok(fn, cfg, kMaxSlots))
     return nullptr;
   (void)golay_tables();  // the tables exist from here on
   kq_ale_bank *b = tc::finish_create<kq_ale_bank>(cfg, kTile);  // Lmin 8 at the most: Bs <= 258

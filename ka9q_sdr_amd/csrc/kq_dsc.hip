@@ -317,12 +317,8 @@ kq_dsc_bank *kq_dsc_create(const kq_dsc_config *cfg) {
     kq_internal_set_error("%s: null config", fn);
     return nullptr;
   }
-  if (!kq::samprate_ok(fn, cfg->samprate) || !kq::field_in_range(fn, "block_len", cfg->block_len, 8, 256) ||
-      !kq::field_in_range(fn, "warm", cfg->warm, 0, 65535) || !kq::field_in_range(fn, "snr", cfg->snr, 16, 4095) ||
-      !kq::min_p_ok(fn, cfg->min_p) || !kq::input_scale_ok(fn, cfg->input_scale) ||
-      !kq::field_in_range(fn, "acq", cfg->acq, 1, 3) || !kq::field_in_range(fn, "lose", cfg->lose, 1, 15) ||
-      !kq::field_in_range(fn, "max_slots", cfg->max_slots, 1, kMaxSlots) ||
-      !kq::field_in_range(fn, "max_events", cfg->max_events, 1, 4096) || !kq::max_samples_ok(fn, cfg->max_samples))
+  if (!tc::config_head_ok(fn, cfg) || !kq::field_in_range(fn, "acq", cfg->acq, 1, 3) ||
+      !kq::field_in_range(fn, "lose", cfg->lose, 1, 15) || !tc::config_tail_ok(fn, cfg, kMaxSlots))
     return nullptr;
   kq_dsc_bank *b = tc::finish_create<kq_dsc_bank>(cfg, kTile);  // Lmin 8 at the most: Bs <= 258
   b->g.acq = cfg->acq;
@@ -336,18 +332,13 @@ int kq_dsc_set(kq_dsc_bank *b, unsigned slot, const kq_dsc_params *p) {
   const char *fn = "kq_dsc_set";
   std::unique_lock<std::mutex> lk;
   if (!tc::open_set(b, fn, slot, p, kMaxSlots, lk)) return -1;
-  double const Fs = b->cfg.samprate, fm = p->mark, fs = p->space;
-  if (!tc::tone_ok(fn, Fs, fm, "mark %g", fm) || !tc::tone_ok(fn, Fs, fs, "space %g", fs)) return -1;
-  if (p->mark == p->space) {
-    kq_internal_set_error("%s: mark and space are both %g", fn, fm);
-    return -1;
-  }
+  double const Fs = b->cfg.samprate;
   DscPar np{};
-  if (!tc::symbol_period(fn, Fs, b->cfg.block_len, p->baud, "bit", &np.tb, &np.W)) return -1;
+  if (!tc::tone_pair(fn, Fs, p->mark, p->space, &np.inc_m, &np.inc_s) ||
+      !tc::symbol_period(fn, Fs, b->cfg.block_len, p->baud, "bit", &np.tb, &np.W))
+    return -1;
   np.active = 1;
   np.source = p->source;
-  np.inc_m = (unsigned)std::llrint(fm * 4294967296.0 / Fs);
-  np.inc_s = (unsigned)std::llrint(fs * 4294967296.0 / Fs);
   b->def.set(slot, np);
   return 0;
 }
@@ -378,10 +369,7 @@ int kq_dsc_get_slot(kq_dsc_bank *b, unsigned slot, kq_dsc_slot *out) {
   std::unique_lock<std::mutex> lk;
   const DscPar *w = tc::wanted(b, "kq_dsc_get_slot", slot, out, "out", lk);
   if (!w) return -1;
-  out->inc_m = w->inc_m;
-  out->inc_s = w->inc_s;
-  out->tb = (uint32_t)w->tb;
-  out->W = (uint32_t)w->W;
+  tc::get_pair_slot(*w, out);
   return 0;
 }
 

@@ -17,9 +17,10 @@
 //                    Tables                             the bank's own device tables (NoTables; kq_ale's Golay tables)
 //                    kZeroCold, cold(par, status &)     a set slot's record starts all zero, or as cold() fills it (kq_cw)
 //                  A set slot's history starts all zero and its arena empty.
+//   config_head_ok, config_tail_ok   the config checks that kq_{rtty,psk,ale,dsc}_create report first and last, in their order
 //   finish_create  the tail of kq_*_create, behind the bank's checks
-//   open_set, tone_ok, symbol_period, wanted, process   the shared parts of kq_*_set, the opening of a getter, and the body
-//                  of kq_*_process around the bank's launch
+//   open_set, tone_ok, tone_pair, symbol_period, wanted, get_pair_slot, process   the shared parts of kq_*_set, the opening
+//                  of a getter, a two-tone getter's assignments, and the body of kq_*_process around the bank's launch
 //
 // What a bank still writes: its K, Geom, Par and CallArgs; the checks of create in the order it reports them and the
 // fields of Geom that are its own; the checks of set that are its own and the slot's record; the getters' assignments; the
@@ -192,6 +193,21 @@ struct GridBank : HostSide {
   }
 };
 
+// The checks of kq_*_create that the banks with frames of 8..256 samples share (kq_cw has other limits and another order):
+// the head, then the bank's own fields, then the tail.  Each reports the first field it refuses.
+template <class Config>
+bool config_head_ok(const char *fn, const Config *cfg) {
+  return kq::samprate_ok(fn, cfg->samprate) && kq::field_in_range(fn, "block_len", cfg->block_len, 8, 256) &&
+         kq::field_in_range(fn, "warm", cfg->warm, 0, 65535) && kq::field_in_range(fn, "snr", cfg->snr, 16, 4095) &&
+         kq::min_p_ok(fn, cfg->min_p) && kq::input_scale_ok(fn, cfg->input_scale);
+}
+
+template <class Config>
+bool config_tail_ok(const char *fn, const Config *cfg, unsigned slot_limit) {
+  return kq::field_in_range(fn, "max_slots", cfg->max_slots, 1, slot_limit) &&
+         kq::field_in_range(fn, "max_events", cfg->max_events, 1, 4096) && kq::max_samples_ok(fn, cfg->max_samples);
+}
+
 // the tail of kq_*_create, once the bank's checks have passed: the bank with its config, its slots, the grid and what every
 // Geom has of the config; `tile`: the samples a wave of the bank's kernel keeps in LDS
 template <class Bank, class Config>
@@ -234,6 +250,20 @@ __attribute__((format(printf, 4, 5))) inline bool tone_ok(const char *fn, double
   return false;
 }
 
+// a mark / space pair (kq_rtty, kq_dsc): both tones against 0 < f < Fs / 2 and against each other, then their phase
+// increments, rint(f 2^32 / Fs) in double
+inline bool tone_pair(const char *fn, double Fs, float mark, float space, unsigned *inc_m, unsigned *inc_s) {
+  double const fm = mark, fs = space;
+  if (!tone_ok(fn, Fs, fm, "mark %g", fm) || !tone_ok(fn, Fs, fs, "space %g", fs)) return false;
+  if (mark == space) {
+    kq_internal_set_error("%s: mark and space are both %g", fn, fm);
+    return false;
+  }
+  *inc_m = (unsigned)std::llrint(fm * 4294967296.0 / Fs);
+  *inc_s = (unsigned)std::llrint(fs * 4294967296.0 / Fs);
+  return true;
+}
+
 // the period of a bit or symbol (`noun`) of `baud` in 1/256 frame, *tb = rint(256 Fs / (B baud)) within 2048..8192, and
 // the window one period long in frames, *W
 inline bool symbol_period(const char *fn, double Fs, unsigned B, double baud, const char *noun, int *tb, int *W) {
@@ -271,6 +301,15 @@ const typename Bank::Par *wanted(Bank *b, const char *fn, unsigned slot, const v
     return nullptr;
   }
   return &b->def.want[slot];
+}
+
+// a two-tone slot's record as kq_*_get_slot hands it out: {inc_m, inc_s, tb, W}
+template <class Par, class Slot>
+void get_pair_slot(Par const &w, Slot *out) {
+  out->inc_m = w.inc_m;
+  out->inc_s = w.inc_s;
+  out->tb = (uint32_t)w.tb;
+  out->W = (uint32_t)w.W;
 }
 
 // The body of kq_*_process.  Args: the bank's argument block, Bank::Args or a struct on it; launch(args, blocks) fills what

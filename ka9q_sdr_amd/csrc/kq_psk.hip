@@ -211,12 +211,7 @@ kq_psk_bank *kq_psk_create(const kq_psk_config *cfg) {
     kq_internal_set_error("%s: null config", fn);
     return nullptr;
   }
-  if (!kq::samprate_ok(fn, cfg->samprate) || !kq::field_in_range(fn, "block_len", cfg->block_len, 8, 256) ||
-      !kq::field_in_range(fn, "warm", cfg->warm, 0, 65535) || !kq::field_in_range(fn, "snr", cfg->snr, 16, 4095) ||
-      !kq::min_p_ok(fn, cfg->min_p) || !kq::input_scale_ok(fn, cfg->input_scale) ||
-      !kq::field_in_range(fn, "max_slots", cfg->max_slots, 1, kMaxSlots) ||
-      !kq::field_in_range(fn, "max_events", cfg->max_events, 1, 4096) || !kq::max_samples_ok(fn, cfg->max_samples))
-    return nullptr;
+  if (!tc::config_head_ok(fn, cfg) || !tc::config_tail_ok(fn, cfg, kMaxSlots)) return nullptr;
   return tc::finish_create<kq_psk_bank>(cfg, kTile);  // Lmin 8 at the most: Bs <= 258
 }
 

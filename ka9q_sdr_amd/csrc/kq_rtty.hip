@@ -194,12 +194,7 @@ kq_rtty_bank *kq_rtty_create(const kq_rtty_config *cfg) {
     kq_internal_set_error("%s: null config", fn);
     return nullptr;
   }
-  if (!kq::samprate_ok(fn, cfg->samprate) || !kq::field_in_range(fn, "block_len", cfg->block_len, 8, 256) ||
-      !kq::field_in_range(fn, "warm", cfg->warm, 0, 65535) || !kq::field_in_range(fn, "snr", cfg->snr, 16, 4095) ||
-      !kq::min_p_ok(fn, cfg->min_p) || !kq::input_scale_ok(fn, cfg->input_scale) ||
-      !kq::field_in_range(fn, "max_slots", cfg->max_slots, 1, kMaxSlots) ||
-      !kq::field_in_range(fn, "max_events", cfg->max_events, 1, 4096) || !kq::max_samples_ok(fn, cfg->max_samples))
-    return nullptr;
+  if (!tc::config_head_ok(fn, cfg) || !tc::config_tail_ok(fn, cfg, kMaxSlots)) return nullptr;
   return tc::finish_create<kq_rtty_bank>(cfg, kTile);  // Lmin 8 at the most: Bs <= 258
 }
 
@@ -209,19 +204,13 @@ int kq_rtty_set(kq_rtty_bank *b, unsigned slot, const kq_rtty_params *p) {
   const char *fn = "kq_rtty_set";
   std::unique_lock<std::mutex> lk;
   if (!tc::open_set(b, fn, slot, p, kMaxSlots, lk)) return -1;
-  double const Fs = b->cfg.samprate, fm = p->mark, fs = p->space;
-  if (!tc::tone_ok(fn, Fs, fm, "mark %g", fm) || !tc::tone_ok(fn, Fs, fs, "space %g", fs)) return -1;
-  if (p->mark == p->space) {
-    kq_internal_set_error("%s: mark and space are both %g", fn, fm);
-    return -1;
-  }
+  double const Fs = b->cfg.samprate;
   RttyPar np{};
-  if (!kq::field_in_range(fn, "nbits", p->nbits, 5, 8) || !tc::symbol_period(fn, Fs, b->cfg.block_len, p->baud, "bit", &np.tb, &np.W))
+  if (!tc::tone_pair(fn, Fs, p->mark, p->space, &np.inc_m, &np.inc_s) || !kq::field_in_range(fn, "nbits", p->nbits, 5, 8) ||
+      !tc::symbol_period(fn, Fs, b->cfg.block_len, p->baud, "bit", &np.tb, &np.W))
     return -1;
   np.active = 1;
   np.source = p->source;
-  np.inc_m = (unsigned)std::llrint(fm * 4294967296.0 / Fs);
-  np.inc_s = (unsigned)std::llrint(fs * 4294967296.0 / Fs);
   np.nbits = (int)p->nbits;
   b->def.set(slot, np);
   return 0;
@@ -253,10 +242,7 @@ int kq_rtty_get_slot(kq_rtty_bank *b, unsigned slot, kq_rtty_slot *out) {
   std::unique_lock<std::mutex> lk;
   const RttyPar *w = tc::wanted(b, "kq_rtty_get_slot", slot, out, "out", lk);
   if (!w) return -1;
-  out->inc_m = w->inc_m;
-  out->inc_s = w->inc_s;
-  out->tb = (uint32_t)w->tb;
-  out->W = (uint32_t)w->W;
+  tc::get_pair_slot(*w, out);
   return 0;
 }
 

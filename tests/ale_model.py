@@ -6,15 +6,14 @@ the two 4096-entry tables of ka9q_sdr_amd/ale2g.py, word sync.  The frame sums a
 and everything from the shifts on in Python ints: there is no float after the quantiser.  The symbol length becomes an
 integer (tb) before any sample is seen, by the header's formula in double."""
 import collections
-import math
 
 import numpy as np
 
-import fsk_model as fm
-import tone_model as tm
+import fsk_model as fm            # (the tests reach the quantiser through the model: fm.quantise)
+import grid_model as gm
 from ka9q_sdr_amd import ale2g
 
-TABLE = tm.TABLE
+TABLE = gm.TABLE
 NT = 8
 M49 = (1 << 49) - 1
 Event = collections.namedtuple("Event", "word flags err_a err_b split reserved end_sample sig nse")
@@ -24,23 +23,13 @@ PARITY = [int(v) for v in ale2g.PARITY]
 ERRORS = [int(v) for v in ale2g.ERRORS]
 IN_SET = [chr(c) in ale2g.CHARSET for c in range(128)]
 
-cos_table = tm.cos_table
+cos_table, symbol_length, window = gm.cos_table, gm.period, gm.window
 
 
 def ale_inc(f0, df, Fs):
     """inc[t] = rint((f0 + t df) 2^32 / Fs) in double, f0 and df floats, the tone's frequency a double"""
     f0, df = float(np.float32(f0)), float(np.float32(df))
     return [int(np.rint((f0 + t * df) * 4294967296.0 / float(Fs))) for t in range(NT)]
-
-
-def symbol_length(Fs, B, baud):
-    """tb = rint(256 Fs / (B baud)) in double, baud a float32: the symbol in 1/256 frame"""
-    return int(np.rint(256.0 * float(Fs) / (float(B) * float(np.float32(baud)))))
-
-
-def window(tb):
-    """W = (tb + 128) >> 8 frames"""
-    return (tb + 128) >> 8
 
 
 def even_bits(x):
@@ -64,54 +53,38 @@ def address_like(w):
     return w >> 21 == ale2g.CMD or (IN_SET[w >> 14 & 0x7F] and IN_SET[w >> 7 & 0x7F] and IN_SET[w & 0x7F])
 
 
-class AleModel:
+class AleModel(gm.GridModel):
     """one slot.  table, inc, tb: the bank's own (kq_ale_get_table, kq_ale_get_slot), or None for the model's; start: the
     sample at which the slot was set (x = 0 before it).  gate=False leaves the validity gate open (the model only: for the
     false-alarm tests)"""
 
     def __init__(self, samprate, block_len, f0=750.0, df=250.0, baud=125.0, warm=64, snr=80, min_p=1 << 16, acq_err=1, lose=2,
                  input_scale=32767.0, max_events=256, table=None, inc=None, tb=None, start=0, gate=True):
-        self.Fs, self.B = float(samprate), int(block_len)
+        super().__init__(samprate, block_len, ale_inc(f0, df, samprate) if inc is None else inc, table,
+                         symbol_length(samprate, block_len, baud) if tb is None else tb, input_scale, max_events, start,
+                         widest=("P", "oth"))
         self.warm, self.snr, self.min_p, self.acq_err, self.lose = int(warm), int(snr), int(min_p), int(acq_err), int(lose)
-        self.scale, self.max_events, self.gate = input_scale, max_events, gate
-        self.C = cos_table() if table is None else np.asarray(table, np.int16)
-        self.inc = ale_inc(f0, df, samprate) if inc is None else [int(v) for v in inc]
-        self.tb = symbol_length(samprate, block_len, baud) if tb is None else int(tb)
-        self.W = window(self.tb)
-        self.q = self.tb >> 2
-        self.n = int(start)
-        self.acc = [[0, 0] for _ in range(NT)]                         # I, Q of the open frame, per tone
-        self.hist = collections.deque([((0, 0),) * NT] * self.W, self.W)
-        self.sums = [[0, 0] for _ in range(NT)]
-        self.ph = self.t = self.sym = 0
-        self.sig = self.nse = self.Ee = self.El = self.Pe = self.Pc = self.oth = 0
+        self.gate = gate
+        self.sym = 0
+        self.sig = self.nse = self.Pc = self.oth = 0
         self.r = [0, 0, 0]
         self.nsym = self.sync_at = self.wpos = self.synced = self.bad = 0
-        self.frames = self.nevents = self.dropped = 0
-        self.events = []
         self.syms = []               # of every symbol: (tone, valid)
-        self.widest = dict(acc=0, red=0, sum=0, P=0, oth=0)
 
     def _file(self, word, flags, ea, eb, split, k):
-        self.nevents = min(self.nevents + 1, 0xFFFFFFFF)
-        if len(self.events) >= self.max_events:
-            self.dropped = min(self.dropped + 1, 0xFFFFFFFF)
-        else:
-            self.events.append(Event(word, flags, ea, eb, split, 0, (k + 1) * self.B, self.sig, self.nse))
+        super()._file(Event(word, flags, ea, eb, split, 0, (k + 1) * self.B, self.sig, self.nse))
+
+    def _centre(self, best):
+        P = self.powers()
+        self.sym = P.index(best)                                        # ties to the lowest tone
+        self.Pc = best
+        self.oth = sum(p >> 3 for t, p in enumerate(P) if t != self.sym)
+        self._note("oth", self.oth)
 
     def _symbol(self, k, Pl):
         """the header's steps 1 to 5 at a late point, frame k"""
-        tb = self.tb
         # 1 timing
-        self.Ee += (self.Pe - self.Ee) >> 3
-        self.El += (Pl - self.El) >> 3
-        m = max(self.Ee, self.El)
-        adj = 0
-        if self.Ee > self.El and self.Ee - self.El > (m >> 3):
-            adj = -(tb >> 5)
-        elif self.El > self.Ee and self.El - self.Ee > (m >> 3):
-            adj = tb >> 5
-        self.t += tb - 2 * self.q + adj
+        self._timing(Pl)
         # 2 levels and gate
         self.sig += (self.Pc - self.sig) >> 4
         self.nse += (self.oth - self.nse) >> 4
@@ -150,71 +123,22 @@ class AleModel:
 
     def _frame(self, k):
         """one completed frame k: the window, then the header's step"""
-        wd = self.widest
-        red = tuple((a[0] >> 12, a[1] >> 12) for a in self.acc)
-        wd["acc"] = max(wd["acc"], *(abs(v) for a in self.acc for v in a))
-        self.acc = [[0, 0] for _ in range(NT)]
-        old = self.hist[0]
-        self.hist.append(red)
-        self.sums = [[s[0] + a[0] - o[0], s[1] + a[1] - o[1]] for s, a, o in zip(self.sums, red, old)]
-        self.frames = min(self.frames + 1, 0xFFFFFFFF)
-        self.t -= 256
-        if self.t >= 128:
+        red = self._close(12)
+        if not self._tick():
             return
-        P = [s[0] * s[0] + s[1] * s[1] for s in self.sums]           # (the powers matter at the points only)
-        best = max(P)
-        wd["red"] = max(wd["red"], *(abs(v) for a in red for v in a))
-        wd["sum"] = max(wd["sum"], *(abs(v) for s in self.sums for v in s))
-        wd["P"] = max(wd["P"], best)
-        if self.ph == 0:
-            self.Pe = best
-            self.t += self.q
-            self.ph = 1
-        elif self.ph == 1:
-            self.sym = P.index(best)                                    # ties to the lowest tone
-            self.Pc = best
-            self.oth = sum(p >> 3 for t, p in enumerate(P) if t != self.sym)
-            wd["oth"] = max(wd["oth"], self.oth)
-            self.t += self.q
-            self.ph = 2
-        else:
-            self.ph = 0
-            self._symbol(k, best)
-
-    def feed(self, x, s16=False):
-        q = fm.quantise(x, self.scale, s16)
-        if not len(q):
-            return self
-        B, n0 = self.B, self.n
-        n = np.arange(n0, n0 + len(q), dtype=np.uint64)
-        Ct = self.C.astype(np.int64)
-        cuts = np.concatenate([[0], np.arange(B - n0 % B, len(q), B)]).astype(np.int64)     # where the chunk's frames begin
-        ends = np.concatenate([cuts[1:], [len(q)]]).tolist()
-        part = []
-        for inc in self.inc:
-            j = (((n * np.uint64(inc)) & np.uint64(0xFFFFFFFF)) >> np.uint64(22)).astype(np.int64)   # mod 2^64 keeps mod 2^32
-            part.append((np.add.reduceat(q * Ct[j], cuts).tolist(),                          # exact: int64, below 2^38
-                         np.add.reduceat(q * Ct[(j - 256) & (TABLE - 1)], cuts).tolist()))
-        for i, e in enumerate(ends):
-            for t in range(NT):
-                self.acc[t][0] += part[t][0][i]
-                self.acc[t][1] += part[t][1][i]
-            self.n = n0 + e
-            if self.n % B == 0:
-                self._frame(self.n // B - 1)
-        return self
+        best = max(self.powers())                                       # (the powers matter at the points only)
+        self._note("red", *red)
+        self._note("sum", *self.sums)
+        self._note("P", best)
+        self._point(k, best, self._centre, self._symbol)
 
     def status(self):
         """kq_ale_status: everything carried but the past frames"""
         return dict(frames=self.frames, ph=self.ph, t=self.t, sym=self.sym, nsym=self.nsym, sync_at=self.sync_at, wpos=self.wpos,
                     synced=self.synced, bad=self.bad, events=self.nevents, dropped=self.dropped, reserved=0, sig=self.sig,
                     nse=self.nse, ee=self.Ee, el=self.El, pe=self.Pe, pc=self.Pc, oth=self.oth, r0=self.r[0], r1=self.r[1],
-                    r2=self.r[2], sum=[list(s) for s in self.sums], acc=[list(a) for a in self.acc])
-
-    def clear_events(self):
-        self.events = []
+                    r2=self.r[2], sum=gm.pairs(self.sums), acc=gm.pairs(self.acc))
 
 
 def noise_sigma(amp, esn0_db, Fs, baud=125.0):
-    """white noise that leaves a tone of amplitude amp at Es/N0: sigma^2 = (amp^2 / 2) / 10^(dB / 10) Fs / (2 baud)"""
-    return math.sqrt(amp * amp / 2.0 / 10.0 ** (esn0_db / 10.0) * float(Fs) / (2.0 * float(baud)))
+    return gm.noise_sigma(amp, esn0_db, Fs, baud)

@@ -8,21 +8,16 @@ import math
 
 import numpy as np
 
-import fsk_model as fm
-import tone_model as tm
+import fsk_model as fm            # (the tests reach the quantiser through the model: fm.quantise)
+import grid_model as gm
 
-TABLE = tm.TABLE
+TABLE = gm.TABLE
 RUN_MAX = 0x0FFFFFFF
 Event = collections.namedtuple("Event", "code nelem unit start_sample end_sample peak")
 STATUS = ("frames", "key", "run", "unit", "events", "dropped", "cand", "code", "nelem", "flags", "hi", "lo", "first", "last",
           "acc_i", "acc_q")           # kq_cw_status: what the issue's status shows, then the rest of what is carried
 
-cos_table = tm.cos_table
-
-
-def cw_inc(pitch, Fs):
-    """inc = rint(pitch 2^32 / Fs) in double, pitch a float32"""
-    return int(np.rint(float(np.float32(pitch)) * 4294967296.0 / float(Fs)))
+cos_table, cw_inc = gm.cos_table, gm.inc
 
 
 def unit_limits(Fs, B, min_wpm, max_wpm):
@@ -46,43 +41,35 @@ def frame_sums(q, n0, inc, C):
     return int((q * Ct[j]).sum()), int((q * Ct[(j - 256) & (TABLE - 1)]).sum())
 
 
-class CwModel:
+class CwModel(gm.GridModel):
     """one slot.  table, inc: the bank's own (kq_cw_get_table, kq_cw_get_inc), or None for the model's; start: the sample
     at which the slot was set (x = 0 before it)"""
 
     def __init__(self, samprate, block_len, pitch=700.0, wpm=20.0, min_wpm=5.0, max_wpm=60.0, deb=2, warm=64, snr=256,
                  min_p=1 << 16, input_scale=32767.0, max_events=256, table=None, inc=None, start=0):
-        self.Fs, self.B = float(samprate), int(block_len)
+        super().__init__(samprate, block_len, (cw_inc(pitch, samprate) if inc is None else inc,), table, None, input_scale,
+                         max_events, start)                        # no window: acc is the open frame's I and Q
         self.deb, self.warm, self.snr, self.min_p = int(deb), int(warm), int(snr), int(min_p)
-        self.scale, self.max_events = input_scale, max_events
-        self.C = cos_table() if table is None else np.asarray(table, np.int16)
-        self.inc = cw_inc(pitch, samprate) if inc is None else int(inc)
         self.u_min, self.u_max = unit_limits(samprate, block_len, min_wpm, max_wpm)
-        self.n = int(start)
-        self.I = self.Q = 0
         self.hi = self.lo = 0
         self.key = self.cand = self.run = 0
         self.u = min(max(unit_start(samprate, block_len, wpm), self.u_min), self.u_max)
         self.code, self.nelem, self.closed, self.worded = 1, 0, 1, 1
         self.first = self.last = 0
-        self.frames = self.nevents = self.dropped = 0
-        self.events = []
         self.P = []                  # of every completed frame
-        self.widest = 0
+        self.widest = 0              # one bound for all of it
+
+    I, Q = property(lambda self: self.acc[0]), property(lambda self: self.acc[1])
 
     def _file(self, code, nelem, start, end):
-        self.nevents += 1
-        if len(self.events) >= self.max_events:
-            self.dropped += 1
-        else:
-            self.events.append(Event(code, nelem, self.u, start * self.B, end * self.B, self.hi))
+        super()._file(Event(code, nelem, self.u, start * self.B, end * self.B, self.hi))
 
     def _frame(self, k):
         """the header's tracker, steps 1 to 7, on frame k"""
         P = (self.I >> 15) ** 2 + (self.Q >> 15) ** 2
         self.widest = max(self.widest, abs(self.I), abs(self.Q), P)
         self.P.append(P)
-        self.I = self.Q = 0
+        self.acc = [0, 0]
         self.frames = min(self.frames + 1, 0xFFFFFFFF)
         # 1 peak
         if P > self.hi:
@@ -137,34 +124,11 @@ class CwModel:
             self.code = 0
         self.closed = self.worded = 0
 
-    def feed(self, x, s16=False):
-        q = fm.quantise(x, self.scale, s16)
-        if not len(q):
-            return self
-        B, n0 = self.B, self.n
-        n = np.arange(n0, n0 + len(q), dtype=np.uint64)
-        j = (((n * np.uint64(self.inc)) & np.uint64(0xFFFFFFFF)) >> np.uint64(22)).astype(np.int64)   # mod 2^64 keeps mod 2^32
-        Ct = self.C.astype(np.int64)
-        cuts = np.concatenate([[0], np.arange(B - n0 % B, len(q), B)]).astype(np.int64)     # where the chunk's frames begin
-        sI = np.add.reduceat(q * Ct[j], cuts)                                                # exact: int64, below 2^42
-        sQ = np.add.reduceat(q * Ct[(j - 256) & (TABLE - 1)], cuts)
-        ends = np.concatenate([cuts[1:], [len(q)]])
-        for i, e in enumerate(ends):
-            self.I += int(sI[i])
-            self.Q += int(sQ[i])
-            self.n = n0 + int(e)
-            if self.n % B == 0:
-                self._frame(self.n // B - 1)
-        return self
-
     def status(self):
         """kq_cw_status: every counter, the whole tracker state and the open frame's sums"""
         return dict(frames=self.frames, key=self.key, run=self.run, unit=self.u, events=self.nevents, dropped=self.dropped,
                     cand=self.cand, code=self.code, nelem=self.nelem, flags=self.closed | self.worded << 1, hi=self.hi,
                     lo=self.lo, first=self.first, last=self.last, acc_i=self.I, acc_q=self.Q)
-
-    def clear_events(self):
-        self.events = []
 
 
 def noise_sigma(amp, snr_db, B):

@@ -6,14 +6,11 @@ from its DX and RX copies up to its end.  The frame sums are taken in int64 (the
 shifts on in Python ints: there is no float after the quantiser.  The bit length becomes an integer (tb) before any sample
 is seen, by the header's formula in double."""
 import collections
-import math
 
-import numpy as np
+import fsk_model as fm            # (the tests reach the quantiser through the model: fm.quantise)
+import grid_model as gm
 
-import fsk_model as fm
-import tone_model as tm
-
-TABLE = tm.TABLE
+TABLE = gm.TABLE
 M64 = (1 << 64) - 1
 MAX_SYMBOLS = 64
 W125 = 0b1011111001
@@ -23,22 +20,7 @@ STATUS = ("frames", "ph", "t", "bit", "nbits", "synced", "bitpos", "events", "dr
           "nse", "ee", "el", "ec", "pe", "hi", "lo", "r", "sum", "acc", "inverted", "place", "nsym", "nres", "holes", "from_rx", "run",
           "ecc", "eos", "reserved2", "hole_mask", "sync_sample", "msg")
 
-cos_table = tm.cos_table
-
-
-def dsc_inc(f, Fs):
-    """inc = rint(f 2^32 / Fs) in double, f a float32"""
-    return int(np.rint(float(np.float32(f)) * 4294967296.0 / float(Fs)))
-
-
-def bit_length(Fs, B, baud):
-    """tb = rint(256 Fs / (B baud)) in double, baud a float32: the bit in 1/256 frame"""
-    return int(np.rint(256.0 * float(Fs) / (float(B) * float(np.float32(baud)))))
-
-
-def window(tb):
-    """W = (tb + 128) >> 8 frames"""
-    return (tb + 128) >> 8
+cos_table, dsc_inc, bit_length, window = gm.cos_table, gm.inc, gm.period, gm.window
 
 
 def is_symbol(w):
@@ -66,59 +48,41 @@ def phasing(x, acq):
     return 2 * (111 - v) + 1 if m >= acq else -1
 
 
-class DscModel:
+class DscModel(gm.GridModel):
     """one slot.  table, incs, tb: the bank's own (kq_dsc_get_table, kq_dsc_get_slot), or None for the model's; start: the
     sample at which the slot was set (x = 0 before it).  gate=False leaves the gate open, nudge=False leaves out step 1's push from half a bit
     out (the model only: for the false-alarm tests, and to show what the push is for)"""
 
     def __init__(self, samprate, block_len, mark=1785.0, space=1615.0, baud=100.0, warm=64, snr=64, min_p=1 << 16, acq=2, lose=3,
                  input_scale=32767.0, max_events=64, table=None, incs=None, tb=None, start=0, gate=True, nudge=True):
-        self.Fs, self.B = float(samprate), int(block_len)
+        incs = (dsc_inc(mark, samprate), dsc_inc(space, samprate)) if incs is None else incs   # mark, then space
+        super().__init__(samprate, block_len, incs, table, bit_length(samprate, block_len, baud) if tb is None else tb, input_scale,
+                         max_events, start, widest=("P",))
         self.warm, self.snr, self.min_p, self.acq, self.lose = int(warm), int(snr), int(min_p), int(acq), int(lose)
-        self.scale, self.max_events, self.gate, self.nudge = input_scale, max_events, gate, nudge
-        self.C = cos_table() if table is None else np.asarray(table, np.int16)
-        self.incs = (dsc_inc(mark, samprate), dsc_inc(space, samprate)) if incs is None else tuple(int(v) for v in incs)
-        self.tb = bit_length(samprate, block_len, baud) if tb is None else int(tb)
-        self.W = window(self.tb)
-        self.q = self.tb >> 2
-        self.n = int(start)
-        self.acc = [0, 0, 0, 0]                                     # I, Q of mark, I, Q of space: the open frame
-        self.hist = collections.deque([(0, 0, 0, 0)] * self.W, self.W)
-        self.sums = [0, 0, 0, 0]
-        self.ph = self.t = self.bit = self.nbits = self.synced = self.bitpos = 0
-        self.Ec = self.sig = self.nse = self.Ee = self.El = self.Pe = self.hi = self.lo = self.r = 0
+        self.gate, self.nudge = gate, nudge
+        self.bit = self.nbits = self.synced = self.bitpos = 0
+        self.Ec = self.sig = self.nse = self.hi = self.lo = self.r = 0
         self.inverted = self.place = self.nsym = self.nres = self.holes = self.from_rx = self.run = self.ecc = self.eos = 0
         self.hole_mask = self.sync_sample = 0
         self.msg = [0] * MAX_SYMBOLS
-        self.frames = self.nevents = self.dropped = self.syncs = self.aborted = 0
-        self.events = []
+        self.syncs = self.aborted = 0
         self.bits = []               # of every bit: (bit, open)
-        self.widest = dict(acc=0, red=0, sum=0, P=0)
 
     def _file(self, flags, k):
-        self.nevents = min(self.nevents + 1, 0xFFFFFFFF)
-        if len(self.events) >= self.max_events:
-            self.dropped = min(self.dropped + 1, 0xFFFFFFFF)
-        else:
-            self.events.append(Event(bytes(self.msg), self.nsym, flags | (INVERTED if self.inverted else 0), self.holes,
-                                     self.from_rx, self.hole_mask, self.sync_sample, (k + 1) * self.B, self.sig, self.nse))
+        super()._file(Event(bytes(self.msg), self.nsym, flags | (INVERTED if self.inverted else 0), self.holes, self.from_rx,
+                            self.hole_mask, self.sync_sample, (k + 1) * self.B, self.sig, self.nse))
+
+    def _centre(self, best):
+        Pm, Ps = self.powers()
+        self.bit, self.hi, self.lo = int(Pm >= Ps), best, min(Pm, Ps)
 
     def _bit(self, k, Pl):
         """the header's steps 1 to 5 at a late point, frame k"""
-        tb = self.tb
         # 1 timing
-        self.Ee += (self.Pe - self.Ee) >> 3
-        self.El += (Pl - self.El) >> 3
-        m = max(self.Ee, self.El)
-        adj = 0
-        if self.Ee > self.El and self.Ee - self.El > (m >> 3):
-            adj = -(tb >> 5)
-        elif self.El > self.Ee and self.El - self.Ee > (m >> 3):
-            adj = tb >> 5
-        self.t += tb - 2 * self.q + adj
+        adj, m = self._timing(Pl)
         self.Ec += (self.hi - self.Ec) >> 3
         if self.nudge and adj == 0 and self.Ec + (m >> 3) < min(self.Ee, self.El):
-            self.t += tb >> 5                                        # half a bit out: the walk has no slope there
+            self.t += self.tb >> 5                                   # half a bit out: the walk has no slope there
         # 2 levels and gate
         self.sig += (self.hi - self.sig) >> 4
         self.nse += (self.lo - self.nse) >> 4
@@ -190,71 +154,24 @@ class DscModel:
 
     def _frame(self, k):
         """one completed frame k: the window, then the header's step"""
-        wd = self.widest
-        red = tuple(v >> 12 for v in self.acc)
-        wd["acc"] = max(wd["acc"], *(abs(v) for v in self.acc))
-        wd["red"] = max(wd["red"], *(abs(v) for v in red))
-        self.acc = [0, 0, 0, 0]
-        old = self.hist[0]
-        self.hist.append(red)
-        self.sums = [s + a - o for s, a, o in zip(self.sums, red, old)]
-        self.frames = min(self.frames + 1, 0xFFFFFFFF)
-        self.t -= 256
-        if self.t >= 128:
+        self._note("red", *self._close(12))
+        if not self._tick():
             return
-        Pm = self.sums[0] ** 2 + self.sums[1] ** 2                    # (the powers matter at the points only)
-        Ps = self.sums[2] ** 2 + self.sums[3] ** 2
-        best = max(Pm, Ps)
-        wd["sum"] = max(wd["sum"], *(abs(v) for v in self.sums))
-        wd["P"] = max(wd["P"], best)
-        if self.ph == 0:
-            self.Pe = best
-            self.t += self.q
-            self.ph = 1
-        elif self.ph == 1:
-            self.bit, self.hi, self.lo = int(Pm >= Ps), best, min(Pm, Ps)
-            self.t += self.q
-            self.ph = 2
-        else:
-            self.ph = 0
-            self._bit(k, best)
-
-    def feed(self, x, s16=False):
-        q = fm.quantise(x, self.scale, s16)
-        if not len(q):
-            return self
-        B, n0 = self.B, self.n
-        n = np.arange(n0, n0 + len(q), dtype=np.uint64)
-        Ct = self.C.astype(np.int64)
-        cuts = np.concatenate([[0], np.arange(B - n0 % B, len(q), B)]).astype(np.int64)     # where the chunk's frames begin
-        ends = np.concatenate([cuts[1:], [len(q)]])
-        part = []
-        for inc in self.incs:
-            j = (((n * np.uint64(inc)) & np.uint64(0xFFFFFFFF)) >> np.uint64(22)).astype(np.int64)   # mod 2^64 keeps mod 2^32
-            part.append(np.add.reduceat(q * Ct[j], cuts).tolist())                         # exact: int64, below 2^38
-            part.append(np.add.reduceat(q * Ct[(j - 256) & (TABLE - 1)], cuts).tolist())
-        for i, e in enumerate(ends.tolist()):
-            for c in range(4):
-                self.acc[c] += part[c][i]
-            self.n = n0 + e
-            if self.n % B == 0:
-                self._frame(self.n // B - 1)
-        return self
+        best = max(self.powers())                                     # (the powers matter at the points only)
+        self._note("sum", *self.sums)
+        self._note("P", best)
+        self._point(k, best, self._centre, self._bit)
 
     def status(self):
         """kq_dsc_status: everything carried but the past frames"""
         return dict(frames=self.frames, ph=self.ph, t=self.t, bit=self.bit, nbits=self.nbits, synced=self.synced,
                     bitpos=self.bitpos, events=self.nevents, dropped=self.dropped, syncs=self.syncs, aborted=self.aborted,
                     reserved=0, sig=self.sig, nse=self.nse, ee=self.Ee, el=self.El, ec=self.Ec, pe=self.Pe, hi=self.hi, lo=self.lo, r=self.r,
-                    sum=[self.sums[0:2], self.sums[2:4]], acc=[self.acc[0:2], self.acc[2:4]], inverted=self.inverted,
+                    sum=gm.pairs(self.sums), acc=gm.pairs(self.acc), inverted=self.inverted,
                     place=self.place, nsym=self.nsym, nres=self.nres, holes=self.holes, from_rx=self.from_rx, run=self.run,
                     ecc=self.ecc, eos=self.eos, reserved2=0, hole_mask=self.hole_mask, sync_sample=self.sync_sample,
                     msg=list(self.msg))
 
-    def clear_events(self):
-        self.events = []
-
 
 def noise_sigma(amp, esn0_db, Fs, baud=100.0):
-    """white noise that leaves a tone of amplitude amp at Es/N0: sigma^2 = (amp^2 / 2) / 10^(dB / 10) Fs / (2 baud)"""
-    return math.sqrt(amp * amp / 2.0 / 10.0 ** (esn0_db / 10.0) * float(Fs) / (2.0 * float(baud)))
+    return gm.noise_sigma(amp, esn0_db, Fs, baud)

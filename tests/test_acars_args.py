@@ -7,30 +7,67 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import bank_args
 import acars_model as am
 import ka9q_sdr_amd as kq
 from ka9q_sdr_amd.acars import INFO_DTYPE, STATUS_DTYPE, STATUS_WORDS, AcarsConfig, AcarsParams, AcarsSlot, _bind, acars_params
 
 
-@pytest.fixture(scope="module")
-def lib():
-    kq.build_library()
-    return _bind(kq.load_library())
+def _slot_checks(lib, bank):
+    """no slot is set yet; a set slot reads back; the getters' own refusals"""
+    out = AcarsSlot()
+    assert lib.kq_acars_get_slot(bank, 0, C.byref(out)) == -1
+    assert b"slot 0 holds no decoder" in lib.kq_last_error()
+    assert lib.kq_acars_set(bank, 1, C.byref(acars_params(5))) == 0, lib.kq_last_error()
+    assert lib.kq_acars_get_slot(bank, 1, C.byref(out)) == 0 and out.source == 5
+    assert lib.kq_acars_get_slot(bank, 8, C.byref(out)) == -1 and lib.kq_acars_get_slot(bank, 1, None) == -1
+    assert lib.kq_last_error() == b"kq_acars_get_slot: null out"
+    assert lib.kq_acars_get_taps(bank, None, 4) == -1
+    assert lib.kq_last_error() == b"kq_acars_get_taps: null dst"
+    assert lib.kq_acars_remove(bank, 1) == 0
 
 
-def _cfg(**kw):
-    c = dict(device=0, samprate=12000.0, input_scale=32767.0, sync_num=1, sync_den=2, max_parity_errors=3, max_block_bytes=256,
-             max_slots=8, max_blocks=4, max_samples=1 << 14, stream=None)
-    c.update(kw)
-    return AcarsConfig(*c.values())
-
-
-@pytest.fixture
-def bank(lib):
-    h = lib.kq_acars_create(C.byref(_cfg()))
-    assert h, lib.kq_last_error()
-    yield h
-    assert lib.kq_acars_destroy(h) == 0
+BLOCK, INFO = np.zeros(256, np.uint8), np.zeros(1, INFO_DTYPE)
+SUITE = bank_args.Suite(
+    "acars", AcarsConfig, acars_params, _bind, status=STATUS_DTYPE, record="block", pull=(BLOCK.ctypes.data, 256, INFO.ctypes.data),
+    null_pull=b"null dst", slot_limit=4096,
+    default=dict(device=0, samprate=12000.0, input_scale=32767.0, sync_num=1, sync_den=2, max_parity_errors=3, max_block_bytes=256,
+                 max_slots=8, max_blocks=4, max_samples=1 << 14, stream=None),
+    bad_configs=[
+        (dict(samprate=0.0), b"samprate 0 must be positive and finite"),
+        (dict(samprate=float("nan")), b"samprate nan"),
+        (dict(samprate=float("inf")), b"samprate inf"),
+        (dict(samprate=9599.0), b"samprate 9599 must be 9600..96000"),
+        (dict(samprate=96000.5), b"samprate 96000.5 must be 9600..96000"),
+        (dict(samprate=-12000.0), b"samprate -12000"),
+        (dict(input_scale=0.0), b"input_scale"),
+        (dict(input_scale=-1.0), b"input_scale"),
+        (dict(input_scale=float("nan")), b"input_scale"),
+        (dict(input_scale=float("inf")), b"input_scale"),
+        (dict(sync_den=0), b"sync_den 0 must be 1..255"),
+        (dict(sync_den=256), b"sync_den 256 must be 1..255"),
+        (dict(sync_num=0), b"sync_num 0 must be 1..2"),
+        (dict(sync_num=3), b"sync_num 3 must be 1..2"),
+        (dict(max_parity_errors=256), b"max_parity_errors 256 must be 0..255"),
+        (dict(max_block_bytes=15), b"max_block_bytes 15 must be 16..256"),
+        (dict(max_block_bytes=257), b"max_block_bytes 257 must be 16..256"),
+        (dict(max_slots=0), b"max_slots 0 must be 1..4096"),
+        (dict(max_slots=4097), b"max_slots 4097"),
+        (dict(max_blocks=0), b"max_blocks 0 must be 1..4096"),
+        (dict(max_blocks=4097), b"max_blocks 4097"),
+        (dict(max_samples=0), b"max_samples 0"),
+        (dict(max_samples=(1 << 28) + 1), b"max_samples 268435457"),
+    ],
+    more_slot_checks=_slot_checks,
+    null_handles=[("destroy", ()), ("sync", ()), ("reset", ()), ("remove", (0,)), ("clear_blocks", ()), ("pull_counts", (None,)),
+                  ("get_taps", (None, 0)), ("get_slot", (0, None)), ("pull_block", (0, 0, None, 0, None))],
+    first_call=dict(bank=kq.AcarsBank, geometry=(12000.0,), set=dict(source=3), read=lambda b: b.get_slot(0).source, want=3,
+                    again=dict(source=0), refused=[((8000.0,), {}, "samprate 8000 must be 9600..96000")]))
+lib, bank, _cfg = SUITE.lib, SUITE.bank, SUITE.cfg
+test_null_config_refused, test_bad_config_refused, test_bad_process_refused = SUITE.null_config, SUITE.bad_config, SUITE.bad_process
+test_bad_slot_and_params_refused, test_null_handles_refused = SUITE.bad_slot, SUITE.null_handles
+test_without_a_slot_nothing_touches_a_device = SUITE.without_a_slot
+test_set_needs_no_device_and_the_first_call_says_where_there_is_none = SUITE.first_call
 
 
 NAMES = {"kq_acars_create", "kq_acars_destroy", "kq_acars_set", "kq_acars_remove", "kq_acars_process", "kq_acars_pull_counts",
@@ -67,11 +104,6 @@ def test_record_layouts():
     assert kq.arinc618.Record._fields == am.Record._fields
 
 
-def test_null_config_refused(lib):
-    assert lib.kq_acars_create(None) is None
-    assert lib.kq_last_error() == b"kq_acars_create: null config"
-
-
 def test_good_configs_accepted(lib):
     """the limits themselves, and the geometries of the GPU tests; none of them asks for a device"""
     for kw in (dict(), dict(samprate=9600.0), dict(samprate=96000.0), dict(samprate=39062.5), dict(sync_num=255, sync_den=255),
@@ -80,126 +112,6 @@ def test_good_configs_accepted(lib):
         h = lib.kq_acars_create(C.byref(_cfg(**kw)))
         assert h, (kw, lib.kq_last_error())
         assert lib.kq_acars_destroy(h) == 0
-
-
-@pytest.mark.parametrize("kw,why", [
-    (dict(samprate=0.0), b"samprate 0 must be positive and finite"),
-    (dict(samprate=float("nan")), b"samprate nan"),
-    (dict(samprate=float("inf")), b"samprate inf"),
-    (dict(samprate=9599.0), b"samprate 9599 must be 9600..96000"),
-    (dict(samprate=96000.5), b"samprate 96000.5 must be 9600..96000"),
-    (dict(samprate=-12000.0), b"samprate -12000"),
-    (dict(input_scale=0.0), b"input_scale"),
-    (dict(input_scale=-1.0), b"input_scale"),
-    (dict(input_scale=float("nan")), b"input_scale"),
-    (dict(input_scale=float("inf")), b"input_scale"),
-    (dict(sync_den=0), b"sync_den 0 must be 1..255"),
-    (dict(sync_den=256), b"sync_den 256 must be 1..255"),
-    (dict(sync_num=0), b"sync_num 0 must be 1..2"),
-    (dict(sync_num=3), b"sync_num 3 must be 1..2"),
-    (dict(max_parity_errors=256), b"max_parity_errors 256 must be 0..255"),
-    (dict(max_block_bytes=15), b"max_block_bytes 15 must be 16..256"),
-    (dict(max_block_bytes=257), b"max_block_bytes 257 must be 16..256"),
-    (dict(max_slots=0), b"max_slots 0 must be 1..4096"),
-    (dict(max_slots=4097), b"max_slots 4097"),
-    (dict(max_blocks=0), b"max_blocks 0 must be 1..4096"),
-    (dict(max_blocks=4097), b"max_blocks 4097"),
-    (dict(max_samples=0), b"max_samples 0"),
-    (dict(max_samples=(1 << 28) + 1), b"max_samples 268435457"),
-])
-def test_bad_config_refused(lib, kw, why):
-    assert lib.kq_acars_create(C.byref(_cfg(**kw))) is None
-    msg = lib.kq_last_error()
-    assert msg.startswith(b"kq_acars_create: ") and why in msg, msg
-
-
-def test_bad_slot_and_params_refused(lib, bank):
-    p = acars_params()
-    assert lib.kq_acars_set(None, 4096, C.byref(p)) == -1
-    assert b"slot 4096" in lib.kq_last_error()
-    assert lib.kq_acars_set(bank, 8, C.byref(p)) == -1      # max_slots = 8
-    assert b"slot 8 >= max_slots 8" in lib.kq_last_error()
-    assert lib.kq_acars_set(bank, 0, None) == -1
-    assert lib.kq_last_error() == b"kq_acars_set: null params"
-    assert lib.kq_acars_set(None, 0, C.byref(p)) == -1
-    assert lib.kq_last_error() == b"kq_acars_set: null bank"
-    out = AcarsSlot()
-    assert lib.kq_acars_get_slot(bank, 0, C.byref(out)) == -1          # none of those set the slot
-    assert b"slot 0 holds no decoder" in lib.kq_last_error()
-    assert lib.kq_acars_set(bank, 1, C.byref(acars_params(5))) == 0, lib.kq_last_error()
-    assert lib.kq_acars_get_slot(bank, 1, C.byref(out)) == 0 and out.source == 5
-    assert lib.kq_acars_get_slot(bank, 8, C.byref(out)) == -1 and lib.kq_acars_get_slot(bank, 1, None) == -1
-    assert lib.kq_last_error() == b"kq_acars_get_slot: null out"
-    assert lib.kq_acars_remove(bank, 3) == -1
-    assert b"slot 3 holds no decoder" in lib.kq_last_error()
-    assert lib.kq_acars_remove(bank, 8) == -1
-    buf, info = np.zeros(256, np.uint8), np.zeros(1, INFO_DTYPE)
-    assert lib.kq_acars_pull_block(bank, 9, 0, buf.ctypes.data, 256, info.ctypes.data) == -1
-    assert b"slot 9 >= max_slots 8" in lib.kq_last_error()
-    assert lib.kq_acars_pull_block(bank, 0, 0, None, 256, None) == -1
-    assert lib.kq_last_error() == b"kq_acars_pull_block: null dst"
-    assert lib.kq_acars_pull_counts(bank, None) == -1
-    assert lib.kq_last_error() == b"kq_acars_pull_counts: null counts"
-    assert lib.kq_acars_get_taps(bank, None, 4) == -1
-    assert lib.kq_last_error() == b"kq_acars_get_taps: null dst"
-    assert lib.kq_acars_remove(bank, 1) == 0
-
-
-def test_bad_process_refused(lib, bank):
-    buf = np.zeros(1 << 15, np.float32)
-    st = np.zeros(8, STATUS_DTYPE)
-    assert lib.kq_acars_process(bank, buf.ctypes.data, 0, 0, 4096, 4096, 5, 0, None, 0) == -1    # 20480 > 16384
-    assert b"max_samples" in lib.kq_last_error()
-    assert lib.kq_acars_process(bank, buf.ctypes.data, 0, 0, 100, 200, 2, 0, None, 0) == -1
-    assert b"row_stride 100 < block_len 200" in lib.kq_last_error()
-    assert lib.kq_acars_process(bank, buf.ctypes.data, 2, 0, 16, 16, 1, 0, None, 0) == -1        # KQ_PCM_S16: the modulator's
-    assert b"unknown sample format 2" in lib.kq_last_error()
-    assert lib.kq_acars_process(bank, buf.ctypes.data, 0, 0, 16, 16, 1, 0, st.ctypes.data, 0) == -1
-    assert b"status_stride 0 < 1" in lib.kq_last_error()
-    assert lib.kq_acars_process(bank, None, 0, 0, 16, 16, 1, 0, None, 0) == -1
-    assert b"null src" in lib.kq_last_error()
-    assert lib.kq_acars_process(bank, None, 0, 0, 0, 0, 0, 0, None, 0) == 0         # nothing to do
-    assert lib.kq_acars_process(None, buf.ctypes.data, 0, 0, 16, 16, 1, 0, None, 0) == -1
-    assert lib.kq_last_error() == b"kq_acars_process: null bank"
-
-
-def test_without_a_slot_nothing_touches_a_device(lib, bank):
-    """with no slot set -- or one set and removed again -- process, counts, clear, sync and reset succeed and touch no
-    device"""
-    buf = np.zeros(1 << 14, np.float32)
-    assert lib.kq_acars_set(bank, 5, C.byref(acars_params())) == 0 and lib.kq_acars_remove(bank, 5) == 0
-    for n in (1, 1000, 16384):
-        assert lib.kq_acars_process(bank, buf.ctypes.data, 0, 0, n, n, 1, 0, None, 0) == 0
-    counts = np.full(8, 7, np.uint32)
-    assert lib.kq_acars_pull_counts(bank, counts.ctypes.data) == 0 and not counts.any()
-    assert lib.kq_acars_clear_blocks(bank) == 0 and lib.kq_acars_sync(bank) == 0 and lib.kq_acars_reset(bank) == 0
-    out = np.zeros(256, np.uint8)
-    assert lib.kq_acars_pull_block(bank, 0, 0, out.ctypes.data, 256, None) == -1
-    assert b"slot 0 has 0 blocks" in lib.kq_last_error()
-
-
-def test_set_needs_no_device_and_the_first_call_says_where_there_is_none(lib):
-    b = kq.AcarsBank(12000.0, max_slots=4, max_samples=4096)
-    b.set(0, source=3)                                                # no device asked for yet
-    assert b.get_slot(0).source == 3
-    b.remove(0)
-    b.set(0, source=0)
-    try:
-        b.process(np.zeros((1, 480), np.float32))
-        assert lib.kq_device_count() > 0
-    except kq.KqError as e:
-        assert lib.kq_device_count() <= 0, str(e)
-    b.close()
-    with pytest.raises(kq.KqError, match="samprate 8000 must be 9600..96000"):
-        kq.AcarsBank(8000.0, max_slots=4, max_samples=4096)
-
-
-def test_null_handles_refused(lib):
-    for fn, args in ((lib.kq_acars_destroy, ()), (lib.kq_acars_sync, ()), (lib.kq_acars_reset, ()), (lib.kq_acars_remove, (0,)),
-                     (lib.kq_acars_clear_blocks, ()), (lib.kq_acars_pull_counts, (None,)), (lib.kq_acars_get_taps, (None, 0)),
-                     (lib.kq_acars_get_slot, (0, None)), (lib.kq_acars_pull_block, (0, 0, None, 0, None))):
-        assert fn(None, *args) == -1
-        assert b"null bank" in lib.kq_last_error()
 
 
 @pytest.mark.parametrize("Fs", [9600.0, 12000.0, 16000.0, 22050.0, 39062.5, 48000.0, 96000.0])

@@ -7,31 +7,80 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import bank_args
 import ale_model as am
 import ka9q_sdr_amd as kq
 from ka9q_sdr_amd import ale2g
 from ka9q_sdr_amd.ale import EVENT_DTYPE, STATUS_DTYPE, STATUS_WORDS, AleConfig, AleParams, AleSlot, _bind, ale_params
 
 
-@pytest.fixture(scope="module")
-def lib():
-    kq.build_library()
-    return _bind(kq.load_library())
+def _slot_checks(lib, bank):
+    """behind the refused params: none of them set the slot; the limits of baud themselves, an LSB channel; the getter's
+    own refusals"""
+    out = AleSlot()
+    assert lib.kq_ale_get_slot(bank, 0, C.byref(out)) == -1
+    assert b"slot 0 holds no decoder" in lib.kq_last_error()
+    for baud, tb in ((125.0, 2048), (31.25, 8192)):
+        assert lib.kq_ale_set(bank, 1, C.byref(ale_params(baud=baud))) == 0, lib.kq_last_error()
+        assert lib.kq_ale_get_slot(bank, 1, C.byref(out)) == 0 and out.tb == tb and out.W == tb // 256
+    assert lib.kq_ale_set(bank, 2, C.byref(ale_params(f0=2500.0, df=-250.0))) == 0, lib.kq_last_error()   # an LSB channel
+    assert lib.kq_ale_get_slot(bank, 2, C.byref(out)) == 0 and list(out.inc) == list(reversed(am.ale_inc(750.0, 250.0, 12000.0)))
+    assert lib.kq_ale_get_slot(bank, 8, C.byref(out)) == -1 and lib.kq_ale_get_slot(bank, 1, None) == -1
+    assert lib.kq_last_error() == b"kq_ale_get_slot: null out"
+    assert lib.kq_ale_remove(bank, 1) == 0
 
 
-def _cfg(**kw):
-    c = dict(device=0, samprate=12000.0, block_len=12, warm=64, snr=80, min_p=1 << 16, input_scale=32767.0, max_slots=8,
-             max_events=4, max_samples=1 << 14, stream=None, acq_err=1, lose=2)
-    c.update(kw)
-    return AleConfig(*c.values())
-
-
-@pytest.fixture
-def bank(lib):
-    h = lib.kq_ale_create(C.byref(_cfg()))
-    assert h, lib.kq_last_error()
-    yield h
-    assert lib.kq_ale_destroy(h) == 0
+EVENT = np.zeros(1, EVENT_DTYPE)
+SUITE = bank_args.Suite(
+    "ale", AleConfig, ale_params, _bind, status=STATUS_DTYPE, record="event", pull=(EVENT.ctypes.data,), null_pull=b"null event",
+    default=dict(device=0, samprate=12000.0, block_len=12, warm=64, snr=80, min_p=1 << 16, input_scale=32767.0, max_slots=8,
+                 max_events=4, max_samples=1 << 14, stream=None, acq_err=1, lose=2),
+    bad_configs=[
+        (dict(samprate=0.0), b"samprate 0 must be positive and finite"),
+        (dict(samprate=-8000.0), b"samprate -8000"),
+        (dict(samprate=float("nan")), b"samprate nan"),
+        (dict(samprate=float("inf")), b"samprate inf"),
+        (dict(block_len=7), b"block_len 7 must be 8..256"),
+        (dict(block_len=257), b"block_len 257 must be 8..256"),
+        (dict(warm=65536), b"warm 65536 must be 0..65535"),
+        (dict(snr=15), b"snr 15 must be 16..4095"),
+        (dict(snr=4096), b"snr 4096 must be 16..4095"),
+        (dict(min_p=(1 << 55) + 1), b"min_p 36028797018963969 must be 0..2^55"),
+        (dict(input_scale=0.0), b"input_scale"),
+        (dict(input_scale=-1.0), b"input_scale"),
+        (dict(input_scale=float("nan")), b"input_scale"),
+        (dict(input_scale=float("inf")), b"input_scale"),
+        (dict(acq_err=4), b"acq_err 4 must be 0..3"),
+        (dict(lose=0), b"lose 0 must be 1..15"),
+        (dict(lose=16), b"lose 16 must be 1..15"),
+        (dict(max_slots=0), b"max_slots 0 must be 1..16384"),
+        (dict(max_slots=16385), b"max_slots 16385"),
+        (dict(max_events=0), b"max_events 0 must be 1..4096"),
+        (dict(max_events=4097), b"max_events 4097"),
+        (dict(max_samples=0), b"max_samples 0"),
+        (dict(max_samples=(1 << 28) + 1), b"max_samples 268435457"),
+    ],
+    bad_params=[
+        (dict(f0=0.0), b"tone 0 at 0 (f0 0, df 250) must be above 0 and below samprate / 2"), (dict(f0=-1.0), b"tone 0 at -1"),
+        (dict(f0=4250.0), b"tone 7 at 6000"), (dict(f0=1750.0, df=-250.0), b"tone 7 at 0"),
+        (dict(f0=6000.0, df=-250.0), b"tone 0 at 6000"),
+        (dict(df=0.0), b"df 0 must be finite and df not 0"), (dict(f0=float("nan")), b"f0 nan"), (dict(df=float("inf")), b"df inf"),
+        (dict(baud=0.0), b"baud 0 must be positive and finite"), (dict(baud=-125.0), b"baud -125"),
+        (dict(baud=float("nan")), b"baud nan"), (dict(baud=float("inf")), b"baud inf"),
+        # B = 12 at 12 kHz: 250 baud is 4 frames a symbol, 30 baud 33.3; 125 and 31.25 are the limits themselves
+        (dict(baud=250.0), b"baud 250 makes tb 1024"), (dict(baud=125.2), b"outside 2048..8192"),
+        (dict(baud=30.0), b"baud 30 makes tb 8533"), (dict(baud=31.2), b"outside 2048..8192")],
+    more_slot_checks=_slot_checks,
+    null_handles=[("destroy", ()), ("sync", ()), ("reset", ()), ("remove", (0,)), ("clear_events", ()), ("pull_counts", (None,)),
+                  ("get_table", (None, 0)), ("get_slot", (0, None)), ("pull_event", (0, 0, None))],
+    first_call=dict(bank=kq.AleBank, geometry=(12000.0, 12), set=dict(source=0, f0=750.0, df=250.0, baud=125.0),
+                    read=lambda b: b.get_slot(0), want=(tuple(am.ale_inc(750.0, 250.0, 12000.0)), 2048, 8), again=dict(),
+                    refused=[((12000.0, 512), {}, "block_len 512 must be 8..256")]))
+lib, bank, _cfg = SUITE.lib, SUITE.bank, SUITE.cfg
+test_null_config_refused, test_bad_config_refused, test_bad_process_refused = SUITE.null_config, SUITE.bad_config, SUITE.bad_process
+test_bad_slot_and_params_refused, test_null_handles_refused = SUITE.bad_slot, SUITE.null_handles
+test_without_a_slot_nothing_touches_a_device = SUITE.without_a_slot
+test_set_needs_no_device_and_the_first_call_says_where_there_is_none = SUITE.first_call
 
 
 NAMES = {"kq_ale_create", "kq_ale_destroy", "kq_ale_set", "kq_ale_remove", "kq_ale_process", "kq_ale_pull_counts",
@@ -64,11 +113,6 @@ def test_record_layouts():
     assert tuple(STATUS_DTYPE.names) == am.STATUS and tuple(EVENT_DTYPE.names) == am.Event._fields
 
 
-def test_null_config_refused(lib):
-    assert lib.kq_ale_create(None) is None
-    assert lib.kq_last_error() == b"kq_ale_create: null config"
-
-
 def test_good_configs_accepted(lib):
     """the limits themselves, and the geometries of the GPU tests; none of them asks for a device"""
     for kw in (dict(), dict(block_len=8), dict(block_len=256, samprate=512000.0), dict(samprate=39062.5, block_len=32),
@@ -84,139 +128,6 @@ def test_good_configs_accepted(lib):
         b.set(0)
         assert b.get_slot(0).W in (8, 16)
         b.close()
-
-
-@pytest.mark.parametrize("kw,why", [
-    (dict(samprate=0.0), b"samprate 0 must be positive and finite"),
-    (dict(samprate=-8000.0), b"samprate -8000"),
-    (dict(samprate=float("nan")), b"samprate nan"),
-    (dict(samprate=float("inf")), b"samprate inf"),
-    (dict(block_len=7), b"block_len 7 must be 8..256"),
-    (dict(block_len=257), b"block_len 257 must be 8..256"),
-    (dict(warm=65536), b"warm 65536 must be 0..65535"),
-    (dict(snr=15), b"snr 15 must be 16..4095"),
-    (dict(snr=4096), b"snr 4096 must be 16..4095"),
-    (dict(min_p=(1 << 55) + 1), b"min_p 36028797018963969 must be 0..2^55"),
-    (dict(input_scale=0.0), b"input_scale"),
-    (dict(input_scale=-1.0), b"input_scale"),
-    (dict(input_scale=float("nan")), b"input_scale"),
-    (dict(input_scale=float("inf")), b"input_scale"),
-    (dict(acq_err=4), b"acq_err 4 must be 0..3"),
-    (dict(lose=0), b"lose 0 must be 1..15"),
-    (dict(lose=16), b"lose 16 must be 1..15"),
-    (dict(max_slots=0), b"max_slots 0 must be 1..16384"),
-    (dict(max_slots=16385), b"max_slots 16385"),
-    (dict(max_events=0), b"max_events 0 must be 1..4096"),
-    (dict(max_events=4097), b"max_events 4097"),
-    (dict(max_samples=0), b"max_samples 0"),
-    (dict(max_samples=(1 << 28) + 1), b"max_samples 268435457"),
-])
-def test_bad_config_refused(lib, kw, why):
-    assert lib.kq_ale_create(C.byref(_cfg(**kw))) is None
-    msg = lib.kq_last_error()
-    assert msg.startswith(b"kq_ale_create: ") and why in msg, msg
-
-
-def test_bad_slot_and_params_refused(lib, bank):
-    p = ale_params()
-    assert lib.kq_ale_set(None, 16384, C.byref(p)) == -1
-    assert b"slot 16384" in lib.kq_last_error()
-    assert lib.kq_ale_set(bank, 8, C.byref(p)) == -1      # max_slots = 8
-    assert b"slot 8 >= max_slots 8" in lib.kq_last_error()
-    assert lib.kq_ale_set(bank, 0, None) == -1
-    assert lib.kq_last_error() == b"kq_ale_set: null params"
-    assert lib.kq_ale_set(None, 0, C.byref(p)) == -1
-    assert lib.kq_last_error() == b"kq_ale_set: null bank"
-    bad = [(dict(f0=0.0), b"tone 0 at 0 (f0 0, df 250) must be above 0 and below samprate / 2"), (dict(f0=-1.0), b"tone 0 at -1"),
-           (dict(f0=4250.0), b"tone 7 at 6000"), (dict(f0=1750.0, df=-250.0), b"tone 7 at 0"),
-           (dict(f0=6000.0, df=-250.0), b"tone 0 at 6000"),
-           (dict(df=0.0), b"df 0 must be finite and df not 0"), (dict(f0=float("nan")), b"f0 nan"), (dict(df=float("inf")), b"df inf"),
-           (dict(baud=0.0), b"baud 0 must be positive and finite"), (dict(baud=-125.0), b"baud -125"),
-           (dict(baud=float("nan")), b"baud nan"), (dict(baud=float("inf")), b"baud inf"),
-           # B = 12 at 12 kHz: 250 baud is 4 frames a symbol, 30 baud 33.3; 125 and 31.25 are the limits themselves
-           (dict(baud=250.0), b"baud 250 makes tb 1024"), (dict(baud=125.2), b"outside 2048..8192"),
-           (dict(baud=30.0), b"baud 30 makes tb 8533"), (dict(baud=31.2), b"outside 2048..8192")]
-    for kw, why in bad:
-        assert lib.kq_ale_set(bank, 0, C.byref(ale_params(**kw))) == -1, kw
-        assert lib.kq_last_error().startswith(b"kq_ale_set: ") and why in lib.kq_last_error(), (kw, lib.kq_last_error())
-    out = AleSlot()
-    assert lib.kq_ale_get_slot(bank, 0, C.byref(out)) == -1          # none of those set the slot
-    assert b"slot 0 holds no decoder" in lib.kq_last_error()
-    for baud, tb in ((125.0, 2048), (31.25, 8192)):
-        assert lib.kq_ale_set(bank, 1, C.byref(ale_params(baud=baud))) == 0, lib.kq_last_error()
-        assert lib.kq_ale_get_slot(bank, 1, C.byref(out)) == 0 and out.tb == tb and out.W == tb // 256
-    assert lib.kq_ale_set(bank, 2, C.byref(ale_params(f0=2500.0, df=-250.0))) == 0, lib.kq_last_error()   # an LSB channel
-    assert lib.kq_ale_get_slot(bank, 2, C.byref(out)) == 0 and list(out.inc) == list(reversed(am.ale_inc(750.0, 250.0, 12000.0)))
-    assert lib.kq_ale_get_slot(bank, 8, C.byref(out)) == -1 and lib.kq_ale_get_slot(bank, 1, None) == -1
-    assert lib.kq_last_error() == b"kq_ale_get_slot: null out"
-    assert lib.kq_ale_remove(bank, 3) == -1
-    assert b"slot 3 holds no decoder" in lib.kq_last_error()
-    assert lib.kq_ale_remove(bank, 8) == -1
-    ev = np.zeros(1, EVENT_DTYPE)
-    assert lib.kq_ale_pull_event(bank, 9, 0, ev.ctypes.data) == -1
-    assert b"slot 9 >= max_slots 8" in lib.kq_last_error()
-    assert lib.kq_ale_pull_event(bank, 0, 0, None) == -1
-    assert lib.kq_last_error() == b"kq_ale_pull_event: null event"
-    assert lib.kq_ale_pull_counts(bank, None) == -1
-    assert lib.kq_last_error() == b"kq_ale_pull_counts: null counts"
-    assert lib.kq_ale_remove(bank, 1) == 0
-
-
-def test_bad_process_refused(lib, bank):
-    buf = np.zeros(1 << 15, np.float32)
-    st = np.zeros(8, STATUS_DTYPE)
-    assert lib.kq_ale_process(bank, buf.ctypes.data, 0, 0, 4096, 4096, 5, 0, None, 0) == -1    # 20480 > 16384
-    assert b"max_samples" in lib.kq_last_error()
-    assert lib.kq_ale_process(bank, buf.ctypes.data, 0, 0, 100, 200, 2, 0, None, 0) == -1
-    assert b"row_stride 100 < block_len 200" in lib.kq_last_error()
-    assert lib.kq_ale_process(bank, buf.ctypes.data, 2, 0, 16, 16, 1, 0, None, 0) == -1        # KQ_PCM_S16: the modulator's
-    assert b"unknown sample format 2" in lib.kq_last_error()
-    assert lib.kq_ale_process(bank, buf.ctypes.data, 0, 0, 16, 16, 1, 0, st.ctypes.data, 0) == -1
-    assert b"status_stride 0 < 1" in lib.kq_last_error()
-    assert lib.kq_ale_process(bank, None, 0, 0, 16, 16, 1, 0, None, 0) == -1
-    assert b"null src" in lib.kq_last_error()
-    assert lib.kq_ale_process(bank, None, 0, 0, 0, 0, 0, 0, None, 0) == 0         # nothing to do
-    assert lib.kq_ale_process(None, buf.ctypes.data, 0, 0, 16, 16, 1, 0, None, 0) == -1
-    assert lib.kq_last_error() == b"kq_ale_process: null bank"
-
-
-def test_without_a_slot_nothing_touches_a_device(lib, bank):
-    """with no slot set -- or one set and removed again -- process, counts, clear, sync and reset succeed and touch no
-    device"""
-    buf = np.zeros(1 << 14, np.float32)
-    assert lib.kq_ale_set(bank, 5, C.byref(ale_params())) == 0 and lib.kq_ale_remove(bank, 5) == 0
-    for n in (1, 1000, 16384):
-        assert lib.kq_ale_process(bank, buf.ctypes.data, 0, 0, n, n, 1, 0, None, 0) == 0
-    counts = np.full(8, 7, np.uint32)
-    assert lib.kq_ale_pull_counts(bank, counts.ctypes.data) == 0 and not counts.any()
-    assert lib.kq_ale_clear_events(bank) == 0 and lib.kq_ale_sync(bank) == 0 and lib.kq_ale_reset(bank) == 0
-    ev = np.zeros(1, EVENT_DTYPE)
-    assert lib.kq_ale_pull_event(bank, 0, 0, ev.ctypes.data) == -1
-    assert b"slot 0 has 0 events" in lib.kq_last_error()
-
-
-def test_set_needs_no_device_and_the_first_call_says_where_there_is_none(lib):
-    b = kq.AleBank(12000.0, 12, max_slots=4, max_samples=4096)
-    b.set(0, source=0, f0=750.0, df=250.0, baud=125.0)                # no device asked for yet
-    assert b.get_slot(0) == (tuple(am.ale_inc(750.0, 250.0, 12000.0)), 2048, 8)
-    b.remove(0)
-    b.set(0)
-    try:
-        b.process(np.zeros((1, 480), np.float32))
-        assert lib.kq_device_count() > 0
-    except kq.KqError as e:
-        assert lib.kq_device_count() <= 0, str(e)
-    b.close()
-    with pytest.raises(kq.KqError, match="block_len 512 must be 8..256"):
-        kq.AleBank(12000.0, 512, max_slots=4, max_samples=4096)
-
-
-def test_null_handles_refused(lib):
-    for fn, args in ((lib.kq_ale_destroy, ()), (lib.kq_ale_sync, ()), (lib.kq_ale_reset, ()), (lib.kq_ale_remove, (0,)),
-                     (lib.kq_ale_clear_events, ()), (lib.kq_ale_pull_counts, (None,)), (lib.kq_ale_get_table, (None, 0)),
-                     (lib.kq_ale_get_slot, (0, None)), (lib.kq_ale_pull_event, (0, 0, None))):
-        assert fn(None, *args) == -1
-        assert b"null bank" in lib.kq_last_error()
 
 
 @pytest.mark.parametrize("Fs,B", [(8000.0, 8), (12000.0, 8), (12000.0, 12), (39062.5, 32), (48000.0, 24), (48000.0, 48)])

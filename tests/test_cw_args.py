@@ -6,31 +6,74 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import bank_args
 import cw_model as cm
 import ka9q_sdr_amd as kq
 from ka9q_sdr_amd import morse
 from ka9q_sdr_amd.cw import EVENT_DTYPE, STATUS_DTYPE, STATUS_WORDS, CwConfig, CwParams, _bind, cw_params
 
 
-@pytest.fixture(scope="module")
-def lib():
-    kq.build_library()
-    return _bind(kq.load_library())
+def _slot_checks(lib, bank):
+    """behind the refused params: none of them set the slot; the getter's own refusals"""
+    inc = np.zeros(1, np.uint32)
+    assert lib.kq_cw_get_inc(bank, 0, inc.ctypes.data) == -1
+    assert b"slot 0 holds no decoder" in lib.kq_last_error()
+    assert lib.kq_cw_get_inc(bank, 8, inc.ctypes.data) == -1 and lib.kq_cw_get_inc(bank, 0, None) == -1
+    assert lib.kq_last_error() == b"kq_cw_get_inc: null inc"
 
 
-def _cfg(**kw):
-    c = dict(device=0, samprate=12000.0, block_len=48, min_wpm=5.0, max_wpm=60.0, deb=2, warm=64, snr=256, min_p=1 << 16,
-             input_scale=32767.0, max_slots=8, max_events=4, max_samples=1 << 14, stream=None)
-    c.update(kw)
-    return CwConfig(*c.values())
-
-
-@pytest.fixture
-def bank(lib):
-    h = lib.kq_cw_create(C.byref(_cfg()))
-    assert h, lib.kq_last_error()
-    yield h
-    assert lib.kq_cw_destroy(h) == 0
+EVENT = np.zeros(1, EVENT_DTYPE)
+SUITE = bank_args.Suite(
+    "cw", CwConfig, cw_params, _bind, status=STATUS_DTYPE, record="event", pull=(EVENT.ctypes.data,), null_pull=b"null event",
+    default=dict(device=0, samprate=12000.0, block_len=48, min_wpm=5.0, max_wpm=60.0, deb=2, warm=64, snr=256, min_p=1 << 16,
+                 input_scale=32767.0, max_slots=8, max_events=4, max_samples=1 << 14, stream=None),
+    bad_configs=[
+        (dict(samprate=0.0), b"samprate 0 must be positive and finite"),
+        (dict(samprate=-8000.0), b"samprate -8000"),
+        (dict(samprate=float("nan")), b"samprate nan"),
+        (dict(samprate=float("inf")), b"samprate inf"),
+        (dict(block_len=7), b"block_len 7 must be 8..4096"),
+        (dict(block_len=4097), b"block_len 4097 must be 8..4096"),
+        (dict(min_wpm=0.0), b"speeds 0..60 WPM must be positive, finite and in order"),
+        (dict(min_wpm=-5.0), b"speeds -5..60 WPM"),
+        (dict(min_wpm=30.0, max_wpm=20.0), b"speeds 30..20 WPM"),
+        (dict(max_wpm=float("inf")), b"speeds 5..inf WPM"),
+        (dict(max_wpm=float("nan")), b"speeds 5..nan WPM"),
+        (dict(min_wpm=float("nan")), b"speeds nan..60 WPM"),
+        (dict(max_wpm=101.0), b"max_wpm 101 leaves a dot 47 sixteenths of a frame of 48 samples, fewer than 48"),
+        (dict(block_len=4096, max_wpm=20.0), b"fewer than 48"),
+        (dict(block_len=8, min_wpm=0.01, samprate=48000.0), b"min_wpm 0.01 makes a dot"),
+        (dict(deb=0), b"deb 0 must be 1..16"),
+        (dict(deb=17), b"deb 17 must be 1..16"),
+        (dict(warm=65536), b"warm 65536 must be 0..65535"),
+        (dict(snr=15), b"snr 15 must be 16..4095"),
+        (dict(snr=4096), b"snr 4096 must be 16..4095"),
+        (dict(min_p=(1 << 55) + 1), b"min_p 36028797018963969 must be 0..2^55"),
+        (dict(input_scale=0.0), b"input_scale"),
+        (dict(input_scale=-1.0), b"input_scale"),
+        (dict(input_scale=float("nan")), b"input_scale"),
+        (dict(input_scale=float("inf")), b"input_scale"),
+        (dict(max_slots=0), b"max_slots 0 must be 1..16384"),
+        (dict(max_slots=16385), b"max_slots 16385"),
+        (dict(max_events=0), b"max_events 0 must be 1..4096"),
+        (dict(max_events=4097), b"max_events 4097"),
+        (dict(max_samples=0), b"max_samples 0"),
+        (dict(max_samples=(1 << 28) + 1), b"max_samples 268435457"),
+    ],
+    bad_params=[
+        (dict(pitch=0.0), b"pitch 0 must be above 0 and below samprate / 2"), (dict(pitch=6000.0), b"pitch 6000"),
+        (dict(pitch=-700.0), b"pitch -700"), (dict(pitch=float("nan")), b"pitch nan"),
+        (dict(wpm=4.0), b"wpm 4 must be within the bank's 5..60"), (dict(wpm=61.0), b"wpm 61"), (dict(wpm=float("nan")), b"wpm nan")],
+    more_slot_checks=_slot_checks,
+    null_handles=[("destroy", ()), ("sync", ()), ("reset", ()), ("remove", (0,)), ("clear_events", ()), ("pull_counts", (None,)),
+                  ("get_table", (None, 0)), ("get_inc", (0, None)), ("pull_event", (0, 0, None))],
+    first_call=dict(bank=kq.CwBank, geometry=(12000.0, 48), set=dict(source=0, pitch=700.0, wpm=20.0),
+                    read=lambda b: b.get_inc(0), want=cm.cw_inc(700.0, 12000.0), refused=[((12000.0, 480), {}, "fewer than 48")]))
+lib, bank, _cfg = SUITE.lib, SUITE.bank, SUITE.cfg
+test_null_config_refused, test_bad_config_refused, test_bad_process_refused = SUITE.null_config, SUITE.bad_config, SUITE.bad_process
+test_bad_slot_and_params_refused, test_null_handles_refused = SUITE.bad_slot, SUITE.null_handles
+test_without_a_slot_nothing_touches_a_device = SUITE.without_a_slot
+test_set_needs_no_device_and_the_first_call_says_where_there_is_none = SUITE.first_call
 
 
 NAMES = {"kq_cw_create", "kq_cw_destroy", "kq_cw_set", "kq_cw_remove", "kq_cw_process", "kq_cw_pull_counts",
@@ -55,11 +98,6 @@ def test_record_layouts():
     assert CwConfig.input_scale.offset == 48 and CwConfig.max_samples.offset == 64 and CwConfig.stream.offset == 72
 
 
-def test_null_config_refused(lib):
-    assert lib.kq_cw_create(None) is None
-    assert lib.kq_last_error() == b"kq_cw_create: null config"
-
-
 def test_good_configs_accepted(lib):
     """the limits themselves, and the geometries of the GPU tests; none of them asks for a device"""
     for kw in (dict(), dict(block_len=8), dict(block_len=4096, samprate=48000.0 * 64, max_wpm=60.0),
@@ -75,134 +113,6 @@ def test_good_configs_accepted(lib):
             kq.CwBank(fs, max_slots=4, max_samples=4096, **morse.cw_config(fs, top)).close()
         except kq.KqError as e:
             raise AssertionError("%g Hz, %g WPM: %s" % (fs, top, e))
-
-
-@pytest.mark.parametrize("kw,why", [
-    (dict(samprate=0.0), b"samprate 0 must be positive and finite"),
-    (dict(samprate=-8000.0), b"samprate -8000"),
-    (dict(samprate=float("nan")), b"samprate nan"),
-    (dict(samprate=float("inf")), b"samprate inf"),
-    (dict(block_len=7), b"block_len 7 must be 8..4096"),
-    (dict(block_len=4097), b"block_len 4097 must be 8..4096"),
-    (dict(min_wpm=0.0), b"speeds 0..60 WPM must be positive, finite and in order"),
-    (dict(min_wpm=-5.0), b"speeds -5..60 WPM"),
-    (dict(min_wpm=30.0, max_wpm=20.0), b"speeds 30..20 WPM"),
-    (dict(max_wpm=float("inf")), b"speeds 5..inf WPM"),
-    (dict(max_wpm=float("nan")), b"speeds 5..nan WPM"),
-    (dict(min_wpm=float("nan")), b"speeds nan..60 WPM"),
-    (dict(max_wpm=101.0), b"max_wpm 101 leaves a dot 47 sixteenths of a frame of 48 samples, fewer than 48"),
-    (dict(block_len=4096, max_wpm=20.0), b"fewer than 48"),
-    (dict(block_len=8, min_wpm=0.01, samprate=48000.0), b"min_wpm 0.01 makes a dot"),
-    (dict(deb=0), b"deb 0 must be 1..16"),
-    (dict(deb=17), b"deb 17 must be 1..16"),
-    (dict(warm=65536), b"warm 65536 must be 0..65535"),
-    (dict(snr=15), b"snr 15 must be 16..4095"),
-    (dict(snr=4096), b"snr 4096 must be 16..4095"),
-    (dict(min_p=(1 << 55) + 1), b"min_p 36028797018963969 must be 0..2^55"),
-    (dict(input_scale=0.0), b"input_scale"),
-    (dict(input_scale=-1.0), b"input_scale"),
-    (dict(input_scale=float("nan")), b"input_scale"),
-    (dict(input_scale=float("inf")), b"input_scale"),
-    (dict(max_slots=0), b"max_slots 0 must be 1..16384"),
-    (dict(max_slots=16385), b"max_slots 16385"),
-    (dict(max_events=0), b"max_events 0 must be 1..4096"),
-    (dict(max_events=4097), b"max_events 4097"),
-    (dict(max_samples=0), b"max_samples 0"),
-    (dict(max_samples=(1 << 28) + 1), b"max_samples 268435457"),
-])
-def test_bad_config_refused(lib, kw, why):
-    assert lib.kq_cw_create(C.byref(_cfg(**kw))) is None
-    msg = lib.kq_last_error()
-    assert msg.startswith(b"kq_cw_create: ") and why in msg, msg
-
-
-def test_bad_slot_and_params_refused(lib, bank):
-    p = cw_params()
-    assert lib.kq_cw_set(None, 16384, C.byref(p)) == -1
-    assert b"slot 16384" in lib.kq_last_error()
-    assert lib.kq_cw_set(bank, 8, C.byref(p)) == -1     # max_slots = 8
-    assert b"slot 8 >= max_slots 8" in lib.kq_last_error()
-    assert lib.kq_cw_set(bank, 0, None) == -1
-    assert lib.kq_last_error() == b"kq_cw_set: null params"
-    assert lib.kq_cw_set(None, 0, C.byref(p)) == -1
-    assert lib.kq_last_error() == b"kq_cw_set: null bank"
-    for pitch, why in ((0.0, b"pitch 0 must be above 0 and below samprate / 2"), (6000.0, b"pitch 6000"), (-700.0, b"pitch -700"),
-                       (float("nan"), b"pitch nan")):
-        assert lib.kq_cw_set(bank, 0, C.byref(cw_params(pitch=pitch))) == -1
-        assert lib.kq_last_error().startswith(b"kq_cw_set: ") and why in lib.kq_last_error()
-    for wpm, why in ((4.0, b"wpm 4 must be within the bank's 5..60"), (61.0, b"wpm 61"), (float("nan"), b"wpm nan")):
-        assert lib.kq_cw_set(bank, 0, C.byref(cw_params(wpm=wpm))) == -1
-        assert why in lib.kq_last_error()
-    inc = np.zeros(1, np.uint32)
-    assert lib.kq_cw_get_inc(bank, 0, inc.ctypes.data) == -1         # none of those set the slot
-    assert b"slot 0 holds no decoder" in lib.kq_last_error()
-    assert lib.kq_cw_get_inc(bank, 8, inc.ctypes.data) == -1 and lib.kq_cw_get_inc(bank, 0, None) == -1
-    assert lib.kq_last_error() == b"kq_cw_get_inc: null inc"
-    assert lib.kq_cw_remove(bank, 3) == -1
-    assert b"slot 3 holds no decoder" in lib.kq_last_error()
-    assert lib.kq_cw_remove(bank, 8) == -1
-    ev = np.zeros(1, EVENT_DTYPE)
-    assert lib.kq_cw_pull_event(bank, 9, 0, ev.ctypes.data) == -1
-    assert b"slot 9 >= max_slots 8" in lib.kq_last_error()
-    assert lib.kq_cw_pull_event(bank, 0, 0, None) == -1
-    assert lib.kq_last_error() == b"kq_cw_pull_event: null event"
-    assert lib.kq_cw_pull_counts(bank, None) == -1
-    assert lib.kq_last_error() == b"kq_cw_pull_counts: null counts"
-
-
-def test_bad_process_refused(lib, bank):
-    buf = np.zeros(1 << 15, np.float32)
-    st = np.zeros(8, STATUS_DTYPE)
-    assert lib.kq_cw_process(bank, buf.ctypes.data, 0, 0, 4096, 4096, 5, 0, None, 0) == -1   # 20480 > 16384
-    assert b"max_samples" in lib.kq_last_error()
-    assert lib.kq_cw_process(bank, buf.ctypes.data, 0, 0, 100, 200, 2, 0, None, 0) == -1
-    assert b"row_stride 100 < block_len 200" in lib.kq_last_error()
-    assert lib.kq_cw_process(bank, buf.ctypes.data, 2, 0, 16, 16, 1, 0, None, 0) == -1       # KQ_PCM_S16: the modulator's
-    assert b"unknown sample format 2" in lib.kq_last_error()
-    assert lib.kq_cw_process(bank, buf.ctypes.data, 0, 0, 16, 16, 1, 0, st.ctypes.data, 0) == -1
-    assert b"status_stride 0 < 1" in lib.kq_last_error()
-    assert lib.kq_cw_process(bank, None, 0, 0, 16, 16, 1, 0, None, 0) == -1
-    assert b"null src" in lib.kq_last_error()
-    assert lib.kq_cw_process(bank, None, 0, 0, 0, 0, 0, 0, None, 0) == 0        # nothing to do
-    assert lib.kq_cw_process(None, buf.ctypes.data, 0, 0, 16, 16, 1, 0, None, 0) == -1
-    assert lib.kq_last_error() == b"kq_cw_process: null bank"
-
-
-def test_without_a_slot_nothing_touches_a_device(lib, bank):
-    """with no slot set -- or one set and removed again -- process, counts, clear, sync and reset succeed and touch no
-    device"""
-    buf = np.zeros(1 << 14, np.float32)
-    assert lib.kq_cw_set(bank, 5, C.byref(cw_params())) == 0 and lib.kq_cw_remove(bank, 5) == 0
-    for n in (1, 1000, 16384):
-        assert lib.kq_cw_process(bank, buf.ctypes.data, 0, 0, n, n, 1, 0, None, 0) == 0
-    counts = np.full(8, 7, np.uint32)
-    assert lib.kq_cw_pull_counts(bank, counts.ctypes.data) == 0 and not counts.any()
-    assert lib.kq_cw_clear_events(bank) == 0 and lib.kq_cw_sync(bank) == 0 and lib.kq_cw_reset(bank) == 0
-    ev = np.zeros(1, EVENT_DTYPE)
-    assert lib.kq_cw_pull_event(bank, 0, 0, ev.ctypes.data) == -1
-    assert b"slot 0 has 0 events" in lib.kq_last_error()
-
-
-def test_set_needs_no_device_and_the_first_call_says_where_there_is_none(lib):
-    b = kq.CwBank(12000.0, 48, max_slots=4, max_samples=4096)
-    b.set(0, source=0, pitch=700.0, wpm=20.0)                        # no device asked for yet
-    assert b.get_inc(0) == cm.cw_inc(700.0, 12000.0)
-    try:
-        b.process(np.zeros((1, 480), np.float32))
-        assert lib.kq_device_count() > 0
-    except kq.KqError as e:
-        assert lib.kq_device_count() <= 0, str(e)
-    b.close()
-    with pytest.raises(kq.KqError, match="fewer than 48"):
-        kq.CwBank(12000.0, 480, max_slots=4, max_samples=4096)
-
-
-def test_null_handles_refused(lib):
-    for fn, args in ((lib.kq_cw_destroy, ()), (lib.kq_cw_sync, ()), (lib.kq_cw_reset, ()), (lib.kq_cw_remove, (0,)),
-                     (lib.kq_cw_clear_events, ()), (lib.kq_cw_pull_counts, (None,)), (lib.kq_cw_get_table, (None, 0)),
-                     (lib.kq_cw_get_inc, (0, None)), (lib.kq_cw_pull_event, (0, 0, None))):
-        assert fn(None, *args) == -1
-        assert b"null bank" in lib.kq_last_error()
 
 
 @pytest.mark.parametrize("Fs", [12000.0, 39062.5, 48000.0, 8000.0])

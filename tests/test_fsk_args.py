@@ -6,30 +6,55 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import bank_args
 import ka9q_sdr_amd as kq
 import fsk_model as fm
 from ka9q_sdr_amd.fsk import INFO_DTYPE, STATUS_DTYPE, FskConfig, FskParams, _bind, fsk_params
 
 
-@pytest.fixture(scope="module")
-def lib():
-    kq.build_library()
-    return _bind(kq.load_library())
-
-
-def _cfg(**kw):
-    c = dict(device=0, samprate=48000, baud=9600, taps=21, cutoff_hz=5760.0, kaiser_beta=2.0, window_bits=16.0,
-             input_scale=4096.0, pll_shift=3, max_slots=8, max_frames=4, max_frame_bytes=64, max_samples=1 << 14, stream=None)
-    c.update(kw)
-    return FskConfig(*c.values())
-
-
-@pytest.fixture
-def bank(lib):
-    h = lib.kq_fsk_create(C.byref(_cfg()))
-    assert h, lib.kq_last_error()
-    yield h
-    assert lib.kq_fsk_destroy(h) == 0
+FRAME = np.zeros(64, np.uint8)
+SUITE = bank_args.Suite(
+    "fsk", FskConfig, fsk_params, _bind, status=STATUS_DTYPE, record="frame", pull=(FRAME.ctypes.data, 64, None), null_pull=b"null dst",
+    slot_limit=4096, set_needs_device=True,
+    default=dict(device=0, samprate=48000, baud=9600, taps=21, cutoff_hz=5760.0, kaiser_beta=2.0, window_bits=16.0,
+                 input_scale=4096.0, pll_shift=3, max_slots=8, max_frames=4, max_frame_bytes=64, max_samples=1 << 14, stream=None),
+    bad_configs=[
+        (dict(samprate=38399), b"samprate 38399 must be 4 .. 40 times baud 9600"),
+        (dict(samprate=384001), b"samprate 384001 must be 4 .. 40 times baud 9600"),
+        (dict(samprate=24000), b"samprate 24000"),                         # 2.5 samples per bit
+        (dict(baud=0), b"baud 0"),
+        (dict(samprate=-1), b"samprate -1"),
+        (dict(taps=20), b"taps 20 must be odd"),
+        (dict(taps=1), b"taps 1"),
+        (dict(taps=129), b"taps 129"),
+        (dict(window_bits=0.2), b"window_bits 0.2 gives W = 1 samples"),
+        (dict(window_bits=205.0), b"gives W = 1025 samples"),
+        (dict(window_bits=float("nan")), b"window_bits"),
+        (dict(window_bits=-4.0), b"window_bits"),
+        (dict(cutoff_hz=0.0), b"cutoff_hz 0"),
+        (dict(cutoff_hz=24000.0), b"cutoff_hz 24000"),
+        (dict(cutoff_hz=float("nan")), b"cutoff_hz"),
+        (dict(kaiser_beta=-1.0), b"kaiser_beta"),
+        (dict(kaiser_beta=float("inf")), b"kaiser_beta"),
+        (dict(pll_shift=0), b"pll_shift 0"),
+        (dict(pll_shift=9), b"pll_shift 9"),
+        (dict(input_scale=0.0), b"input_scale"),
+        (dict(input_scale=-1.0), b"input_scale"),
+        (dict(input_scale=float("nan")), b"input_scale"),
+        (dict(max_slots=0), b"max_slots 0"),
+        (dict(max_slots=4097), b"max_slots 4097"),
+        (dict(max_frames=0), b"max_frames 0"),
+        (dict(max_frame_bytes=7), b"max_frame_bytes 7"),
+        (dict(max_frame_bytes=1025), b"max_frame_bytes 1025"),
+        (dict(max_samples=0), b"max_samples 0"),
+        (dict(samprate=38400, taps=127), b"sum |hq| = 66153 > 65535"),     # long filter, four samples per bit: could overflow
+    ],
+    null_handles=[("destroy", ()), ("sync", ()), ("reset", ()), ("remove", (0,)), ("clear_frames", ()), ("pull_counts", (None,)),
+                  ("get_taps", (None, 0)), ("pull_frame", (0, 0, None, 0, None))])
+lib, bank, _cfg = SUITE.lib, SUITE.bank, SUITE.cfg
+test_null_config_refused, test_bad_config_refused, test_bad_process_refused = SUITE.null_config, SUITE.bad_config, SUITE.bad_process
+test_bad_slot_refused, test_null_handles_refused = SUITE.bad_slot, SUITE.null_handles
+test_without_a_slot_nothing_touches_a_device = SUITE.without_a_slot
 
 
 NAMES = {"kq_fsk_create", "kq_fsk_destroy", "kq_fsk_set", "kq_fsk_remove", "kq_fsk_process", "kq_fsk_pull_counts",
@@ -53,11 +78,6 @@ def test_record_layouts():
     assert FskConfig.max_samples.offset == 48 and FskConfig.stream.offset == 56
 
 
-def test_null_config_refused(lib):
-    assert lib.kq_fsk_create(None) is None
-    assert lib.kq_last_error() == b"kq_fsk_create: null config"
-
-
 def test_good_configs_accepted(lib):
     for kw in (dict(), dict(samprate=38400), dict(samprate=384000, window_bits=25.6),   # Fs = 4 and 40 baud; W = 1024
                dict(samprate=39062, taps=17), dict(taps=3), dict(taps=127), dict(window_bits=0.4),     # W = 2
@@ -66,43 +86,6 @@ def test_good_configs_accepted(lib):
         h = lib.kq_fsk_create(C.byref(_cfg(**kw)))
         assert h, (kw, lib.kq_last_error())
         assert lib.kq_fsk_destroy(h) == 0
-
-
-@pytest.mark.parametrize("kw,why", [
-    (dict(samprate=38399), b"samprate 38399 must be 4 .. 40 times baud 9600"),
-    (dict(samprate=384001), b"samprate 384001 must be 4 .. 40 times baud 9600"),
-    (dict(samprate=24000), b"samprate 24000"),                         # 2.5 samples per bit
-    (dict(baud=0), b"baud 0"),
-    (dict(samprate=-1), b"samprate -1"),
-    (dict(taps=20), b"taps 20 must be odd"),
-    (dict(taps=1), b"taps 1"),
-    (dict(taps=129), b"taps 129"),
-    (dict(window_bits=0.2), b"window_bits 0.2 gives W = 1 samples"),
-    (dict(window_bits=205.0), b"gives W = 1025 samples"),
-    (dict(window_bits=float("nan")), b"window_bits"),
-    (dict(window_bits=-4.0), b"window_bits"),
-    (dict(cutoff_hz=0.0), b"cutoff_hz 0"),
-    (dict(cutoff_hz=24000.0), b"cutoff_hz 24000"),
-    (dict(cutoff_hz=float("nan")), b"cutoff_hz"),
-    (dict(kaiser_beta=-1.0), b"kaiser_beta"),
-    (dict(kaiser_beta=float("inf")), b"kaiser_beta"),
-    (dict(pll_shift=0), b"pll_shift 0"),
-    (dict(pll_shift=9), b"pll_shift 9"),
-    (dict(input_scale=0.0), b"input_scale"),
-    (dict(input_scale=-1.0), b"input_scale"),
-    (dict(input_scale=float("nan")), b"input_scale"),
-    (dict(max_slots=0), b"max_slots 0"),
-    (dict(max_slots=4097), b"max_slots 4097"),
-    (dict(max_frames=0), b"max_frames 0"),
-    (dict(max_frame_bytes=7), b"max_frame_bytes 7"),
-    (dict(max_frame_bytes=1025), b"max_frame_bytes 1025"),
-    (dict(max_samples=0), b"max_samples 0"),
-    (dict(samprate=38400, taps=127), b"sum |hq| = 66153 > 65535"),     # long filter, four samples per bit: could overflow
-])
-def test_bad_config_refused(lib, kw, why):
-    assert lib.kq_fsk_create(C.byref(_cfg(**kw))) is None
-    msg = lib.kq_last_error()
-    assert msg.startswith(b"kq_fsk_create: ") and why in msg, msg
 
 
 def test_bad_params_refused(lib, bank):
@@ -114,65 +97,6 @@ def test_bad_params_refused(lib, bank):
             assert msg.startswith(b"kq_fsk_set: ") and b"min_bytes %d" % mb in msg, msg
     assert lib.kq_fsk_set(bank, 0, C.byref(fsk_params(min_bytes=65))) == -1      # max_frame_bytes = 64
     assert lib.kq_last_error() == b"kq_fsk_set: min_bytes 65 > max_frame_bytes 64"
-
-
-def test_bad_slot_refused(lib, bank):
-    p = fsk_params()
-    assert lib.kq_fsk_set(None, 4096, C.byref(p)) == -1
-    assert b"slot 4096" in lib.kq_last_error()
-    assert lib.kq_fsk_set(bank, 8, C.byref(p)) == -1     # max_slots = 8
-    assert b"slot 8 >= max_slots 8" in lib.kq_last_error()
-    assert lib.kq_fsk_set(bank, 0, None) == -1
-    assert lib.kq_last_error() == b"kq_fsk_set: null params"
-    assert lib.kq_fsk_set(None, 0, C.byref(p)) == -1
-    assert lib.kq_last_error() == b"kq_fsk_set: null bank"
-    assert lib.kq_fsk_remove(bank, 3) == -1
-    assert b"slot 3 holds no decoder" in lib.kq_last_error()
-    buf = np.zeros(64, np.uint8)
-    assert lib.kq_fsk_pull_frame(bank, 9, 0, buf.ctypes.data, 64, None) == -1
-    assert b"slot 9 >= max_slots 8" in lib.kq_last_error()
-    assert lib.kq_fsk_pull_frame(bank, 0, 0, None, 64, None) == -1
-    assert lib.kq_last_error() == b"kq_fsk_pull_frame: null dst"
-    assert lib.kq_fsk_pull_counts(bank, None) == -1
-    assert lib.kq_last_error() == b"kq_fsk_pull_counts: null counts"
-
-
-def test_bad_process_refused(lib, bank):
-    buf = np.zeros(1 << 15, np.float32)
-    st = np.zeros(8, STATUS_DTYPE)
-    assert lib.kq_fsk_process(bank, buf.ctypes.data, 0, 0, 4096, 4096, 5, 0, None, 0) == -1   # 20480 > 16384
-    assert b"max_samples" in lib.kq_last_error()
-    assert lib.kq_fsk_process(bank, buf.ctypes.data, 0, 0, 100, 200, 2, 0, None, 0) == -1
-    assert b"row_stride 100 < block_len 200" in lib.kq_last_error()
-    assert lib.kq_fsk_process(bank, buf.ctypes.data, 2, 0, 16, 16, 1, 0, None, 0) == -1         # KQ_PCM_S16: the modulator's
-    assert b"unknown sample format 2" in lib.kq_last_error()
-    assert lib.kq_fsk_process(bank, buf.ctypes.data, 0, 0, 16, 16, 1, 0, st.ctypes.data, 0) == -1
-    assert b"status_stride 0 < 1" in lib.kq_last_error()
-    assert lib.kq_fsk_process(bank, None, 0, 0, 16, 16, 1, 0, None, 0) == -1
-    assert b"null src" in lib.kq_last_error()
-    assert lib.kq_fsk_process(bank, None, 0, 0, 0, 0, 0, 0, None, 0) == 0        # nothing to do
-    assert lib.kq_fsk_process(None, buf.ctypes.data, 0, 0, 16, 16, 1, 0, None, 0) == -1
-    assert lib.kq_last_error() == b"kq_fsk_process: null bank"
-
-
-def test_without_a_slot_nothing_touches_a_device(lib, bank):
-    """with no slot set, process, counts, clear, sync and reset succeed and touch no device"""
-    buf = np.zeros(1 << 14, np.float32)
-    for n in (1, 1000, 16384):
-        assert lib.kq_fsk_process(bank, buf.ctypes.data, 0, 0, n, n, 1, 0, None, 0) == 0
-    counts = np.full(8, 7, np.uint32)
-    assert lib.kq_fsk_pull_counts(bank, counts.ctypes.data) == 0 and not counts.any()
-    assert lib.kq_fsk_clear_frames(bank) == 0 and lib.kq_fsk_sync(bank) == 0 and lib.kq_fsk_reset(bank) == 0
-    assert lib.kq_fsk_pull_frame(bank, 0, 0, buf.ctypes.data, 64, None) == -1
-    assert b"slot 0 has 0 frames" in lib.kq_last_error()
-
-
-def test_null_handles_refused(lib):
-    for fn, args in ((lib.kq_fsk_destroy, ()), (lib.kq_fsk_sync, ()), (lib.kq_fsk_reset, ()), (lib.kq_fsk_remove, (0,)),
-                     (lib.kq_fsk_clear_frames, ()), (lib.kq_fsk_pull_counts, (None,)), (lib.kq_fsk_get_taps, (None, 0)),
-                     (lib.kq_fsk_pull_frame, (0, 0, None, 0, None))):
-        assert fn(None, *args) == -1
-        assert b"null bank" in lib.kq_last_error()
 
 
 @pytest.mark.parametrize("kw", [dict(), dict(samprate=39062, taps=17), dict(samprate=96000, taps=41, kaiser_beta=3.5),

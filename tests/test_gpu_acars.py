@@ -16,6 +16,7 @@ import pytest
 import torch
 
 import acars_model as am
+import bank_gpu
 import ka9q_sdr_amd as kq
 from ka9q_sdr_amd import arinc618
 from ka9q_sdr_amd.acars import STATUS_DTYPE, STATUS_WORDS, AcarsBank, acars_params, status_array
@@ -82,26 +83,10 @@ def _model(bank, **kw):
                          max_blocks=bank.max_blocks, taps=bank.get_taps(), **kw)
 
 
-def _status(rec):
-    return {k: int(rec[k]) for k in STATUS_DTYPE.names}
-
-
-def _snap(models):
-    return [(m.status(), list(m.blocks)) for m in models]
-
-
-def _check(bank, want, st, slots=None, what=None, seen=None):
-    """want: per slot (status, records) of the model.  seen: per slot the records already compared (arenas only grow
-    between clears), so that a record is pulled once"""
-    counts = bank.counts()
-    for s in (range(len(want)) if slots is None else slots):
-        status, blocks = want[s]
-        assert _status(st[s]) == status, (what, s, _status(st[s]), status)
-        assert int(counts[s]) == len(blocks), (what, s)
-        k0 = seen[s] if seen is not None else 0
-        assert [bank.block(s, k) for k in range(k0, len(blocks))] == blocks[k0:], (what, s)
-        if seen is not None:
-            seen[s] = len(blocks)
+_status = functools.partial(bank_gpu.status_of, STATUS_DTYPE)
+_snap = functools.partial(bank_gpu.snap, "blocks")
+_check = functools.partial(bank_gpu.check, _status, "block")
+_device_call, _plane = functools.partial(bank_gpu.device_call, status_array), functools.partial(bank_gpu.plane, STATUS_WORDS)
 
 
 def _cuts(n, sizes, special=()):
@@ -130,28 +115,6 @@ def _special(Fs):
     assert r.flags & am.GOOD and g.w >= 4
     mid = r.end_sample - int(8 * Fs / 2400.0)
     return [r.sync_sample + 2, r.sync_sample + 3, r.sync_sample + 4, mid, mid + 1, mid + g.w + 3]
-
-
-def _device_call(bank, chunk, nblocks, st, fmt=kq.KQ_PCM_F32, pad=5):
-    """the chunk from device memory: nblocks blocks of block_len in rows of block_len + pad (NaN / junk in between); the
-    status plane on the device"""
-    rows, n = chunk.shape
-    bl = n // nblocks
-    if fmt == kq.KQ_PCM_S16BE:
-        buf = np.full((rows, nblocks, bl + pad), 0x0080, np.int16)              # the word -32768, byte-swapped
-        buf[:, :, :bl] = chunk.astype(">i2").view(np.int16).reshape(rows, nblocks, bl)
-    else:
-        buf = np.full((rows, nblocks, bl + pad), np.nan, np.float32)
-        buf[:, :, :bl] = chunk.reshape(rows, nblocks, bl)
-    t = torch.from_numpy(buf).cuda()
-    torch.cuda.synchronize()
-    bank.process_device(t.data_ptr(), nblocks * (bl + pad), bl + pad, bl, nblocks, st.data_ptr(), 1, fmt=fmt)
-    bank.sync()
-    return status_array(st)
-
-
-def _plane(bank):
-    return torch.zeros((bank.max_slots, STATUS_WORDS), dtype=torch.int32, device="cuda")
 
 
 @pytest.mark.parametrize("Fs", [12000.0, 39062.5])

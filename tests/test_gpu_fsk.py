@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import bank_gpu
 import ka9q_sdr_amd as kq
 import fsk_model as fm
 from ka9q_sdr_amd.fsk import STATUS_DTYPE, TILE, FskBank, fsk_params, status_array
@@ -51,45 +52,10 @@ def _setup(bank, S):
         bank.set(s, fsk_params(source=s, scrambled=s % 2 == 0))
 
 
-def _status(rec):
-    return {k: int(rec[k]) for k in STATUS_DTYPE.names}
-
-
-def _check(bank, models, st, slots=None, what=None):
-    counts = bank.counts()
-    for s in (range(len(models)) if slots is None else slots):
-        m = models[s]
-        assert _status(st[s]) == m.status(), (what, s, _status(st[s]), m.status())
-        assert int(counts[s]) == len(m.frames), (what, s)
-        assert bank.frames(s, len(m.frames)) == m.frames, (what, s)
-
-
-def _chunks(n, sizes):
-    """cut points: the sizes in turn, over and over"""
-    at, k, out = 0, 0, []
-    while at < n:
-        m = min(sizes[k % len(sizes)], n - at)
-        out.append((at, at + m))
-        at += m
-        k += 1
-    return out
-
-
-def _device_call(bank, chunk, nblocks, st, fmt=kq.KQ_PCM_F32, pad=5):
-    """the chunk from device memory: nblocks blocks of block_len in rows of block_len + pad (NaN / junk in between)"""
-    rows, n = chunk.shape
-    bl = n // nblocks
-    if fmt == kq.KQ_PCM_S16BE:
-        buf = np.full((rows, nblocks, bl + pad), 0x0080, np.int16)              # the word -32768, byte-swapped
-        buf[:, :, :bl] = chunk.astype(">i2").view(np.int16).reshape(rows, nblocks, bl)
-    else:
-        buf = np.full((rows, nblocks, bl + pad), np.nan, np.float32)
-        buf[:, :, :bl] = chunk.reshape(rows, nblocks, bl)
-    t = torch.from_numpy(buf).cuda()
-    torch.cuda.synchronize()
-    bank.process_device(t.data_ptr(), nblocks * (bl + pad), bl + pad, bl, nblocks, st.data_ptr(), 1, fmt=fmt)
-    bank.sync()
-    return status_array(st)
+_status = functools.partial(bank_gpu.status_of, STATUS_DTYPE)
+_snap, _chunks = functools.partial(bank_gpu.snap, "frames"), bank_gpu.chunks
+_check = functools.partial(bank_gpu.check, _status, "frame")
+_device_call = functools.partial(bank_gpu.device_call, status_array)
 
 
 # Fs, baud, K, window_bits, slots: 5, 4.07 and 40 samples per bit; K = 3 and 127; W = 2 and 1024; 65 slots put k_fsk_track on two
@@ -119,7 +85,7 @@ def test_parity_from_host_and_device_memory(gpu, Fs, baud, K, wb, S):
                 st = bank.process(x[:, a:b], nblocks)
             for s, m in enumerate(models):
                 m.feed(x[s, a:b])
-            _check(bank, models, st, what=(device, a, b))
+            _check(bank, _snap(models), st, what=(device, a, b))
         decoded = sum([f[0] for f in m.frames] == sent(frames[s]) for s, m in enumerate(models))
         bank.close()
     print("fsk parity %s: %d of %d slots decode every frame" % ((Fs, baud, K, wb, S), decoded, S))
@@ -145,7 +111,7 @@ def test_int16_input_and_clipping(gpu, device):
             st = _device_call(bank, data[:, a:b], 1, st_t, fmt) if device else bank.process(data[:, a:b], 1, fmt)
             for s, m in enumerate(models):
                 m.feed(data[s, a:b], s16=fmt == kq.KQ_PCM_S16BE)
-            _check(bank, models, st, what=(fmt, a, b))
+            _check(bank, _snap(models), st, what=(fmt, a, b))
         assert all([f[0] for f in m.frames] == sent(frames[s]) for s, m in enumerate(models))
         bank.close()
 
@@ -173,7 +139,7 @@ def test_call_splits_change_nothing(gpu):
             n = b - a
             nblocks = next(k for k in (8, 3, 2, 1) if n % k == 0)
             st = bank.process(x[:, a:b], nblocks)
-        _check(bank, ref, st, what=sizes)
+        _check(bank, _snap(ref), st, what=sizes)
         bank.close()
 
 
@@ -215,7 +181,7 @@ def test_remove_reset_full_arena_and_clear(gpu):
     st = bank.process(x)
     for s, m in enumerate(models):
         m.feed(x[s])
-    _check(bank, models, st)
+    _check(bank, _snap(models), st)
     # the arena holds two: the first two stay intact, the others are counted
     assert [int(st[s]["dropped"]) for s in range(2)] == [2, 2] and [int(st[s]["frames_good"]) for s in range(2)] == [4, 4]
     assert [f[0] for f in bank.frames(1)] == sent(frames[1])[:2]
@@ -227,7 +193,7 @@ def test_remove_reset_full_arena_and_clear(gpu):
     st = bank.process(x)
     for s, m in enumerate(models):
         m.feed(x[s])
-    _check(bank, models, st)
+    _check(bank, _snap(models), st)
     assert [int(st[s]["dropped"]) for s in range(2)] == [4, 4] and list(bank.counts()) == [2, 2]
     assert bank.frames(0)[0][1] > x.shape[1]                  # end_sample runs on
     # a removed slot stops: nothing is written for it, its arena stays; the other goes on
@@ -237,13 +203,13 @@ def test_remove_reset_full_arena_and_clear(gpu):
     st = bank.process(x)
     models[1].feed(x[1])
     assert not st[0].tobytes().strip(b"\0")
-    _check(bank, models, st, slots=[1])
+    _check(bank, _snap(models), st, slots=[1])
     # reset: the grid starts over and every slot still set restarts cold
     bank.reset()
     fresh = _models(bank, 2, max_frames=2)
     st = bank.process(x)
     fresh[1].feed(x[1])
-    _check(bank, fresh, st, slots=[1])
+    _check(bank, _snap(fresh), st, slots=[1])
     assert bank.frames(1)[0][1] < x.shape[1] and int(bank.counts()[0]) == 0
     bank.close()
 
@@ -270,7 +236,7 @@ def test_bad_and_aborted_frames(gpu):
         st = bank.process(x)
         for s, m in enumerate(models):
             m.feed(x[s])
-        _check(bank, models, st, what=mfb)
+        _check(bank, _snap(models), st, what=mfb)
         got = [(int(r["frames_good"]), int(r["frames_bad"]), int(r["aborts"])) for r in st[:3]]
         assert got == want, (mfb, got)
         bank.close()

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+import bank_gpu
 import ka9q_sdr_amd as kq
 import pag_model as pm
 from ka9q_sdr_amd import pocsag
@@ -71,50 +72,10 @@ def _setup(bank, S):
         bank.set(s, pag_params(source=s))
 
 
-def _status(rec):
-    return {k: int(rec[k]) for k in STATUS_DTYPE.names}
-
-
-def _check(bank, want, st, slots=None, what=None):
-    """want: per slot (status, pages) of the model"""
-    counts = bank.counts()
-    for s in (range(len(want)) if slots is None else slots):
-        status, pages = want[s]
-        assert _status(st[s]) == status, (what, s, _status(st[s]), status)
-        assert int(counts[s]) == len(pages), (what, s)
-        assert bank.pages(s, len(pages)) == pages, (what, s)
-
-
-def _snap(models):
-    return [(m.status(), list(m.pages)) for m in models]
-
-
-def _chunks(n, sizes):
-    """cut points: the sizes in turn, over and over"""
-    at, k, out = 0, 0, []
-    while at < n:
-        m = min(sizes[k % len(sizes)], n - at)
-        out.append((at, at + m))
-        at += m
-        k += 1
-    return out
-
-
-def _device_call(bank, chunk, nblocks, st, fmt=kq.KQ_PCM_F32, pad=5):
-    """the chunk from device memory: nblocks blocks of block_len in rows of block_len + pad (NaN / junk in between)"""
-    rows, n = chunk.shape
-    bl = n // nblocks
-    if fmt == kq.KQ_PCM_S16BE:
-        buf = np.full((rows, nblocks, bl + pad), 0x0080, np.int16)              # the word -32768, byte-swapped
-        buf[:, :, :bl] = chunk.astype(">i2").view(np.int16).reshape(rows, nblocks, bl)
-    else:
-        buf = np.full((rows, nblocks, bl + pad), np.nan, np.float32)
-        buf[:, :, :bl] = chunk.reshape(rows, nblocks, bl)
-    t = torch.from_numpy(buf).cuda()
-    torch.cuda.synchronize()
-    bank.process_device(t.data_ptr(), nblocks * (bl + pad), bl + pad, bl, nblocks, st.data_ptr(), 1, fmt=fmt)
-    bank.sync()
-    return status_array(st)
+_status = functools.partial(bank_gpu.status_of, STATUS_DTYPE)
+_snap, _chunks = functools.partial(bank_gpu.snap, "pages"), bank_gpu.chunks
+_check = functools.partial(bank_gpu.check, _status, "page")
+_device_call = functools.partial(bank_gpu.device_call, status_array)
 
 
 # Fs, bit/s, K, slots: 16, 20 and 16 samples per bit; 70 slots put k_pag_track on two waves

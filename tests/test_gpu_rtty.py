@@ -20,6 +20,7 @@ import pytest
 import torch
 
 import rtty_model as rm
+import bank_gpu
 import ka9q_sdr_amd as kq
 from ka9q_sdr_amd import baudot
 from ka9q_sdr_amd.rtty import STATUS_DTYPE, STATUS_WORDS, RttyBank, rtty_params, status_array
@@ -63,59 +64,10 @@ def _models(bank, plan, **kw):
     return out
 
 
-def _status(rec):
-    return {k: int(rec[k]) for k in STATUS_DTYPE.names}
-
-
-def _snap(models):
-    return [(m.status(), list(m.events)) for m in models]
-
-
-def _check(bank, want, st, slots=None, what=None, seen=None):
-    """want: per slot (status, events) of the model.  seen: per slot the events already compared (arenas only grow between
-    clears), so that an event is pulled once"""
-    counts = bank.counts()
-    for s in (range(len(want)) if slots is None else slots):
-        status, events = want[s]
-        assert _status(st[s]) == status, (what, s, _status(st[s]), status)
-        assert int(counts[s]) == len(events), (what, s)
-        k0 = seen[s] if seen is not None else 0
-        assert [bank.event(s, k) for k in range(k0, len(events))] == events[k0:], (what, s)
-        if seen is not None:
-            seen[s] = len(events)
-
-
-def _chunks(n, sizes):
-    """cut points: the sizes in turn, over and over"""
-    at, k, out = 0, 0, []
-    while at < n:
-        m = min(sizes[k % len(sizes)], n - at)
-        out.append((at, at + m))
-        at += m
-        k += 1
-    return out
-
-
-def _device_call(bank, chunk, nblocks, st, fmt=kq.KQ_PCM_F32, pad=5):
-    """the chunk from device memory: nblocks blocks of block_len in rows of block_len + pad (NaN / junk in between); the
-    status plane on the device"""
-    rows, n = chunk.shape
-    bl = n // nblocks
-    if fmt == kq.KQ_PCM_S16BE:
-        buf = np.full((rows, nblocks, bl + pad), 0x0080, np.int16)              # the word -32768, byte-swapped
-        buf[:, :, :bl] = chunk.astype(">i2").view(np.int16).reshape(rows, nblocks, bl)
-    else:
-        buf = np.full((rows, nblocks, bl + pad), np.nan, np.float32)
-        buf[:, :, :bl] = chunk.reshape(rows, nblocks, bl)
-    t = torch.from_numpy(buf).cuda()
-    torch.cuda.synchronize()
-    bank.process_device(t.data_ptr(), nblocks * (bl + pad), bl + pad, bl, nblocks, st.data_ptr(), 1, fmt=fmt)
-    bank.sync()
-    return status_array(st)
-
-
-def _plane(bank):
-    return torch.zeros((bank.max_slots, STATUS_WORDS), dtype=torch.int32, device="cuda")
+_status = functools.partial(bank_gpu.status_of, STATUS_DTYPE)
+_snap, _chunks = functools.partial(bank_gpu.snap, "events"), bank_gpu.chunks
+_check = functools.partial(bank_gpu.check, _status, "event")
+_device_call, _plane = functools.partial(bank_gpu.device_call, status_array), functools.partial(bank_gpu.plane, STATUS_WORDS)
 
 
 PARITY = [(12000.0, 24, 70, 3.0, (45.45, 50.0)), (12000.0, 16, 6, 3.0, (45.45, 50.0, 75.0)), (12000.0, 8, 3, 3.0, (50.0,)),

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+import bank_gpu
 import ka9q_sdr_amd as kq
 import tone_model as tm
 from ka9q_sdr_amd import selcall as sc
@@ -45,58 +46,19 @@ def _models(bank, n, cfg, **kw):
                          **cfg, **kw) for _ in range(n)]
 
 
-def _status(rec):
-    return {k: int(rec[k]) for k in STATUS_DTYPE.names}
-
-
-def _snap(models):
-    return [(m.status(), m.powers(), list(m.events)) for m in models]
-
-
-def _check(bank, want, st, pw, slots=None, what=None):
-    """want: per slot (status, powers, events) of the model"""
-    counts = bank.counts()
-    for s in (range(len(want)) if slots is None else slots):
-        status, powers, events = want[s]
-        assert _status(st[s]) == status, (what, s, _status(st[s]), status)
-        assert [int(v) for v in pw[s]] == powers, (what, s)
-        assert int(counts[s]) == len(events), (what, s)
-        assert bank.events(s, len(events)) == events, (what, s)
-
-
-def _chunks(n, sizes):
-    """cut points: the sizes in turn, over and over"""
-    at, k, out = 0, 0, []
-    while at < n:
-        m = min(sizes[k % len(sizes)], n - at)
-        out.append((at, at + m))
-        at += m
-        k += 1
-    return out
-
-
-def _device_call(bank, chunk, nblocks, st, pw, fmt=kq.KQ_PCM_F32, pad=5):
-    """the chunk from device memory: nblocks blocks of block_len in rows of block_len + pad (NaN / junk in between);
-    status and powers planes on the device, the powers' rows one value longer than they need be"""
-    rows, n = chunk.shape
-    bl = n // nblocks
-    if fmt == kq.KQ_PCM_S16BE:
-        buf = np.full((rows, nblocks, bl + pad), 0x0080, np.int16)              # the word -32768, byte-swapped
-        buf[:, :, :bl] = chunk.astype(">i2").view(np.int16).reshape(rows, nblocks, bl)
-    else:
-        buf = np.full((rows, nblocks, bl + pad), np.nan, np.float32)
-        buf[:, :, :bl] = chunk.reshape(rows, nblocks, bl)
-    t = torch.from_numpy(buf).cuda()
-    torch.cuda.synchronize()
-    bank.process_device(t.data_ptr(), nblocks * (bl + pad), bl + pad, bl, nblocks, st.data_ptr(), 1, pw.data_ptr(),
-                        pw.shape[1], fmt=fmt)
-    bank.sync()
-    return status_array(st), pw.cpu().numpy().view(np.uint64)[:, :bank.ntones + 1]
+_status = functools.partial(bank_gpu.status_of, STATUS_DTYPE)
+_snap, _chunks = functools.partial(bank_gpu.snap, "events", planes=("powers",)), bank_gpu.chunks
+_check = functools.partial(bank_gpu.check, _status, "event")
+_device_call, _plane = functools.partial(bank_gpu.device_call, status_array), functools.partial(bank_gpu.plane, STATUS_WORDS)
 
 
 def _planes(bank):
-    return (torch.zeros((bank.max_slots, STATUS_WORDS), dtype=torch.int32, device="cuda"),
-            torch.zeros((bank.max_slots, bank.ntones + 2), dtype=torch.int64, device="cuda"))
+    """status and powers planes on the device, the powers' rows one value longer than they need be"""
+    return _plane(bank), torch.zeros((bank.max_slots, bank.ntones + 2), dtype=torch.int64, device="cuda")
+
+
+def _powers(bank, pw):
+    return pw.cpu().numpy().view(np.uint64)[:, :bank.ntones + 1]
 
 
 def _sent(plan, events, B):
@@ -131,7 +93,8 @@ def test_parity_from_host_and_device_memory(gpu, Fs, B, plan, S):
         for (a, b), w in zip(cuts, want):
             nblocks = 4 if (b - a) % 4 == 0 else 1
             if device:
-                st, pw = _device_call(bank, x[:, a:b], nblocks, st_t, pw_t)
+                st = _device_call(bank, x[:, a:b], nblocks, st_t, extra=(pw_t.data_ptr(), pw_t.shape[1]))
+                pw = _powers(bank, pw_t)
             else:
                 st, pw = bank.process(x[:, a:b], nblocks)
             _check(bank, w, st, pw, what=(device, a, b))
@@ -161,7 +124,8 @@ def test_int16_input_shared_rows_and_clipping(gpu, device):
         st_t, pw_t = _planes(bank)
         for a, b in _chunks(x.shape[1], (1000, 8192)):
             if device:
-                st, pw = _device_call(bank, data[:, a:b], 1, st_t, pw_t, fmt)
+                st = _device_call(bank, data[:, a:b], 1, st_t, fmt, extra=(pw_t.data_ptr(), pw_t.shape[1]))
+                pw = _powers(bank, pw_t)
             else:
                 st, pw = bank.process(data[:, a:b], 1, fmt)
             for m, r in zip(models, src):

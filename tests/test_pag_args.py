@@ -8,31 +8,64 @@ import itertools
 import numpy as np
 import pytest
 
+import bank_args
 import ka9q_sdr_amd as kq
 import fsk_model as fm
 import pag_model as pm
 from ka9q_sdr_amd.pag import INFO_DTYPE, STATUS_DTYPE, STATUS_WORDS, PagConfig, PagParams, _bind, correct, pag_params
 
 
-@pytest.fixture(scope="module")
-def lib():
-    kq.build_library()
-    return _bind(kq.load_library())
-
-
-def _cfg(**kw):
-    c = dict(device=0, samprate=19200.0, baud=1200, taps=31, cutoff_hz=900.0, kaiser_beta=2.0, window_bits=24.0,
-             input_scale=4096.0, pll_shift=3, max_slots=8, max_pages=4, max_page_words=16, max_samples=1 << 14, stream=None)
-    c.update(kw)
-    return PagConfig(*c.values())
-
-
-@pytest.fixture
-def bank(lib):
-    h = lib.kq_pag_create(C.byref(_cfg()))
-    assert h, lib.kq_last_error()
-    yield h
-    assert lib.kq_pag_destroy(h) == 0
+PAGE = np.zeros(64, np.uint8)
+SUITE = bank_args.Suite(
+    "pag", PagConfig, pag_params, _bind, status=STATUS_DTYPE, record="page", pull=(PAGE.ctypes.data, 64, None), null_pull=b"null dst",
+    slot_limit=4096, set_needs_device=True,
+    default=dict(device=0, samprate=19200.0, baud=1200, taps=31, cutoff_hz=900.0, kaiser_beta=2.0, window_bits=24.0,
+                 input_scale=4096.0, pll_shift=3, max_slots=8, max_pages=4, max_page_words=16, max_samples=1 << 14, stream=None),
+    bad_configs=[
+        (dict(samprate=4799.0), b"samprate 4799 must be 4 .. 40 times baud 1200"),
+        (dict(samprate=48000.5), b"samprate 48000.5 must be 4 .. 40 times baud 1200"),
+        (dict(samprate=39062.5, baud=512, cutoff_hz=384.0), b"samprate 39062.5 must be 4 .. 40 times baud 512"),   # via kq_rsmp_*
+        (dict(samprate=3000.0), b"samprate 3000"),                         # 2.5 samples per bit
+        (dict(baud=0), b"baud 0"),
+        (dict(baud=-1200), b"baud -1200"),
+        (dict(samprate=-1.0), b"samprate -1"),
+        (dict(samprate=0.0), b"samprate 0"),
+        (dict(samprate=float("nan")), b"samprate nan"),
+        (dict(samprate=float("inf")), b"samprate inf"),
+        (dict(taps=30), b"taps 30 must be odd"),
+        (dict(taps=1), b"taps 1"),
+        (dict(taps=129), b"taps 129"),
+        (dict(window_bits=0.05), b"window_bits 0.05 gives W = 1 samples"),
+        (dict(window_bits=64.1), b"gives W = 1026 samples"),
+        (dict(samprate=48000.0, window_bits=25.7), b"gives W = 1028 samples"),
+        (dict(window_bits=float("nan")), b"window_bits"),
+        (dict(window_bits=-4.0), b"window_bits"),
+        (dict(cutoff_hz=0.0), b"cutoff_hz 0"),
+        (dict(cutoff_hz=9600.0), b"cutoff_hz 9600"),
+        (dict(cutoff_hz=float("nan")), b"cutoff_hz"),
+        (dict(kaiser_beta=-1.0), b"kaiser_beta"),
+        (dict(kaiser_beta=float("inf")), b"kaiser_beta"),
+        (dict(pll_shift=0), b"pll_shift 0"),
+        (dict(pll_shift=9), b"pll_shift 9"),
+        (dict(input_scale=0.0), b"input_scale"),
+        (dict(input_scale=-1.0), b"input_scale"),
+        (dict(input_scale=float("nan")), b"input_scale"),
+        (dict(max_slots=0), b"max_slots 0"),
+        (dict(max_slots=4097), b"max_slots 4097"),
+        (dict(max_pages=0), b"max_pages 0"),
+        (dict(max_pages=4097), b"max_pages 4097"),
+        (dict(max_page_words=0), b"max_page_words 0"),
+        (dict(max_page_words=257), b"max_page_words 257"),
+        (dict(max_samples=0), b"max_samples 0"),
+        (dict(max_samples=(1 << 28) + 1), b"max_samples 268435457"),
+        (dict(samprate=4800.0, taps=127, cutoff_hz=720.0), b"> 65535"),   # long filter, four samples per bit: could overflow
+    ],
+    null_handles=[("destroy", ()), ("sync", ()), ("reset", ()), ("remove", (0,)), ("clear_pages", ()), ("pull_counts", (None,)),
+                  ("get_taps", (None, 0)), ("pull_page", (0, 0, None, 0, None))])
+lib, bank, _cfg = SUITE.lib, SUITE.bank, SUITE.cfg
+test_null_config_refused, test_bad_config_refused, test_bad_process_refused = SUITE.null_config, SUITE.bad_config, SUITE.bad_process
+test_bad_slot_refused, test_null_handles_refused = SUITE.bad_slot, SUITE.null_handles
+test_without_a_slot_nothing_touches_a_device = SUITE.without_a_slot
 
 
 NAMES = {"kq_pag_create", "kq_pag_destroy", "kq_pag_set", "kq_pag_remove", "kq_pag_process", "kq_pag_pull_counts",
@@ -57,11 +90,6 @@ def test_record_layouts():
     assert PagConfig.max_samples.offset == 56 and PagConfig.stream.offset == 64
 
 
-def test_null_config_refused(lib):
-    assert lib.kq_pag_create(None) is None
-    assert lib.kq_last_error() == b"kq_pag_create: null config"
-
-
 def test_good_configs_accepted(lib):
     """the limits themselves, and the six geometries of the design; none of them asks for a device"""
     for kw in (dict(), dict(samprate=4800.0), dict(samprate=48000.0, window_bits=25.6),      # Fs = 4 and 40 baud; W = 1024
@@ -77,51 +105,6 @@ def test_good_configs_accepted(lib):
                                             window_bits=pm.default_window(Fs, baud))))
         assert h, (Fs, baud, K, lib.kq_last_error())
         assert lib.kq_pag_destroy(h) == 0
-
-
-@pytest.mark.parametrize("kw,why", [
-    (dict(samprate=4799.0), b"samprate 4799 must be 4 .. 40 times baud 1200"),
-    (dict(samprate=48000.5), b"samprate 48000.5 must be 4 .. 40 times baud 1200"),
-    (dict(samprate=39062.5, baud=512, cutoff_hz=384.0), b"samprate 39062.5 must be 4 .. 40 times baud 512"),   # via kq_rsmp_*
-    (dict(samprate=3000.0), b"samprate 3000"),                         # 2.5 samples per bit
-    (dict(baud=0), b"baud 0"),
-    (dict(baud=-1200), b"baud -1200"),
-    (dict(samprate=-1.0), b"samprate -1"),
-    (dict(samprate=0.0), b"samprate 0"),
-    (dict(samprate=float("nan")), b"samprate nan"),
-    (dict(samprate=float("inf")), b"samprate inf"),
-    (dict(taps=30), b"taps 30 must be odd"),
-    (dict(taps=1), b"taps 1"),
-    (dict(taps=129), b"taps 129"),
-    (dict(window_bits=0.05), b"window_bits 0.05 gives W = 1 samples"),
-    (dict(window_bits=64.1), b"gives W = 1026 samples"),
-    (dict(samprate=48000.0, window_bits=25.7), b"gives W = 1028 samples"),
-    (dict(window_bits=float("nan")), b"window_bits"),
-    (dict(window_bits=-4.0), b"window_bits"),
-    (dict(cutoff_hz=0.0), b"cutoff_hz 0"),
-    (dict(cutoff_hz=9600.0), b"cutoff_hz 9600"),
-    (dict(cutoff_hz=float("nan")), b"cutoff_hz"),
-    (dict(kaiser_beta=-1.0), b"kaiser_beta"),
-    (dict(kaiser_beta=float("inf")), b"kaiser_beta"),
-    (dict(pll_shift=0), b"pll_shift 0"),
-    (dict(pll_shift=9), b"pll_shift 9"),
-    (dict(input_scale=0.0), b"input_scale"),
-    (dict(input_scale=-1.0), b"input_scale"),
-    (dict(input_scale=float("nan")), b"input_scale"),
-    (dict(max_slots=0), b"max_slots 0"),
-    (dict(max_slots=4097), b"max_slots 4097"),
-    (dict(max_pages=0), b"max_pages 0"),
-    (dict(max_pages=4097), b"max_pages 4097"),
-    (dict(max_page_words=0), b"max_page_words 0"),
-    (dict(max_page_words=257), b"max_page_words 257"),
-    (dict(max_samples=0), b"max_samples 0"),
-    (dict(max_samples=(1 << 28) + 1), b"max_samples 268435457"),
-    (dict(samprate=4800.0, taps=127, cutoff_hz=720.0), b"> 65535"),   # long filter, four samples per bit: could overflow
-])
-def test_bad_config_refused(lib, kw, why):
-    assert lib.kq_pag_create(C.byref(_cfg(**kw))) is None
-    msg = lib.kq_last_error()
-    assert msg.startswith(b"kq_pag_create: ") and why in msg, msg
 
 
 def test_limits_are_checked_before_any_device_is_asked_for(lib):
@@ -140,65 +123,6 @@ def test_limits_are_checked_before_any_device_is_asked_for(lib):
     except kq.KqError as e:
         assert lib.kq_device_count() <= 0, str(e)
     b.close()
-
-
-def test_bad_slot_refused(lib, bank):
-    p = pag_params()
-    assert lib.kq_pag_set(None, 4096, C.byref(p)) == -1
-    assert b"slot 4096" in lib.kq_last_error()
-    assert lib.kq_pag_set(bank, 8, C.byref(p)) == -1     # max_slots = 8
-    assert b"slot 8 >= max_slots 8" in lib.kq_last_error()
-    assert lib.kq_pag_set(bank, 0, None) == -1
-    assert lib.kq_last_error() == b"kq_pag_set: null params"
-    assert lib.kq_pag_set(None, 0, C.byref(p)) == -1
-    assert lib.kq_last_error() == b"kq_pag_set: null bank"
-    assert lib.kq_pag_remove(bank, 3) == -1
-    assert b"slot 3 holds no decoder" in lib.kq_last_error()
-    buf = np.zeros(64, np.uint8)
-    assert lib.kq_pag_pull_page(bank, 9, 0, buf.ctypes.data, 64, None) == -1
-    assert b"slot 9 >= max_slots 8" in lib.kq_last_error()
-    assert lib.kq_pag_pull_page(bank, 0, 0, None, 64, None) == -1
-    assert lib.kq_last_error() == b"kq_pag_pull_page: null dst"
-    assert lib.kq_pag_pull_counts(bank, None) == -1
-    assert lib.kq_last_error() == b"kq_pag_pull_counts: null counts"
-
-
-def test_bad_process_refused(lib, bank):
-    buf = np.zeros(1 << 15, np.float32)
-    st = np.zeros(8, STATUS_DTYPE)
-    assert lib.kq_pag_process(bank, buf.ctypes.data, 0, 0, 4096, 4096, 5, 0, None, 0) == -1   # 20480 > 16384
-    assert b"max_samples" in lib.kq_last_error()
-    assert lib.kq_pag_process(bank, buf.ctypes.data, 0, 0, 100, 200, 2, 0, None, 0) == -1
-    assert b"row_stride 100 < block_len 200" in lib.kq_last_error()
-    assert lib.kq_pag_process(bank, buf.ctypes.data, 2, 0, 16, 16, 1, 0, None, 0) == -1         # KQ_PCM_S16: the modulator's
-    assert b"unknown sample format 2" in lib.kq_last_error()
-    assert lib.kq_pag_process(bank, buf.ctypes.data, 0, 0, 16, 16, 1, 0, st.ctypes.data, 0) == -1
-    assert b"status_stride 0 < 1" in lib.kq_last_error()
-    assert lib.kq_pag_process(bank, None, 0, 0, 16, 16, 1, 0, None, 0) == -1
-    assert b"null src" in lib.kq_last_error()
-    assert lib.kq_pag_process(bank, None, 0, 0, 0, 0, 0, 0, None, 0) == 0        # nothing to do
-    assert lib.kq_pag_process(None, buf.ctypes.data, 0, 0, 16, 16, 1, 0, None, 0) == -1
-    assert lib.kq_last_error() == b"kq_pag_process: null bank"
-
-
-def test_without_a_slot_nothing_touches_a_device(lib, bank):
-    """with no slot set, process, counts, clear, sync and reset succeed and touch no device"""
-    buf = np.zeros(1 << 14, np.float32)
-    for n in (1, 1000, 16384):
-        assert lib.kq_pag_process(bank, buf.ctypes.data, 0, 0, n, n, 1, 0, None, 0) == 0
-    counts = np.full(8, 7, np.uint32)
-    assert lib.kq_pag_pull_counts(bank, counts.ctypes.data) == 0 and not counts.any()
-    assert lib.kq_pag_clear_pages(bank) == 0 and lib.kq_pag_sync(bank) == 0 and lib.kq_pag_reset(bank) == 0
-    assert lib.kq_pag_pull_page(bank, 0, 0, buf.ctypes.data, 64, None) == -1
-    assert b"slot 0 has 0 pages" in lib.kq_last_error()
-
-
-def test_null_handles_refused(lib):
-    for fn, args in ((lib.kq_pag_destroy, ()), (lib.kq_pag_sync, ()), (lib.kq_pag_reset, ()), (lib.kq_pag_remove, (0,)),
-                     (lib.kq_pag_clear_pages, ()), (lib.kq_pag_pull_counts, (None,)), (lib.kq_pag_get_taps, (None, 0)),
-                     (lib.kq_pag_pull_page, (0, 0, None, 0, None))):
-        assert fn(None, *args) == -1
-        assert b"null bank" in lib.kq_last_error()
 
 
 @pytest.mark.parametrize("Fs,baud,K,W", pm.CASES + [(19200.0, 1200, 3, 384), (9600.0, 1200, 127, 192)])

@@ -7,35 +7,75 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import bank_args
 import ka9q_sdr_amd as kq
 import tone_model as tm
 from ka9q_sdr_amd import selcall as sc
 from ka9q_sdr_amd.tone import EVENT_DTYPE, STATUS_DTYPE, STATUS_WORDS, ToneConfig, ToneParams, _bind, tone_params
 
 
-@pytest.fixture(scope="module")
-def lib():
-    kq.build_library()
-    return _bind(kq.load_library())
-
-
 def _cfg(freqs=sc.DTMF.freqs, **kw):
-    f = np.ascontiguousarray(freqs, np.float32)
+    """freqs=None: DTMF's counts with a null pointer"""
+    f = np.ascontiguousarray(sc.DTMF.freqs if freqs is None else freqs, np.float32)
     c = dict(device=0, samprate=8000.0, block_len=102, ntones=f.size, freqs=f.ctypes.data_as(C.POINTER(C.c_float)), group0=4,
              group1=f.size - 4, min_ms=16, frac=16, ratio=64, twist=160, min_blocks=2, input_scale=32767.0, max_slots=8,
              max_events=4, max_samples=1 << 14, stream=None)
     c.update(kw)
     cfg = ToneConfig(*c.values())
     cfg._keep = f
+    if freqs is None:
+        cfg.freqs = None
     return cfg
 
 
-@pytest.fixture
-def bank(lib):
-    h = lib.kq_tone_create(C.byref(_cfg()))
-    assert h, lib.kq_last_error()
-    yield h
-    assert lib.kq_tone_destroy(h) == 0
+EVENT, POWERS = np.zeros(1, EVENT_DTYPE), np.zeros((8, 9), np.uint64)
+SUITE = bank_args.Suite(
+    "tone", ToneConfig, tone_params, _bind, status=STATUS_DTYPE, record="event", pull=(EVENT.ctypes.data,), null_pull=b"null event",
+    slot_limit=4096, cfg=_cfg, set_needs_device=True,
+    process_extra=(None, 0), bad_process=[((POWERS.ctypes.data, 8), b"powers_stride 8 < ntones + 1 = 9")],
+    bad_configs=[
+        (dict(samprate=0.0), b"samprate 0 must be positive and finite"),
+        (dict(samprate=-8000.0), b"samprate -8000"),
+        (dict(samprate=float("nan")), b"samprate nan"),
+        (dict(samprate=float("inf")), b"samprate inf"),
+        (dict(block_len=7), b"block_len 7 must be 8..4096"),
+        (dict(block_len=4097), b"block_len 4097 must be 8..4096"),
+        (dict(ntones=0, group0=0, group1=0), b"ntones 0 must be 1..32"),
+        (dict(freqs=np.linspace(300.0, 3400.0, 33), group0=33, group1=0), b"ntones 33 must be 1..32"),
+        (dict(group0=0, group1=8), b"groups of 0 and 8 tones"),
+        (dict(group0=4, group1=3), b"groups of 4 and 3 tones"),
+        (dict(group0=8, group1=1), b"groups of 8 and 1 tones"),
+        (dict(group0=0xFFFFFFFF, group1=9), b"groups of 4294967295 and 9 tones"),
+        (dict(freqs=None), b"null freqs"),
+        (dict(freqs=[697.0, 0.0, 852.0, 941.0, 1209.0, 1336.0, 1477.0, 1633.0]), b"freqs[1] 0 must be above 0"),
+        (dict(freqs=[697.0, 770.0, 852.0, 941.0, 1209.0, 1336.0, 1477.0, 4000.0]), b"freqs[7] 4000 must be above 0 and below"),
+        (dict(freqs=[697.0, 770.0, -852.0, 941.0, 1209.0, 1336.0, 1477.0, 1633.0]), b"freqs[2] -852"),
+        (dict(freqs=[float("nan")] * 8), b"freqs[0] nan"),
+        (dict(frac=0), b"frac 0 must be 1..128"),
+        (dict(frac=129), b"frac 129 must be 1..128"),
+        (dict(ratio=15), b"ratio 15 must be 16..4095"),
+        (dict(ratio=4096), b"ratio 4096 must be 16..4095"),
+        (dict(twist=15), b"twist 15 must be 16..4095"),
+        (dict(twist=4096), b"twist 4096 must be 16..4095"),
+        (dict(min_blocks=0), b"min_blocks 0 must be 1..65535"),
+        (dict(min_blocks=65536), b"min_blocks 65536 must be 1..65535"),
+        (dict(input_scale=0.0), b"input_scale"),
+        (dict(input_scale=-1.0), b"input_scale"),
+        (dict(input_scale=float("nan")), b"input_scale"),
+        (dict(input_scale=float("inf")), b"input_scale"),
+        (dict(max_slots=0), b"max_slots 0 must be 1..4096"),
+        (dict(max_slots=4097), b"max_slots 4097"),
+        (dict(max_events=0), b"max_events 0 must be 1..4096"),
+        (dict(max_events=4097), b"max_events 4097"),
+        (dict(max_samples=0), b"max_samples 0"),
+        (dict(max_samples=(1 << 28) + 1), b"max_samples 268435457"),
+    ],
+    null_handles=[("destroy", ()), ("sync", ()), ("reset", ()), ("remove", (0,)), ("clear_events", ()), ("pull_counts", (None,)),
+                  ("get_table", (None, 0)), ("get_incs", (None, 0)), ("pull_event", (0, 0, None))])
+lib, bank = SUITE.lib, SUITE.bank
+test_null_config_refused, test_bad_config_refused, test_bad_process_refused = SUITE.null_config, SUITE.bad_config, SUITE.bad_process
+test_bad_slot_refused, test_null_handles_refused = SUITE.bad_slot, SUITE.null_handles
+test_without_a_slot_nothing_touches_a_device = SUITE.without_a_slot
 
 
 NAMES = {"kq_tone_create", "kq_tone_destroy", "kq_tone_set", "kq_tone_remove", "kq_tone_process", "kq_tone_pull_counts",
@@ -61,11 +101,6 @@ def test_record_layouts():
     assert ToneConfig.input_scale.offset == 60 and ToneConfig.max_samples.offset == 72 and ToneConfig.stream.offset == 80
 
 
-def test_null_config_refused(lib):
-    assert lib.kq_tone_create(None) is None
-    assert lib.kq_last_error() == b"kq_tone_create: null config"
-
-
 def test_good_configs_accepted(lib):
     """the limits themselves, and the geometries of the GPU tests; none of them asks for a device"""
     one = dict(freqs=[1000.0], group0=1, group1=0)
@@ -85,54 +120,6 @@ def test_good_configs_accepted(lib):
             raise AssertionError("%s at %g: %s" % (plan.name, Fs, e))
 
 
-@pytest.mark.parametrize("kw,why", [
-    (dict(samprate=0.0), b"samprate 0 must be positive and finite"),
-    (dict(samprate=-8000.0), b"samprate -8000"),
-    (dict(samprate=float("nan")), b"samprate nan"),
-    (dict(samprate=float("inf")), b"samprate inf"),
-    (dict(block_len=7), b"block_len 7 must be 8..4096"),
-    (dict(block_len=4097), b"block_len 4097 must be 8..4096"),
-    (dict(ntones=0, group0=0, group1=0), b"ntones 0 must be 1..32"),
-    (dict(freqs=np.linspace(300.0, 3400.0, 33), group0=33, group1=0), b"ntones 33 must be 1..32"),
-    (dict(group0=0, group1=8), b"groups of 0 and 8 tones"),
-    (dict(group0=4, group1=3), b"groups of 4 and 3 tones"),
-    (dict(group0=8, group1=1), b"groups of 8 and 1 tones"),
-    (dict(group0=0xFFFFFFFF, group1=9), b"groups of 4294967295 and 9 tones"),
-    (dict(freqs=None), b"null freqs"),
-    (dict(freqs=[697.0, 0.0, 852.0, 941.0, 1209.0, 1336.0, 1477.0, 1633.0]), b"freqs[1] 0 must be above 0"),
-    (dict(freqs=[697.0, 770.0, 852.0, 941.0, 1209.0, 1336.0, 1477.0, 4000.0]), b"freqs[7] 4000 must be above 0 and below"),
-    (dict(freqs=[697.0, 770.0, -852.0, 941.0, 1209.0, 1336.0, 1477.0, 1633.0]), b"freqs[2] -852"),
-    (dict(freqs=[float("nan")] * 8), b"freqs[0] nan"),
-    (dict(frac=0), b"frac 0 must be 1..128"),
-    (dict(frac=129), b"frac 129 must be 1..128"),
-    (dict(ratio=15), b"ratio 15 must be 16..4095"),
-    (dict(ratio=4096), b"ratio 4096 must be 16..4095"),
-    (dict(twist=15), b"twist 15 must be 16..4095"),
-    (dict(twist=4096), b"twist 4096 must be 16..4095"),
-    (dict(min_blocks=0), b"min_blocks 0 must be 1..65535"),
-    (dict(min_blocks=65536), b"min_blocks 65536 must be 1..65535"),
-    (dict(input_scale=0.0), b"input_scale"),
-    (dict(input_scale=-1.0), b"input_scale"),
-    (dict(input_scale=float("nan")), b"input_scale"),
-    (dict(input_scale=float("inf")), b"input_scale"),
-    (dict(max_slots=0), b"max_slots 0 must be 1..4096"),
-    (dict(max_slots=4097), b"max_slots 4097"),
-    (dict(max_events=0), b"max_events 0 must be 1..4096"),
-    (dict(max_events=4097), b"max_events 4097"),
-    (dict(max_samples=0), b"max_samples 0"),
-    (dict(max_samples=(1 << 28) + 1), b"max_samples 268435457"),
-])
-def test_bad_config_refused(lib, kw, why):
-    if "freqs" in kw and kw["freqs"] is None:
-        cfg = _cfg(**{k: v for k, v in kw.items() if k != "freqs"})
-        cfg.freqs = None
-    else:
-        cfg = _cfg(**kw)
-    assert lib.kq_tone_create(C.byref(cfg)) is None
-    msg = lib.kq_last_error()
-    assert msg.startswith(b"kq_tone_create: ") and why in msg, msg
-
-
 def test_limits_are_checked_before_any_device_is_asked_for(lib):
     """every refusal above and every acceptance happen in kq_tone_create, which touches no device: with or without a GPU
     in the box a good plan gives a handle, and what needs a device (the first set) says so where there is none"""
@@ -149,69 +136,6 @@ def test_limits_are_checked_before_any_device_is_asked_for(lib):
     except kq.KqError as e:
         assert lib.kq_device_count() <= 0, str(e)
     b.close()
-
-
-def test_bad_slot_refused(lib, bank):
-    p = tone_params()
-    assert lib.kq_tone_set(None, 4096, C.byref(p)) == -1
-    assert b"slot 4096" in lib.kq_last_error()
-    assert lib.kq_tone_set(bank, 8, C.byref(p)) == -1     # max_slots = 8
-    assert b"slot 8 >= max_slots 8" in lib.kq_last_error()
-    assert lib.kq_tone_set(bank, 0, None) == -1
-    assert lib.kq_last_error() == b"kq_tone_set: null params"
-    assert lib.kq_tone_set(None, 0, C.byref(p)) == -1
-    assert lib.kq_last_error() == b"kq_tone_set: null bank"
-    assert lib.kq_tone_remove(bank, 3) == -1
-    assert b"slot 3 holds no decoder" in lib.kq_last_error()
-    ev = np.zeros(1, EVENT_DTYPE)
-    assert lib.kq_tone_pull_event(bank, 9, 0, ev.ctypes.data) == -1
-    assert b"slot 9 >= max_slots 8" in lib.kq_last_error()
-    assert lib.kq_tone_pull_event(bank, 0, 0, None) == -1
-    assert lib.kq_last_error() == b"kq_tone_pull_event: null event"
-    assert lib.kq_tone_pull_counts(bank, None) == -1
-    assert lib.kq_last_error() == b"kq_tone_pull_counts: null counts"
-
-
-def test_bad_process_refused(lib, bank):
-    buf = np.zeros(1 << 15, np.float32)
-    st = np.zeros(8, STATUS_DTYPE)
-    pw = np.zeros((8, 9), np.uint64)
-    assert lib.kq_tone_process(bank, buf.ctypes.data, 0, 0, 4096, 4096, 5, 0, None, 0, None, 0) == -1   # 20480 > 16384
-    assert b"max_samples" in lib.kq_last_error()
-    assert lib.kq_tone_process(bank, buf.ctypes.data, 0, 0, 100, 200, 2, 0, None, 0, None, 0) == -1
-    assert b"row_stride 100 < block_len 200" in lib.kq_last_error()
-    assert lib.kq_tone_process(bank, buf.ctypes.data, 2, 0, 16, 16, 1, 0, None, 0, None, 0) == -1       # KQ_PCM_S16: the modulator's
-    assert b"unknown sample format 2" in lib.kq_last_error()
-    assert lib.kq_tone_process(bank, buf.ctypes.data, 0, 0, 16, 16, 1, 0, st.ctypes.data, 0, None, 0) == -1
-    assert b"status_stride 0 < 1" in lib.kq_last_error()
-    assert lib.kq_tone_process(bank, buf.ctypes.data, 0, 0, 16, 16, 1, 0, None, 0, pw.ctypes.data, 8) == -1
-    assert b"powers_stride 8 < ntones + 1 = 9" in lib.kq_last_error()
-    assert lib.kq_tone_process(bank, None, 0, 0, 16, 16, 1, 0, None, 0, None, 0) == -1
-    assert b"null src" in lib.kq_last_error()
-    assert lib.kq_tone_process(bank, None, 0, 0, 0, 0, 0, 0, None, 0, None, 0) == 0        # nothing to do
-    assert lib.kq_tone_process(None, buf.ctypes.data, 0, 0, 16, 16, 1, 0, None, 0, None, 0) == -1
-    assert lib.kq_last_error() == b"kq_tone_process: null bank"
-
-
-def test_without_a_slot_nothing_touches_a_device(lib, bank):
-    """with no slot set, process, counts, clear, sync and reset succeed and touch no device"""
-    buf = np.zeros(1 << 14, np.float32)
-    for n in (1, 1000, 16384):
-        assert lib.kq_tone_process(bank, buf.ctypes.data, 0, 0, n, n, 1, 0, None, 0, None, 0) == 0
-    counts = np.full(8, 7, np.uint32)
-    assert lib.kq_tone_pull_counts(bank, counts.ctypes.data) == 0 and not counts.any()
-    assert lib.kq_tone_clear_events(bank) == 0 and lib.kq_tone_sync(bank) == 0 and lib.kq_tone_reset(bank) == 0
-    ev = np.zeros(1, EVENT_DTYPE)
-    assert lib.kq_tone_pull_event(bank, 0, 0, ev.ctypes.data) == -1
-    assert b"slot 0 has 0 events" in lib.kq_last_error()
-
-
-def test_null_handles_refused(lib):
-    for fn, args in ((lib.kq_tone_destroy, ()), (lib.kq_tone_sync, ()), (lib.kq_tone_reset, ()), (lib.kq_tone_remove, (0,)),
-                     (lib.kq_tone_clear_events, ()), (lib.kq_tone_pull_counts, (None,)), (lib.kq_tone_get_table, (None, 0)),
-                     (lib.kq_tone_get_incs, (None, 0)), (lib.kq_tone_pull_event, (0, 0, None))):
-        assert fn(None, *args) == -1
-        assert b"null bank" in lib.kq_last_error()
 
 
 @pytest.mark.parametrize("plan,Fs", [(sc.DTMF, 8000.0), (sc.DTMF, 48000.0), (sc.ZVEI1, 39062.5), (sc.CCIR, 19200.0)])
