@@ -2202,8 +2202,8 @@ int kq_ale_reset(kq_ale_bank *bank);
  * the sync attempt only: noise and a steady tone take no sync and file nothing in 240 s with the gate held open either, by
  * the phasing sequence and the symbol code alone (tests/test_dsc_model.py).  So a gate that opens on noise costs nothing
  * but the attempts, while one that shuts on a weak signal costs messages.
- * Absent: NAVTEX / SITOR-B (the same modulation and five-place diversity, but the CCIR 476 alphabet, 35 code words that
- * were not at hand and cannot be derived: nothing is built for it); soft decisions and a bit-wise vote between the copies;
+ * NAVTEX / SITOR-B, the other half of the watch (the same modulation and five-place diversity with the CCIR 476 alphabet),
+ * is kq_navtex_*, below.  Absent: soft decisions and a bit-wise vote between the copies;
  * AFC; a per-tone threshold under selective fading; the message semantics beyond itu493.py's three builders.  NOTHING HERE
  * HAS MET A SIGNAL OFF THE AIR.  In the model, with white noise, eight individual calls (23 message symbols each behind a
  * 20-bit dot pattern, each in a run of its own) are filed whole with the check good at both (12000, 12) and (39062.5, 32)
@@ -2311,6 +2311,186 @@ int kq_dsc_get_slot(kq_dsc_bank *bank, unsigned slot, kq_dsc_slot *out);
 int kq_dsc_sync(kq_dsc_bank *bank);
 /* Stream index back to 0; every slot restarts cold with its settings at the next call, as if set again */
 int kq_dsc_reset(kq_dsc_bank *bank);
+
+/* --- NAVTEX / SITOR-B (CCIR 476, ITU-R M.476 / M.625 collective B mode) decoder bank --------------------------------------
+ * Up to 16384 decoder slots, each reading a forward-error-corrected broadcast from one audio row, one event per character:
+ * a receiver bank with a USB channel parked on each of 518, 490 and 4209.5 kHz (and on the HF SITOR-B weather and
+ * navigational broadcasts), and a slot on each, reads every broadcast at once.  A bank's channels can be decoded in place
+ * on its stream after kq_bank_join, and several slots may read one row at different tone pairs.  The host turns the
+ * characters into text and ZCZC .. NNNN messages (ka9q_sdr_amd/ccir476.py).  The reference has no NAVTEX decoder: the
+ * algorithm is defined here.  Everything after the quantiser is exact integer arithmetic, so no result depends on how sums
+ * are ordered or how the stream is cut into calls.
+ * The signal, WRITTEN DOWN FROM MEMORY (no copy of the Recommendations was at hand; ccir476.py says the same).  2-FSK, 100
+ * baud at 1700 +- 85 Hz, state B is 1 and state Y is 0; B is the higher radio frequency, which on a USB channel with the
+ * centre at 1700 Hz makes mark 1785 Hz and space 1615 Hz (kq_dsc_*'s guess, marked as there: the params name both tones,
+ * and the sync attempt takes the complement of the register as well).  A character is seven bits of which exactly four
+ * are B: the 35 words of that kind are the alphabet (26 letters, CR, LF, LTRS, FIGS, SPACE, BLANK and the three service
+ * signals alpha = BBBBYYY = 0x78, beta = BBYYBBY = 0x66, rep = YBBYYBB = 0x33, the first bit sent in bit 6), and any single
+ * wrong bit is seen.  The bit stream is a sequence of seven-bit places, alternately DX and RX; character i goes out in DX
+ * place 2 i and again in RX place 2 i + 5, 35 bits (350 ms) later.  While phasing -- before a message, between messages,
+ * after the last -- the DX places carry rep and the RX places alpha, and so do the places a copy has not reached yet.
+ * VERIFIED by tests/test_ccir476.py: that ccir476.py's table uses each of the C(7,4) = 35 words exactly once; and that for
+ * the 25 ITA2 combinations with two, three or four marks (the letters other than E and T, and FIGS) bits 2..6 of the word,
+ * in sending order, are the ITA2 code in sending order, held against baudot.LETTERS, a table of another origin.  FROM
+ * MEMORY ALONE: which of the ten words left over is which of E, T, SPACE, CR, LF, LTRS, BLANK, alpha, beta and rep (the
+ * device knows three of them by name: alpha, beta, rep); the international figures case of ccir476.py; the place
+ * arithmetic above; which audio tone is B on each sideband.  NOTHING HERE HAS MET A SIGNAL OFF THE AIR.
+ * Per slot, x[n] is its input row; n counts samples since create or kq_navtex_reset on a grid shared by every slot, and
+ * x[n] = 0 before the slot was set.  Fs = samprate, B = block_len (8..256); frame k is the samples [k B, (k + 1) B).
+ *   quantise, table, correlate, window, state (but the register and what is named below), step with its early, centre and
+ *   late points, and at the late point
+ *     1 timing, 2 levels   kq_dsc_*'s, to the letter (above): q[n], C[j], inc_m, inc_s, tb = rint(256 Fs / (B baud)) within
+ *                 2048..8192, W, Pm, Ps, hi, lo, the three-point clock with adj and the centre watch, sig, nse and open.
+ *     3 register  r = (r << 1 | bit) mod 2^128, kept as r_hi and r_lo, the latest bit in bit 0 of r_lo; nbits += 1 (mod
+ *                 2^32): shifted whether in sync or not.  A seven-bit word w (its first bit sent in bit 6) is a character
+ *                 if popcount(w) == 4.
+ *     4 sync      while not synced, and only if open: the attempt on x = r, and if that fails on x = ~r (then inverted = 1,
+ *                 else 0).  On each x, first the phasing signals, and only if they fail the running traffic.
+ *                   phasing   c0 = x & 127, c1 = x >> 7 & 127, c2 = x >> 14 & 127, c3 = x >> 21 & 127, the last four places,
+ *                             c0 the latest.  as_rx = (c0 is alpha) + (c1 is rep) + (c2 is alpha) + (c3 is rep); as_dx =
+ *                             (c0 is rep) + (c1 is alpha) + (c2 is rep) + (c3 is alpha).  If as_rx >= acq the latest place
+ *                             is RX, kind = 1; else if as_dx >= acq it is DX, kind = 0.  Then syncs += 1.  A place equals
+ *                             one word at the most, so as_rx + as_dx <= 4 and with acq >= 3 only one of them passes.  The
+ *                             phasing stream repeats after 14 bits and after no fewer; its places two apart are equal (c0 =
+ *                             c2, c1 = c3).  At an alignment that is off by 1..6 or 8..13 bits the 14 bits read differ
+ *                             from both orders of (alpha, rep), so c0 or c1 is wrong, and with it c2 or c3: two matches at
+ *                             the most, below either value of acq.  Seven bits off is the other kind of place, not an
+ *                             error.  So sync on clean phasing is taken at the right bit and with the right kind or not
+ *                             at all; acq = 3 allows one place of four to be damaged.
+ *                   traffic   pair j = 0 .. pairs - 1 has its RX copy in bits 14 j + 6 .. 14 j of x and its DX copy in bits
+ *                             14 j + 41 .. 14 j + 35 (pairs <= 6: 111 is the highest bit read).  Sync is taken if in every
+ *                             one of these pairs the two words are equal, are a character, and are none of alpha, beta
+ *                             and rep, and if the pairs do not all hold the same character: a run of one character (a line
+ *                             of =, a row of spaces) reads alike with the places' kinds exchanged, and a tracker that
+ *                             took the wrong kind would deliver valid-looking wrong text.  Then the latest place is RX,
+ *                             kind = 1, and tsyncs += 1.  The characters that served for the sync are not filed: a receiver
+ *                             that joins in mid-message reads from the character behind them on.  Noise passes about (35
+ *                             / 128 * 1 / 128)^pairs of the attempts, 2e-11 at pairs = 4 (240 s of noise and of a steady
+ *                             tone with the gate held open take no sync of either kind in the model).  Traffic at a
+ *                             WRONG BIT passes far more often: the copies are 35 bits apart at every bit, so one bit off
+ *                             a place six bits of both windows are the same character's still and the seventh agrees by
+ *                             chance, about one attempt in four per pair.  Of the late joins in the model (random text,
+ *                             every alignment) 2 of 560 took sync at a wrong bit at pairs = 4, none at 6.  Such a sync
+ *                             files garbage, much of it unflagged, and chance pairs keep it alive; it ends for certain
+ *                             `lose` RX places into the next phasing, which read out of step holds no clean pair.  A
+ *                             receiver that must not print garbage sets pairs = 6.
+ *                 On either: synced = 1, bitpos = 0, run = 0.  The step ends here.
+ *     5 characters  while synced (the gate no longer matters, for kq_dsc_*'s reason): bitpos += 1, and at bitpos == 7: bitpos
+ *                 = 0, kind ^= 1, and if kind is now 1 the latest place is an RX place.  With x = ~r if inverted, else r: dx
+ *                 = x >> 35 & 127, rx = x & 127.
+ *                   run     = 0 if (dx is rep and rx is alpha) or (dx and rx are characters and dx == rx); else run += 1.
+ *                   idle    if dx is rep or rx is alpha: idles += 1, nothing is filed.
+ *                   else    if dx is a character: code = dx, flags bit 2 if rx is a character and rx != dx; else if rx is
+ *                           a character: code = rx, flags bit 1; else code = 0x7F, flags bit 0.  Flags bit 3 if inverted.
+ *                           The event is filed.
+ *                   then    if run >= lose: synced = 0, losses += 1.
+ *                 So sync is held as long as one RX place in `lose` shows a clean pair.  `lose` RX places in a row at which
+ *                 one copy alone or neither was good drop it -- a fade of one side alone included, although every
+ *                 character of it was read -- and so does a transmission's end, behind which up to `lose` characters of
+ *                 garbage (from the RX copy or unresolved in the main) are filed.  This tail is not hidden.
+ *   event      code (the word taken, or 0x7F), flags (bit 0 unresolved, bit 1 taken from the RX copy, bit 2 the copies are
+ *              two different characters and DX was taken, bit 3 the stream is inverted), dx, rx (the two words as read,
+ *              of x), end_sample = (k + 1) B of the late point that read the last bit, sig and nse there.  events += 1 for
+ *              each; it goes to the slot's arena, or dropped += 1 when that holds max_events.  frames, events, dropped,
+ *              syncs, tsyncs, losses and idles saturate at 2^32 - 1.
+ * kq_navtex_remove and kq_navtex_reset discard the sync.  Carried between calls: as kq_dsc_*, and all of the state above; so
+ * the same stream split differently into calls or blocks gives the same events and status.  kq_navtex_status holds all of
+ * it but the past frames.
+ * Limits (refused by kq_navtex_create / kq_navtex_set with the reason in kq_last_error, before any HIP call): kq_dsc_*'s for
+ * the fields they share, and acq 3..4, pairs 3..6, lose 1..255.
+ * Device memory per slot: 40 max_events of arena, about 700 bytes of state, history and parameters; 2 KiB of table per
+ * bank.  At 100 baud an arena of max_events holds max_events / 7.1 seconds of traffic between kq_navtex_clear_events calls.
+ * In the model, with white noise, a message of 67 characters behind 20 phasing pairs, four runs (268 characters) at
+ * (12000, 12) and at (39062.5, 32): at an Es/N0 (a tone's power times the bit over N0) of 20 and 14 dB every character is
+ * read with no flag; at 12 dB none is wrong and 3 and 0 are flagged; at 10 dB 0 and 1 wrong, 8 and 12 flagged; at 8 dB 5 and
+ * 10 wrong, 42 and 38 flagged; at 6 dB 58 and 112 wrong.  Measured on the integer model on a CPU
+ * (tests/test_navtex_model.py prints the figures, and asserts 20 dB alone); the kernel equals it bit for bit.
+ * Absent, beside what kq_dsc_* lacks: the mode-A (ARQ) half of SITOR; a confirmation of the traffic sync (see step 4); a
+ * vote that weighs the copies by level; the message store that suppresses a serial number already received (a host's
+ * business).
+ * Calls: as kq_dsc_*.  kq_navtex_create, kq_navtex_set and kq_navtex_remove touch no device. */
+typedef struct kq_navtex_bank kq_navtex_bank;
+typedef struct kq_navtex_config {
+  int device;
+  double samprate;           /* Fs: input samples per second; a double, so that 39 062.5 is exact */
+  unsigned block_len;        /* B: samples per frame, 8..256 */
+  unsigned warm;             /* frames after the set in which no sync is sought while the levels train (64) */
+  unsigned snr;              /* least sig / nse for a sync attempt, in sixteenths (64) */
+  uint64_t min_p;            /* least sig (65536) */
+  float input_scale;         /* 32767 suits audio of full scale 1 */
+  unsigned max_slots;        /* slots 0 .. max_slots - 1 (limit 16384) */
+  unsigned max_events;       /* arena places per slot between kq_navtex_clear_events calls */
+  size_t max_samples;        /* largest nblocks * block_len of one kq_navtex_process call */
+  void *stream;              /* hipStream_t, NULL = own stream; kq_bank_stream(bank) puts it beside a receiver bank */
+  unsigned acq;              /* of the last four places, those that must be phasing signals to take sync, 3..4 (4) */
+  unsigned pairs;            /* pairs of equal copies that take sync in running traffic, 3..6 (4) */
+  unsigned lose;             /* RX places in a row without a clean pair that drop sync, 1..255 (16) */
+} kq_navtex_config;
+typedef struct kq_navtex_params {
+  unsigned source;           /* input row this slot decodes (a receiver bank's channel index) */
+  float mark, space;         /* Hz: state B (1) and state Y (0); 1785 and 1615 are a guess for a USB channel, see above */
+  float baud;                /* 100 */
+} kq_navtex_params;
+typedef struct kq_navtex_status {
+  uint32_t frames;           /* completed since the slot was set */
+  uint32_t ph;               /* the point taken next: 0 early, 1 centre, 2 late */
+  int32_t t;                 /* 1/256 frame to that point */
+  uint32_t bit;              /* at the last centre */
+  uint32_t nbits;            /* bits read since the set */
+  uint32_t synced;
+  uint32_t bitpos;           /* bits of the place behind the last whole one, 0..6, while synced */
+  uint32_t kind;             /* of the last whole place: 1 RX, 0 DX */
+  uint32_t inverted;         /* sync was taken on the complement of the register */
+  uint32_t run;              /* RX places in a row without a clean pair */
+  uint32_t events;           /* filed since the set, those dropped included */
+  uint32_t dropped;
+  uint32_t syncs;            /* times sync was taken on the phasing signals */
+  uint32_t tsyncs;           /* and on running traffic */
+  uint32_t losses;           /* times sync was dropped */
+  uint32_t idles;            /* RX places that were phasing */
+  uint64_t sig, nse;         /* the larger and the smaller power at the bits' centres */
+  uint64_t ee, el, ec;       /* the smoothed early, late and centre power */
+  uint64_t pe, hi, lo;       /* hi at the last early point; hi and lo at the last centre */
+  uint64_t r_hi, r_lo;       /* the last 128 bits, the latest in bit 0 of r_lo */
+  int32_t sum[2][2];         /* SI, SQ of mark and of space at the last completed frame */
+  int64_t acc[2][2];         /* I and Q of the open frame, mark and space */
+} kq_navtex_status;
+typedef struct kq_navtex_event {
+  uint32_t code;             /* the seven-bit word taken, the first bit sent in bit 6; 0x7F where unresolved */
+  uint32_t flags;            /* bit 0: unresolved; 1: from the RX copy; 2: the copies differ; 3: inverted */
+  uint32_t dx, rx;           /* the two words as read */
+  uint64_t end_sample;       /* the end of the frame that read the character's last bit */
+  uint64_t sig, nse;         /* at that bit */
+} kq_navtex_event;
+typedef struct kq_navtex_slot {
+  uint32_t inc_m, inc_s;     /* the phase increments of mark and space */
+  uint32_t tb;               /* the bit in 1/256 frame */
+  uint32_t W;                /* the window in frames */
+} kq_navtex_slot;
+
+kq_navtex_bank *kq_navtex_create(const kq_navtex_config *cfg);
+int kq_navtex_destroy(kq_navtex_bank *bank);
+/* Put a decoder in `slot` (or replace the one there): a cold start at the next call's first sample, its arena empty.
+ * Touches no device, as kq_dsc_set */
+int kq_navtex_set(kq_navtex_bank *bank, unsigned slot, const kq_navtex_params *params);
+/* The slot stops from the next call; its arena stays readable.  Touches no device either */
+int kq_navtex_remove(kq_navtex_bank *bank, unsigned slot);
+/* Input, status and on_device as in kq_dsc_process (status may be NULL; nothing is written for an empty slot). */
+int kq_navtex_process(kq_navtex_bank *bank, const void *src, int format, size_t src_stride, size_t row_stride,
+                      unsigned block_len, unsigned nblocks, int on_device, kq_navtex_status *status, size_t status_stride);
+/* Events in every slot's arena, counts[max_slots], in one copy; synchronous */
+int kq_navtex_pull_counts(kq_navtex_bank *bank, uint32_t *counts);
+/* Copies event `index` of `slot`; returns 0, or -1 */
+int kq_navtex_pull_event(kq_navtex_bank *bank, unsigned slot, unsigned index, kq_navtex_event *event);
+/* Empties every arena (on the handle's stream); the status counters, the register and the sync go on */
+int kq_navtex_clear_events(kq_navtex_bank *bank);
+/* C (at most cap words); returns 1024 */
+int kq_navtex_get_table(const kq_navtex_bank *bank, int16_t *dst, size_t cap);
+/* inc_m, inc_s, tb and W of `slot`, without a device; -1 when the slot holds no decoder */
+int kq_navtex_get_slot(kq_navtex_bank *bank, unsigned slot, kq_navtex_slot *out);
+int kq_navtex_sync(kq_navtex_bank *bank);
+/* Stream index back to 0; every slot restarts cold with its settings at the next call, as if set again */
+int kq_navtex_reset(kq_navtex_bank *bank);
 
 /* --- rational resampler bank ----------------------------------------------------------------------------------------------
  * Up to 65536 slots, each one row of PCM (mono or stereo) resampled from Fi = in_rate_num / in_rate_den Hz (a receiver
