@@ -2492,6 +2492,166 @@ int kq_navtex_sync(kq_navtex_bank *bank);
 /* Stream index back to 0; every slot restarts cold with its settings at the next call, as if set again */
 int kq_navtex_reset(kq_navtex_bank *bank);
 
+/* --- EAS / SAME (Specific Area Message Encoding; 47 CFR 11.31, NWS Instruction 10-1712) decoder bank -----------------------
+ * Up to 16384 decoder slots, each reading the alert headers of one audio row, one event per burst start, per byte of the
+ * header and per burst end: a receiver bank or kq_wfm_* that holds thousands of broadcast and weather-radio channels, and a
+ * slot on each, says which station relayed which alert and when.  A bank's channels can be decoded in place on its stream
+ * after kq_bank_join, and several slots may read one row.  The host votes two of three over the repeats and parses the text
+ * (ka9q_sdr_amd/eas.py).  The reference has no SAME decoder: the algorithm is defined here.  Everything after the quantiser
+ * is exact integer arithmetic, so no result depends on how sums are ordered or how the stream is cut into calls.
+ * The signal, WRITTEN DOWN FROM MEMORY (no copy of the rule or of the Instruction was at hand; eas.py says the same).  AFSK
+ * at 520.83 bit/s (a bit is 1.92 ms): mark (1) is 2083.3 Hz, four cycles to a bit, space (0) is 1562.5 Hz, three.  Bytes of
+ * eight bits, the least significant bit sent first, bit 7 always 0, no start, stop or parity bit.  A burst is 16 bytes of
+ * preamble 0xAB and then the header, ZCZC-ORG-EEE-PSSCCC[-PSSCCC...]+TTTT-JJJHHMM-LLLLLLLL- (1 to 31 location codes, 252
+ * bytes at the most), or the end of message, NNNN.  Each is sent three times, one second apart; between the headers and
+ * the ends of message stand the attention signal (853 + 960 Hz on broadcast stations, 1050 Hz on weather radio) and the
+ * voice message.  There is no checksum: the protection is the threefold repeat, and a receiver votes two of three bit by
+ * bit.  FROM MEMORY, all of it: the tone frequencies, the preamble byte and its count, the bit order, the grammar and the
+ * names of the fields and event codes in eas.py.  NOTHING HERE HAS MET A SIGNAL OFF THE AIR.
+ * Per slot, x[n] is its input row; n counts samples since create or kq_same_reset on a grid shared by every slot, and
+ * x[n] = 0 before the slot was set.  Fs = samprate, B = block_len (8..256); frame k is the samples [k B, (k + 1) B).
+ *   quantise, table, correlate, window, state (but the register and what is named below), step with its early, centre and
+ *   late points, and at the late point
+ *     1 timing, 2 levels   kq_dsc_*'s, to the letter (above): q[n], C[j], inc_m, inc_s, tb = rint(256 Fs / (B baud)) within
+ *                 2048..8192, W, Pm, Ps, hi, lo, the three-point clock with adj and the centre watch, sig, nse and open.
+ *     3 register  r = (r << 1 | bit) mod 2^64, the latest bit in bit 0: shifted whether in sync or not.  The byte
+ *                 whose last bit has just arrived is rev8(r & 255), the eight bits turned end for end.
+ *     4 sync      while not synced, and only if open.  PH and PE are the 48 bits of the bytes AB AB 'Z' 'C' 'Z' 'C' and AB AB
+ *                 'N' 'N' 'N' 'N' in sending order, the first sent highest, each byte turned end for end: 0xD5D55AC25AC2
+ *                 and 0xD5D572727272.  dh = popcount((r ^ PH) & (2^48 - 1)), de likewise of PE.
+ *                   header    if dh <= sync_errs: synced = 1, bitpos = nbytes = bad_run = plus = dashes = 0, syncs += 1,
+ *                             sync_sample = (k + 1) B, and a START event (flags bit 0) with code 'Z' and errs = dh.
+ *                   end       else if de <= sync_errs: eoms += 1, sync_sample = (k + 1) B, a START event with code 'N' and
+ *                             errs = de; no sync is entered, since nothing follows NNNN.
+ *                 Noise passes (1 + 48 + 1128) 2 / 2^48 = 8e-12 of the attempts at sync_errs = 2.  The complement is not
+ *                 tried: FM and AM audio do not exchange the tones, and a user on the other sideband exchanges mark and
+ *                 space.  The step ends here.
+ *     5 text      while synced (the gate no longer matters, for kq_dsc_*'s reason): bitpos += 1, and at bitpos == 8: bitpos
+ *                 = 0, b = rev8(r & 255).
+ *                   good    0x20 <= b <= 0x7E: an event with code b, flags 0, index = nbytes; bad_run = 0; '+' sets plus =
+ *                           1; '-' with plus set counts dashes += 1.
+ *                   bad     else: the event is filed all the same with flags bit 1, so that the host's vote has its bits;
+ *                           bad_run += 1.
+ *                   then    nbytes += 1, and the burst ends at the first of: 1 complete, dashes == 3, the grammar's own
+ *                           end (complete += 1); 2 lost, bad_run == lose (lost += 1); 3 length, nbytes == max_len
+ *                           (truncated += 1).  An END event (flags bit 2) carries the reason in code and nbytes in
+ *                           index, and synced = 0.
+ *                 index counts the bytes behind ZCZC, so the first '-' has index 0 and the whole text is "ZCZC" and the
+ *                 bytes filed.  A '+' that is read wrong leaves the burst to end by 2 or 3, with garbage behind the
+ *                 header's end; the vote over the three bursts mends the text and cuts it at the grammar's end
+ *                 (eas.vote, eas.clip).
+ *   event      code, flags (bit 0 START, bit 1 BAD, bit 2 END), index, errs (of a START; else 0), end_sample = (k + 1) B of
+ *              the late point that read the last bit, sig and nse there.  events += 1 for each; it goes to the slot's
+ *              arena, or dropped += 1 when that holds max_events.  frames, events, dropped, syncs, eoms, complete, lost
+ *              and truncated saturate at 2^32 - 1.  An alert is at most about 3 * 250 + 9 events.
+ * kq_same_remove and kq_same_reset discard the sync.  Carried between calls: as kq_dsc_*, and all of the state above; so the
+ * same stream split differently into calls or blocks gives the same events and status.  kq_same_status holds all of it but
+ * the past frames.
+ * Limits (refused by kq_same_create / kq_same_set with the reason in kq_last_error, before any HIP call): kq_dsc_*'s for the
+ * fields they share, and sync_errs 0..4, lose 1..15, max_len 8..248.  A bit wants 8 to 32 frames of at least 8 samples, so
+ * Fs >= 33.4 kHz: B = 8..11 at 48 kHz, B = 8..9 at 39 062.5 Hz, B = 8..23 at 96 kHz.  A row at 12 or 24 kHz goes through
+ * kq_rsmp_* first, as VHF DSC does.
+ * Device memory per slot: 40 max_events of arena, about 700 bytes of state, history and parameters; 2 KiB of table per
+ * bank.
+ * In the model, with white noise, four alerts of three headers of 42 bytes and three ends of message each, at (48000, 8),
+ * (48000, 11) and (39062.5, 8): at an Es/N0 (a tone's power times the bit over N0) of 20, 16 and 14 dB all 12 headers are
+ * read with no wrong byte at every geometry; at 12 dB 11, 10 and 12 of them, at 10 dB 4, 4 and 3, at 8 dB none.  The vote of
+ * two of three gives the text sent in 4 of 4 alerts down to 12 dB, in 4, 4 and 3 at 10 dB, in 1, 1 and 2 at 8 dB, in none at
+ * 6 dB; all 12 ends of message are seen down to 10 dB.  So 14 dB is the lowest level at which every burst came clean.  A
+ * sender's clock 100, 1000 and 5000 ppm fast or slow (bits, tones and pauses alike) loses nothing: three of three headers
+ * clean and three ends of message at every geometry; 5000 ppm is the largest offset tried, not a limit found.  Measured on
+ * the integer model on a CPU (tests/test_same_model.py prints the figures and asserts none of them: the assertions rest
+ * on the noise-free cases); the kernel equals the model bit for bit.  60 s of white noise and 60 s of a steady mark tone
+ * with the gate forced open (snr 16, min_p 0) file nothing.
+ * Absent: the attention signal (two tones or one: kq_tone_*'s business); the vote and the parse on the device (a host's
+ * business: eas.py); soft decisions; AFC (the tones are fixed by rule); a confirmation of the sync beyond the 48 bits.
+ * Calls: as kq_dsc_*.  kq_same_create, kq_same_set and kq_same_remove touch no device. */
+typedef struct kq_same_bank kq_same_bank;
+typedef struct kq_same_config {
+  int device;
+  double samprate;           /* Fs: input samples per second; a double, so that 39 062.5 is exact */
+  unsigned block_len;        /* B: samples per frame, 8..256 */
+  unsigned warm;             /* frames after the set in which no sync is sought while the levels train (64) */
+  unsigned snr;              /* least sig / nse for a sync attempt, in sixteenths (64) */
+  uint64_t min_p;            /* least sig (65536) */
+  float input_scale;         /* 32767 suits audio of full scale 1 */
+  unsigned max_slots;        /* slots 0 .. max_slots - 1 (limit 16384) */
+  unsigned max_events;       /* arena places per slot between kq_same_clear_events calls */
+  size_t max_samples;        /* largest nblocks * block_len of one kq_same_process call */
+  void *stream;              /* hipStream_t, NULL = own stream; kq_bank_stream(bank) puts it beside a receiver bank */
+  unsigned sync_errs;        /* wrong bits allowed in the 48 that take sync, 0..4 (2) */
+  unsigned lose;             /* bad bytes in a row that end a burst, 1..15 (3) */
+  unsigned max_len;          /* bytes behind ZCZC at which a burst ends at the latest, 8..248 (248) */
+} kq_same_config;
+typedef struct kq_same_params {
+  unsigned source;           /* input row this slot decodes (a receiver bank's channel index) */
+  float mark, space;         /* Hz: 1 and 0; 2083.3333 and 1562.5 */
+  float baud;                /* 520.8333 */
+} kq_same_params;
+typedef struct kq_same_status {
+  uint32_t frames;           /* completed since the slot was set */
+  uint32_t ph;               /* the point taken next: 0 early, 1 centre, 2 late */
+  int32_t t;                 /* 1/256 frame to that point */
+  uint32_t bit;              /* at the last centre */
+  uint32_t synced;
+  uint32_t bitpos;           /* bits of the byte behind the last whole one, 0..7, while synced */
+  uint32_t nbytes;           /* bytes of the burst behind ZCZC */
+  uint32_t bad_run;          /* bad bytes in a row */
+  uint32_t plus;             /* the burst's '+' was seen */
+  uint32_t dashes;           /* '-' behind it */
+  uint32_t events;           /* filed since the set, those dropped included */
+  uint32_t dropped;
+  uint32_t syncs;            /* headers begun */
+  uint32_t eoms;             /* ends of message seen */
+  uint32_t complete;         /* bursts ended by the third dash behind the '+' */
+  uint32_t lost;             /* by `lose` bad bytes in a row */
+  uint32_t truncated;        /* by max_len */
+  uint64_t sync_sample;      /* end_sample of the last START event */
+  uint64_t sig, nse;         /* the larger and the smaller power at the bits' centres */
+  uint64_t ee, el, ec;       /* the smoothed early, late and centre power */
+  uint64_t pe, hi, lo;       /* hi at the last early point; hi and lo at the last centre */
+  uint64_t r;                /* the last 64 bits, the latest in bit 0 */
+  int32_t sum[2][2];         /* SI, SQ of mark and of space at the last completed frame */
+  int64_t acc[2][2];         /* I and Q of the open frame, mark and space */
+} kq_same_status;
+typedef struct kq_same_event {
+  uint32_t code;             /* START: 'Z' or 'N'; a byte as read; END: 1 complete, 2 lost, 3 length */
+  uint32_t flags;            /* bit 0: START; 1: BAD (outside 0x20..0x7E); 2: END */
+  uint32_t index;            /* of the byte behind ZCZC; END: the bytes read; START: 0 */
+  uint32_t errs;             /* START: wrong bits among the 48; else 0 */
+  uint64_t end_sample;       /* the end of the frame that read the last bit */
+  uint64_t sig, nse;         /* at that bit */
+} kq_same_event;
+typedef struct kq_same_slot {
+  uint32_t inc_m, inc_s;     /* the phase increments of mark and space */
+  uint32_t tb;               /* the bit in 1/256 frame */
+  uint32_t W;                /* the window in frames */
+} kq_same_slot;
+
+kq_same_bank *kq_same_create(const kq_same_config *cfg);
+int kq_same_destroy(kq_same_bank *bank);
+/* Put a decoder in `slot` (or replace the one there): a cold start at the next call's first sample, its arena empty.
+ * Touches no device, as kq_dsc_set */
+int kq_same_set(kq_same_bank *bank, unsigned slot, const kq_same_params *params);
+/* The slot stops from the next call; its arena stays readable.  Touches no device either */
+int kq_same_remove(kq_same_bank *bank, unsigned slot);
+/* Input, status and on_device as in kq_dsc_process (status may be NULL; nothing is written for an empty slot). */
+int kq_same_process(kq_same_bank *bank, const void *src, int format, size_t src_stride, size_t row_stride,
+                    unsigned block_len, unsigned nblocks, int on_device, kq_same_status *status, size_t status_stride);
+/* Events in every slot's arena, counts[max_slots], in one copy; synchronous */
+int kq_same_pull_counts(kq_same_bank *bank, uint32_t *counts);
+/* Copies event `index` of `slot`; returns 0, or -1 */
+int kq_same_pull_event(kq_same_bank *bank, unsigned slot, unsigned index, kq_same_event *event);
+/* Empties every arena (on the handle's stream); the status counters, the register and the sync go on */
+int kq_same_clear_events(kq_same_bank *bank);
+/* C (at most cap words); returns 1024 */
+int kq_same_get_table(const kq_same_bank *bank, int16_t *dst, size_t cap);
+/* inc_m, inc_s, tb and W of `slot`, without a device; -1 when the slot holds no decoder */
+int kq_same_get_slot(kq_same_bank *bank, unsigned slot, kq_same_slot *out);
+int kq_same_sync(kq_same_bank *bank);
+/* Stream index back to 0; every slot restarts cold with its settings at the next call, as if set again */
+int kq_same_reset(kq_same_bank *bank);
+
 /* --- rational resampler bank ----------------------------------------------------------------------------------------------
  * Up to 65536 slots, each one row of PCM (mono or stereo) resampled from Fi = in_rate_num / in_rate_den Hz (a receiver
  * bank's samprate and decimate, so 39 062.5 Hz is exact) to Fo = out_rate Hz: kq_afsk_*, RTP PCM and the players are 48 kHz,

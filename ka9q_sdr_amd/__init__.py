@@ -56,5 +56,7 @@ from .dsc import DscBank, DscParams, dsc_params  # noqa: F401,E402  (dsc.STATUS_
 from . import itu493  # noqa: F401,E402
 from .navtex import NavtexBank, NavtexParams, navtex_params  # noqa: F401,E402  (navtex.STATUS_DTYPE: the NAVTEX decoder's)
 from . import ccir476  # noqa: F401,E402
+from .same import SameBank, SameParams, same_params  # noqa: F401,E402  (same.STATUS_DTYPE: the SAME decoder's)
+from . import eas  # noqa: F401,E402
 from .monitor import KQ_MON_F32, KQ_MON_S16BE, MonBank, MonParams, mon_params  # noqa: F401,E402  (monitor.STATUS_DTYPE: the mixer's)
 from .resample import RsmpBank, RsmpParams, rsmp_params  # noqa: F401,E402

@@ -1,7 +1,7 @@
 """What the Python mirrors of the PCM decoder banks share (tone.py, cw.py, rtty.py, psk.py, acars.py, ale.py, dsc.py,
-navtex.py, fsk.py, pag.py; include/ka9q_hip.h: kq_tone_*, kq_cw_*, kq_rtty_*, kq_psk_*, kq_acars_*, kq_ale_*, kq_dsc_*,
-kq_navtex_*, kq_fsk_*, kq_pag_*): the ctypes binding of the entry points they all have, and the methods that differ only in the C prefix.  A
-module keeps its structures, dtypes and constants, its __init__ and the getters that are its own.
+navtex.py, same.py, fsk.py, pag.py; include/ka9q_hip.h: kq_tone_*, kq_cw_*, kq_rtty_*, kq_psk_*, kq_acars_*, kq_ale_*,
+kq_dsc_*, kq_navtex_*, kq_same_*, kq_fsk_*, kq_pag_*): the ctypes binding of the entry points they all have, and the methods
+that differ only in the C prefix.  A module keeps its structures, dtypes and constants, its __init__ and the getters that are its own.
 """
 import ctypes as C
 
