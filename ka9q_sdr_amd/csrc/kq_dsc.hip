@@ -12,13 +12,13 @@
 // kq_dsc_status record, the reduced sums of the last 31 frames, and the arena of events; per bank the table.  The signal
 // format is written down from memory (the header says what is and what is not verified).
 //
-// k_dsc   a frame-grid kernel with a window and a symbol clock (kq_tonecorr.hpp describes the mapping): two tones, four
-//         series, as k_rtty.  Lane f sums its own W entries per series and squares, and lane 0 walks the piece's (Pm, Ps)
-//         pairs in order through the clock: it reads LDS at the points only.  The symbol code is a popcount and a bit
-//         reversal, so the tracker has no table.  The record's tail, the open message (kq_dsc_message: 64 bytes written at a
-//         running index, and the counts beside them that change once in ten bits), goes from the device's memory to LDS and
-//         back by the wave's first lanes and never through lane 0's registers: there the index would put it in scratch, and
-//         its 30 words beside the 40 of the head would cost the fourth workgroup of a CU.
+// k_dsc   the tracker above the bit, and the name of its instance of bc::bit_clock (kq_bitclock.hpp: the frame-grid kernel
+//         with a window and a bit clock, two tones, four series, as k_rtty; lane 0 walks the piece's (Pm, Ps) pairs in order
+//         through the clock).  The symbol code is a popcount and a bit reversal, so the tracker has no table.  The record's
+//         tail, the open message (kq_dsc_message: 64 bytes written at a running index, and the counts beside them that
+//         change once in ten bits), goes from the device's memory to LDS and back by the wave's first lanes and never
+//         through lane 0's registers: there the index would put it in scratch, and its 30 words beside the 40 of the head
+//         would cost the fourth workgroup of a CU.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstddef>
@@ -26,21 +26,15 @@
 #include <mutex>
 
 #include "ka9q_hip.h"
-#include "kq_tonecorr.hpp"
+#include "kq_bitclock.hpp"
 
 namespace tc = kq::tonecorr;
+namespace bc = kq::bitclock;
 
 namespace {
 
-using tc::kHist;
-using tc::kTable;
 using tc::sat_inc;
-using tc::smooth;
 constexpr unsigned kMaxSlots = 16384;
-constexpr int kThreads = 256, kWaves = kThreads / 64;
-constexpr int kTile = 3200;                     // samples a wave keeps in LDS: 64 frames of B = 48 at stride 50; with the rest
-                                                // the workgroup stays under 40 KiB, four workgroups to a CU
-constexpr int kRow = kHist + 64 + 1;            // a wave's reduced sums of one kind: the history and a piece's frames
 constexpr int kMsg = 64;                        // symbols to a message at the most
 constexpr unsigned kW125 = 0x2F9;               // symbol 125 as sent: 1011111001
 constexpr unsigned kCheck = 1, kTruncated = 2, kLost = 4, kInverted = 8;
@@ -52,24 +46,27 @@ struct DscGeom {
   int max_events;
 };
 
-struct DscPar {  // per slot, written by the host when a call finds the slot set anew
-  int active;
-  unsigned source;
-  unsigned inc_m, inc_s;
-  int tb, W;
-};
-
-struct DscKind {
+// the bank's types for tc::GridBank, and its tracker for bc::bit_clock
+struct k_dsc {
   using Config = kq_dsc_config;
   using Geom = DscGeom;
-  using Par = DscPar;
+  using Par = tc::PairPar;
   using Status = kq_dsc_status;
   using Event = kq_dsc_event;
   using Hist = tc::FrameHist<4>;  // a, b of mark, a, b of space
   using Tables = tc::NoTables;
   static constexpr bool kZeroCold = true;
+  using Side = kq_dsc_message;    // the record's tail, the open message
+  static constexpr bool kParks = false;
+
+  template <class Args, class Place>
+  static __device__ kq_dsc_event *load(Args const &c, Place const &w, kq_dsc_status &s, Side (&side)[bc::kWaves], unsigned &nev);
+  template <class Args, class Place>
+  static __device__ void store(Args const &c, Place const &w, kq_dsc_status const &s, Side (&side)[bc::kWaves], unsigned nev);
+  static __device__ void bit_step(DscGeom const &g, Par const &par, kq_dsc_status &s, kq_dsc_message &m, unsigned long long pl,
+                                  unsigned long long k, kq_dsc_event *ev, unsigned &nev);
 };
-using CallArgs = tc::GridBank<DscKind>::Args;
+using CallArgs = tc::GridBank<k_dsc>::Args;
 
 // the symbol code: a ten-bit word, its first bit sent in bit 9
 __device__ __forceinline__ bool is_symbol(unsigned w) { return 7u - (unsigned)__popc(w >> 3) == (w & 7u); }
@@ -110,18 +107,13 @@ __device__ __forceinline__ void file(DscGeom const &g, kq_dsc_status &s, kq_dsc_
   r.nse = s.nse;
 }
 
+constexpr int kHead = (int)offsetof(kq_dsc_status, open), kOpenWords = (int)sizeof(kq_dsc_message) / 4;
+static_assert(kHead % 8 == 0 && sizeof(kq_dsc_message) % 8 == 0 && kOpenWords <= 64, "the record's head and its tail");
+
 // the header's steps 1 to 5: the late point of a bit at frame k, with the late power pl; m: the open message, in LDS
-__device__ __forceinline__ void bit_step(DscGeom const &g, DscPar const &par, kq_dsc_status &s, kq_dsc_message &m,
+__device__ __forceinline__ void k_dsc::bit_step(DscGeom const &g, tc::PairPar const &par, kq_dsc_status &s, kq_dsc_message &m,
                                          unsigned long long pl, unsigned long long k, kq_dsc_event *ev, unsigned &nev) {
-  // 1 timing
-  tc::clock_adjust(s, par.tb, pl);
-  smooth(s.ec, s.hi, 3);
-  unsigned long long const top = s.ee > s.el ? s.ee : s.el, low = s.ee > s.el ? s.el : s.ee;
-  if (top - low <= (top >> 3) && s.ec + (top >> 3) < low) s.t += par.tb >> 5;  // (adj == 0) half a bit out: no slope there
-  // 2 levels and gate
-  smooth(s.sig, s.hi, 4);
-  smooth(s.nse, s.lo, 4);
-  bool const open = s.frames >= g.warm && s.sig >= g.min_p && tc::gate16(s.sig, s.nse, g.snr);
+  bool const open = tc::bit_levels(g, par, s, pl);  // 1 timing, 2 levels and gate
   // 3 register
   s.r = s.r << 1 | (unsigned long long)s.bit;
   s.nbits += 1;
@@ -192,14 +184,12 @@ __device__ __forceinline__ void bit_step(DscGeom const &g, DscPar const &par, kq
   }
 }
 
-constexpr int kHead = (int)offsetof(kq_dsc_status, open), kOpenWords = (int)sizeof(kq_dsc_message) / 4;
-static_assert(kHead % 8 == 0 && sizeof(kq_dsc_message) % 8 == 0 && kOpenWords <= 64, "the record's head and its tail");
-
 // tc::load_record and tc::store_record for a record in two parts: the head into lane 0, the tail (the open message) into
 // LDS by the wave's first lanes
-template <class Place>
-__device__ __forceinline__ kq_dsc_event *load_parts(CallArgs const &c, Place const &w, kq_dsc_status &s, kq_dsc_message &m,
-                                                    unsigned &nev) {
+template <class Args, class Place>
+__device__ __forceinline__ kq_dsc_event *k_dsc::load(Args const &c, Place const &w, kq_dsc_status &s, Side (&side)[bc::kWaves],
+                                                     unsigned &nev) {
+  kq_dsc_message &m = side[w.wave];
   if (w.live && w.lane == 0) {
     __builtin_memcpy(&s, &c.state[w.slot], kHead);
     nev = c.nev[w.slot];
@@ -209,9 +199,10 @@ __device__ __forceinline__ kq_dsc_event *load_parts(CallArgs const &c, Place con
   return c.ev + (size_t)w.slot * c.g.max_events;
 }
 
-template <class Place>
-__device__ __forceinline__ void store_parts(CallArgs const &c, Place const &w, kq_dsc_status const &s, kq_dsc_message const &m,
-                                            unsigned nev) {
+template <class Args, class Place>
+__device__ __forceinline__ void k_dsc::store(Args const &c, Place const &w, kq_dsc_status const &s, Side (&side)[bc::kWaves],
+                                             unsigned nev) {
+  kq_dsc_message const &m = side[w.wave];
   if (!w.live) return;
   kq_dsc_status *const out = c.st ? c.st + (size_t)w.slot * c.sstride : nullptr;
   if (w.lane == 0) {
@@ -226,88 +217,9 @@ __device__ __forceinline__ void store_parts(CallArgs const &c, Place const &w, k
   }
 }
 
-// (four waves to a SIMD asked for: left to itself the allocator takes more VGPRs than the 128 that four workgroups to a CU
-// allow; with the bound it takes 123 and no scratch)
-__global__ __launch_bounds__(kThreads, 4) void k_dsc(CallArgs c) {
-  __shared__ int CS[kTable];                       // C[j] in the low half, C[(j - 256) & 1023] in the high
-  __shared__ short qs[kWaves][kTile];
-  __shared__ int A[kWaves][4][kRow];               // reduced sums: [0, kHist) the frames before the piece, then the piece's
-  __shared__ unsigned long long Pb[kWaves][2][64];
-  __shared__ long long carry[kWaves][4];
-  __shared__ int lastsum[kWaves][4];
-  __shared__ kq_dsc_message OPEN[kWaves];          // the record's tail: between its load and its store lane 0 alone has it
-  DscGeom const &g = c.g;
-  auto const w = tc::wave_place<kThreads>(c, CS);
-  int const wave = w.wave, lane = w.lane, W = tc::window_frames(w.live, w.par.W);
-  unsigned const inc[2] = {w.par.inc_m, w.par.inc_s};
-  int const q = w.par.tb >> 2;
-  kq_dsc_status s{};
-  unsigned nev = 0;
-  kq_dsc_event *ev = load_parts(c, w, s, OPEN[wave], nev);  // (the first barrier of correlate_piece is behind it)
-  tc::load_hist(A[wave], c.hist, w);
-  long long cy[4] = {s.acc[0][0], s.acc[0][1], s.acc[1][0], s.acc[1][1]};
-  for (tc::Piece pc(c.n0, w.B); pc.n < c.n1; pc.next(w.F)) {
-    pc.span(c.n1, w.B, w.F);
-    long long sm[4];  // (its first barrier: the piece before is done with q, A, Pb, carry and lastsum, and A is loaded)
-    tc::correlate_piece<2>(c, w, pc, qs[wave], CS, inc, sm, cy);
-    int const done = pc.done(g.grid);
-    tc::file_sums(A[wave], carry[wave], w, pc, done, sm, 12);
-    __syncthreads();
-    int keep[4] = {0, 0, 0, 0};
-    if (lane < done) {
-      int v[4] = {0, 0, 0, 0};  // the window that ends at frame `lane`: W entries, the last at kHist + lane; the four series
-      for (int i = 0; i < W; i++)  // side by side, as k_rtty has them
-        for (int t = 0; t < 4; t++) v[t] += A[wave][t][kHist + lane - i];
-      Pb[wave][0][lane] = (unsigned long long)((long long)v[0] * v[0]) + (unsigned long long)((long long)v[1] * v[1]);
-      Pb[wave][1][lane] = (unsigned long long)((long long)v[2] * v[2]) + (unsigned long long)((long long)v[3] * v[3]);
-      if (lane == done - 1)
-        for (int t = 0; t < 4; t++) lastsum[wave][t] = v[t];
-    }
-    tc::keep_hist(A[wave], lane, done, keep);
-    __syncthreads();
-    tc::put_hist(A[wave], lane, keep);
-    if (w.live && lane == 0) {
-      for (int i = 0; i < done; i++) {  // the header's step, frame k0 + i
-        s.frames = sat_inc(s.frames);
-        s.t -= 256;
-        if (s.t >= 128) continue;
-        unsigned long long const Pm = Pb[wave][0][i], Ps = Pb[wave][1][i], hi = Pm >= Ps ? Pm : Ps, lo = Pm >= Ps ? Ps : Pm;
-        if (s.ph == 0) {
-          s.pe = hi;
-          s.t += q;
-          s.ph = 1;
-        } else if (s.ph == 1) {
-          s.bit = Pm >= Ps ? 1u : 0u;
-          s.hi = hi;
-          s.lo = lo;
-          s.t += q;
-          s.ph = 2;
-        } else {
-          s.ph = 0;
-          bit_step(g, w.par, s, OPEN[wave], hi, (unsigned long long)(pc.k0 + i), ev, nev);
-        }
-      }
-      if (done) {
-        s.sum[0][0] = lastsum[wave][0];
-        s.sum[0][1] = lastsum[wave][1];
-        s.sum[1][0] = lastsum[wave][2];
-        s.sum[1][1] = lastsum[wave][3];
-      }
-      tc::take_carry(carry[wave], w, pc, done, cy);
-    }
-  }
-  __syncthreads();
-  tc::store_hist(A[wave], c.hist, w);
-  s.acc[0][0] = cy[0];
-  s.acc[0][1] = cy[1];
-  s.acc[1][0] = cy[2];
-  s.acc[1][1] = cy[3];
-  store_parts(c, w, s, OPEN[wave], nev);  // (behind the barrier above)
-}
-
 }  // namespace
 
-struct kq_dsc_bank : tc::GridBank<DscKind> {};
+struct kq_dsc_bank : tc::GridBank<k_dsc> {};
 
 extern "C" {
 
@@ -320,7 +232,7 @@ kq_dsc_bank *kq_dsc_create(const kq_dsc_config *cfg) {
   if (!tc::config_head_ok(fn, cfg) || !kq::field_in_range(fn, "acq", cfg->acq, 1, 3) ||
       !kq::field_in_range(fn, "lose", cfg->lose, 1, 15) || !tc::config_tail_ok(fn, cfg, kMaxSlots))
     return nullptr;
-  kq_dsc_bank *b = tc::finish_create<kq_dsc_bank>(cfg, kTile);  // Lmin 8 at the most: Bs <= 258
+  kq_dsc_bank *b = tc::finish_create<kq_dsc_bank>(cfg, bc::kTile);  // Lmin 8 at the most: Bs <= 258
   b->g.acq = cfg->acq;
   b->g.lose = cfg->lose;
   return b;
@@ -329,18 +241,7 @@ kq_dsc_bank *kq_dsc_create(const kq_dsc_config *cfg) {
 int kq_dsc_destroy(kq_dsc_bank *b) { return kq::destroy_bank(b, "kq_dsc_destroy"); }
 
 int kq_dsc_set(kq_dsc_bank *b, unsigned slot, const kq_dsc_params *p) {
-  const char *fn = "kq_dsc_set";
-  std::unique_lock<std::mutex> lk;
-  if (!tc::open_set(b, fn, slot, p, kMaxSlots, lk)) return -1;
-  double const Fs = b->cfg.samprate;
-  DscPar np{};
-  if (!tc::tone_pair(fn, Fs, p->mark, p->space, &np.inc_m, &np.inc_s) ||
-      !tc::symbol_period(fn, Fs, b->cfg.block_len, p->baud, "bit", &np.tb, &np.W))
-    return -1;
-  np.active = 1;
-  np.source = p->source;
-  b->def.set(slot, np);
-  return 0;
+  return tc::set_pair(b, "kq_dsc_set", slot, p, kMaxSlots);
 }
 
 int kq_dsc_remove(kq_dsc_bank *b, unsigned slot) { return kq::deferred_remove(b, slot, "kq_dsc_remove"); }
@@ -348,8 +249,9 @@ int kq_dsc_remove(kq_dsc_bank *b, unsigned slot) { return kq::deferred_remove(b,
 int kq_dsc_process(kq_dsc_bank *b, const void *src, int format, size_t src_stride, size_t row_stride, unsigned block_len,
                    unsigned nblocks, int on_device, kq_dsc_status *status, size_t status_stride) {
   return tc::process<CallArgs>(b, "kq_dsc_process", src, format, src_stride, row_stride, block_len, nblocks, on_device, status,
-                               status_stride, kWaves, [b](CallArgs &a, unsigned blocks) {
-                                 hipLaunchKernelGGL(k_dsc, dim3(blocks), dim3(kThreads), 0, b->stream, a);
+                               status_stride, bc::kWaves, [b](CallArgs &a, unsigned blocks) {
+                                 hipLaunchKernelGGL((bc::bit_clock<k_dsc, CallArgs>), dim3(blocks), dim3(bc::kThreads), 0,
+                                                    b->stream, a);
                                });
 }
 
@@ -365,13 +267,7 @@ int kq_dsc_get_table(const kq_dsc_bank *b, int16_t *dst, size_t cap) {
   return kq::tonecorr::get_table(b, "kq_dsc_get_table", dst, cap);
 }
 
-int kq_dsc_get_slot(kq_dsc_bank *b, unsigned slot, kq_dsc_slot *out) {
-  std::unique_lock<std::mutex> lk;
-  const DscPar *w = tc::wanted(b, "kq_dsc_get_slot", slot, out, "out", lk);
-  if (!w) return -1;
-  tc::get_pair_slot(*w, out);
-  return 0;
-}
+int kq_dsc_get_slot(kq_dsc_bank *b, unsigned slot, kq_dsc_slot *out) { return tc::get_pair(b, "kq_dsc_get_slot", slot, out); }
 
 int kq_dsc_sync(kq_dsc_bank *b) { return kq::sync_bank(b, "kq_dsc_sync"); }
 

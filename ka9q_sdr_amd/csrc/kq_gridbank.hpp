@@ -1,7 +1,7 @@
-// kq_gridbank.hpp -- the host half that the frame-grid decoders share (kq_cw, kq_rtty, kq_psk, kq_ale, kq_dsc), on top of
-// kq_slots.hpp: deferred event banks of PCM decoders whose kernels correlate frames of B samples on a grid that starts at
-// sample 0 of the stream (the device half: kq_tonecorr.hpp, which includes this file).  Host only, so that it compiles
-// against the device-less stand-in for the runtime; the launch stays with each bank.
+// kq_gridbank.hpp -- the host half that the frame-grid decoders share (kq_cw, kq_rtty, kq_psk, kq_ale, kq_dsc, kq_navtex,
+// kq_same), on top of kq_slots.hpp: deferred event banks of PCM decoders whose kernels correlate frames of B samples on a
+// grid that starts at sample 0 of the stream (the device half: kq_tonecorr.hpp, which includes this file).  Host only, so
+// that it compiles against the device-less stand-in for the runtime; the launch stays with each bank.
 //
 //   cos_table      C[j] = rint(32767 cos(2 pi j / 1024)), one instance for the library, for every bank that correlates
 //                  against it (kq_tone and kq_acars too): alloc_table, its device copy; get_table, the body of kq_*_get_table
@@ -21,6 +21,8 @@
 //   finish_create  the tail of kq_*_create, behind the bank's checks
 //   open_set, tone_ok, tone_pair, symbol_period, wanted, get_pair_slot, process   the shared parts of kq_*_set, the opening
 //                  of a getter, a two-tone getter's assignments, and the body of kq_*_process around the bank's launch
+//   PairPar, set_pair, get_pair   a slot that is a tone pair and a bit rate (kq_dsc, kq_navtex, kq_same): its record and the
+//                  whole bodies of kq_*_set and kq_*_get_slot
 //
 // What a bank still writes: its K, Geom, Par and CallArgs; the checks of create in the order it reports them and the
 // fields of Geom that are its own; the checks of set that are its own and the slot's record; the getters' assignments; the
@@ -250,7 +252,7 @@ __attribute__((format(printf, 4, 5))) inline bool tone_ok(const char *fn, double
   return false;
 }
 
-// a mark / space pair (kq_rtty, kq_dsc): both tones against 0 < f < Fs / 2 and against each other, then their phase
+// a mark / space pair (kq_rtty, set_pair): both tones against 0 < f < Fs / 2 and against each other, then their phase
 // increments, rint(f 2^32 / Fs) in double
 inline bool tone_pair(const char *fn, double Fs, float mark, float space, unsigned *inc_m, unsigned *inc_s) {
   double const fm = mark, fs = space;
@@ -310,6 +312,39 @@ void get_pair_slot(Par const &w, Slot *out) {
   out->inc_s = w.inc_s;
   out->tb = (uint32_t)w.tb;
   out->W = (uint32_t)w.W;
+}
+
+// The banks whose slot is a mark / space pair and a bit rate and nothing else (kq_dsc, kq_navtex, kq_same): the slot's
+// record, and the bodies of kq_*_set and kq_*_get_slot
+struct PairPar {  // per slot, written by the host when a call finds the slot set anew
+  int active;
+  unsigned source;
+  unsigned inc_m, inc_s;
+  int tb, W;
+};
+
+template <class Bank, class Params>
+int set_pair(Bank *b, const char *fn, unsigned slot, const Params *p, unsigned slot_limit) {
+  std::unique_lock<std::mutex> lk;
+  if (!open_set(b, fn, slot, p, slot_limit, lk)) return -1;
+  double const Fs = b->cfg.samprate;
+  PairPar np{};
+  if (!tone_pair(fn, Fs, p->mark, p->space, &np.inc_m, &np.inc_s) ||
+      !symbol_period(fn, Fs, b->cfg.block_len, p->baud, "bit", &np.tb, &np.W))
+    return -1;
+  np.active = 1;
+  np.source = p->source;
+  b->def.set(slot, np);
+  return 0;
+}
+
+template <class Bank, class Slot>
+int get_pair(Bank *b, const char *fn, unsigned slot, Slot *out) {
+  std::unique_lock<std::mutex> lk;
+  const PairPar *w = wanted(b, fn, slot, out, "out", lk);
+  if (!w) return -1;
+  get_pair_slot(*w, out);
+  return 0;
 }
 
 // The body of kq_*_process.  Args: the bank's argument block, Bank::Args or a struct on it; launch(args, blocks) fills what

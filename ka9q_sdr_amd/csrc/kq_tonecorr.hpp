@@ -1,24 +1,25 @@
 // kq_tonecorr.hpp -- the device half of what the banks that correlate PCM against tones from a cosine table share.  The
 // host half (the table itself, the frame grid, the frame-grid banks' host bodies) is kq_gridbank.hpp, included here.
 //
-//   every user       (kq_tone, kq_cw, kq_rtty, kq_psk, kq_acars, kq_ale, kq_dsc; load_q also kq_fskfront.hpp, for kq_fsk
-//                     and kq_pag)
+//   every user       (kq_tone, kq_cw, kq_rtty, kq_psk, kq_acars, kq_ale, and kq_bitclock.hpp for kq_dsc, kq_navtex and
+//                     kq_same; load_q also kq_fskfront.hpp, for kq_fsk and kq_pag)
 //     load_q             the header's quantiser (include/ka9q_hip.h, kq_fsk_*): sample i of a call, f32 or s16be, over kq::PcmIn
 //     load_packed_table  cosine and sine of a table entry in one LDS word
 //     sat_inc, mag, smooth, gate16   the counters, |v|, the one-pole levels and the 128-bit gate 16 sig >= snr nse
-//   frame-grid banks (kq_cw, kq_rtty, kq_psk, kq_ale, kq_dsc)
+//   frame-grid banks (kq_cw, kq_rtty, kq_psk, kq_ale, kq_bitclock.hpp)
 //     Place, wave_place  where a wave stands: its slot, its row of the input, its lanes' frame and place in it
 //     load_record, store_record   the slot's carried record and event count, into lane 0 and back
 //     Piece              the piece loop's bookkeeping
 //     correlate_piece    the front half of the piece loop: 64 / L frames through LDS, NT tones each
 //     take_carry         the sums of the frame a call ends in, back to lane 0
-//   ... with a window (kq_rtty, kq_psk, kq_ale, kq_dsc)
+//   ... with a window (kq_rtty, kq_psk, kq_ale, kq_bitclock.hpp)
 //     window_frames, load_hist, file_sums, keep_hist, put_hist, store_hist   the carried history of 31 frames in front of
 //                        a piece's reduced sums (k_psk keeps the load and the store written out: measured slower there)
 //     window_sum         the window slid over both, a series at a time: k_ale alone calls it (k_rtty and k_psk sum their
 //                        four and two series side by side in one loop, which measured faster there)
-//   ... with a symbol clock (kq_psk, kq_ale, kq_dsc)
-//     clock_adjust       the timing update of a symbol's step 1 (the three-point walk stays in the two kernels: see there)
+//   ... with a symbol clock (kq_psk, kq_ale, kq_bitclock.hpp)
+//     clock_adjust       the timing update of a symbol's step 1 (the three-point walk stays in the kernels: see there)
+//     bit_levels         steps 1 and 2 of a bit of kq_bitclock.hpp's trackers (k_dsc, k_navtex, k_same)
 //
 // The frame-grid kernels, written once.  One wave per slot, four slots to a workgroup: a slot has a few tones and frames of
 // a few dozen samples, so a workgroup per slot (k_tone) would leave most of its lanes without work.  The call's samples go
@@ -291,6 +292,21 @@ __device__ __forceinline__ void clock_adjust(Status &s, int tb, unsigned long lo
   if (s.ee > s.el && s.ee - s.el > (m >> 3)) adj = -(tb >> 5);
   else if (s.el > s.ee && s.el - s.ee > (m >> 3)) adj = tb >> 5;
   s.t += tb - 2 * (tb >> 2) + adj;
+}
+
+// steps 1 and 2 of a bit of the two-tone banks (kq_bitclock.hpp), at its late point with the late power pl: the timing with
+// the centre level, the signal and the noise level; answers whether the gate is open
+template <class Geom, class Par, class Status>
+__device__ __forceinline__ bool bit_levels(Geom const &g, Par const &par, Status &s, unsigned long long pl) {
+  // 1 timing
+  clock_adjust(s, par.tb, pl);
+  smooth(s.ec, s.hi, 3);
+  unsigned long long const top = s.ee > s.el ? s.ee : s.el, low = s.ee > s.el ? s.el : s.ee;
+  if (top - low <= (top >> 3) && s.ec + (top >> 3) < low) s.t += par.tb >> 5;  // (adj == 0) half a bit out: no slope there
+  // 2 levels and gate
+  smooth(s.sig, s.hi, 4);
+  smooth(s.nse, s.lo, 4);
+  return s.frames >= g.warm && s.sig >= g.min_p && gate16(s.sig, s.nse, g.snr);
 }
 
 }  // namespace tonecorr

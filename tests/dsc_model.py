@@ -78,16 +78,7 @@ class DscModel(gm.GridModel):
 
     def _bit(self, k, Pl):
         """the header's steps 1 to 5 at a late point, frame k"""
-        # 1 timing
-        adj, m = self._timing(Pl)
-        self.Ec += (self.hi - self.Ec) >> 3
-        if self.nudge and adj == 0 and self.Ec + (m >> 3) < min(self.Ee, self.El):
-            self.t += self.tb >> 5                                   # half a bit out: the walk has no slope there
-        # 2 levels and gate
-        self.sig += (self.hi - self.sig) >> 4
-        self.nse += (self.lo - self.nse) >> 4
-        is_open = self.frames >= self.warm and self.sig >= self.min_p and 16 * self.sig >= self.snr * self.nse
-        is_open = is_open or not self.gate
+        is_open = self._levels(Pl, self.nudge)  # 1 timing, 2 levels and gate
         self.bits.append((self.bit, is_open))
         # 3 register
         self.r = (self.r << 1 | self.bit) & M64

@@ -2,7 +2,8 @@
 the model side of ka9q_sdr_amd/csrc/kq_tonecorr.hpp: the quantiser of fsk_model, tone_model's cosine table, NT correlators
 whose phases are functions of the sample index alone, the open frame's sums in int64 (exact: they stay below 2^42), the
 shift that reduces a completed frame's sums, the window W frames long over the reduced sums, the early / centre / late
-clock (tc::clock_adjust), and the arena's saturating counts.  Everything behind the quantiser is Python ints.
+clock (tc::clock_adjust), the levels and the gate of a bit of dsc_model, navtex_model and same_model (tc::bit_levels), and
+the arena's saturating counts.  Everything behind the quantiser is Python ints.
 
 What a model still writes: its tracker (`_frame`, and the centre and late points where it has a clock), `status()`, STATUS and
 Event."""
@@ -142,6 +143,20 @@ class GridModel:
             adj = tb >> 5
         self.t += tb - 2 * self.q + adj
         return adj, m
+
+    def _levels(self, Pl, nudge=True):
+        """steps 1 and 2 of a bit of the two-tone decoders with a bit clock, at its late point (tc::bit_levels): the timing, the
+        centre level Ec and the push of tb / 32 where the clock stands half a bit out (no slope there; nudge=False leaves it
+        out), the levels sig and nse of the centre's hi and lo, and the gate over the model's warm, min_p and snr, which its
+        gate=False leaves open; returns whether it is open"""
+        adj, m = self._timing(Pl)
+        self.Ec += (self.hi - self.Ec) >> 3
+        if nudge and adj == 0 and self.Ec + (m >> 3) < min(self.Ee, self.El):
+            self.t += self.tb >> 5
+        self.sig += (self.hi - self.sig) >> 4
+        self.nse += (self.lo - self.nse) >> 4
+        is_open = self.frames >= self.warm and self.sig >= self.min_p and 16 * self.sig >= self.snr * self.nse
+        return is_open or not self.gate
 
     def _file(self, event):
         self.nevents = min(self.nevents + 1, M32)
